@@ -1,8 +1,14 @@
 #!/usr/bin/env python3
 """Headline benchmark of the hydro-force path: all-body force evaluations per second.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
   (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N ...)
+
+A plain run sets up, warms up, times K steps and prints the headline line (`value`, `ms_per_step` = milliseconds per timed step, and
+what the profile of the run's own steps gives, `roofline` among it).  Everything else below -- the secondary figures, the CPU baseline,
+the parity of every step against the CPU oracle, the exchange checks and the launcher child of the N > 1 lines -- runs with --full only.
+--dump-outputs DIR writes the forces of the last timed step (what the caller of the timed path receives: the 6N vector, float64) to
+DIR/forces.npy; the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 N = 1 (default) -- configuration C3 (BASELINE.json configs[2]): synthetic 64-body array, 1024 radiation-IRF samples,
 irregular JONSWAP sea state with 512 wave components, prescribed body motion with dt = dt_rirf = 0.01 s, steady state
@@ -112,7 +118,25 @@ def parse():
                     help="N > 1 under a launcher: how every rank gets all force rows each step.  host (default): hc_step on every rank (direct "
                          "dispatch, results on the host) and a host gather through shared-memory result buffers (hc_set_result_buffer); "
                          "rccl: hc_step_device + RCCL all-gather of the rows on the device + stream synchronise.  The other one is run as a secondary")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="also every figure beside the headline: the secondaries (steady state, chrono-like loops, "
+                    "device_pipelined, plain_per_step_mode, c4_rank_share, c4_one_gpu, the small configs, init, the other exchange mode, the "
+                    "one-process and launcher lines, exchange checks), the CPU baseline and the parity of every step against the CPU oracle.  "
+                    "Without it a run sets up, warms up, times --steps steps and prints the headline line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the forces the timed path returned "
+                    "to its caller in its last timed step as DIR/forces.npy (float64, 6N values)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        # a plain run does what its headline figure needs and nothing else (--no-cpu-baseline also leaves the CPU oracle's threads unmade)
+        args.no_secondary = args.no_cpu_baseline = True
+    return args
+
+
+def dump_outputs(dirname, forces):
+    """--dump-outputs: the 6N force vector of the last timed step, as the timed path handed it to its caller."""
+    os.makedirs(dirname, exist_ok=True)
+    np.save(os.path.join(dirname, "forces.npy"), np.ascontiguousarray(forces, dtype=np.float64))
 
 
 def cpu_baseline(case, motion, t_hist, v_hist, budget_s, step_dt, duration):
@@ -893,8 +917,10 @@ def main():
         devices = [g % max(1, ndev) for g in range(G)]
         if not stub and not args.no_pin:
             capi.load().hc_bind_thread_to_device(devices[0])  # (the calling thread runs context 0; the workers of hc_step_multi bind themselves)
-        info, _ = run_group_sync(args.bodies, G, devices, sdt, args.lookahead, args.warmup, args.steps, check_steps=0 if args.no_secondary else 40,
-                                 stub_cls=HydroForces if stub else None)
+        info, f_timed = run_group_sync(args.bodies, G, devices, sdt, args.lookahead, args.warmup, args.steps, check_steps=0 if args.no_secondary else 40,
+                                       stub_cls=HydroForces if stub else None)
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, f_timed[-1])
         out = {"metric": "hydro-force evals/sec (all bodies)", "value": info["evals_per_s"], "unit": "evals/s", "n_gpus": G, "steps": args.steps,
                "warmup": args.warmup, "alignment_steps": info["alignment_steps"], "passes_in_timed_region": info["passes_in_timed_region"],
                "ms_per_step": info["ms_per_step"], "median_ms_per_step": info["median_ms_per_step"],
@@ -1370,6 +1396,9 @@ def main():
         dist.barrier()
 
     if rank == 0:
+        if args.dump_outputs:
+            # the full 6N vector every rank holds after the exchange (N > 1, one coupled array), else this context's own forces
+            dump_outputs(args.dump_outputs, gathered[total - 1].cpu().numpy() if exchange is not None else forces[total - 1])
         ms = elapsed / args.steps * 1e3
         timed = per_step[pre:total] * 1e3
         # dominant kernel: the look-ahead pass when blocking is on (one launch covers `lookahead` steps), else the per-step kernel.

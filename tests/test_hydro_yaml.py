@@ -1,17 +1,20 @@
 """hydro.yaml ingest (hc_yaml_*) against the REFERENCE's own parser.
 
 oracle/_ref/libref_yaml.so is src/hydro_yaml_parser.cpp of the reference compiled as it lies (oracle/Makefile `ref`) plus a
-dump shim; every field of YAMLHydroData is compared.  Inputs: hand-written variants below (covering the reference's
-unit-test cases tests/unit/test_hydro_yaml_parser.cpp:69-262, whose data files are not in the snapshot) and, when the
-reference tree is present, every *.hydro.yaml it ships."""
+dump shim; every field of YAMLHydroData is compared.  Its answers are stored in tests/golden/hydro_yaml_reference.json
+(tests/golden/make_yaml_goldens.py), so the comparison needs neither the reference tree nor oracle/_ref; where oracle/_ref is
+built, the parser itself is asked as well and must still give the stored answer.  Inputs: hand-written variants below (covering
+the reference's unit-test cases tests/unit/test_hydro_yaml_parser.cpp:69-262, whose data files are not in the snapshot) and every
+*.hydro.yaml the reference ships (stored with the answers)."""
 import ctypes as C
-import glob
+import json
 import os
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 REF_LIB = os.path.join(ROOT, "oracle", "_ref", "libref_yaml.so")
+GOLDEN = os.path.join(ROOT, "tests", "golden", "hydro_yaml_reference.json")
 
 BODY_STR = ["name", "h5_file", "radiation_calculation", "radiation_convolution_mode", "td_smoothing"]
 BODY_NUM = ["include_excitation", "include_radiation", "td_window_length", "td_rms_threshold_factor",
@@ -21,17 +24,26 @@ TOP_NUM = ["waves.height", "waves.period", "waves.direction", "waves.phase", "wa
            "td_taper_start_percent", "td_taper_end_percent", "td_taper_final_amplitude", "td_export_plot_csv"]
 
 
-def ref_parse(path):
-    if not os.path.exists(REF_LIB):
-        import subprocess
-        subprocess.run(["make", "-C", os.path.join(ROOT, "oracle"), "ref"], check=True, stdout=subprocess.DEVNULL)
-    if not os.path.exists(REF_LIB):
-        pytest.skip("reference parser not built (no /root/reference and no prebuilt oracle/_ref)")
-    lib = C.CDLL(REF_LIB)
-    lib.ref_yaml_dump.restype = C.c_char_p
-    st = C.c_int()
-    text = lib.ref_yaml_dump(path.encode(), C.byref(st)).decode()
-    if st.value:
+def golden():
+    with open(GOLDEN) as fh:
+        return json.load(fh)
+
+
+def case_path(name):
+    """Where a hand-written case lies below its base directory (the stored answers were made at the same place)."""
+    return os.path.join("cfg", f"{name}.hydro.yaml")
+
+
+def ref_parse(path, answer, base):
+    """The reference parser's answer for the document at `path` below `base`: the stored one with `base` put back in."""
+    text = answer["dump"].replace("{base}", os.path.realpath(base))
+    if os.path.exists(REF_LIB):
+        lib = C.CDLL(REF_LIB)
+        lib.ref_yaml_dump.restype = C.c_char_p
+        st = C.c_int()
+        live = lib.ref_yaml_dump(path.encode(), C.byref(st)).decode()
+        assert (live, st.value == 0) == (text, answer["ok"]), f"{GOLDEN} is stale for {path}: run tests/golden/make_yaml_goldens.py"
+    if not answer["ok"]:
         return None, text
     return dict(line.split("=", 1) for line in text.splitlines() if "=" in line), None
 
@@ -63,8 +75,8 @@ def ours_parse(path):
     return out, None
 
 
-def compare(path):
-    ref, ref_err = ref_parse(path)
+def compare(path, answer, base):
+    ref, ref_err = ref_parse(path, answer, base)
     got, got_err = ours_parse(path)
     if ref is None:
         assert got is None, f"reference rejects {path} ({ref_err}) but hc_yaml_read accepted it"
@@ -174,11 +186,12 @@ hydrodynamics:
 
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_hand_written_cases_match_reference_parser(tmp_path, name):
-    d = tmp_path / "cfg"
-    d.mkdir()
-    p = d / f"{name}.hydro.yaml"
+    answer = golden()["hand_written"][name]
+    assert answer["text"] == CASES[name], f"{GOLDEN} is stale for {name}: run tests/golden/make_yaml_goldens.py"
+    p = tmp_path / case_path(name)
+    p.parent.mkdir()
     p.write_bytes(CASES[name].encode())
-    verdict = compare(str(p))
+    verdict = compare(str(p), answer, tmp_path)
     expect_error = {"minimal_stale", "malformed", "amplitude_inconsistent", "period_nested_values", "period_nested_linspace",
                     "regular_no_period", "crlf"}
     assert verdict == ("error" if name in expect_error else "ok")
@@ -189,10 +202,11 @@ def test_missing_file_message():
     assert got is None and "Could not open hydro file" in err and "nonexistent.hydro.yaml" in err
 
 
-def test_every_reference_hydro_yaml():
-    files = sorted(glob.glob("/root/reference/**/*.hydro.yaml", recursive=True))
-    if not files:
-        pytest.skip("reference tree not present")
+def test_every_reference_hydro_yaml(tmp_path):
+    files = golden()["reference_files"]
     assert len(files) >= 10
-    for f in files:
-        compare(f)
+    for rel, answer in sorted(files.items()):
+        p = tmp_path / rel  # (at its place in the reference tree: h5_file paths resolve against it)
+        p.parent.mkdir(parents=True, exist_ok=True)
+        p.write_bytes(answer["text"].encode())
+        compare(str(p), answer, tmp_path)

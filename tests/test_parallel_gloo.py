@@ -328,7 +328,7 @@ def test_bench_multi_rank_control_flow_world8_stub(exchange, bodies):
     world = 8
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "24", "--warmup", "5",
-           "--stub-context", "--bodies", str(bodies), "--exchange", exchange]
+           "--stub-context", "--bodies", str(bodies), "--exchange", exchange, "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root, env=dict(os.environ, OMP_NUM_THREADS="1"))
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -363,7 +363,7 @@ def test_bench_no_launcher_gpus8_line_is_first_contact_proof_stub():
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     world, bodies = 8, 44
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "24", "--warmup", "5", "--stub-context", "--bodies", str(bodies)]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", str(world), "--steps", "24", "--warmup", "5", "--stub-context", "--bodies", str(bodies), "--full"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=900, cwd=root, env=dict(env, OMP_NUM_THREADS="1"))
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-4000:])
