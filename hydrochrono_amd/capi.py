@@ -33,6 +33,11 @@ class TaperedDirectOptions(C.Structure):
                 ("taper_final_amplitude", C.c_double), ("export_plot_csv", C.c_int)]
 
 
+class WaveKinematicsOpts(C.Structure):
+    """hc_wave_kinematics_opts: WaveBase::mwl_, RegularWave::regular_wave_phase_, IrregularWaveParams::wave_stretching_."""
+    _fields_ = [("mwl", C.c_double), ("regular_phase", C.c_double), ("wave_stretching", C.c_int)]
+
+
 class ProfileStats(C.Structure):
     _fields_ = [("hydrostatics_seconds", C.c_double), ("radiation_seconds", C.c_double), ("waves_seconds", C.c_double),
                 ("hydrostatics_calls", C.c_int), ("radiation_calls", C.c_int), ("waves_calls", C.c_int),
@@ -138,6 +143,10 @@ SIGNATURES = {
     "hc_get_eta_table": (C.c_int, [C.c_void_p, c_double_p, c_double_p]),
     "hc_export_irregular_inputs_h5": (C.c_int, [C.c_void_p, C.c_char_p]),
     "hc_get_regular_coeffs": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p]),
+    "hc_get_simulation_parameters": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p]),
+    "hc_wave_kinematics_opts_default": (None, [C.POINTER(WaveKinematicsOpts)]),
+    "hc_wave_kinematics": (C.c_int, [C.c_void_p, C.POINTER(WaveKinematicsOpts), C.c_int, c_double_p, C.c_int, c_double_p,
+                                     c_double_p, c_double_p, c_double_p]),
     "hc_synth_fill": (C.c_int, [C.c_void_p, C.c_ulonglong, C.c_int, C.c_double, C.c_int, C.c_double]),
 }
 

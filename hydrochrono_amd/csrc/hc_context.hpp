@@ -239,6 +239,14 @@ struct hc_ctx {
     std::vector<double> eta_t, eta;
     hc::DeviceBuffer<double> d_kex, d_ex_tau, d_ex_width, d_eta_t, d_eta;
     hc::DeviceBuffer<double> d_spec_mag, d_spec_phase, d_spec_amp, d_spec_omega, d_spec_phi;  // spectral (component-sum) mode
+    unsigned long long wave_serial = 0;  // counts the hc_set_wave_* calls (voids the kinematics table below)
+
+    // wave kinematics (hc_wave_kinematics, hc_wave_kin.hip): the component table of the wave model it was built for (wave_serial,
+    // and the phase of a regular wave), and a grow-only buffer for points, times and outputs
+    unsigned long long kin_serial = ~0ULL;
+    double kin_phase = 0.0;
+    int kin_nf = 0;
+    hc::DeviceBuffer<double> d_kin_tab, d_kin_io;
 
     // GEMV configuration + scratch
     int chunk_gp = 0, nchunks_rad = 0, chunk_gp_ex = 0, nchunks_ex = 0, ngp_ex = 0;

@@ -145,6 +145,15 @@ int hc_get_regular_coeffs(hc_ctx* c, double* mag, double* phase, double* wavenum
     HC_API_END(c)
 }
 
+int hc_get_simulation_parameters(hc_ctx* c, double* rho, double* g, double* water_depth) {
+    HC_API_BEGIN(c)
+    require(c->have_sim, HC_ERR_INVALID, "no simulation parameters set");
+    if (rho) *rho = c->rho;
+    if (g) *g = c->g;
+    if (water_depth) *water_depth = c->depth;
+    HC_API_END(c)
+}
+
 // Diagnostics (not part of the public header): copies an internal device buffer to the host.  which: 0 = P [16][Dpad],
 // 1 = E [16][Dpad], 2 = Y [16][kScatterSamples][Dpad].
 int hc_debug_read(hc_ctx* c, int which, double* out, long long n) {

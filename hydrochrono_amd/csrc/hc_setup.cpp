@@ -611,6 +611,7 @@ int hc_set_gravity(hc_ctx* c, const double g[3]) {
 int hc_set_wave_none(hc_ctx* c, int num_bodies_arg) {
     HC_API_BEGIN(c)
     drop_lookahead_excitation(c);
+    ++c->wave_serial;
     HC_HIP(hipDeviceSynchronize());  // the tables replaced below may be in use by steps on a caller's stream
     require(c->finalized, HC_ERR_INVALID, "hc_finalize has not been called");
     require(num_bodies_arg >= 0, HC_ERR_INVALID, "negative body count");
@@ -623,6 +624,7 @@ int hc_set_wave_none(hc_ctx* c, int num_bodies_arg) {
 int hc_set_wave_regular(hc_ctx* c, int num_bodies_arg, double amplitude, double omega) {
     HC_API_BEGIN(c)
     drop_lookahead_excitation(c);
+    ++c->wave_serial;
     HC_HIP(hipDeviceSynchronize());  // the tables replaced below may be in use by steps on a caller's stream
     require(c->finalized, HC_ERR_INVALID, "hc_finalize has not been called");
     require(num_bodies_arg >= 1 && num_bodies_arg <= c->N, HC_ERR_OUT_OF_RANGE, "regular wave created for more bodies than the hydro data holds");
@@ -679,6 +681,7 @@ void hc_irregular_wave_params_default(hc_irregular_wave_params* p) {
 int hc_set_wave_irregular(hc_ctx* c, const hc_irregular_wave_params* pp) {
     HC_API_BEGIN(c)
     drop_lookahead_excitation(c);
+    ++c->wave_serial;
     HC_HIP(hipDeviceSynchronize());  // the tables replaced below may be in use by steps on a caller's stream
     require(c->finalized, HC_ERR_INVALID, "hc_finalize has not been called");
     require(pp, HC_ERR_INVALID, "null parameters");
@@ -841,6 +844,7 @@ int hc_set_wave_irregular(hc_ctx* c, const hc_irregular_wave_params* pp) {
 int hc_set_wave_irregular_spectral(hc_ctx* c, const hc_irregular_wave_params* pp) {
     HC_API_BEGIN(c)
     drop_lookahead_excitation(c);
+    ++c->wave_serial;
     HC_HIP(hipDeviceSynchronize());  // the tables replaced below may be in use by steps on a caller's stream
     require(c->finalized, HC_ERR_INVALID, "hc_finalize has not been called");
     require(pp, HC_ERR_INVALID, "null parameters");

@@ -1,0 +1,254 @@
+// hc_wave_kin.hip -- wave kinematics: WaveBase::GetElevation / GetVelocity / GetAcceleration of the reference
+// (include/hydroc/wave_types.h:69-73; src/wave_types.cpp:14-158 for the sums, :301-313 RegularWave, :515-550 IrregularWaves with
+// Wheeler stretching) for the context's wave model, batched over P points x T times.  Off the force path: the kernel reads its own
+// component table and writes its own buffers, nothing a step uses.  DESIGN.md 3.7a describes the kernel and the reference
+// behaviour reproduced here, INTEGRATION.md 2 the one deviation (infinite depth under stretching).
+#include "hc_internal.hpp"
+
+using namespace hc::detail;
+
+namespace hc {
+namespace {
+
+constexpr int kKinThreads = 256;  // work items per workgroup, one per (point, time)
+constexpr int kKinTile    = 256;  // wave components staged in LDS per tile
+// (point, time) pairs per call: the grid's work-item count stays below 2^31
+constexpr long long kKinMaxItems = (1LL << 31) - kKinThreads;
+
+// The per-component table, struct of arrays [kKinCols][nf], built once per wave model on the host (kin_table).
+enum KinCol {
+    kKinAmp = 0,   // A
+    kKinOmega,     // omega
+    kKinK,         // wavenumber k
+    kKinPhase,     // phi
+    kKinWA,        // omega * A
+    kKinW2A,       // omega * omega * A
+    kKinInvSinh,   // 1 / sinh(k d) (finite-depth profile; 0 where the exponential profile applies)
+    kKinDeep,      // 1: exponential profile (2 pi / k > d || k d > 500, per component as the reference tests it)
+    kKinCols
+};
+
+struct KinArgs {
+    const double* tab;  // [kKinCols][nf]
+    int nf;
+    int P, T;
+    const double* xyz;  // [P][3]
+    const double* t;    // [T]
+    double depth, mwl;
+    int stretch;       // Wheeler stretching (IrregularWaveParams::wave_stretching_)
+    int finite_depth;  // 0: water depth +inf, the stretched z is the limit z' - eta
+    double* eta;       // [T][P]    } NULL: not wanted
+    double* vel;       // [T][P][3] }
+    double* acc;       // [T][P][3] }
+};
+
+// One work item per (point, time), item o = j * P + p.  Every item sums the components in index order from the same LDS tiles, so
+// its bits do not depend on P, T or where in the grid it sits.  With stretching, eta is summed first (the reference's
+// GetEtaIrregular) and the kinematics are evaluated at the stretched z in a second pass.
+__global__ void __launch_bounds__(kKinThreads) wave_kinematics_kernel(KinArgs a) {
+    __shared__ double s[kKinCols][kKinTile];
+    const long long n  = static_cast<long long>(a.P) * a.T;
+    const long long o  = static_cast<long long>(blockIdx.x) * kKinThreads + threadIdx.x;
+    const bool active  = o < n;
+    const long long oc = active ? o : 0;  // items past the end evaluate item 0 and store nothing (all take part in the staging)
+    const int p = static_cast<int>(oc % a.P), j = static_cast<int>(oc / a.P);
+    const double x = a.xyz[3 * p], z = a.xyz[3 * p + 2], t = a.t[j];
+    const bool want_kin = a.vel || a.acc;
+
+    // ---- eta = sum_i A_i cos(k_i x - w_i t + phi_i)  (src/wave_types.cpp:14-44; the expression of eta_kernel at x = 0) ----
+    double eta = 0.0;
+    if (a.eta || (a.stretch && want_kin)) {
+        for (int i0 = 0; i0 < a.nf; i0 += kKinTile) {
+            const int m = min(kKinTile, a.nf - i0);
+            __syncthreads();
+            for (int i = threadIdx.x; i < m; i += kKinThreads) {
+                s[kKinAmp][i]   = a.tab[kKinAmp * a.nf + i0 + i];
+                s[kKinOmega][i] = a.tab[kKinOmega * a.nf + i0 + i];
+                s[kKinK][i]     = a.tab[kKinK * a.nf + i0 + i];
+                s[kKinPhase][i] = a.tab[kKinPhase * a.nf + i0 + i];
+            }
+            __syncthreads();
+            for (int i = 0; i < m; ++i) eta += s[kKinAmp][i] * cos(s[kKinK][i] * x - s[kKinOmega][i] * t + s[kKinPhase][i]);
+        }
+    }
+    if (!want_kin) {  // (uniform over the launch)
+        if (active) a.eta[o] = eta;
+        return;
+    }
+
+    // ---- z at which the profiles are evaluated (:515-544; GetWaterVelocity subtracts mwl from what it is given, :69-71) ----
+    double zs = z;
+    if (a.stretch) {
+        const double zr = z - a.mwl;
+        zs = a.finite_depth ? a.depth * (zr - eta) / (a.depth + eta) : zr - eta;
+    }
+    const double ze = zs - a.mwl;  // under stretching mwl is subtracted a second time, as in the reference
+
+    // ---- velocity and acceleration (:61-158) ----
+    double ux = 0.0, uz = 0.0, ax = 0.0, az = 0.0;
+    for (int i0 = 0; i0 < a.nf; i0 += kKinTile) {
+        const int m = min(kKinTile, a.nf - i0);
+        __syncthreads();
+        for (int i = threadIdx.x; i < m; i += kKinThreads) {
+#pragma unroll
+            for (int col = kKinOmega; col < kKinCols; ++col) s[col][i] = a.tab[col * a.nf + i0 + i];
+        }
+        __syncthreads();
+        for (int i = 0; i < m; ++i) {
+            const double k = s[kKinK][i];
+            double sn, cs;
+            sincos(k * x - s[kKinOmega][i] * t + s[kKinPhase][i], &sn, &cs);
+            double px, pz;
+            if (s[kKinDeep][i] != 0.0) {  // (the same branch for every item: no divergence)
+                px = pz = exp(k * ze);
+            } else {
+                const double q = k * (ze + a.depth);
+                px = cosh(q) * s[kKinInvSinh][i];
+                pz = sinh(q) * s[kKinInvSinh][i];
+            }
+            const double wa = s[kKinWA][i], w2a = s[kKinW2A][i];
+            ux += wa * px * cs;
+            uz += wa * pz * sn;
+            ax += w2a * px * sn;
+            az -= w2a * pz * cs;
+        }
+    }
+    if (!active) return;
+    if (a.eta) a.eta[o] = eta;
+    if (a.vel) {
+        a.vel[3 * o]     = ux;
+        a.vel[3 * o + 1] = 0.0;
+        a.vel[3 * o + 2] = uz;
+    }
+    if (a.acc) {
+        a.acc[3 * o]     = ax;
+        a.acc[3 * o + 1] = 0.0;
+        a.acc[3 * o + 2] = az;
+    }
+}
+
+// The component table of the context's wave model (regular: one component with the caller's phase; irregular and spectral: the
+// spectrum of the context, A_i = sqrt(2 S_i df_i) and w_i = 2 pi f_i as build_spectrum / the reference compute them).  Rebuilt when
+// a hc_set_wave_* call has come in since (wave_serial) or the regular wave's phase differs from the cached one.
+void kin_table(hc_ctx* c, double regular_phase) {
+    const bool regular = c->wave_kind == kWaveRegular;
+    if (c->kin_serial == c->wave_serial && (!regular || std::memcmp(&c->kin_phase, &regular_phase, sizeof(double)) == 0)) return;
+    std::vector<double> amp, omega, k, phase;
+    if (regular) {
+        amp   = {c->reg_amp};
+        omega = {c->reg_omega};
+        k     = {c->reg_wavenumber};
+        phase = {regular_phase};
+    } else {
+        const size_t nf = c->spec_f.size();
+        amp.resize(nf);
+        omega.resize(nf);
+        for (size_t i = 0; i < nf; ++i) {
+            amp[i]   = std::sqrt(2 * c->spec_S[i] * c->spec_df[i]);
+            omega[i] = 2 * M_PI * c->spec_f[i];
+        }
+        k     = c->spec_k;
+        phase = c->spec_phase;
+    }
+    const int nf = static_cast<int>(amp.size());
+    const double d = c->depth;
+    std::vector<double> tab(static_cast<size_t>(kKinCols) * nf);
+    auto at = [&](int col, int i) -> double& { return tab[static_cast<size_t>(col) * nf + i]; };
+    for (int i = 0; i < nf; ++i) {
+        const bool deep     = 2 * M_PI / k[i] > d || k[i] * d > 500.0;  // src/wave_types.cpp:74,108
+        at(kKinAmp, i)      = amp[i];
+        at(kKinOmega, i)    = omega[i];
+        at(kKinK, i)        = k[i];
+        at(kKinPhase, i)    = phase[i];
+        at(kKinWA, i)       = omega[i] * amp[i];
+        at(kKinW2A, i)      = omega[i] * omega[i] * amp[i];
+        at(kKinInvSinh, i)  = deep ? 0.0 : 1.0 / std::sinh(k[i] * d);
+        at(kKinDeep, i)     = deep ? 1.0 : 0.0;
+    }
+    c->d_kin_tab.upload(tab, c->stream);
+    c->kin_nf     = nf;
+    c->kin_serial = c->wave_serial;
+    c->kin_phase  = regular_phase;
+}
+
+void grow(hc::DeviceBuffer<double>& b, size_t n) {
+    if (b.n < n) b.alloc(n);
+}
+
+}  // namespace
+}  // namespace hc
+
+extern "C" {
+
+void hc_wave_kinematics_opts_default(hc_wave_kinematics_opts* o) {
+    if (!o) return;
+    o->mwl             = 0.0;
+    o->regular_phase   = 0.0;
+    o->wave_stretching = 1;
+}
+
+// Touches no step state, so it is not ordered against the direct queue (HC_API_BEGIN_HOT): a call between steps leaves a pass that
+// is running alone.
+int hc_wave_kinematics(hc_ctx* c, const hc_wave_kinematics_opts* opts, int n_points, const double* xyz, int n_times, const double* t,
+                       double* eta, double* vel, double* acc) {
+    HC_API_BEGIN_HOT(c)
+    require(c->finalized, HC_ERR_INVALID, "hc_finalize has not been called");
+    hc_wave_kinematics_opts o;
+    hc_wave_kinematics_opts_default(&o);
+    if (opts) o = *opts;
+    require(std::isfinite(o.mwl) && std::isfinite(o.regular_phase), HC_ERR_INVALID, "non-finite mwl or regular_phase");
+    require(n_points >= 0 && n_times >= 0, HC_ERR_INVALID, "negative point or time count");
+    require((n_points == 0 || xyz) && (n_times == 0 || t), HC_ERR_INVALID, "null points or times");
+    for (int p = 0; p < n_points; ++p)
+        require(std::isfinite(xyz[3 * p]) && std::isfinite(xyz[3 * p + 2]), HC_ERR_INVALID, "non-finite x or z of a point");
+    for (int j = 0; j < n_times; ++j) require(std::isfinite(t[j]), HC_ERR_INVALID, "non-finite time");
+    const long long n = static_cast<long long>(n_points) * n_times;
+    require(n <= hc::kKinMaxItems, HC_ERR_INVALID, "too many (point, time) pairs for one call");
+    if (n == 0 || !(eta || vel || acc)) return HC_OK;
+    if (c->wave_kind == hc::kWaveNone) {  // NoWave (wave_types.h:103-109): zeros, no launch
+        if (eta) std::fill(eta, eta + n, 0.0);
+        if (vel) std::fill(vel, vel + 3 * n, 0.0);
+        if (acc) std::fill(acc, acc + 3 * n, 0.0);
+        return HC_OK;
+    }
+    hc::kin_table(c, o.regular_phase);
+    // one buffer: points, times, then the requested outputs
+    const size_t n_in = 3 * static_cast<size_t>(n_points) + n_times;
+    const size_t n_out = (eta ? n : 0) + (vel ? 3 * n : 0) + (acc ? 3 * n : 0);
+    hc::grow(c->d_kin_io, n_in + n_out);
+    double* d_xyz = c->d_kin_io.p;
+    double* d_t   = d_xyz + 3 * static_cast<size_t>(n_points);
+    double* d_out = d_t + n_times;
+    hc::KinArgs a{};
+    a.tab          = c->d_kin_tab.p;
+    a.nf           = c->kin_nf;
+    a.P            = n_points;
+    a.T            = n_times;
+    a.xyz          = d_xyz;
+    a.t            = d_t;
+    a.depth        = c->depth;
+    a.mwl          = o.mwl;
+    a.stretch      = (c->wave_kind != hc::kWaveRegular && o.wave_stretching) ? 1 : 0;  // RegularWave has none (:301-313)
+    a.finite_depth = std::isfinite(c->depth) ? 1 : 0;
+    if (eta) {
+        a.eta = d_out;
+        d_out += n;
+    }
+    if (vel) {
+        a.vel = d_out;
+        d_out += 3 * n;
+    }
+    if (acc) a.acc = d_out;
+    HC_HIP(hipMemcpyAsync(d_xyz, xyz, 3 * static_cast<size_t>(n_points) * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HC_HIP(hipMemcpyAsync(d_t, t, static_cast<size_t>(n_times) * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    const unsigned blocks = static_cast<unsigned>((n + hc::kKinThreads - 1) / hc::kKinThreads);
+    hipLaunchKernelGGL(hc::wave_kinematics_kernel, dim3(blocks), dim3(hc::kKinThreads), 0, c->stream, a);
+    HC_HIP(hipGetLastError());
+    if (eta) HC_HIP(hipMemcpyAsync(eta, a.eta, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (vel) HC_HIP(hipMemcpyAsync(vel, a.vel, 3 * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (acc) HC_HIP(hipMemcpyAsync(acc, a.acc, 3 * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HC_HIP(hipStreamSynchronize(c->stream));
+    HC_API_END(c)
+}
+
+}  // extern "C"

@@ -373,6 +373,26 @@ class HydroForces:
         self._chk(self.lib.hc_get_regular_coeffs(self.ctx, _dp(mag), _dp(ph), C.byref(k)))
         return mag, ph, k.value
 
+    def simulation_parameters(self):
+        rho, g, depth = C.c_double(), C.c_double(), C.c_double()
+        self._chk(self.lib.hc_get_simulation_parameters(self.ctx, C.byref(rho), C.byref(g), C.byref(depth)))
+        return rho.value, g.value, depth.value
+
+    # -- wave kinematics (WaveBase::GetElevation / GetVelocity / GetAcceleration) --
+    def wave_kinematics(self, points, times, mwl=0.0, regular_phase=0.0, wave_stretching=True):
+        """Free-surface elevation, water velocity and acceleration of the wave model in force at every point (P x 3) and time (T):
+        returns eta (T, P), vel (T, P, 3), acc (T, P, 3)."""
+        xyz = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        t = _arr(times)
+        P, T = xyz.shape[0], t.size
+        eta, vel, acc = np.empty((T, P)), np.empty((T, P, 3)), np.empty((T, P, 3))
+        o = capi.WaveKinematicsOpts()
+        self.lib.hc_wave_kinematics_opts_default(C.byref(o))
+        o.mwl, o.regular_phase, o.wave_stretching = float(mwl), float(regular_phase), int(bool(wave_stretching))
+        self._chk(self.lib.hc_wave_kinematics(self.ctx, C.byref(o), P, _dp(xyz.reshape(-1)), T, _dp(t), _dp(eta.reshape(-1)),
+                                              _dp(vel.reshape(-1)), _dp(acc.reshape(-1))))
+        return eta, vel, acc
+
 
 class HydroGroup:
     """G row-sharded contexts of ONE coupled N-body system driven by one host process through hc_step_multi /
@@ -418,6 +438,10 @@ class HydroGroup:
     def components(self):
         parts = [h.components() for h in sorted(self.shards, key=lambda h: h.b0)]
         return tuple(np.concatenate([p[k] for p in parts]) for k in range(3))
+
+    def wave_kinematics(self, points, times, **opts):
+        # every shard holds the whole wave model and answers with the same bits
+        return self.shards[0].wave_kinematics(points, times, **opts)
 
     def added_mass_mv(self, R, w, c):
         R = _arr(R).copy()

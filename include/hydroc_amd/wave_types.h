@@ -6,9 +6,14 @@
 // `using namespace hydroc_amd;` -- the wave set-up lines stay as they are (demos/sphere/demo_sphere_reg_waves.cpp:126-128,
 // tests/regression/sphere/irreg_waves/sphere_irreg_waves_test.cpp:113-122).
 //
-// Not mirrored (off the force path): GetElevation / GetVelocity / GetAcceleration (wave kinematics), eta_file_path_
-// (undefined behaviour in the reference, src/wave_types.cpp:480-500 vs :784-785).  The mesh helper the irregular demos call
-// (SetUpWaveMesh / GetMeshFile / GetWaveMeshVelocity) is there so that they compile.
+// Wave kinematics (GetElevation / GetVelocity / GetAcceleration, include/hydroc/wave_types.h:69-73) run on the GPU through
+// hc_wave_kinematics for all three classes.  Differences: positions are std::array<double, 3> or any type with
+// .x() .y() .z() (Eigen::Vector3d, ChVector3d); GetVelocity / GetAcceleration return std::array<double, 3>; GetKinematics evaluates
+// a grid of points x a series of times in one call; a model that is not attached throws std::runtime_error.  Attach copies g_ and
+// water_depth_ from the hydro data as the reference's AddH5Data does; the kinematics use the context's values, so writing these
+// members afterwards has no effect.  Not mirrored: eta_file_path_ (undefined behaviour in the reference, src/wave_types.cpp:480-500
+// vs :784-785).  The mesh helper the irregular demos call (SetUpWaveMesh / GetMeshFile / GetWaveMeshVelocity) is there so that they
+// compile.
 #pragma once
 
 #include <algorithm>
@@ -17,6 +22,7 @@
 #include <memory>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "../hydrochrono_amd.h"
@@ -62,10 +68,74 @@ class WaveBase {  // :52-79
         check(ctx_, hc_compute_waves(ctx_, t, f.data()));
         return f;
     }
+    // Wave kinematics of the attached model (src/wave_types.cpp:14-158,301-313,515-550; NoWave: zeros).  Non-virtual: a subclass
+    // supplies its options through KinematicsOptions(), so the overloads for Eigen / Chrono vectors below stay visible.
+    double GetElevation(const std::array<double, 3>& position, double time) {
+        double eta = 0.0;
+        kinematics(1, position.data(), 1, &time, &eta, nullptr, nullptr);
+        return eta;
+    }
+    std::array<double, 3> GetVelocity(const std::array<double, 3>& position, double time) {
+        std::array<double, 3> v{};
+        kinematics(1, position.data(), 1, &time, nullptr, v.data(), nullptr);
+        return v;
+    }
+    std::array<double, 3> GetAcceleration(const std::array<double, 3>& position, double time) {
+        std::array<double, 3> a{};
+        kinematics(1, position.data(), 1, &time, nullptr, nullptr, a.data());
+        return a;
+    }
+    // the same for any vector type with .x() .y() .z() (Eigen::Vector3d, chrono::ChVector3d)
+    template <class V, class = decltype(std::declval<const V&>().x() + std::declval<const V&>().z())>
+    double GetElevation(const V& position, double time) {
+        return GetElevation(as_array(position), time);
+    }
+    template <class V, class = decltype(std::declval<const V&>().x() + std::declval<const V&>().z())>
+    std::array<double, 3> GetVelocity(const V& position, double time) {
+        return GetVelocity(as_array(position), time);
+    }
+    template <class V, class = decltype(std::declval<const V&>().x() + std::declval<const V&>().z())>
+    std::array<double, 3> GetAcceleration(const V& position, double time) {
+        return GetAcceleration(as_array(position), time);
+    }
+    // Batched: every point at every time in one GPU call.  eta [T][P], vel / acc [T][P][3] (row-major, T = times.size(),
+    // P = points.size()); a null output is not computed.  Each value has the bits of the single-point call.
+    void GetKinematics(const std::vector<std::array<double, 3>>& points, const std::vector<double>& times, std::vector<double>* eta,
+                       std::vector<double>* vel = nullptr, std::vector<double>* acc = nullptr) {
+        const size_t n = points.size() * times.size();
+        if (eta) eta->assign(n, 0.0);
+        if (vel) vel->assign(3 * n, 0.0);
+        if (acc) acc->assign(3 * n, 0.0);
+        kinematics(static_cast<int>(points.size()), points.empty() ? nullptr : points[0].data(), static_cast<int>(times.size()),
+                   times.data(), eta ? eta->data() : nullptr, vel ? vel->data() : nullptr, acc ? acc->data() : nullptr);
+    }
     double mwl_ = 0.0, g_ = 9.81, water_depth_ = 0.0;  // public members of the reference's base class (:74-78); unused by the force path
 
   protected:
-    hc_ctx* ctx_ = nullptr;  // the first context the model was attached to (getters)
+    hc_ctx* ctx_ = nullptr;  // the first context the model was attached to (getters, kinematics)
+    // what the model adds to the call's options (RegularWave: its phase, IrregularWaves: stretching); the base gives mwl_
+    virtual hc_wave_kinematics_opts KinematicsOptions() const {
+        hc_wave_kinematics_opts o;
+        hc_wave_kinematics_opts_default(&o);
+        o.mwl = mwl_;
+        return o;
+    }
+    // end of every Attach: the context the getters use, and g_ / water_depth_ as the reference's AddH5Data sets them (:280-281,509-510)
+    void attached(hc_ctx* ctx) {
+        ctx_ = ctx;
+        check(ctx, hc_get_simulation_parameters(ctx, nullptr, &g_, &water_depth_));
+    }
+
+  private:
+    template <class V>
+    static std::array<double, 3> as_array(const V& p) {
+        return {static_cast<double>(p.x()), static_cast<double>(p.y()), static_cast<double>(p.z())};
+    }
+    void kinematics(int n_points, const double* xyz, int n_times, const double* t, double* eta, double* vel, double* acc) {
+        if (!ctx_) throw std::runtime_error("wave model is not attached to a TestHydro");
+        const hc_wave_kinematics_opts o = KinematicsOptions();
+        check(ctx_, hc_wave_kinematics(ctx_, &o, n_points, xyz, n_times, t, eta, vel, acc));
+    }
 };
 
 class NoWave : public WaveBase {  // :84-104
@@ -75,7 +145,7 @@ class NoWave : public WaveBase {  // :84-104
     WaveMode GetWaveMode() override { return WaveMode::noWaveCIC; }
     void Attach(hc_ctx* ctx) override {
         check(ctx, hc_set_wave_none(ctx, static_cast<int>(num_bodies_)));
-        ctx_ = ctx;
+        attached(ctx);
     }
 
   private:
@@ -89,12 +159,19 @@ class RegularWave : public WaveBase {  // :109-158
     WaveMode GetWaveMode() override { return WaveMode::regular; }
     void Attach(hc_ctx* ctx) override {
         check(ctx, hc_set_wave_regular(ctx, static_cast<int>(num_bodies_), regular_wave_amplitude_, regular_wave_omega_));
-        ctx_ = ctx;
+        attached(ctx);
     }
     // user input variables
     double regular_wave_amplitude_ = 0.0;
     double regular_wave_omega_     = 0.0;
-    double regular_wave_phase_     = 0.0;  // unused by the force, as in the reference (src/wave_types.cpp:315-327)
+    double regular_wave_phase_     = 0.0;  // unused by the force, as in the reference (src/wave_types.cpp:315-327); the kinematics' phase
+
+  protected:
+    hc_wave_kinematics_opts KinematicsOptions() const override {
+        hc_wave_kinematics_opts o = WaveBase::KinematicsOptions();
+        o.regular_phase           = regular_wave_phase_;
+        return o;
+    }
 
   private:
     unsigned int num_bodies_;
@@ -114,7 +191,7 @@ struct IrregularWaveParams {  // :277-292
     double peak_enhancement_factor_ = 1.0;
     bool is_normalized_             = false;
     int seed_                       = 1;
-    bool wave_stretching_           = true;
+    bool wave_stretching_           = true;  // Wheeler stretching of the kinematics (src/wave_types.cpp:515-544); not on the force path
 };
 
 class IrregularWaves : public WaveBase {  // :294-380
@@ -138,7 +215,7 @@ class IrregularWaves : public WaveBase {  // :294-380
         p.is_normalized           = params_.is_normalized_ ? 1 : 0;
         p.seed                    = params_.seed_;
         check(ctx, hc_set_wave_irregular(ctx, &p));
-        ctx_ = ctx;
+        attached(ctx);
     }
     // Exporter inputs (src/wave_types.cpp:461-478, read by the runner at run_hydrochrono_from_yaml.cpp:668-679).  GetSpectrum returns
     // the spectral densities S(f) its comment promises; the reference returns a member it never fills ("do not reproduce").
@@ -168,6 +245,13 @@ class IrregularWaves : public WaveBase {  // :294-380
     }
     std::string GetMeshFile() { return mesh_file_name_; }
     std::array<double, 3> GetWaveMeshVelocity() { return {1.0, 0.0, 0.0}; }  // (an Eigen::Vector3d in the reference; ChVector3d(v[0], v[1], v[2]))
+
+  protected:
+    hc_wave_kinematics_opts KinematicsOptions() const override {
+        hc_wave_kinematics_opts o = WaveBase::KinematicsOptions();
+        o.wave_stretching         = params_.wave_stretching_ ? 1 : 0;
+        return o;
+    }
 
   private:
     std::vector<double> spectrum(int which) const {

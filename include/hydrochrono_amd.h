@@ -439,6 +439,36 @@ int hc_get_eta_table(hc_ctx* ctx, double* t_nt, double* eta_nt);
 int hc_export_irregular_inputs_h5(hc_ctx* ctx, const char* path);
 /* RegularWave::excitation_force_mag_/phase_ and wavenumber_ (:278-299) */
 int hc_get_regular_coeffs(hc_ctx* ctx, double* mag_D, double* phase_D, double* wavenumber);
+/* rho, g, water_depth of the context (hc_set_simulation_parameters / the HDF5 file): what WaveBase::AddH5Data copies into
+ * g_ and water_depth_ (src/wave_types.cpp:280-281,509-510).  Any pointer may be NULL. */
+int hc_get_simulation_parameters(hc_ctx* ctx, double* rho, double* g, double* water_depth);
+
+/* ------------------------------------------------------------------------------------------------
+ * Wave kinematics: WaveBase::GetElevation / GetVelocity / GetAcceleration (include/hydroc/wave_types.h:69-73) of the wave model
+ * in force, batched over points x times, on the GPU.  Per component (A, w, k, phi) at x = position.x, z' = position.z - mwl:
+ * eta = A cos(k x - w t + phi) (src/wave_types.cpp:14-44); velocity / acceleration (:61-158) with the exponential profile when
+ * 2 pi / k > depth || k depth > 500, else cosh / sinh (k (z' + depth)) / sinh(k depth); y components 0.
+ *   RegularWave (:301-313): one component, phi = regular_phase, no stretching.
+ *   IrregularWaves (:515-550, both hc_set_wave_irregular and hc_set_wave_irregular_spectral): the sum over the spectrum in
+ *   index order, A_i = sqrt(2 S_i df_i), w_i = 2 pi f_i; with wave_stretching the kinematics are evaluated at
+ *   z_s = depth (z' - eta) / (depth + eta) (Wheeler), from which the profile subtracts mwl once more, as the reference does; for
+ *   an infinite depth (where the reference gives NaN) at the limit z_s = z' - eta.
+ *   NoWave (include/hydroc/wave_types.h:103-109), or no wave model: zeros, no launch.
+ * Not ramped (the eta(t) table is; kinematics are not); the wave direction is ignored (only x enters the phase).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct hc_wave_kinematics_opts {
+    double mwl;            /* WaveBase::mwl_ (0) */
+    double regular_phase;  /* RegularWave::regular_wave_phase_ (0) */
+    int wave_stretching;   /* IrregularWaveParams::wave_stretching_ (1) */
+} hc_wave_kinematics_opts;
+void hc_wave_kinematics_opts_default(hc_wave_kinematics_opts* o);
+/* xyz[n_points][3], t[n_times] -> eta[T][P], vel[T][P][3], acc[T][P][3]; any output may be NULL, o NULL = the defaults.
+ * Synchronous on the context's stream; needs hc_finalize.  Counts must be >= 0 and a pointer is required where its count is > 0;
+ * non-finite x, z or t, non-finite options, or more than 2^31 - 256 (point, time) pairs give HC_ERR_INVALID.  Every output sums
+ * the components in index order on its own, so its bits do not depend on the batch it is part of, nor on which shard context of
+ * the system answers.  Changes no force and no step state. */
+int hc_wave_kinematics(hc_ctx* ctx, const hc_wave_kinematics_opts* o, int n_points, const double* xyz,
+                       int n_times, const double* t, double* eta, double* vel, double* acc);
 
 /* ------------------------------------------------------------------------------------------------
  * Synthetic many-body inputs generated directly in HBM (benchmark configurations C3/C4 of SURVEY 8d;
