@@ -54,7 +54,8 @@ class ProfileStats(C.Structure):
                 ("multi_doorbell_offset_last", C.c_double), ("multi_doorbell_offset_sum", C.c_double), ("multi_calls", C.c_longlong),
                 ("slot_state_steps", C.c_longlong), ("wide_fused_steps", C.c_longlong),
                 ("schedule_blocks_ahead", C.c_longlong), ("schedule_blocks_at_start", C.c_longlong), ("ring_grows_for_pass", C.c_longlong),
-                ("hot_steps", C.c_longlong)]
+                ("hot_steps", C.c_longlong), ("tail_launches", C.c_longlong), ("tail_seconds", C.c_double),
+                ("tail_bytes", C.c_double), ("tail_blocks", C.c_longlong)]
 
 
 class InitStats(C.Structure):
@@ -114,6 +115,7 @@ SIGNATURES = {
     "hc_compute_waves": (C.c_int, [C.c_void_p, C.c_double, c_double_p]),
     "hc_set_lookahead": (C.c_int, [C.c_void_p, C.c_int]),
     "hc_set_pass_schedule": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
+    "hc_set_radiation_tail": (C.c_int, [C.c_void_p, C.c_int]),
     "hc_get_schedule": (C.c_int, [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]),
     "hc_direct_dispatch_active": (C.c_int, [C.c_void_p]),
     "hc_dispatch_mode_reason": (C.c_char_p, [C.c_void_p]),

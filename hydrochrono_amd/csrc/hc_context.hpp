@@ -141,7 +141,7 @@ struct ExGroup {
 enum WaveKind { kWaveNone = 0, kWaveRegular = 1, kWaveIrregular = 2, kWaveSpectral = 3 };
 
 // One timed kernel launch (HIP events before / after it on the stream it was launched on).
-enum EventKind { kEvConvPlain = 0, kEvPass = 1, kEvStep = 2, kEvScatter = 3, kEvConvExc = 4, kEvMiniPass = 5 };
+enum EventKind { kEvConvPlain = 0, kEvPass = 1, kEvStep = 2, kEvScatter = 3, kEvConvExc = 4, kEvMiniPass = 5, kEvTail = 6 };
 struct EventPair {
     hipEvent_t a = nullptr, b = nullptr;
     int kind = 0;
@@ -251,6 +251,7 @@ struct hc_ctx {
     // GEMV configuration + scratch
     int chunk_gp = 0, nchunks_rad = 0, chunk_gp_ex = 0, nchunks_ex = 0, ngp_ex = 0;
     int chunk_gp_block = 0, nchunks_block = 0;
+    int chunk_gp_head = 0;  // chunk length of the head pass of the spectral tail (lags below kTailP)
     hc::DeviceBuffer<double> d_partials, d_partials_block, d_P, d_E;
     hc::DeviceBuffer<double> d_near_partials;  // [16][Dpad] slice partials of near_split_kernel (wide systems)
     hc::DeviceBuffer<int> d_tile_counter;      // [ntiles] arrival counters of wide_step_kernel (zero between launches)
@@ -279,6 +280,19 @@ struct hc_ctx {
     std::chrono::steady_clock::time_point t_multi_end{};  // (kept on the group's first context) end of the last hc_step_multi
     bool have_t_multi_end = false;
     hc::AheadPass ahead;
+    // spectral radiation tail (hc_tail.hpp, hc_pass.cpp): lags s >= kTailP of the at-start pass by partitioned FFT convolution
+    int radiation_tail = 1;  // hc_set_radiation_tail: 0 always the full pass, 1 the tail where eligible
+    struct SpectralTail {
+        bool khat_ok = false;     // d_khat holds the transform of the current K (or tapered K) and widths
+        bool active = false;      // a superblock is running: its tail rows are in d_tail_out
+        int k = 0, Q = 0;         // blocks of the superblock issued so far / per superblock
+        int cur = 0;              // half of d_tail_yfar that belongs to the running superblock
+        unsigned far_cur = 0, far_next = 0;  // far chunks done for the running / the next superblock (bit k: chunk k)
+        unsigned long long serial = 0;       // plan serial of the last block that took its rows from the tail
+        double t0 = 0.0, dt = 0.0;           // first step of the superblock, step
+    } spec;
+    hc::DeviceBuffer<double> d_khat, d_tail_xw, d_tail_yfar, d_tail_out, d_tail_tw;
+    hc::DirectKernel dk_tail_fwd, dk_tail_gemv, dk_tail_inv;
     hc::DeviceBuffer<double> d_partials_far;  // partial sums of the pass in the making (the short passes keep d_partials_block)
     hc::DeviceBuffer<double> d_partials_next; // ... and of the short passes towards the next block when they run on the pass lane
     // The pass lane (lane 2 of the direct queue): passes in the making run there BESIDE the steps of lane 0, on a queue that leaves

@@ -144,10 +144,13 @@ struct PassSetup {
     bool exc_block = false;
     double rad_once = 0.0, exc_once = 0.0, bytes_steps = 0.0;
 };
-PassSetup make_pass(hc_ctx* c, bool with_exc, bool next_block);
+PassSetup make_pass(hc_ctx* c, bool with_exc, bool next_block, bool head_only = false);
 void issue_pass_chunks(hc_ctx* c, const PassSetup& ps, int first, int last, bool with_items, hipStream_t stream, bool direct, int lane = 0);
-void issue_pass_reduce(hc_ctx* c, const PassSetup& ps, double* P, double* E, hipStream_t stream, bool direct, int lane = 0);
-void launch_pass(hc_ctx* c, hipStream_t stream, bool with_exc, bool direct = false);
+void issue_pass_reduce(hc_ctx* c, const PassSetup& ps, double* P, double* E, hipStream_t stream, bool direct, int lane = 0, const double* tail = nullptr,
+                       int tail_j0 = 0);
+void launch_pass(hc_ctx* c, hipStream_t stream, bool with_exc, bool direct = false, bool spec_goes_on = false);
+void spec_drop(hc_ctx* c, bool k_changed);
+void spec_build_khat(hc_ctx* c);
 void launch_mini_pass(hc_ctx* c, int i0, hipStream_t stream, bool direct, int next_kw = 0, int lane = 0);
 void ahead_drop(hc_ctx* c);
 void ahead_issue_slice(hc_ctx* c, hipStream_t stream, bool direct);

@@ -1303,6 +1303,7 @@ __global__ void __launch_bounds__(256) reduce_block_kernel(ReduceArgs a) {
             const int j = out / a.Dpad;
             if (!exc && j < a.j_cnt) a.P[out + (size_t)a.j_off * a.Dpad] += v;
         } else {
+            if (!exc && a.tail) v += a.tail[(size_t)(a.tail_j0 + out / a.Dpad) * a.Dpad + out % a.Dpad];
             (exc ? a.E : a.P)[out] = v;
         }
     }
@@ -2762,3 +2763,5 @@ void launch_synth_rirf(double* d_K, int ntiles, int ngp, int Dloc, int D, int S,
 }
 
 }  // namespace hc
+
+#include "hc_tail_kernels.hpp"

@@ -5,6 +5,7 @@
 #include <cstddef>
 
 #include "hc_limits.hpp"
+#include "hc_tail.hpp"
 
 namespace hc {
 
@@ -327,10 +328,12 @@ struct ReduceArgs {
     int accumulate, j_off, j_cnt;
     int rad_first;  // first radiation chunk to add (short passes that start past IRF sample 0)
     // narrow short pass (BlockArgs::mini_narrow): the partials of chunk c are [16][Dpad] and belong to steps jbase[c] .. jbase[c] + 15
-    int narrow, pad_;
+    int narrow;
+    int tail_j0;         // spectral radiation tail (hc_tail.hpp): row j of P gets tail[tail_j0 + j] as its last addend
     unsigned char jbase[kMiniChunks];
+    const double* tail;  // [kTailP][Dpad] (null: no tail)
 };
-static_assert(sizeof(ReduceArgs) == 72 + kMiniChunks, "kernarg layout of reduce_block_kernel");
+static_assert(sizeof(ReduceArgs) == 80 + kMiniChunks && kMiniChunks % 8 == 0, "kernarg layout of reduce_block_kernel");
 
 struct TaperArgs {
     Panel Kraw;
@@ -414,5 +417,48 @@ void launch_ring_transpose(const double* d_ring_v, int Hcap, int HcapT, int D, d
 // synthetic many-body coefficient generator: fills the whole panel matrix (padding = 0)
 void launch_synth_rirf(double* d_K, int ntiles, int ngp, int Dloc, int D, int S, int row0, double dt, unsigned long long seed, double rho,
                        hipStream_t stream);
+
+// ---- spectral radiation tail (hc_tail.hpp; kernels: hc_tail_kernels.hpp) ----
+struct TailKhatArgs {
+    Panel K;              // the radiation panel the pass reads (K or the tapered K)
+    const double* width;  // [S]
+    const double* tw;     // [kTailN][2]
+    double* Khat;         // [kTailBins][Dloc][NP * D] complex
+    int Dloc, D, S, NP;
+};
+
+struct TailFwdArgs {
+    const double* ring_vT;  // [D][HcapT]
+    int HcapT, Hcap, head;  // head: ring slot of the newest sample (step m0 - 1)
+    int D, S, NP;
+    const double* tw;
+    double* Xw;             // [kTailBins][NP * D] complex
+};
+
+struct TailGemvArgs {
+    const double* Khat;  // [kTailBins][Dloc][ncols] complex
+    const double* Xw;    // [kTailBins][ncols] complex
+    const double* Yin;   // [kTailBins][Dloc] complex, added first (null: nothing)
+    double* Yout;        // [kTailBins][Dloc] complex (may be Yin: each element is read and written by the same work item)
+    int Dloc, ncols;
+    int bin_lo, bin_hi;
+    int col_lo, col_hi;  // Khat columns of the sum
+    int x_shift;         // Xw column = Khat column + x_shift
+    int rows_per_wg;     // a multiple of 4 (one wave per row at a time)
+};
+
+struct TailInvArgs {
+    const double* Y;  // [kTailBins][Dloc] complex
+    const double* tw;
+    double* tail;     // [kTailP][Dpad]
+    int Dloc, Dpad;
+};
+constexpr int kTailGemvRows = 32;  // rows of one tail_gemv workgroup (a multiple of 16: four waves of four-row batches)
+int tail_gemv_lds_bytes(const TailGemvArgs& g);
+int tail_gemv_grid(const TailGemvArgs& g);
+void launch_tail_khat(const TailKhatArgs& a, hipStream_t s);
+void launch_tail_fwd(const TailFwdArgs& a, hipStream_t s);
+void launch_tail_gemv(const TailGemvArgs& a, hipStream_t s);
+void launch_tail_inv(const TailInvArgs& a, hipStream_t s);
 
 }  // namespace hc

@@ -198,6 +198,7 @@ int history_push(hc_ctx* c, double t) {
         // while they are overwritten; a rewind is rare, so it is simply waited for)
         pass_lane_drain(c);
         c->ahead.active = false;
+        c->spec.active  = false;  // the samples the running superblock's tail was made from may be among those replaced
         c->plan.valid  = false;
         c->plan.misses = 0;
         c->rewinds++;
@@ -240,6 +241,10 @@ void profile_account(hc_ctx* c, int kind, double sec, double waves_share) {
             c->prof.mini_pass_launches += 1;
             c->prof.radiation_seconds += sec;
             break;
+        case hc::kEvTail:  // spectral radiation tail: transforms and frequency-domain products
+            c->prof.tail_seconds += sec;
+            c->prof.radiation_seconds += sec;
+            break;
         default:  // excitation-only convolution launch
             c->prof.waves_seconds += sec;
             break;
@@ -274,7 +279,7 @@ void profile_begin_step(hc_ctx* c) {
 
 // Event pair around one launch, or null.  The look-ahead pass (one per block) is timed whatever the stride.
 hc::EventPair* ev_begin(hc_ctx* c, int kind, hipStream_t stream, double waves_share) {
-    if (!c->profiling || !(c->sample_this_step || kind == hc::kEvPass)) return nullptr;
+    if (!c->profiling || !(c->sample_this_step || kind == hc::kEvPass || kind == hc::kEvTail)) return nullptr;
     if (c->events_used == c->events.size()) {
         if (c->events.size() >= kEventPoolMax) return nullptr;
         hc::EventPair ev;
@@ -301,7 +306,7 @@ bool profiling_tool_attached() {
 }
 
 // direct dispatches: the tag to time a launch with (-1: not timed), same sampling rule as ev_begin
-int direct_tag(const hc_ctx* c, int kind) { return (c->profiling && (c->sample_this_step || kind == hc::kEvPass)) ? kind : -1; }
+int direct_tag(const hc_ctx* c, int kind) { return (c->profiling && (c->sample_this_step || kind == hc::kEvPass || kind == hc::kEvTail)) ? kind : -1; }
 
 void ev_end(hc::EventPair* ev, hipStream_t stream) {
     if (ev) HC_HIP(hipEventRecord(ev->b, stream));
@@ -401,6 +406,14 @@ void choose_conv_config(hc_ctx* c) {
     bgps                = std::max<long long>(16, ((bgps + 15) / 16) * 16);  // whole 16-group sub-tiles
     c->chunk_gp_block   = static_cast<int>(bgps);
     c->nchunks_block    = static_cast<int>((c->ngp + bgps - 1) / bgps);
+    // The head pass of the spectral tail (hc_pass.cpp: the IRF samples below kTailP only) keeps the round of workgroups of the full pass:
+    // as many chunks over a fraction of the columns (a function of the column count only, like every chunk length).
+    {
+        const long long ngp_head = (static_cast<long long>(hc::kTailP) * c->D + 7) / 8;
+        const long long nch      = std::max<long long>(1, c->nchunks_block);
+        long long hg             = std::min<long long>((ngp_head + nch - 1) / nch, bgps);
+        c->chunk_gp_head         = static_cast<int>(std::max<long long>(16, ((hg + 15) / 16) * 16));
+    }
 }
 
 // Chunk length of a pass that is issued in slices (pass schedule "one block ahead").  The pass of a block is ONE round of long-lived
@@ -588,6 +601,7 @@ void ensure_processed(hc_ctx* c) {
     HC_HIP(hipStreamSynchronize(c->stream));
     c->proc_ready = true;
     c->plan.valid = false;
+    spec_drop(c, true);
     if (c->taper.export_plot_csv) export_taper_csv(c, effective);
 }
 
@@ -730,6 +744,12 @@ void setup_direct(hc_ctx* c) {
     c->step_hot = c->slot_state && c->dk_step_hot[0].ok() && c->dk_step_hot[1].ok() && HC_TUNE_INT("HC_STEP_HOT", 1) != 0;
     c->step_halves = HC_TUNE_INT("HC_STEP_HALVES", 1) == 2 ? 2 : 1;
     c->dk_reduce   = q->find("reduce_block_kernelE");
+    c->dk_tail_fwd  = q->find("tail_fft_fwdENS_11TailFwdArgsE");  // optional: without them the tail goes through HIP launches
+    c->dk_tail_gemv = q->find("tail_gemvENS_12TailGemvArgsE");
+    c->dk_tail_inv  = q->find("tail_fft_invENS_11TailInvArgsE");
+    if (c->dk_tail_fwd.kernarg != sizeof(hc::TailFwdArgs) || c->dk_tail_gemv.kernarg != sizeof(hc::TailGemvArgs) ||
+        c->dk_tail_inv.kernarg != sizeof(hc::TailInvArgs) || c->dk_tail_fwd.priv || c->dk_tail_gemv.priv || c->dk_tail_inv.priv)
+        c->dk_tail_fwd = c->dk_tail_gemv = c->dk_tail_inv = hc::DirectKernel{};
     c->dk_added_mass = q->find("added_mass_mv_tagged_kernelE");  // optional: hc_added_mass_mv falls back to a HIP launch
     {   // the plain per-step convolution of this context's tiling; optional: without it plain steps go through HIP launches
         hc::StepArgs a{};

@@ -223,6 +223,8 @@ void enqueue_tail(hc_ctx* c) {
     if (plan_now) {
         const unsigned long long ended = c->plan_serial;
         const bool clean_end           = block && m == c->lookahead;
+        // the superblock of the spectral tail goes on only from a block that took its rows from it and was stepped to its end
+        const bool spec_goes_on        = clean_end && c->spec.active && c->spec.serial == ended;
         if (block) c->plan.misses = 0;  // a block was consumed completely
         // Rows made ahead exist for the block that starts now: it is planned with this step's sample as its own grid index 0 (the
         // short passes that completed the rows stopped one sample earlier), and takes the rows if the plan comes out as predicted.
@@ -244,11 +246,12 @@ void enqueue_tail(hc_ctx* c) {
                 c->prof.ahead_blocks += 1;
                 if (c->plan.scat_hi[0] >= c->plan.scat_lo[0]) launch_scatter_of(c, 0, bs, direct);  // this step's sample -> the block's steps
             } else {
-                launch_pass(c, bs, c->tail.waves, direct);
+                launch_pass(c, bs, c->tail.waves, direct, spec_goes_on);
             }
             ahead_begin(c, bs, c->tail.waves, direct);
         } else {
             ahead_drop(c);
+            c->spec.active = false;
         }
     }
     if (bs != stream) {
@@ -1358,6 +1361,7 @@ int hc_set_lookahead(hc_ctx* c, int steps) {
     alloc_partials(c);
     c->plan      = hc::Plan{};
     c->ahead.active = false;
+    c->spec.active  = false;
     HC_API_END(c)
 }
 
@@ -1456,6 +1460,14 @@ int hc_tuning_time_pass(hc_ctx* c, int depth, int reps, double* mean_us, double*
 }
 #endif
 
+int hc_set_radiation_tail(hc_ctx* c, int mode) {
+    HC_API_BEGIN(c)
+    require(mode == 0 || mode == 1, HC_ERR_INVALID, "mode must be 0 (full pass) or 1 (spectral tail where eligible)");
+    c->radiation_tail = mode;
+    c->spec.active    = false;
+    HC_API_END(c)
+}
+
 int hc_set_pass_schedule(hc_ctx* c, int one_block_ahead, int slices) {
     HC_API_BEGIN(c)
     require(c->finalized, HC_ERR_INVALID, "hc_finalize has not been called");
@@ -1464,6 +1476,7 @@ int hc_set_pass_schedule(hc_ctx* c, int one_block_ahead, int slices) {
     reset_schedule_state(c);
     c->pass_slices  = slices > 0 ? std::min(slices, hc::kDepthDefault - 1) : default_pass_slices(c);
     c->ahead.active = false;
+    c->spec.active  = false;
     alloc_partials(c);
     c->plan = hc::Plan{};
     if (pass_ahead_possible(c) && c->lookahead > 0) (void)pass_lane_ready(c);  // (created and self-tested here, off the step path)
@@ -1528,6 +1541,7 @@ int hc_set_history(hc_ctx* c, int n, const double* times, const double* vel) {
     HC_HIP(hipStreamSynchronize(c->stream));  // tt / vv are released on return
     c->head      = n - 1;
     c->plan      = hc::Plan{};
+    c->spec.active = false;
     c->ahead.active = false;
     // No step has been evaluated at times[0], so the per-time cache holds nothing (a step at exactly that time is the
     // reference's duplicate-time error, raised by the history push).

@@ -266,6 +266,11 @@ class HydroForces:
         mode = -1 if one_block_ahead is None or int(one_block_ahead) < 0 else int(bool(one_block_ahead))
         self._chk(self.lib.hc_set_pass_schedule(self.ctx, mode, int(slices)))
 
+    def set_radiation_tail(self, mode):
+        """hc_set_radiation_tail: 1 (default) = lags from 256 on by partitioned FFT convolution where eligible (step = IRF spacing,
+        full history, pass at block start, 6N < 1024, S >= 512); 0 = the full pass always."""
+        self._chk(self.lib.hc_set_radiation_tail(self.ctx, int(mode)))
+
     def schedule(self):
         """hc_get_schedule: {"lookahead": 0 | 16 | 32 (what hc_set_lookahead made of its argument), "pass_schedule": -1 adaptive | 0 | 1,
         "ahead_now": the adaptive rule's current answer, "slices"}."""

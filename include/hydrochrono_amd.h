@@ -293,6 +293,14 @@ int hc_set_lookahead(hc_ctx* ctx, int steps);
  * REPRODUCIBILITY: with the schedule pinned (0 or 1) a run is bitwise repeatable whatever the caller's timing; under the adaptive
  * default it is repeatable to rounding ("Reproducibility"). */
 int hc_set_pass_schedule(hc_ctx* ctx, int one_block_ahead, int slices);
+/* Spectral radiation tail.  mode 1 (the default): where the step equals the IRF spacing, the history covers the IRF window on that
+ * grid, the look-ahead depth is 16 or 32 and the pass of a block runs at block start, the lags from 256 on (IRF samples s >= 256) of the
+ * pass come from a partitioned FFT convolution made once per 256 steps (a superblock), and the pass itself streams the first 256
+ * samples of K only.  Systems with 6N >= 1024 and IRFs of fewer than 512 samples keep the full pass.  The transform of K it needs
+ * (complex FP64, 2 x (S - 256) x 6N x 6N_loc x 8 bytes) is made at the first superblock and again after any change of K, the
+ * taper or the convolution mode.  Results are those of mode 0 up to rounding.  mode 0: the full pass always.  Part of the
+ * configuration: the row shards of one array must use the same mode. */
+int hc_set_radiation_tail(hc_ctx* ctx, int mode);
 /* What is in force: the look-ahead depth (0, 16 or 32: hc_set_lookahead clamps what it is given to what this build of the library
  * holds), the pass schedule (-1 adaptive, 0 at block start, 1 one block ahead), under the adaptive schedule the rule's current answer
  * (1: the next pass goes one block ahead), and the slice count of a pass made ahead.  Any pointer may be NULL.  For hosts that drive
@@ -382,6 +390,13 @@ typedef struct hc_profile_stats {
                                     * history while the block's steps push their samples (steps well below the IRF spacing) */
     long long hot_steps;           /* of slot_state_steps: block steps that went to the step kernel of the common case (step_hot_kernel: the
                                     * step's own IRF samples against its own velocity only, no plain partials, no spectral wave mode) */
+    /* spectral radiation tail (hc_set_radiation_tail): launches of its kernels (forward transforms, frequency-domain products,
+     * inverse transforms), their GPU time where it was measured, the bytes they move, and the look-ahead blocks whose lags from
+     * 256 on came from it.  block_kernel_* above then count the head pass (lags below 256) alone. */
+    long long tail_launches;
+    double tail_seconds;
+    double tail_bytes;
+    long long tail_blocks;
 } hc_profile_stats;
 /* HIP events around the kernels of every `on`-th step (on = 1: every step; 0: off, the default), and around every
  * look-ahead pass (one per block) whatever the stride.  Event records perturb the launch stream by a few

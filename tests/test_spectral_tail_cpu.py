@@ -1,0 +1,103 @@
+"""CPU test of the spectral radiation tail's index arithmetic (hydrochrono_amd/csrc/hc_tail.hpp, host-only C++): an overlap-save
+convolution in NumPy that takes its windows, partitions, K-hat / X-hat columns and far-chunk bin ranges from the header reproduces
+the direct lag sum  sum_{s >= P} G_s v_{m-s}  for the P steps of a superblock -- this superblock's near partition from this
+superblock's windows, the far partitions from the windows of the superblock BEFORE it (as the far chunks make them), and the
+fallback that makes the far part from this superblock's own windows.  S a multiple of P and not, both look-ahead depths."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+@pytest.fixture(scope="module")
+def dump_exe(tmp_path_factory):
+    exe = str(tmp_path_factory.mktemp("tail") / "tail_index_dump")
+    subprocess.run(["g++", "-std=c++17", "-O1", "-Wall", "-Werror", os.path.join(ROOT, "tests", "cpp", "tail_index_dump.cpp"), "-o", exe], check=True)
+    return exe
+
+
+def load(exe, S, L, D):
+    out = subprocess.run([exe, str(S), str(L), str(D)], capture_output=True, text=True, check=True).stdout.splitlines()
+    head = out[0].split()
+    g = dict(zip(head[0::2], map(int, head[1::2])))
+    g["chunks"] = [tuple(map(int, ln.split()[2:])) for ln in out if ln.startswith("chunk ")]
+    win = {}
+    cols = {}
+    for ln in out:
+        f = ln.split()
+        if f[0] == "win":
+            win[(int(f[1]), int(f[2]))] = (int(f[3]), int(f[4]))
+        elif f[0] == "col":
+            cols[(int(f[1]), int(f[2]))] = int(f[3])
+        elif f[0] == "shift":
+            g["shift_cur"], g["shift_next"] = int(f[1]), int(f[2])
+    g["win"], g["cols"] = win, cols
+    return g
+
+
+def windows(g, S, D, vhist):
+    """X-hat [bins][NP*D] of the windows at a superblock start; vhist[b] = sample b behind the newest (b = 0: step m0 - 1)."""
+    P, N, NP = g["P"], g["N"], g["NP"]
+    X = np.zeros((NP, D, N))
+    for a in range(1, NP + 1):
+        for k in range(N):
+            back, live = g["win"][(a, k)]
+            if live:
+                X[a - 1, :, k] = vhist[back]
+    Xh = np.fft.rfft(X, axis=-1)  # [NP][D][bins]
+    return np.transpose(Xh, (2, 0, 1)).reshape(Xh.shape[2], NP * D)
+
+
+def khat(g, G, D):
+    """K-hat [bins][rows][NP*D] from G[s][row][col] (S lags)."""
+    P, N, NP = g["P"], g["N"], g["NP"]
+    S, rows = G.shape[0], G.shape[1]
+    Kh = np.zeros((g["bins"], rows, NP * D), dtype=complex)
+    for p in range(1, NP + 1):
+        h = np.zeros((rows, D, N))
+        seg = G[p * P:min(S, (p + 1) * P)]  # [r][row][col]
+        h[:, :, :seg.shape[0]] = np.transpose(seg, (1, 2, 0))
+        H = np.fft.rfft(h, axis=-1)  # [row][col][bins]
+        for c in range(D):
+            Kh[:, :, g["cols"][(p, c)]] = H[:, c, :].T
+    return Kh
+
+
+def gemv(Kh, X, bins, col_lo, col_hi, shift):
+    lo, hi = bins
+    return np.einsum("brc,bc->br", Kh[lo:hi, :, col_lo:col_hi], X[lo:hi, col_lo + shift:col_hi + shift])
+
+
+@pytest.mark.parametrize("S", [1024, 700, 512])
+@pytest.mark.parametrize("L", [16, 32])
+def test_overlap_save_with_header_indices_equals_direct_sum(dump_exe, S, L):
+    D, rows = 6, 4
+    g = load(dump_exe, S, L, D)
+    P, NP, Q = g["P"], g["NP"], g["Q"]
+    assert NP == -(-S // P) - 1 and Q * L == P
+    assert g["chunks"][0][0] == 0 and g["chunks"][-1][1] == g["bins"]
+    assert len(g["chunks"]) == Q - 1 and all(g["chunks"][i][1] == g["chunks"][i + 1][0] for i in range(Q - 2))
+    rng = np.random.default_rng(S + L)
+    G = rng.standard_normal((S, rows, D))
+    T = 3 * P + S  # samples 0 .. T-1; superblock q starts at step m0
+    v = rng.standard_normal((T, D))
+    Kh = khat(g, G, D)
+    m_prev, m0 = T - 2 * P, T - P  # two consecutive superblocks
+    X_prev = windows(g, S, D, v[m_prev - 1::-1])
+    X_cur = windows(g, S, D, v[m0 - 1::-1])
+    Y_far = np.zeros((g["bins"], rows), dtype=complex)
+    for lo, hi in g["chunks"]:  # made during the superblock before, one chunk per block after its first
+        Y_far[lo:hi] = gemv(Kh, X_prev, (lo, hi), D, NP * D, g["shift_next"]) if NP > 1 else 0.0
+    Y_fallback = gemv(Kh, X_cur, (0, g["bins"]), D, NP * D, g["shift_cur"]) if NP > 1 else 0.0
+    Y_near = gemv(Kh, X_cur, (0, g["bins"]), 0, D, g["shift_cur"])
+    for Yf in (Y_far, Y_fallback):
+        y = np.fft.irfft(Yf + Y_near, n=g["N"], axis=0)[P:]  # [j][row]
+        direct = np.zeros((P, rows))
+        for j in range(P):
+            m = m0 + j
+            for s in range(P, S):
+                direct[j] += G[s] @ v[m - s]
+        assert np.max(np.abs(y - direct)) <= 1e-11 * np.max(np.abs(direct))
