@@ -18,6 +18,6 @@ import os as _os
 if _os.environ.get("HC_QUEUE_DEV_MEM", "0") not in ("", "0"):
     _os.environ.setdefault("HSA_ALLOCATE_QUEUE_DEV_MEM", "1")
 
-from .hydro import HydroError, HydroForces  # noqa: F401,E402
+from .hydro import HydroError, HydroForces, read_eta_file  # noqa: F401,E402
 
-__all__ = ["HydroForces", "HydroError"]
+__all__ = ["HydroForces", "HydroError", "read_eta_file"]

@@ -92,6 +92,8 @@ SIGNATURES = {
     "hc_set_wave_regular": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double]),
     "hc_irregular_wave_params_default": (None, [C.POINTER(IrregularWaveParams)]),
     "hc_set_wave_irregular": (C.c_int, [C.c_void_p, C.POINTER(IrregularWaveParams)]),
+    "hc_set_wave_irregular_eta": (C.c_int, [C.c_void_p, C.POINTER(IrregularWaveParams), c_double_p, c_double_p, C.c_int]),
+    "hc_read_eta_file": (C.c_int, [C.c_char_p, c_double_p, c_double_p, C.c_int, c_int_p]),
     "hc_set_eta_synthesis": (C.c_int, [C.c_void_p, C.c_int]),
     "hc_set_wave_irregular_spectral": (C.c_int, [C.c_void_p, C.POINTER(IrregularWaveParams)]),
     "hc_set_convolution_mode": (C.c_int, [C.c_void_p, C.c_int]),

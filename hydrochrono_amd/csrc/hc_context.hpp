@@ -236,7 +236,12 @@ struct hc_ctx {
     std::vector<hc::ExGroup> ex_groups;             // per-body excitation-IRF grids (src/wave_types.cpp:432-459), see hc_set_wave_irregular
     std::vector<int> ex_group_of;                   // [N]
     std::vector<double> spec_f, spec_S, spec_df, spec_phase, spec_k;
-    std::vector<double> eta_t, eta;
+    std::vector<double> eta_t, eta;  // the table the kernels interpolate in ([nt])
+    // imported record (hc_set_wave_irregular_eta): eta_t / eta above are the record extended by zeros (hc_eta_record.hpp), the record
+    // itself is kept as given for the queries; eta_h = its mean spacing, the kernels' search hint in place of simulation_dt
+    bool eta_record = false;
+    std::vector<double> rec_t, rec_eta;
+    double eta_h = 0.0;
     hc::DeviceBuffer<double> d_kex, d_ex_tau, d_ex_width, d_eta_t, d_eta;
     hc::DeviceBuffer<double> d_spec_mag, d_spec_phase, d_spec_amp, d_spec_omega, d_spec_phi;  // spectral (component-sum) mode
     unsigned long long wave_serial = 0;  // counts the hc_set_wave_* calls (voids the kinematics table below)

@@ -113,6 +113,19 @@ std::string library_dir();
 bool direct_selftest_rewrites(hc_ctx* c, hc::DirectQueue* q, int lane, bool* abandon);
 void setup_direct(hc_ctx* c);
 
+// ---- hc_setup.cpp: the excitation side of an irregular wave model (hc_set_wave_irregular, hc_set_wave_irregular_eta) ----
+struct ExcitationGrid {
+    std::vector<hc::ExGroup> groups;
+    std::vector<int> group_of;               // [N]
+    std::vector<double> tau, width, vals;    // [L], [L], [Dloc][L]
+    int L = 0;
+    double tau_min = 0.0, tau_max = 0.0;     // min / max over the groups' ends and 0 (CreateFreeSurfaceElevation's scan)
+};
+ExcitationGrid resample_excitation(hc_ctx* c, double dt);  // groups + ResampleIRF on a grid of step dt
+void upload_excitation(hc_ctx* c, const ExcitationGrid& ex);  // Kex in panel layout, ex_tau, ex_width
+void commit_excitation(hc_ctx* c, ExcitationGrid& ex);  // into the context; wave_kind = irregular, launch configuration
+void drop_lookahead_excitation(hc_ctx* c);
+
 // ---- hc_step.cpp ----
 struct StepFlags {
     bool hs = true, rad = true, waves = true;

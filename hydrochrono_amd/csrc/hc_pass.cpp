@@ -21,7 +21,7 @@ StepViews make_views(const hc_ctx* c) {
     v.ex.eta_t    = c->d_eta_t.p;
     v.ex.eta      = c->d_eta.p;
     v.ex.nt       = c->nt;
-    v.ex.eta_dt   = irregular ? c->irr.simulation_dt : 1.0;
+    v.ex.eta_dt   = irregular ? (c->eta_record ? c->eta_h : c->irr.simulation_dt) : 1.0;  // search hint: the table's spacing
     v.ex.eta_t0   = (irregular && !c->eta_t.empty()) ? c->eta_t.front() : 0.0;
     return v;
 }

@@ -42,7 +42,7 @@ int hc_get_sizes(hc_ctx* c, int* N, int* n_local, int* S, int* L, int* nf, int* 
     if (S) *S = c->S;
     if (L) *L = c->L;
     if (nf) *nf = c->nf;
-    if (nt) *nt = c->nt;
+    if (nt) *nt = c->eta_record ? static_cast<int>(c->rec_t.size()) : c->nt;  // an imported record: as given, without its zero extension
     if (H) *H = static_cast<int>(c->times.size());
     if (Hcap) *Hcap = c->Hcap;
     HC_API_END(c)
@@ -131,8 +131,10 @@ int hc_get_spectrum(hc_ctx* c, double* f, double* S, double* df, double* phase, 
 int hc_get_eta_table(hc_ctx* c, double* t, double* eta) {
     HC_API_BEGIN(c)
     require(c->wave_kind == hc::kWaveIrregular || c->wave_kind == hc::kWaveSpectral, HC_ERR_INVALID, "no irregular wave model attached");
-    if (t) std::copy(c->eta_t.begin(), c->eta_t.end(), t);
-    if (eta) std::copy(c->eta.begin(), c->eta.end(), eta);
+    const std::vector<double>& tt = c->eta_record ? c->rec_t : c->eta_t;
+    const std::vector<double>& ee = c->eta_record ? c->rec_eta : c->eta;
+    if (t) std::copy(tt.begin(), tt.end(), t);
+    if (eta) std::copy(ee.begin(), ee.end(), eta);
     HC_API_END(c)
 }
 

@@ -459,6 +459,7 @@ int hc_export_irregular_inputs_h5(hc_ctx* c, const char* path) {
     HC_API_BEGIN(c)
     require(path, HC_ERR_INVALID, "null path");
     require(c->wave_kind == hc::kWaveIrregular || c->wave_kind == hc::kWaveSpectral, HC_ERR_INVALID, "no irregular wave model attached");
+    require(!c->eta_record, HC_ERR_INVALID, "the irregular wave model is an imported eta record: it has no spectrum to export");
     using export_fn_t = int (*)(const char*, const double*, const double*, int, const double*, const double*, int, char*, size_t);
     const export_fn_t fn = reinterpret_cast<export_fn_t>(bemio_symbol("hc_bemio_export_irregular"));
     // what SimulationExporter::WriteIrregularInputs writes (src/simulation_exporter.cpp:365-393): spectrum and free-surface table
@@ -612,17 +613,126 @@ int hc_finalize(hc_ctx* c) {
     HC_API_END(c)
 }
 
+}  // extern "C"
+
+namespace hc {
+namespace detail {
+// Excitation-IRF time grids.  The reference keeps one grid per body (ex_irf_time_sampled_[b], src/wave_types.cpp:432-459) and
+// resamples each on its own (:572-606).  BEMIO writes one grid per file, so bodies normally share it; bodies with the same
+// grid (within 1e-10, the tolerance the reference applies to the radiation grids) form a group, and the columns of Kex are
+// the groups' resampled grids one after the other -- a body's rows are non-zero in the columns of its own group only, so
+// one launch still serves all bodies.  Groups are formed over ALL bodies (not only the local ones): the column layout, and
+// with it the summation order, is the same in every row shard of the system.
+ExcitationGrid resample_excitation(hc_ctx* c, double dt) {
+    ExcitationGrid ex;
+    std::vector<hc::ExGroup>& groups = ex.groups;
+    std::vector<int>& group_of       = ex.group_of;
+    group_of.assign(c->N, -1);
+    for (int b = 0; b < c->N; ++b) {
+        if (!c->bodies[b].have_exirf) {
+            // a row-sharded context whose caller ingested its own bodies only: the other bodies' grids are unknown here
+            require(!is_local(c, b), HC_ERR_INVALID, "excitation IRF missing for a local body");
+            continue;
+        }
+        const auto& tb = c->bodies[b].exirf_t;
+        require(tb.size() >= 2, HC_ERR_INVALID, "excitation IRF with fewer than two samples");
+        for (size_t g = 0; g < groups.size() && group_of[b] < 0; ++g) {
+            const auto& tg = c->bodies[groups[g].first_body].exirf_t;
+            bool same = tg.size() == tb.size();
+            for (size_t j = 0; j < tb.size() && same; ++j) same = std::fabs(tb[j] - tg[j]) <= 1e-10;
+            if (same) group_of[b] = static_cast<int>(g);
+        }
+        if (group_of[b] < 0) {
+            hc::ExGroup g;
+            g.first_body = b;
+            group_of[b]  = static_cast<int>(groups.size());
+            groups.push_back(g);
+        }
+    }
+    const auto t_call = std::chrono::steady_clock::now();
+    // ResampleIRF (src/wave_types.cpp:572-606), per group
+    int L = 0;
+    for (auto& g : groups) {
+        const auto& t_old = c->bodies[g.first_body].exirf_t;
+        const double t0 = t_old.front(), t1 = t_old.back();
+        g.L   = static_cast<int>(std::ceil((t1 - t0) / dt));
+        require(g.L >= 2, HC_ERR_INVALID, "excitation IRF resamples to fewer than two points");
+        g.off = L;
+        const std::vector<double> tg = hc::linspaced(g.L, t0, t1), wg = hc::trapezoid_widths(tg);
+        g.tau_front = tg.front();
+        g.tau_back  = tg.back();
+        ex.tau.insert(ex.tau.end(), tg.begin(), tg.end());
+        ex.width.insert(ex.width.end(), wg.begin(), wg.end());
+        L += g.L;
+    }
+    ex.L = L;
+    ex.vals.assign(static_cast<size_t>(c->Dloc) * L, 0.0);
+    for (int bl = 0; bl < c->nloc; ++bl) {
+        const auto& bd = c->bodies[c->b0 + bl];
+        const hc::ExGroup& g = groups[group_of[c->b0 + bl]];
+        const auto r = hc::resample_cubic_bspline6(bd.exirf_f, static_cast<int>(bd.exirf_t.size()), g.L);
+        for (int d = 0; d < 6; ++d)
+            std::copy(r.begin() + static_cast<size_t>(d) * g.L, r.begin() + static_cast<size_t>(d + 1) * g.L,
+                      ex.vals.begin() + static_cast<size_t>(6 * bl + d) * L + g.off);
+    }
+    // the min/max scan of CreateFreeSurfaceElevation (:717-774) over every body's resampled grid = over the groups' ends
+    for (const auto& g : groups) {
+        if (g.tau_front < ex.tau_min) ex.tau_min = g.tau_front;
+        if (g.tau_front > ex.tau_max) ex.tau_max = g.tau_front;
+        if (g.tau_back > ex.tau_max) ex.tau_max = g.tau_back;
+        if (g.tau_back < ex.tau_min) ex.tau_min = g.tau_back;
+    }
+    c->init.wave_resample_seconds += seconds_since(t_call);
+    return ex;
+}
+
+void upload_excitation(hc_ctx* c, const ExcitationGrid& ex) {
+    {   // excitation IRF into the same panel layout as K (row tiles of 16, column groups of 8)
+        hc::DeviceBuffer<double> d_rowmajor;
+        d_rowmajor.upload(ex.vals, c->stream);
+        c->ngp_ex = ((ex.L + 7) & ~7) / 8;
+        c->d_kex.alloc(hc::panel_doubles(c->ntiles, c->ngp_ex));
+        HC_HIP(hipMemsetAsync(c->d_kex.p, 0, c->d_kex.n * sizeof(double), c->stream));
+        hc::launch_relayout_rowmajor(d_rowmajor.p, c->Dloc, ex.L, c->d_kex.p, c->ngp_ex, 0, c->stream);
+        HC_HIP(hipGetLastError());
+        HC_HIP(hipStreamSynchronize(c->stream));
+    }
+    c->d_ex_tau.upload(ex.tau, c->stream);
+    c->d_ex_width.upload(ex.width, c->stream);
+}
+
+void commit_excitation(hc_ctx* c, ExcitationGrid& ex) {
+    const int L = ex.L;
+    c->L    = L;
+    c->Lpad = (L + 7) & ~7;
+    c->ex_tau.swap(ex.tau);
+    c->ex_width.swap(ex.width);
+    c->ex_vals.swap(ex.vals);
+    c->ex_groups.swap(ex.groups);
+    c->ex_group_of.swap(ex.group_of);
+    c->wave_kind = hc::kWaveIrregular;
+    choose_exc_config(c);
+    alloc_partials(c);
+    c->prof.conv_kernel_bytes = 8.0 * (static_cast<double>(c->Dloc) * c->S * c->D + static_cast<double>(c->S) * c->D +
+                                       static_cast<double>(c->Dloc) * L + L);
+    c->prof.block_kernel_bytes = hc::kDepthDefault * 8.0 * (static_cast<double>(c->Dloc) * c->S * c->D + static_cast<double>(c->S) * c->D);
+}
+
 // The wave model is about to change: excitation rows a look-ahead pass has precomputed belong to the previous model -- those of the
 // current block (Plan::has_exc) AND those of the pass one block ahead, whether its rows are complete already (the next block would adopt
 // them, hc_step.cpp: plan.has_exc = ahead.has_exc) or its last slice, which carries the excitation work items with the OLD tables in
 // its arguments, is still to be issued.  The radiation rows stay valid.  (Found by profiles/fuzz_parity.py, seed 40: a wave model
 // redrawn under "one block ahead" gave the next block the old model's excitation force.)
-static void drop_lookahead_excitation(hc_ctx* c) {
+void drop_lookahead_excitation(hc_ctx* c) {
     c->plan.has_exc        = false;
     c->ahead.has_exc       = false;
     c->ahead.exc_once      = 0.0;
     c->ahead.args.nchunks_ex = 0;
 }
+}  // namespace detail
+}  // namespace hc
+
+extern "C" {
 
 // ---- configuration ----------------------------------------------------------------------------
 int hc_set_gravity(hc_ctx* c, const double g[3]) {
@@ -641,6 +751,7 @@ int hc_set_wave_none(hc_ctx* c, int num_bodies_arg) {
     require(num_bodies_arg >= 0, HC_ERR_INVALID, "negative body count");
     c->wave_kind   = hc::kWaveNone;
     c->wave_nb_arg = num_bodies_arg;
+    c->eta_record  = false;
     choose_exc_config(c);
     HC_API_END(c)
 }
@@ -682,6 +793,7 @@ int hc_set_wave_regular(hc_ctx* c, int num_bodies_arg, double amplitude, double 
     c->d_reg_mag.upload(local, c->stream);
     c->wave_kind   = hc::kWaveRegular;
     c->wave_nb_arg = num_bodies_arg;
+    c->eta_record  = false;
     choose_exc_config(c);
     HC_API_END(c)
 }
@@ -714,63 +826,9 @@ int hc_set_wave_irregular(hc_ctx* c, const hc_irregular_wave_params* pp) {
     require(p.simulation_dt > 0.0, HC_ERR_INVALID, "simulation_dt must be positive");
     require(p.wave_height != 0.0 && p.wave_period != 0.0, HC_ERR_INVALID,
             "wave_height and wave_period must be non-zero (the reference leaves the free-surface table empty otherwise)");
-    // Excitation-IRF time grids.  The reference keeps one grid per body (ex_irf_time_sampled_[b], src/wave_types.cpp:432-459) and
-    // resamples each on its own (:572-606).  BEMIO writes one grid per file, so bodies normally share it; bodies with the same
-    // grid (within 1e-10, the tolerance the reference applies to the radiation grids) form a group, and the columns of Kex are
-    // the groups' resampled grids one after the other -- a body's rows are non-zero in the columns of its own group only, so
-    // one launch still serves all bodies.  Groups are formed over ALL bodies (not only the local ones): the column layout, and
-    // with it the summation order, is the same in every row shard of the system.
-    std::vector<hc::ExGroup> groups;
-    std::vector<int> group_of(c->N, -1);
-    for (int b = 0; b < c->N; ++b) {
-        if (!c->bodies[b].have_exirf) {
-            // a row-sharded context whose caller ingested its own bodies only: the other bodies' grids are unknown here
-            require(!is_local(c, b), HC_ERR_INVALID, "excitation IRF missing for a local body");
-            continue;
-        }
-        const auto& tb = c->bodies[b].exirf_t;
-        require(tb.size() >= 2, HC_ERR_INVALID, "excitation IRF with fewer than two samples");
-        for (size_t g = 0; g < groups.size() && group_of[b] < 0; ++g) {
-            const auto& tg = c->bodies[groups[g].first_body].exirf_t;
-            bool same = tg.size() == tb.size();
-            for (size_t j = 0; j < tb.size() && same; ++j) same = std::fabs(tb[j] - tg[j]) <= 1e-10;
-            if (same) group_of[b] = static_cast<int>(g);
-        }
-        if (group_of[b] < 0) {
-            hc::ExGroup g;
-            g.first_body = b;
-            group_of[b]  = static_cast<int>(groups.size());
-            groups.push_back(g);
-        }
-    }
     const auto t_call = std::chrono::steady_clock::now();
-    // ResampleIRF (src/wave_types.cpp:572-606), per group
-    std::vector<double> ex_tau, ex_width;
-    int L = 0;
-    for (auto& g : groups) {
-        const auto& t_old = c->bodies[g.first_body].exirf_t;
-        const double t0 = t_old.front(), t1 = t_old.back();
-        g.L   = static_cast<int>(std::ceil((t1 - t0) / p.simulation_dt));
-        require(g.L >= 2, HC_ERR_INVALID, "excitation IRF resamples to fewer than two points");
-        g.off = L;
-        const std::vector<double> tg = hc::linspaced(g.L, t0, t1), wg = hc::trapezoid_widths(tg);
-        g.tau_front = tg.front();
-        g.tau_back  = tg.back();
-        ex_tau.insert(ex_tau.end(), tg.begin(), tg.end());
-        ex_width.insert(ex_width.end(), wg.begin(), wg.end());
-        L += g.L;
-    }
-    const int Lpad = (L + 7) & ~7;
-    std::vector<double> vals(static_cast<size_t>(c->Dloc) * L, 0.0);
-    for (int bl = 0; bl < c->nloc; ++bl) {
-        const auto& bd = c->bodies[c->b0 + bl];
-        const hc::ExGroup& g = groups[group_of[c->b0 + bl]];
-        const auto r = hc::resample_cubic_bspline6(bd.exirf_f, static_cast<int>(bd.exirf_t.size()), g.L);
-        for (int d = 0; d < 6; ++d)
-            std::copy(r.begin() + static_cast<size_t>(d) * g.L, r.begin() + static_cast<size_t>(d + 1) * g.L,
-                      vals.begin() + static_cast<size_t>(6 * bl + d) * L + g.off);
-    }
-    c->init.wave_resample_seconds += seconds_since(t_call);
+    ExcitationGrid ex = resample_excitation(c, p.simulation_dt);
+    const int L = ex.L;
     // CreateSpectrum (:643-676)
     const auto t_spec = std::chrono::steady_clock::now();
     Spectrum sp = build_spectrum(c, p);
@@ -778,13 +836,7 @@ int hc_set_wave_irregular(hc_ctx* c, const hc_irregular_wave_params* pp) {
     const int nf = sp.nf;
     std::vector<double>&f = sp.f, &Sd = sp.S, &dfv = sp.df, &phase = sp.phase, &kk = sp.k, &amp = sp.amp, &omg = sp.omega;
     // CreateFreeSurfaceElevation (:717-774): the min/max scan over every body's resampled grid = over the groups' ends
-    double t_irf_min = 0.0, t_irf_max = 0.0;
-    for (const auto& g : groups) {
-        if (g.tau_front < t_irf_min) t_irf_min = g.tau_front;
-        if (g.tau_front > t_irf_max) t_irf_max = g.tau_front;
-        if (g.tau_back > t_irf_max) t_irf_max = g.tau_back;
-        if (g.tau_back < t_irf_min) t_irf_min = g.tau_back;
-    }
+    const double t_irf_min = ex.tau_min, t_irf_max = ex.tau_max;
     const double duration = p.simulation_duration + 2 * (t_irf_max - t_irf_min);
     const int nts         = static_cast<int>(std::ceil(duration / p.simulation_dt));
     std::vector<double> eta_t = hc::linspaced(nts + 1, 0, nts * p.simulation_dt);
@@ -822,30 +874,12 @@ int hc_set_wave_irregular(hc_ctx* c, const hc_irregular_wave_params* pp) {
     HC_HIP(hipMemcpyAsync(eta.data(), c->d_eta.p, nt * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     HC_HIP(hipStreamSynchronize(c->stream));
 
-    {   // excitation IRF into the same panel layout as K (row tiles of 16, column groups of 8)
-        hc::DeviceBuffer<double> d_rowmajor;
-        d_rowmajor.upload(vals, c->stream);
-        c->ngp_ex = Lpad / 8;
-        c->d_kex.alloc(hc::panel_doubles(c->ntiles, c->ngp_ex));
-        HC_HIP(hipMemsetAsync(c->d_kex.p, 0, c->d_kex.n * sizeof(double), c->stream));
-        hc::launch_relayout_rowmajor(d_rowmajor.p, c->Dloc, L, c->d_kex.p, c->ngp_ex, 0, c->stream);
-        HC_HIP(hipGetLastError());
-        HC_HIP(hipStreamSynchronize(c->stream));
-    }
-    c->d_ex_tau.upload(ex_tau, c->stream);
-    c->d_ex_width.upload(ex_width, c->stream);
+    upload_excitation(c, ex);
     c->init.wave_upload_seconds += up_s + seconds_since(t_up2);
     c->init.wave_upload_bytes += 8.0 * (3.0 * nf + 3.0 * nt + 2.0 * static_cast<double>(c->Dloc) * L + 2.0 * L);
     c->irr = p;
-    c->L = L;
-    c->Lpad = Lpad;
     c->nf = nf;
     c->nt = nt;
-    c->ex_tau.swap(ex_tau);
-    c->ex_width.swap(ex_width);
-    c->ex_vals.swap(vals);
-    c->ex_groups.swap(groups);
-    c->ex_group_of.swap(group_of);
     c->spec_f.swap(f);
     c->spec_S.swap(Sd);
     c->spec_df.swap(dfv);
@@ -853,13 +887,9 @@ int hc_set_wave_irregular(hc_ctx* c, const hc_irregular_wave_params* pp) {
     c->spec_k.swap(kk);
     c->eta_t.swap(eta_t);
     c->eta.swap(eta);
-    c->wave_kind   = hc::kWaveIrregular;
+    c->eta_record = false;
+    commit_excitation(c, ex);
     c->wave_nb_arg = p.num_bodies;
-    choose_exc_config(c);
-    alloc_partials(c);
-    c->prof.conv_kernel_bytes = 8.0 * (static_cast<double>(c->Dloc) * c->S * c->D + static_cast<double>(c->S) * c->D +
-                                       static_cast<double>(c->Dloc) * L + L);
-    c->prof.block_kernel_bytes = hc::kDepthDefault * 8.0 * (static_cast<double>(c->Dloc) * c->S * c->D + static_cast<double>(c->S) * c->D);
     HC_HIP(hipStreamSynchronize(c->stream));
     c->init.wave_total_seconds += seconds_since(t_call);
     HC_API_END(c)
@@ -913,6 +943,7 @@ int hc_set_wave_irregular_spectral(hc_ctx* c, const hc_irregular_wave_params* pp
     c->spec_k.swap(sp.k);
     c->wave_kind   = hc::kWaveSpectral;
     c->wave_nb_arg = p.num_bodies;
+    c->eta_record  = false;
     choose_exc_config(c);
     HC_API_END(c)
 }

@@ -205,7 +205,8 @@ int hc_wave_kinematics(hc_ctx* c, const hc_wave_kinematics_opts* opts, int n_poi
     const long long n = static_cast<long long>(n_points) * n_times;
     require(n <= hc::kKinMaxItems, HC_ERR_INVALID, "too many (point, time) pairs for one call");
     if (n == 0 || !(eta || vel || acc)) return HC_OK;
-    if (c->wave_kind == hc::kWaveNone) {  // NoWave (wave_types.h:103-109): zeros, no launch
+    // NoWave (wave_types.h:103-109), and an imported eta record (no spectrum: GetEtaIrregular & co. over no component): zeros, no launch
+    if (c->wave_kind == hc::kWaveNone || (c->wave_kind == hc::kWaveIrregular && c->eta_record)) {
         if (eta) std::fill(eta, eta + n, 0.0);
         if (vel) std::fill(vel, vel + 3 * n, 0.0);
         if (acc) std::fill(acc, acc + 3 * n, 0.0);

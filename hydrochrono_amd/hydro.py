@@ -157,6 +157,18 @@ class HydroForces:
         fn = self.lib.hc_set_wave_irregular_spectral if spectral else self.lib.hc_set_wave_irregular
         self._chk(fn(self.ctx, C.byref(p)))
 
+    def add_waves_irregular_eta(self, t, eta, simulation_dt, num_bodies=None):
+        """IrregularWaves with eta_file_path_: the excitation convolution against an imported free-surface record (t strictly
+        increasing, n >= 2), zero-extended over the excitation IRF; the IRF is resampled on simulation_dt.  See
+        hc_set_wave_irregular_eta in include/hydrochrono_amd.h."""
+        t = _arr(t)
+        eta = _arr(eta, t.size)
+        p = capi.IrregularWaveParams()
+        self.lib.hc_irregular_wave_params_default(C.byref(p))
+        p.num_bodies = self.N if num_bodies is None else int(num_bodies)
+        p.simulation_dt = simulation_dt
+        self._chk(self.lib.hc_set_wave_irregular_eta(self.ctx, C.byref(p), _dp(t), _dp(eta), t.size))
+
     def set_eta_synthesis(self, mode):
         """0 = direct FP64 sum (default), 1 = rocFFT chirp-z."""
         self._chk(self.lib.hc_set_eta_synthesis(self.ctx, int(mode)))
@@ -399,6 +411,21 @@ class HydroForces:
         return eta, vel, acc
 
 
+def read_eta_file(path):
+    """IrregularWaves::ReadEtaFromFile: the `time : eta` lines of an eta file as (t, eta); HydroError with the reference's message
+    on a file that cannot be opened or a line that cannot be parsed."""
+    lib = capi.load()
+    path = str(path).encode()
+    n = C.c_int()
+    rc = lib.hc_read_eta_file(path, None, None, 0, C.byref(n))
+    if rc == capi.HC_OK:
+        t, eta = np.empty(n.value), np.empty(n.value)
+        rc = lib.hc_read_eta_file(path, _dp(t), _dp(eta), n.value, C.byref(n))
+    if rc != capi.HC_OK:
+        raise HydroError(rc, lib.hc_last_error(None).decode())
+    return t, eta
+
+
 class HydroGroup:
     """G row-sharded contexts of ONE coupled N-body system driven by one host process through hc_step_multi /
     hc_added_mass_mv_multi (drop-in variant: host holds all state -> a state store per GPU -> host gather).
@@ -439,6 +466,11 @@ class HydroGroup:
         if rc:
             raise HydroError(rc, self.lib.hc_last_error(self.shards[0].ctx).decode())
         return out
+
+    def add_waves_irregular_eta(self, t, eta, simulation_dt, num_bodies=None):
+        # every shard takes the whole record
+        for h in self.shards:
+            h.add_waves_irregular_eta(t, eta, simulation_dt, num_bodies)
 
     def components(self):
         parts = [h.components() for h in sorted(self.shards, key=lambda h: h.b0)]

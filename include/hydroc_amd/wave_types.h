@@ -11,8 +11,10 @@
 // .x() .y() .z() (Eigen::Vector3d, ChVector3d); GetVelocity / GetAcceleration return std::array<double, 3>; GetKinematics evaluates
 // a grid of points x a series of times in one call; a model that is not attached throws std::runtime_error.  Attach copies g_ and
 // water_depth_ from the hydro data as the reference's AddH5Data does; the kinematics use the context's values, so writing these
-// members afterwards has no effect.  Not mirrored: eta_file_path_ (undefined behaviour in the reference, src/wave_types.cpp:480-500
-// vs :784-785).  The mesh helper the irregular demos call (SetUpWaveMesh / GetMeshFile / GetWaveMeshVelocity) is there so that they
+// members afterwards has no effect.  eta_file_path_ reads the record with hc_read_eta_file and attaches it with
+// hc_set_wave_irregular_eta, whose defined behaviour replaces the reference's undefined one (src/wave_types.cpp:480-500 vs :784-785;
+// DESIGN.md section 3): the record is zero-extended, there is no spectrum (GetSpectrum throws the reference's message), and the
+// kinematics are zeros.  The mesh helper the irregular demos call (SetUpWaveMesh / GetMeshFile / GetWaveMeshVelocity) is there so that they
 // compile.
 #pragma once
 
@@ -182,7 +184,7 @@ struct IrregularWaveParams {  // :277-292
     double simulation_dt_           = 0.0;
     double simulation_duration_     = 0.0;
     double ramp_duration_           = 0.0;
-    std::string eta_file_path_;     // not supported
+    std::string eta_file_path_;     // a "time : eta" record (ReadEtaFromFile, src/wave_types.cpp:480-500); replaces the spectrum
     double wave_height_             = 0.0;
     double wave_period_             = 0.0;
     double frequency_min_           = 0.001;
@@ -199,7 +201,6 @@ class IrregularWaves : public WaveBase {  // :294-380
     IrregularWaves(const IrregularWaveParams& params) : params_(params) {}
     WaveMode GetWaveMode() override { return WaveMode::irregular; }
     void Attach(hc_ctx* ctx) override {
-        if (!params_.eta_file_path_.empty()) throw std::runtime_error("eta_file_path_ is not supported by the GPU path");
         hc_irregular_wave_params p;
         hc_irregular_wave_params_default(&p);
         p.num_bodies              = static_cast<int>(params_.num_bodies_);
@@ -214,12 +215,25 @@ class IrregularWaves : public WaveBase {  // :294-380
         p.peak_enhancement_factor = params_.peak_enhancement_factor_;
         p.is_normalized           = params_.is_normalized_ ? 1 : 0;
         p.seed                    = params_.seed_;
-        check(ctx, hc_set_wave_irregular(ctx, &p));
+        if (!params_.eta_file_path_.empty()) {  // InitializeIRFVectors (src/wave_types.cpp:451-453): the record instead of a spectrum
+            int n = 0;
+            if (hc_read_eta_file(params_.eta_file_path_.c_str(), nullptr, nullptr, 0, &n) != HC_OK) throw std::runtime_error(hc_last_error(nullptr));
+            std::vector<double> t(n), eta(n);
+            if (hc_read_eta_file(params_.eta_file_path_.c_str(), t.data(), eta.data(), n, &n) != HC_OK)
+                throw std::runtime_error(hc_last_error(nullptr));
+            check(ctx, hc_set_wave_irregular_eta(ctx, &p, t.data(), eta.data(), n));
+        } else {
+            check(ctx, hc_set_wave_irregular(ctx, &p));
+        }
         attached(ctx);
     }
     // Exporter inputs (src/wave_types.cpp:461-478, read by the runner at run_hydrochrono_from_yaml.cpp:668-679).  GetSpectrum returns
     // the spectral densities S(f) its comment promises; the reference returns a member it never fills ("do not reproduce").
-    std::vector<double> GetSpectrum() { return spectrum(1); }
+    std::vector<double> GetSpectrum() {
+        if (!params_.eta_file_path_.empty())  // spectrumCreated_ == false (src/wave_types.cpp:461-467)
+            throw std::runtime_error("Spectrum has not been created. Initialize with wave height and period to create spectrum.");
+        return spectrum(1);
+    }
     std::vector<double> GetFreeSurfaceElevation() { return table(false); }
     std::vector<double> GetFreeSurfaceTime() const { return table(true); }
     std::vector<double> GetFrequenciesHz() const { return spectrum(0); }

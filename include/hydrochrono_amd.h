@@ -121,8 +121,8 @@ int hc_set_wave_none(hc_ctx* ctx, int num_bodies_arg);
  * (src/wave_types.cpp:274-352). */
 int hc_set_wave_regular(hc_ctx* ctx, int num_bodies_arg, double amplitude, double omega);
 
-/* IrregularWaveParams (include/hydroc/wave_types.h:277-292); eta_file_path_ is not supported (that
- * reference branch is undefined behaviour), wave_stretching_ does not affect forces. */
+/* IrregularWaveParams (include/hydroc/wave_types.h:277-292); eta_file_path_ is hc_read_eta_file + hc_set_wave_irregular_eta below,
+ * wave_stretching_ does not affect forces. */
 typedef struct hc_irregular_wave_params {
     int num_bodies;
     double simulation_dt;
@@ -141,6 +141,28 @@ void hc_irregular_wave_params_default(hc_irregular_wave_params* p);
 /* AddWaves(IrregularWaves(params)): excitation-IRF resampling, spectrum, phases, eta(t) table
  * (src/wave_types.cpp:432-459,572-606,643-676,717-774). */
 int hc_set_wave_irregular(hc_ctx* ctx, const hc_irregular_wave_params* params);
+
+/* AddWaves(IrregularWaves(params)) with params.eta_file_path_ set (src/wave_types.cpp:451-458): irregular waves from a measured or
+ * precomputed free-surface elevation record instead of a spectrum.  The reference reads the record but convolves against a table
+ * it never fills on that branch; the behaviour here is defined as follows (a deviation):
+ *   record       t[0..n), n >= 2, finite and strictly increasing (spacing need not be uniform); eta[0..n) finite.  Used exactly as
+ *                given: ramp_duration is not applied (as in ReadEtaFromFile).
+ *   extension    eta(q) is the piecewise-linear interpolant of the record extended on both sides by eta = 0 samples spaced by the mean
+ *                spacing h = (t[n-1] - t[0]) / (n-1): ceil(max(tau_max, 0) / h) + 1 before and ceil(max(-tau_min, 0) / h) + 1 after, for
+ *                an excitation IRF on [tau_min, tau_max].  Forces are defined for every step time in [t[0], t[n-1]]; outside, the
+ *                excitation-window error of hc_step applies.
+ *   excitation   the IRF is resampled on the simulation_dt grid as by hc_set_wave_irregular; simulation_duration, the spectrum
+ *                parameters and hc_set_eta_synthesis are ignored.
+ *   queries      hc_get_eta_table returns the record as given (nt = n, without the zero extension); nf = 0, hc_get_spectrum returns
+ *                nothing; hc_wave_kinematics returns zeros (the reference's kinematics over an empty spectrum);
+ *                hc_export_irregular_inputs_h5 gives HC_ERR_INVALID.
+ * Row-sharded contexts take the whole record each. */
+int hc_set_wave_irregular_eta(hc_ctx* ctx, const hc_irregular_wave_params* params, const double* t, const double* eta, int n);
+/* IrregularWaves::ReadEtaFromFile (src/wave_types.cpp:480-500) without a context: every line is `time : eta` (read as
+ * `ss >> time >> delimiter >> eta`; the delimiter must be ':', what follows the value is ignored).  *n = number of samples;
+ * t = eta = NULL: size query.  Errors (message in hc_last_error(NULL)): HC_ERR_RUNTIME "Unable to open file at: <path>." and
+ * "Could not parse line: <line>." as the reference throws them; HC_ERR_OUT_OF_RANGE when capacity < *n (nothing copied). */
+int hc_read_eta_file(const char* path, double* t, double* eta, int capacity, int* n);
 
 /* How hc_set_wave_irregular builds the free-surface table eta(t) (GetEtaIrregularTimeSeries, src/wave_types.cpp:27-59):
  * 0 = direct FP64 sum of the Nf cosines per time sample on the GPU (default; same summation order as the reference),
