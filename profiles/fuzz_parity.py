@@ -8,7 +8,8 @@ history or a cold start, gravity -- and, between two steps now and then, a chang
 history taken out and injected again, an added-mass product, a step back in time (a rejected step), a reset of the history or of the profiling stride, the
 diagnostic entry points (hc_compute_hydrostatics / hc_compute_waves), a switch Baseline <-> TaperedDirect; in a quarter of the
 unsharded cases a third of the steps go through hc_step_device on a caller's stream.  Every step's total and its three components against the oracle, each at 1e-9 relative to its own largest
-entry; a failure prints the case's seed and stops.   python profiles/fuzz_parity.py [seconds = 300] [first seed = 1]"""
+entry; a failure prints the case's seed and stops.  FUZZ_TAIL=1: every case long enough for the spectral radiation
+tail (S 512..1399, 1-12 bodies, mostly on the IRF grid, depth 16 / 32, schedule at block start / adaptive); the tail blocks run are counted.   python profiles/fuzz_parity.py [seconds = 300] [first seed = 1]"""
 import os
 import sys
 import time
@@ -47,6 +48,9 @@ def one_case(seed):
         N, S = int(rng.choice([28, 30, 32, 36, 40])), int(rng.integers(1000, 1150))  # 8 (6N)^2 S >= 256 MB
     elif rng.random() < float(os.environ.get("FUZZ_WIDE", "0.02")):  # now and then (FUZZ_WIDE=1: always) a genuinely wide system (6N >= 1024: column slices, fused wide step, two-level form by default)
         N, S = int(rng.choice([171, 172, 176, 180, 192, 200])), int(rng.integers(12, 48) if rng.random() < 0.3 else rng.integers(70, 110))  # (S >= 70: room for look-ahead blocks)
+    tail_draw = bool(os.environ.get("FUZZ_TAIL"))  # (FUZZ_TAIL=1: every case long enough for the spectral radiation tail, S >= 512)
+    if tail_draw:
+        N, S = int(rng.integers(1, 13)), int(rng.integers(512, 1400))
     if os.environ.get("FUZZ_SHARDS") and N < 3:  # (FUZZ_SHARDS=1: every case behind hc_step_multi, 2-4 row shards)
         N = int(rng.choice([3, 4, 5, 8, 9]))
     dt_r = float(rng.choice([0.01, 0.015, 0.02, 0.0125]))
@@ -57,6 +61,8 @@ def one_case(seed):
         case["g_sys"] = [float(rng.normal() * 0.3), float(rng.normal() * 0.3), -9.81 + float(rng.normal() * 0.2)]
     lookahead = int(rng.choice([0, 16, 32, 32]))
     sched = int(rng.choice([-1, 0, 1, 1]))
+    if tail_draw:  # depths and schedules the tail runs under
+        lookahead, sched = int(rng.choice([16, 32])), int(rng.choice([-1, 0]))
     sub = int(rng.choice([-1, -1, 0, 4, 8]))
     direct = int(rng.random() < 0.7)
     shards = int(rng.choice([1, 1, 1, 2, 3])) if N >= 3 else 1
@@ -71,12 +77,15 @@ def one_case(seed):
     os.environ["HC_MINI_NARROW"] = str(int(rng.random() < 0.7))  # narrow / wide form of the short passes
     slices = int(rng.choice([0, 0, 1, 3, 7, 12]))
     dev_mix = shards == 1 and rng.random() < 0.25                # some of the steps through hc_step_device on a caller's stream
-    desc = (f"seed {seed}: N {N} S {S} dt_rirf {dt_r} lookahead {lookahead} schedule {sched} sub {sub} direct {direct} shards {shards} "
+    desc = (f"seed {seed}: {'tail ' if tail_draw else ''}N {N} S {S} dt_rirf {dt_r} lookahead {lookahead} schedule {sched} sub {sub} direct {direct} shards {shards} "
             f"waves {wave} mode {mode} cold {int(cold)} slices {slices} dev {int(dev_mix)} slot {os.environ['HC_SLOT_STATE']} narrow {os.environ['HC_MINI_NARROW']}")
     gpu = HydroGroup.from_case(case, shards) if shards > 1 else HydroForces.from_case(case)
     orc = load_into_oracle(case)
     base_dt = float(rng.choice([dt_r, dt_r, dt_r, 0.7 * dt_r, 1.3 * dt_r, 0.5 * dt_r, 0.01, 0.2 * dt_r, 3.0 * dt_r]))  # (0.2: the ring grows; 3.0: blocks would span the window)
     n_steps = int(rng.integers(150, 420)) if N < 20 else int(rng.integers(80, 160))
+    if tail_draw:  # mostly on the IRF grid, and long enough for superblocks of 256 steps
+        base_dt = dt_r if rng.random() < 0.8 else base_dt
+        n_steps = int(rng.integers(400, 900))
     span = S * dt_r
     t0 = 0.0 if cold else span + 1.0 + float(rng.uniform(0, 1))
     dur = t0 + n_steps * 2.2 * max(base_dt, dt_r) + 10.0
@@ -118,6 +127,8 @@ def one_case(seed):
     while len(times) < n_steps:
         kind = rng.random()
         n = int(rng.integers(3, 90))
+        if tail_draw and not times:
+            kind, n = 0.0, int(rng.integers(300, 700))  # a first stretch on the step of the draw
         if kind < 0.6:
             d = base_dt
             seq = [d] * n
@@ -247,11 +258,12 @@ def one_case(seed):
     gpu.close()
     orc.close()
     return True, desc, worst, np.array([prof["block_kernel_launches"], prof["mini_pass_launches"], prof["ahead_blocks"], prof["scatter_kernel_launches"],
-                                        prof["conv_kernel_launches"], prof["direct_dispatches"], prof["hip_launches"]], dtype=np.int64)
+                                        prof["conv_kernel_launches"], prof["direct_dispatches"], prof["hip_launches"], prof["tail_blocks"],
+                                        int(prof["tail_blocks"] > 0)], dtype=np.int64)
 
 
 t_end = time.time() + budget
-n_ok, worst_all, passes = 0, 0.0, np.zeros(7, dtype=np.int64)
+n_ok, worst_all, passes = 0, 0.0, np.zeros(9, dtype=np.int64)
 while time.time() < t_end:
     if os.environ.get("FUZZ_PRINT_SEEDS"):  # (a case that takes the process down -- a GPU memory fault -- is the last one named)
         print(f"case {seed}", flush=True)
@@ -268,4 +280,4 @@ from hydrochrono_amd import capi  # noqa: E402
 print(f"library: {capi.load().hc_version().decode()}, flavour {os.environ['HYDROCHRONO_AMD_FLAVOR']}")
 print(f"fuzz ok: {n_ok} cases, seeds up to {seed - 1}, worst relative error {worst_all:.2e}; launches over all cases (first shard of a group): passes {passes[0]}, "
       f"short passes {passes[1]} and scatters {passes[3]} (counted in every fourth case only), blocks that started with rows made ahead {passes[2]}, plain per-step kernels {passes[4]}; "
-      f"AQL dispatches {passes[5]}, HIP launches {passes[6]}")
+      f"AQL dispatches {passes[5]}, HIP launches {passes[6]}; spectral tail blocks {passes[7]}, cases with tail blocks {passes[8]}")

@@ -19,6 +19,7 @@ LEGS = [  # id, environment, seconds, first seed (None: derived from the clock),
     ("release_build_wide_only", {"FUZZ_RELEASE": "1", "FUZZ_WIDE": "1"}, 30, 510001, 3),
     ("release_build_shards_only", {"FUZZ_RELEASE": "1", "FUZZ_SHARDS": "1"}, 30, 520001, 5),
     ("release_build_seed_from_the_clock", {"FUZZ_RELEASE": "1"}, 20, None, 3),
+    ("release_build_tail_only", {"FUZZ_RELEASE": "1", "FUZZ_TAIL": "1"}, 30, 530001, 3),
 ]
 
 
@@ -29,7 +30,7 @@ def test_randomised_differential_run_leg(leg):
     if seed is None:
         seed = 600000000 + int(time.time()) % 100000000
     env = dict(os.environ)
-    for k in ("HYDROCHRONO_AMD_FLAVOR", "FUZZ_RELEASE", "FUZZ_WIDE", "FUZZ_SHARDS", "FUZZ_FLAVOR"):
+    for k in ("HYDROCHRONO_AMD_FLAVOR", "FUZZ_RELEASE", "FUZZ_WIDE", "FUZZ_SHARDS", "FUZZ_TAIL", "FUZZ_FLAVOR"):
         env.pop(k, None)
     env.update(extra)
     print(f"fuzz leg {name}: {seconds} s from seed {seed}")
@@ -38,4 +39,6 @@ def test_randomised_differential_run_leg(leg):
     assert r.returncode == 0 and "fuzz ok:" in r.stdout, tail
     cases = int(r.stdout.split("fuzz ok:")[1].split("cases")[0])
     assert cases >= fewest, tail
+    if "FUZZ_TAIL" in extra:  # the draw is there to reach the spectral tail: some case must have run it
+        assert int(r.stdout.split("cases with tail blocks")[1].split()[0]) >= 1, tail
     print(r.stdout.strip().splitlines()[-1])

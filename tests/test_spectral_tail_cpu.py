@@ -71,17 +71,35 @@ def gemv(Kh, X, bins, col_lo, col_hi, shift):
     return np.einsum("brc,bc->br", Kh[lo:hi, :, col_lo:col_hi], X[lo:hi, col_lo + shift:col_hi + shift])
 
 
+def direct_tail(G, v, m0, P, S):
+    """sum_{s = P .. S-1} G_s v_{m-s} for the P steps m = m0 .. m0 + P - 1 of a superblock: [j][row]."""
+    Gm = np.transpose(G[P:S], (1, 0, 2)).reshape(G.shape[1], -1)  # [row][(s - P) * D + col]
+    return np.stack([Gm @ v[m0 + j - S + 1:m0 + j - P + 1][::-1].reshape(-1) for j in range(P)])
+
+
 @pytest.mark.parametrize("S", [1024, 700, 512])
 @pytest.mark.parametrize("L", [16, 32])
 def test_overlap_save_with_header_indices_equals_direct_sum(dump_exe, S, L):
-    D, rows = 6, 4
+    overlap_save_against_direct_sum(dump_exe, S, L, 6, seed=S + L)
+
+
+@pytest.mark.parametrize("S", [512, 513, 700, 767, 768, 769, 1024, 1300, 8448])
+@pytest.mark.parametrize("L", [16, 32])
+@pytest.mark.parametrize("D", [6, 30])
+def test_overlap_save_at_partition_edges_and_widths(dump_exe, S, L, D):
+    """One lag in the last partition (513, 769), S around a partition boundary, many partitions (8448: NP = 32), two widths."""
+    overlap_save_against_direct_sum(dump_exe, S, L, D, seed=S + L + D)
+
+
+def overlap_save_against_direct_sum(dump_exe, S, L, D, seed):
+    rows = 4
     g = load(dump_exe, S, L, D)
     P, NP, Q = g["P"], g["NP"], g["Q"]
     assert NP == -(-S // P) - 1 and Q * L == P
     assert g["chunks"][0][0] == 0 and g["chunks"][-1][1] == g["bins"]
     assert len(g["chunks"]) == Q - 1 and all(g["chunks"][i][1] == g["chunks"][i + 1][0] for i in range(Q - 2))
-    rng = np.random.default_rng(S + L)
-    G = rng.standard_normal((S, rows, D))
+    rng = np.random.default_rng(seed)
+    G = rng.standard_normal((S, rows, D))  # a flat envelope: the oldest lag weighs as much as the newest
     T = 3 * P + S  # samples 0 .. T-1; superblock q starts at step m0
     v = rng.standard_normal((T, D))
     Kh = khat(g, G, D)
@@ -93,11 +111,71 @@ def test_overlap_save_with_header_indices_equals_direct_sum(dump_exe, S, L):
         Y_far[lo:hi] = gemv(Kh, X_prev, (lo, hi), D, NP * D, g["shift_next"]) if NP > 1 else 0.0
     Y_fallback = gemv(Kh, X_cur, (0, g["bins"]), D, NP * D, g["shift_cur"]) if NP > 1 else 0.0
     Y_near = gemv(Kh, X_cur, (0, g["bins"]), 0, D, g["shift_cur"])
-    for Yf in (Y_far, Y_fallback):
+    direct = direct_tail(G, v, m0, P, S)
+    for name, Yf in (("far chunks", Y_far), ("fallback", Y_fallback)):
         y = np.fft.irfft(Yf + Y_near, n=g["N"], axis=0)[P:]  # [j][row]
-        direct = np.zeros((P, rows))
-        for j in range(P):
-            m = m0 + j
-            for s in range(P, S):
-                direct[j] += G[s] @ v[m - s]
-        assert np.max(np.abs(y - direct)) <= 1e-11 * np.max(np.abs(direct))
+        err = np.max(np.abs(y - direct), axis=1)
+        j = int(np.argmax(err))
+        assert err[j] <= 1e-11 * np.max(np.abs(direct)), f"{name}: step j = {j} of the superblock, error {err[j]:.3e}"
+
+
+# ---- tail_grid_ok (hc_tail.hpp): the eligibility test of a superblock's grid --------------------------------------------------------
+def grid_ok(exe, times, tau, dt, t_first):
+    """hc::tail_grid_ok(times newest first, tau, dt, t_first) through the driver's "grid" mode."""
+    arg = " ".join(["%d %d" % (len(times), len(tau))] + ["%.17g" % x for x in list(times) + list(tau) + [dt, t_first]])
+    out = subprocess.run([exe, "grid"], input=arg, capture_output=True, text=True, check=True).stdout.split()
+    return out == ["1"]
+
+
+def tols(dt, t_first, tau_last):
+    eps = np.finfo(np.float64).eps
+    return max(1e-9 * dt, 64.0 * eps * abs(t_first)), max(1e-9 * dt, 64.0 * eps * abs(tau_last))
+
+
+@pytest.mark.parametrize("S", [512, 700])
+def test_tail_grid_ok_edges(dump_exe, S):
+    dt, t0 = 2.0 ** -7, 64.0  # t0: the newest history sample; t_first = t0 + dt
+    tau = np.arange(S) * dt
+    t_first = t0 + dt
+    tol_t, tol_s = tols(dt, t_first, tau[-1])
+
+    def hist(n):
+        return t0 - dt * np.arange(n)
+
+    # the history must hold S samples on the grid (and reach past the oldest query: S samples reach S dt back)
+    assert grid_ok(dump_exe, hist(S), tau, dt, t_first)
+    assert not grid_ok(dump_exe, hist(S - 1), tau, dt, t_first)
+    # the first predicted step: on the grid within the planner's tolerance
+    assert grid_ok(dump_exe, hist(S + 4), tau, dt, t_first + 0.9 * tol_t)
+    assert grid_ok(dump_exe, hist(S + 4), tau, dt, t_first - 0.9 * tol_t)
+    assert not grid_ok(dump_exe, hist(S + 4), tau, dt, t_first + 1.1 * tol_t)
+    assert not grid_ok(dump_exe, hist(S + 4), tau, dt, t_first - 1.1 * tol_t)
+    # one history time of the window off the grid
+    for k in (1, S // 2, S - 1):
+        h = hist(S + 4)
+        h[k] += 0.9 * tol_t
+        assert grid_ok(dump_exe, h, tau, dt, t_first), k
+        h[k] += 0.2 * tol_t
+        assert not grid_ok(dump_exe, h, tau, dt, t_first), k
+    # one IRF time off the grid of the step
+    for s in (1, 256, S - 1):
+        ts = tau.copy()
+        ts[s] += 0.9 * tol_s
+        assert grid_ok(dump_exe, hist(S + 4), ts, dt, t_first), s
+        ts[s] += 0.2 * tol_s
+        assert not grid_ok(dump_exe, hist(S + 4), ts, dt, t_first), s
+    # the margin: the oldest kept sample must lie more than tau_{S-1} + 8 tol_t before t_first (samples past index S - 1 are not
+    # held to the grid)
+    margin = 8.0 * tol_t
+    for delta, ok in ((0.25 * margin, True), (-0.25 * margin, False)):
+        h = hist(S + 1)
+        h[-1] = t_first - tau[-1] - margin - delta
+        assert grid_ok(dump_exe, h, tau, dt, t_first) == ok, delta
+    # a step other than the IRF spacing
+    assert not grid_ok(dump_exe, t0 - 1.5 * dt * np.arange(S + 4), tau, 1.5 * dt, t0 + 1.5 * dt)
+
+
+def test_tail_grid_ok_needs_two_partitions(dump_exe):
+    dt, t0 = 2.0 ** -7, 64.0
+    for S, ok in ((511, False), (512, True)):
+        assert grid_ok(dump_exe, t0 - dt * np.arange(S + 4), np.arange(S) * dt, dt, t0 + dt) == ok, S
