@@ -131,6 +131,7 @@ int hc_get_spectrum(hc_ctx* c, double* f, double* S, double* df, double* phase, 
 int hc_get_eta_table(hc_ctx* c, double* t, double* eta) {
     HC_API_BEGIN(c)
     require(c->wave_kind == hc::kWaveIrregular || c->wave_kind == hc::kWaveSpectral, HC_ERR_INVALID, "no irregular wave model attached");
+    if (c->wave_kind == hc::kWaveSpectral) return HC_OK;  // the component sum has no table (hc_get_sizes: nt = 0): nothing is copied
     const std::vector<double>& tt = c->eta_record ? c->rec_t : c->eta_t;
     const std::vector<double>& ee = c->eta_record ? c->rec_eta : c->eta;
     if (t) std::copy(tt.begin(), tt.end(), t);

@@ -460,6 +460,8 @@ int hc_export_irregular_inputs_h5(hc_ctx* c, const char* path) {
     require(path, HC_ERR_INVALID, "null path");
     require(c->wave_kind == hc::kWaveIrregular || c->wave_kind == hc::kWaveSpectral, HC_ERR_INVALID, "no irregular wave model attached");
     require(!c->eta_record, HC_ERR_INVALID, "the irregular wave model is an imported eta record: it has no spectrum to export");
+    require(c->wave_kind != hc::kWaveSpectral, HC_ERR_INVALID,
+            "the wave model is the spectral component sum: it has no free-surface table to export (hc_get_spectrum returns its spectrum)");
     using export_fn_t = int (*)(const char*, const double*, const double*, int, const double*, const double*, int, char*, size_t);
     const export_fn_t fn = reinterpret_cast<export_fn_t>(bemio_symbol("hc_bemio_export_irregular"));
     // what SimulationExporter::WriteIrregularInputs writes (src/simulation_exporter.cpp:365-393): spectrum and free-surface table
@@ -936,6 +938,8 @@ int hc_set_wave_irregular_spectral(hc_ctx* c, const hc_irregular_wave_params* pp
     c->irr = p;
     c->nf  = sp.nf;
     c->L = c->Lpad = c->nt = 0;
+    c->eta_t.clear();  // no free-surface table in this mode: an IRF model's before it must not be handed out or exported (hc_get_eta_table)
+    c->eta.clear();
     c->spec_f.swap(sp.f);
     c->spec_S.swap(sp.S);
     c->spec_df.swap(sp.df);

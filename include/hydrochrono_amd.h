@@ -174,7 +174,11 @@ int hc_set_eta_synthesis(hc_ctx* ctx, int mode);
  *   f[row](t) = ramp(t) * sum_i |X_row(w_i)| * a_i * cos(w_i t - phi_i + arg X_row(w_i)),   a_i = sqrt(2 S_i df_i),
  * with the excitation RAO interpolated per component by RegularWave's interpolator (src/wave_types.cpp:329-352, held
  * constant outside the BEM frequency range) and per-body phases.  Agrees with the IRF convolution up to the IRF's
- * truncation / resampling error (a few per cent on the sphere data), so it is validated at a looser tolerance. */
+ * truncation / resampling error (a few per cent on the sphere data), so it is validated at a looser tolerance.
+ *   queries      hc_get_spectrum as for hc_set_wave_irregular; the mode has neither a resampled excitation IRF nor a free-surface
+ *                table: hc_get_sizes gives L = 0 and nt = 0, hc_get_excitation_irf_size / _resampled give HC_ERR_INVALID,
+ *                hc_get_eta_table succeeds and copies nothing (also on a context that held an IRF model's table before), and
+ *                hc_export_irregular_inputs_h5 is refused with HC_ERR_INVALID (the file's free-surface datasets would be empty). */
 int hc_set_wave_irregular_spectral(hc_ctx* ctx, const hc_irregular_wave_params* params);
 
 /* TestHydro::SetRadiationConvolutionMode: 0 = Baseline, 1 = TaperedDirect (include/hydroc/hydro_forces.h:234-243) */

@@ -9,7 +9,10 @@ history taken out and injected again, an added-mass product, a step back in time
 diagnostic entry points (hc_compute_hydrostatics / hc_compute_waves), a switch Baseline <-> TaperedDirect; in a quarter of the
 unsharded cases a third of the steps go through hc_step_device on a caller's stream.  Every step's total and its three components against the oracle, each at 1e-9 relative to its own largest
 entry; a failure prints the case's seed and stops.  FUZZ_TAIL=1: every case long enough for the spectral radiation
-tail (S 512..1399, 1-12 bodies, mostly on the IRF grid, depth 16 / 32, schedule at block start / adaptive); the tail blocks run are counted.   python profiles/fuzz_parity.py [seconds = 300] [first seed = 1]"""
+tail (S 512..1399, 1-12 bodies, mostly on the IRF grid, depth 16 / 32, schedule at block start / adaptive); the tail blocks run are counted.
+FUZZ_SPECTRAL=1: the wave draw (the initial one and the mid-run model change) also yields the spectral component sum, which the oracle
+does not have: the oracle then runs without waves and the wave rows come from tests/spectral_ref.py -- the wave component within that
+file's bound B row by row, the total against oracle + reference; the steps taken under a spectral model are counted.   python profiles/fuzz_parity.py [seconds = 300] [first seed = 1]"""
 import os
 import sys
 import time
@@ -34,6 +37,12 @@ orc_mod.set_num_threads(min(32, os.cpu_count() or 1))
 budget = float(sys.argv[1]) if len(sys.argv) > 1 else 300.0
 seed = int(sys.argv[2]) if len(sys.argv) > 2 else 1
 TOL = 1e-9
+SPECTRAL = bool(os.environ.get("FUZZ_SPECTRAL"))  # (every extra random draw below sits behind it: without it the cases are what they were)
+spectral_ref = None
+if SPECTRAL:  # (only this draw needs tests/spectral_ref.py: every other leg runs without that file)
+    import spectral_ref  # noqa: E402
+    if not spectral_ref.longdouble_ok():
+        sys.exit("FUZZ_SPECTRAL needs an np.longdouble wider than FP64 for its reference")
 
 
 def relerr(a, b):
@@ -69,6 +78,8 @@ def one_case(seed):
     if os.environ.get("FUZZ_SHARDS"):
         shards = int(rng.choice([2, 3, 4])) if N >= 4 else 2
     wave = str(rng.choice(["none", "regular", "irregular", "irregular"]))
+    if SPECTRAL and rng.random() < 0.6:
+        wave = "spectral"
     mode = int(rng.random() < 0.2)  # 1: TaperedDirect
     cold = rng.random() < 0.3
     os.environ["HC_SUB_BLOCK"] = str(sub)
@@ -77,6 +88,7 @@ def one_case(seed):
     os.environ["HC_MINI_NARROW"] = str(int(rng.random() < 0.7))  # narrow / wide form of the short passes
     slices = int(rng.choice([0, 0, 1, 3, 7, 12]))
     dev_mix = shards == 1 and rng.random() < 0.25                # some of the steps through hc_step_device on a caller's stream
+    spec = {"tab": None, "ramp": 0.0, "steps": 0}  # the reference's tables while a spectral model is attached
     desc = (f"seed {seed}: {'tail ' if tail_draw else ''}N {N} S {S} dt_rirf {dt_r} lookahead {lookahead} schedule {sched} sub {sub} direct {direct} shards {shards} "
             f"waves {wave} mode {mode} cold {int(cold)} slices {slices} dev {int(dev_mix)} slot {os.environ['HC_SLOT_STATE']} narrow {os.environ['HC_MINI_NARROW']}")
     gpu = HydroGroup.from_case(case, shards) if shards > 1 else HydroForces.from_case(case)
@@ -95,7 +107,10 @@ def one_case(seed):
         for h in (gpu, orc):
             h.set_convolution_mode(1)
             h.set_tapered_direct_options(**opts)
+    first = gpu.shards[0] if shards > 1 else gpu
+
     def draw_waves(kind):
+        spec["tab"] = None
         if kind == "none":
             for h in (gpu, orc):
                 h.add_waves_none()
@@ -107,6 +122,11 @@ def one_case(seed):
             kw = dict(simulation_dt=base_dt, simulation_duration=dur, ramp_duration=float(rng.choice([0.0, 2.0])), wave_height=float(rng.uniform(0.5, 3.0)),
                       wave_period=float(rng.uniform(5.0, 11.0)), frequency_min=0.02, frequency_max=0.5, nfrequencies=int(rng.choice([16, 64])),
                       peak_enhancement_factor=float(rng.choice([1.0, 3.3])), seed=int(rng.integers(1, 9)))
+            if kind == "spectral":  # not in the oracle: it carries no waves, the wave rows come from tests/spectral_ref.py
+                gpu.add_waves_irregular(spectral=True, **kw)
+                orc.add_waves_none()
+                spec["tab"], spec["ramp"] = spectral_ref.tables(case, first.irreg_spectrum()), kw["ramp_duration"]
+                return
             for h in (gpu, orc):
                 h.add_waves_irregular(**kw)
     draw_waves(wave)
@@ -145,7 +165,6 @@ def one_case(seed):
     times = times[:n_steps]
     worst = 0.0
     events = 0
-    first = gpu.shards[0] if shards > 1 else gpu
     offset, t_prev, rewinds = 0.0, None, 0
     if dev_mix:
         stream = torch.cuda.Stream()
@@ -163,7 +182,10 @@ def one_case(seed):
             elif ev == 1:
                 gpu.set_pass_schedule(int(rng.choice([-1, 0, 1])))
             elif ev == 2:
-                draw_waves(str(rng.choice(["none", "regular", "irregular"])))
+                kind = str(rng.choice(["none", "regular", "irregular"]))
+                if SPECTRAL and rng.random() < 0.5:
+                    kind = "spectral"
+                draw_waves(kind)
             elif ev == 3:  # the kept history taken out and injected again into both (a restart from a checkpoint)
                 th_, vh_ = first.get_history()
                 gpu.set_history(th_, vh_)
@@ -175,6 +197,12 @@ def one_case(seed):
                 st_p = motion.state(t_prev)
                 hs_d, wv_d = gpu.compute_hydrostatics(st_p[0], st_p[1]), gpu.compute_waves(t_prev)
                 hs_o, _, wv_o = orc.components()
+                if spec["tab"] is not None:
+                    Fp, Bp = spectral_ref.forces(spec["tab"], spec["ramp"], [t_prev])[0], spectral_ref.bound(spec["tab"], [t_prev])[0]
+                    if not np.all(np.abs(wv_d.astype(np.longdouble) - Fp).astype(np.float64) <= Bp):
+                        print(f"FAIL {desc}: hc_compute_waves (spectral) before step {k}", flush=True)
+                        return False, desc, worst, None
+                    wv_d = wv_o
                 for nm, a_, b_ in (("hydrostatics", hs_d, hs_o), ("waves", wv_d, wv_o)):
                     sc = float(np.max(np.abs(b_)))
                     if (sc > 0.0 and float(np.max(np.abs(a_ - b_))) / sc > TOL) or (sc == 0.0 and np.any(a_ != 0.0)):
@@ -230,9 +258,24 @@ def one_case(seed):
             log.append((tt, motion.velocity6(tt)))
             log = log[-6000:]
         t_prev = tt
-        e = relerr(fg, fo)
+        comps_g, comps_o = None, None
+        if spec["tab"] is not None:
+            # a spectral model: total against oracle (no waves) + reference within TOL max|total| + B, the wave rows within B row by row
+            spec["steps"] += 1
+            Fs, Bs = spectral_ref.forces(spec["tab"], spec["ramp"], [tt])[0], spectral_ref.bound(spec["tab"], [tt])[0]
+            want = fo.astype(np.longdouble) + Fs
+            comps_g, comps_o = gpu.components(), orc.components()
+            excess = np.abs(fg.astype(np.longdouble) - want).astype(np.float64) - Bs
+            e = max(0.0, float(np.max(excess))) / max(float(np.max(np.abs(want))), 1e-300)
+            if not np.all(np.abs(comps_g[2].astype(np.longdouble) - Fs).astype(np.float64) <= Bs):
+                ratio = np.max(np.abs(comps_g[2].astype(np.longdouble) - Fs).astype(np.float64) / np.where(Bs > 0, Bs, 1e-300))
+                print(f"FAIL {desc}: step {k} t {tt!r}: spectral wave rows at {ratio:.3f} of their bound", flush=True)
+                return False, desc, worst, None
+            comps_g, comps_o = comps_g[:2], comps_o[:2]
+        else:
+            e = relerr(fg, fo)
         if e <= TOL:  # the three components, each relative to ITS OWN largest entry (a radiation error must not hide behind the hydrostatics)
-            for a, b in zip(gpu.components(), orc.components()):
+            for a, b in zip(comps_g or gpu.components(), comps_o or orc.components()):
                 sc = float(np.max(np.abs(b)))
                 if sc > 0.0:
                     e = max(e, float(np.max(np.abs(a - b))) / sc)
@@ -259,11 +302,11 @@ def one_case(seed):
     orc.close()
     return True, desc, worst, np.array([prof["block_kernel_launches"], prof["mini_pass_launches"], prof["ahead_blocks"], prof["scatter_kernel_launches"],
                                         prof["conv_kernel_launches"], prof["direct_dispatches"], prof["hip_launches"], prof["tail_blocks"],
-                                        int(prof["tail_blocks"] > 0)], dtype=np.int64)
+                                        int(prof["tail_blocks"] > 0), spec["steps"]], dtype=np.int64)
 
 
 t_end = time.time() + budget
-n_ok, worst_all, passes = 0, 0.0, np.zeros(9, dtype=np.int64)
+n_ok, worst_all, passes = 0, 0.0, np.zeros(10, dtype=np.int64)
 while time.time() < t_end:
     if os.environ.get("FUZZ_PRINT_SEEDS"):  # (a case that takes the process down -- a GPU memory fault -- is the last one named)
         print(f"case {seed}", flush=True)
@@ -278,6 +321,7 @@ while time.time() < t_end:
     seed += 1
 from hydrochrono_amd import capi  # noqa: E402
 print(f"library: {capi.load().hc_version().decode()}, flavour {os.environ['HYDROCHRONO_AMD_FLAVOR']}")
+print(f"steps under a spectral model {passes[9]}" + ("" if SPECTRAL else " (FUZZ_SPECTRAL is not set)"))
 print(f"fuzz ok: {n_ok} cases, seeds up to {seed - 1}, worst relative error {worst_all:.2e}; launches over all cases (first shard of a group): passes {passes[0]}, "
       f"short passes {passes[1]} and scatters {passes[3]} (counted in every fourth case only), blocks that started with rows made ahead {passes[2]}, plain per-step kernels {passes[4]}; "
       f"AQL dispatches {passes[5]}, HIP launches {passes[6]}; spectral tail blocks {passes[7]}, cases with tail blocks {passes[8]}")

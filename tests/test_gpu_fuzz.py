@@ -20,6 +20,7 @@ LEGS = [  # id, environment, seconds, first seed (None: derived from the clock),
     ("release_build_shards_only", {"FUZZ_RELEASE": "1", "FUZZ_SHARDS": "1"}, 30, 520001, 5),
     ("release_build_seed_from_the_clock", {"FUZZ_RELEASE": "1"}, 20, None, 3),
     ("release_build_tail_only", {"FUZZ_RELEASE": "1", "FUZZ_TAIL": "1"}, 30, 530001, 3),
+    ("release_build_spectral_only", {"FUZZ_RELEASE": "1", "FUZZ_SPECTRAL": "1"}, 30, 540001, 3),
 ]
 
 
@@ -30,7 +31,7 @@ def test_randomised_differential_run_leg(leg):
     if seed is None:
         seed = 600000000 + int(time.time()) % 100000000
     env = dict(os.environ)
-    for k in ("HYDROCHRONO_AMD_FLAVOR", "FUZZ_RELEASE", "FUZZ_WIDE", "FUZZ_SHARDS", "FUZZ_TAIL", "FUZZ_FLAVOR"):
+    for k in ("HYDROCHRONO_AMD_FLAVOR", "FUZZ_RELEASE", "FUZZ_WIDE", "FUZZ_SHARDS", "FUZZ_TAIL", "FUZZ_FLAVOR", "FUZZ_SPECTRAL"):
         env.pop(k, None)
     env.update(extra)
     print(f"fuzz leg {name}: {seconds} s from seed {seed}")
@@ -41,4 +42,6 @@ def test_randomised_differential_run_leg(leg):
     assert cases >= fewest, tail
     if "FUZZ_TAIL" in extra:  # the draw is there to reach the spectral tail: some case must have run it
         assert int(r.stdout.split("cases with tail blocks")[1].split()[0]) >= 1, tail
+    if "FUZZ_SPECTRAL" in extra:  # ... and this one to reach the spectral wave model, which the oracle does not have
+        assert int(r.stdout.split("steps under a spectral model")[1].split()[0]) > 0, tail
     print(r.stdout.strip().splitlines()[-1])
