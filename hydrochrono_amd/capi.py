@@ -38,6 +38,11 @@ class WaveKinematicsOpts(C.Structure):
     _fields_ = [("mwl", C.c_double), ("regular_phase", C.c_double), ("wave_stretching", C.c_int)]
 
 
+class MorisonElement(C.Structure):
+    """hc_morison_element: position in the body frame, Cd_i A_i and Cm_i V per body axis."""
+    _fields_ = [("r", C.c_double * 3), ("cd_area", C.c_double * 3), ("cm_vol", C.c_double * 3)]
+
+
 class ProfileStats(C.Structure):
     _fields_ = [("hydrostatics_seconds", C.c_double), ("radiation_seconds", C.c_double), ("waves_seconds", C.c_double),
                 ("hydrostatics_calls", C.c_int), ("radiation_calls", C.c_int), ("waves_calls", C.c_int),
@@ -151,6 +156,12 @@ SIGNATURES = {
     "hc_wave_kinematics_opts_default": (None, [C.POINTER(WaveKinematicsOpts)]),
     "hc_wave_kinematics": (C.c_int, [C.c_void_p, C.POINTER(WaveKinematicsOpts), C.c_int, c_double_p, C.c_int, c_double_p,
                                      c_double_p, c_double_p, c_double_p]),
+    "hc_set_morison_elements": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(MorisonElement), C.c_int]),
+    "hc_get_morison_count": (C.c_int, [C.c_void_p, C.c_int, c_int_p]),
+    "hc_set_morison_options": (C.c_int, [C.c_void_p, C.POINTER(WaveKinematicsOpts)]),
+    "hc_morison_begin": (C.c_int, [C.c_void_p, C.c_double, c_double_p, c_double_p, c_double_p, c_double_p]),
+    "hc_morison_end": (C.c_int, [C.c_void_p, c_double_p]),
+    "hc_compute_morison": (C.c_int, [C.c_void_p, C.c_double, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
     "hc_synth_fill": (C.c_int, [C.c_void_p, C.c_ulonglong, C.c_int, C.c_double, C.c_int, C.c_double]),
 }
 

@@ -253,6 +253,21 @@ struct hc_ctx {
     int kin_nf = 0;
     hc::DeviceBuffer<double> d_kin_tab, d_kin_io;
 
+    // Morison elements (hc_set_morison_elements, hc_morison.hip): the lists of all bodies of the system on the host, those of the
+    // owned bodies flattened body-major on the device; its own stream, component table and pinned staging, nothing a step uses
+    std::vector<std::vector<hc_morison_element>> mor_elems;  // [N]
+    hc_wave_kinematics_opts mor_opts{0.0, 0.0, 1};
+    hipStream_t stream_mor = nullptr;  // created by the first hc_set_morison_elements
+    bool mor_dirty = false;            // the lists have changed since the device copy was made
+    int mor_items = 0;                 // elements of the owned bodies
+    int mor_pending = 0;               // hc_morison_begin without its hc_morison_end: 1 zeros (nothing launched), 2 a launch is in flight
+    unsigned long long mor_serial = ~0ULL;
+    double mor_phase = 0.0;
+    int mor_nf = 0;
+    hc::DeviceBuffer<double> d_mor_tab, d_mor_elem, d_mor_state, d_mor_item, d_mor_out;
+    hc::DeviceBuffer<int> d_mor_body, d_mor_off;  // [items] body of an element, [nloc + 1] first element of an owned body
+    hc::PinnedBuffer<double> h_mor_state, h_mor_out;
+
     // GEMV configuration + scratch
     int chunk_gp = 0, nchunks_rad = 0, chunk_gp_ex = 0, nchunks_ex = 0, ngp_ex = 0;
     int chunk_gp_block = 0, nchunks_block = 0;

@@ -39,6 +39,8 @@ constexpr int kSlotStateDoubles  = 2048;  // kExtraBytes / 8
 constexpr int kSlotStateMaxBodies = 170;  // 12 N + 1 doubles fit, and 6 N <= 4 x 256: four early loads per work-item cover every column
                                           // (every system whose step is ONE launch: wide systems begin at 6 N = 1024)
 
+constexpr int kMorisonMaxElements = 4096;  // Morison elements one body may carry (hc_set_morison_elements)
+
 #if defined(__HIPCC__)
 #define HC_HOST_DEVICE __host__ __device__
 #else

@@ -4,29 +4,54 @@
 // component table and writes its own buffers, nothing a step uses.  DESIGN.md 3.7a describes the kernel and the reference
 // behaviour reproduced here, INTEGRATION.md 2 the one deviation (infinite depth under stretching).
 #include "hc_internal.hpp"
+#include "hc_wave_kin.hpp"
 
 using namespace hc::detail;
 
 namespace hc {
+
+std::vector<double> kin_table_host(const hc_ctx* c, double regular_phase) {
+    if (c->wave_kind == kWaveNone || (c->wave_kind == kWaveIrregular && c->eta_record)) return {};
+    std::vector<double> amp, omega, k, phase;
+    if (c->wave_kind == kWaveRegular) {
+        amp   = {c->reg_amp};
+        omega = {c->reg_omega};
+        k     = {c->reg_wavenumber};
+        phase = {regular_phase};
+    } else {
+        const size_t nf = c->spec_f.size();
+        amp.resize(nf);
+        omega.resize(nf);
+        for (size_t i = 0; i < nf; ++i) {
+            amp[i]   = std::sqrt(2 * c->spec_S[i] * c->spec_df[i]);
+            omega[i] = 2 * M_PI * c->spec_f[i];
+        }
+        k     = c->spec_k;
+        phase = c->spec_phase;
+    }
+    const int nf = static_cast<int>(amp.size());
+    const double d = c->depth;
+    std::vector<double> tab(static_cast<size_t>(kKinCols) * nf);
+    auto at = [&](int col, int i) -> double& { return tab[static_cast<size_t>(col) * nf + i]; };
+    for (int i = 0; i < nf; ++i) {
+        const bool deep     = 2 * M_PI / k[i] > d || k[i] * d > 500.0;  // src/wave_types.cpp:74,108
+        at(kKinAmp, i)      = amp[i];
+        at(kKinOmega, i)    = omega[i];
+        at(kKinK, i)        = k[i];
+        at(kKinPhase, i)    = phase[i];
+        at(kKinWA, i)       = omega[i] * amp[i];
+        at(kKinW2A, i)      = omega[i] * omega[i] * amp[i];
+        at(kKinInvSinh, i)  = deep ? 0.0 : 1.0 / std::sinh(k[i] * d);
+        at(kKinDeep, i)     = deep ? 1.0 : 0.0;
+    }
+    return tab;
+}
+
 namespace {
 
 constexpr int kKinThreads = 256;  // work items per workgroup, one per (point, time)
-constexpr int kKinTile    = 256;  // wave components staged in LDS per tile
 // (point, time) pairs per call: the grid's work-item count stays below 2^31
 constexpr long long kKinMaxItems = (1LL << 31) - kKinThreads;
-
-// The per-component table, struct of arrays [kKinCols][nf], built once per wave model on the host (kin_table).
-enum KinCol {
-    kKinAmp = 0,   // A
-    kKinOmega,     // omega
-    kKinK,         // wavenumber k
-    kKinPhase,     // phi
-    kKinWA,        // omega * A
-    kKinW2A,       // omega * omega * A
-    kKinInvSinh,   // 1 / sinh(k d) (finite-depth profile; 0 where the exponential profile applies)
-    kKinDeep,      // 1: exponential profile (2 pi / k > d || k d > 500, per component as the reference tests it)
-    kKinCols
-};
 
 struct KinArgs {
     const double* tab;  // [kKinCols][nf]
@@ -127,46 +152,14 @@ __global__ void __launch_bounds__(kKinThreads) wave_kinematics_kernel(KinArgs a)
     }
 }
 
-// The component table of the context's wave model (regular: one component with the caller's phase; irregular and spectral: the
-// spectrum of the context, A_i = sqrt(2 S_i df_i) and w_i = 2 pi f_i as build_spectrum / the reference compute them).  Rebuilt when
-// a hc_set_wave_* call has come in since (wave_serial) or the regular wave's phase differs from the cached one.
+// The component table of the context's wave model on the device.  Rebuilt when a hc_set_wave_* call has come in since
+// (wave_serial) or the regular wave's phase differs from the cached one.
 void kin_table(hc_ctx* c, double regular_phase) {
     const bool regular = c->wave_kind == kWaveRegular;
     if (c->kin_serial == c->wave_serial && (!regular || std::memcmp(&c->kin_phase, &regular_phase, sizeof(double)) == 0)) return;
-    std::vector<double> amp, omega, k, phase;
-    if (regular) {
-        amp   = {c->reg_amp};
-        omega = {c->reg_omega};
-        k     = {c->reg_wavenumber};
-        phase = {regular_phase};
-    } else {
-        const size_t nf = c->spec_f.size();
-        amp.resize(nf);
-        omega.resize(nf);
-        for (size_t i = 0; i < nf; ++i) {
-            amp[i]   = std::sqrt(2 * c->spec_S[i] * c->spec_df[i]);
-            omega[i] = 2 * M_PI * c->spec_f[i];
-        }
-        k     = c->spec_k;
-        phase = c->spec_phase;
-    }
-    const int nf = static_cast<int>(amp.size());
-    const double d = c->depth;
-    std::vector<double> tab(static_cast<size_t>(kKinCols) * nf);
-    auto at = [&](int col, int i) -> double& { return tab[static_cast<size_t>(col) * nf + i]; };
-    for (int i = 0; i < nf; ++i) {
-        const bool deep     = 2 * M_PI / k[i] > d || k[i] * d > 500.0;  // src/wave_types.cpp:74,108
-        at(kKinAmp, i)      = amp[i];
-        at(kKinOmega, i)    = omega[i];
-        at(kKinK, i)        = k[i];
-        at(kKinPhase, i)    = phase[i];
-        at(kKinWA, i)       = omega[i] * amp[i];
-        at(kKinW2A, i)      = omega[i] * omega[i] * amp[i];
-        at(kKinInvSinh, i)  = deep ? 0.0 : 1.0 / std::sinh(k[i] * d);
-        at(kKinDeep, i)     = deep ? 1.0 : 0.0;
-    }
+    const std::vector<double> tab = kin_table_host(c, regular_phase);
     c->d_kin_tab.upload(tab, c->stream);
-    c->kin_nf     = nf;
+    c->kin_nf     = static_cast<int>(tab.size() / kKinCols);
     c->kin_serial = c->wave_serial;
     c->kin_phase  = regular_phase;
 }

@@ -1,0 +1,30 @@
+// hc_wave_kin.hpp -- the per-component table of the wave kinematics, shared by the kernels that sum over it (hc_wave_kin.hip:
+// wave_kinematics_kernel; hc_morison.hip: morison_items_kernel).  Built on the host once per wave model (hc_wave_kin.hip).
+#pragma once
+#include <vector>
+
+struct hc_ctx;
+
+namespace hc {
+
+constexpr int kKinTile = 256;  // wave components staged in LDS per tile
+
+// The per-component table, struct of arrays [kKinCols][nf].
+enum KinCol {
+    kKinAmp = 0,   // A
+    kKinOmega,     // omega
+    kKinK,         // wavenumber k
+    kKinPhase,     // phi
+    kKinWA,        // omega * A
+    kKinW2A,       // omega * omega * A
+    kKinInvSinh,   // 1 / sinh(k d) (finite-depth profile; 0 where the exponential profile applies)
+    kKinDeep,      // 1: exponential profile (2 pi / k > d || k d > 500, per component as the reference tests it)
+    kKinCols
+};
+
+// The table of the context's wave model (regular: one component with the caller's phase; irregular and spectral: the spectrum of
+// the context, A_i = sqrt(2 S_i df_i) and w_i = 2 pi f_i as build_spectrum / the reference compute them).  Empty for NoWave and
+// for an imported eta record (no spectrum).
+std::vector<double> kin_table_host(const hc_ctx* c, double regular_phase);
+
+}  // namespace hc

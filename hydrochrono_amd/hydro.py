@@ -191,6 +191,15 @@ class HydroForces:
         a = [x if (type(x) is np.ndarray and x.dtype == np.float64 and x.size == n3 and x.flags.c_contiguous) else _arr(x, n3)
              for x in (pos, rpy, linvel, angvel)]
         out = np.empty(self.D_local)
+        if self.__dict__.get("_morison_any"):
+            # the Morison term runs on its own stream beside the step; the sum is made here (the C ABI total stays the reference's)
+            self._chk(self.lib.hc_morison_begin(self.ctx, t, _dp(a[0]), _dp(a[1]), _dp(a[2]), _dp(a[3])))
+            rc = capi.step_raw(self.lib)(self.ctx, t, a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, a[3].ctypes.data, out.ctypes.data)
+            mor = np.empty(self.D_local)
+            rc_end = self.lib.hc_morison_end(self.ctx, _dp(mor))
+            self._chk(rc or rc_end)
+            self._morison_last = mor
+            return out + mor
         # raw addresses through a c_void_p prototype: this call sits in per-step loops
         rc = capi.step_raw(self.lib)(self.ctx, t, a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, a[3].ctypes.data, out.ctypes.data)
         if rc:
@@ -410,6 +419,56 @@ class HydroForces:
                                               _dp(vel.reshape(-1)), _dp(acc.reshape(-1))))
         return eta, vel, acc
 
+    # -- Morison drag and inertia elements (an extension beyond the reference) --
+    def set_morison_elements(self, b, r, cd_area, cm_vol):
+        """Replaces the element list of body b (0-based): r, cd_area, cm_vol are (n, 3) -- positions in the body frame, Cd_i A_i [m^2]
+        and Cm_i V [m^3] per body axis; empty arrays clear it.  From then on step() returns total + Morison term."""
+        r, cd, cm = (np.ascontiguousarray(x, dtype=np.float64).reshape(-1, 3) for x in (r, cd_area, cm_vol))
+        if not (r.shape == cd.shape == cm.shape):
+            raise ValueError("r, cd_area and cm_vol must have the same shape (n, 3)")
+        n = r.shape[0]
+        elems = (capi.MorisonElement * max(n, 1))()
+        flat = np.concatenate([r, cd, cm], axis=1)
+        if n:
+            C.memmove(elems, flat.ctypes.data, flat.nbytes)
+        self._chk(self.lib.hc_set_morison_elements(self.ctx, int(b), elems, n))
+        counts = self.__dict__.setdefault("_morison_counts", {})
+        counts[int(b)] = n
+        self._morison_any = any(counts.values())
+
+    def morison_count(self, b):
+        n = C.c_int()
+        self._chk(self.lib.hc_get_morison_count(self.ctx, int(b), C.byref(n)))
+        return n.value
+
+    def set_morison_options(self, mwl=0.0, regular_phase=0.0, wave_stretching=True):
+        """mwl, regular_phase, wave_stretching of the wave kinematics the elements see (those of wave_kinematics())."""
+        o = capi.WaveKinematicsOpts(float(mwl), float(regular_phase), int(bool(wave_stretching)))
+        self._chk(self.lib.hc_set_morison_options(self.ctx, C.byref(o)))
+
+    def morison_begin(self, t, pos, rpy, linvel, angvel):
+        n3 = 3 * self.N
+        a = [_arr(x, n3) for x in (pos, rpy, linvel, angvel)]
+        self._chk(self.lib.hc_morison_begin(self.ctx, float(t), _dp(a[0]), _dp(a[1]), _dp(a[2]), _dp(a[3])))
+
+    def morison_end(self):
+        out = np.empty(self.D_local)
+        self._chk(self.lib.hc_morison_end(self.ctx, _dp(out)))
+        return out
+
+    def compute_morison(self, t, pos, rpy, linvel, angvel):
+        """The Morison 6-vectors of the owned bodies (world frame, at the body reference) for the given state; zeros without elements."""
+        n3 = 3 * self.N
+        a = [_arr(x, n3) for x in (pos, rpy, linvel, angvel)]
+        out = np.empty(self.D_local)
+        self._chk(self.lib.hc_compute_morison(self.ctx, float(t), _dp(a[0]), _dp(a[1]), _dp(a[2]), _dp(a[3]), _dp(out)))
+        return out
+
+    def morison(self):
+        """The Morison term of the last step() (zeros when no element is set)."""
+        m = self.__dict__.get("_morison_last")
+        return np.zeros(self.D_local) if m is None or not self.__dict__.get("_morison_any") else m.copy()
+
 
 def read_eta_file(path):
     """IrregularWaves::ReadEtaFromFile: the `time : eta` lines of an eta file as (t, eta); HydroError with the reference's message
@@ -462,10 +521,50 @@ class HydroGroup:
         n3 = 3 * self.N
         a = [_arr(x, n3) for x in (pos, rpy, linvel, angvel)]
         out = np.empty(self.D)
+        morison = any(h.__dict__.get("_morison_any") for h in self.shards)
+        if morison:
+            self._morison_begin(t, a)
         rc = self._step(self._ctxs, len(self.shards), t, a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, a[3].ctypes.data, out.ctypes.data)
+        if morison:
+            self._morison_last = self._morison_end(check=not rc)
         if rc:
             raise HydroError(rc, self.lib.hc_last_error(self.shards[0].ctx).decode())
+        return out + self._morison_last if morison else out
+
+    # -- Morison elements: every shard holds the lists of all bodies and computes those of its own --
+    def _morison_begin(self, t, a):
+        begun = []
+        try:
+            for h in self.shards:
+                h._chk(self.lib.hc_morison_begin(h.ctx, float(t), _dp(a[0]), _dp(a[1]), _dp(a[2]), _dp(a[3])))
+                begun.append(h)
+        except HydroError:
+            for h in begun:
+                self.lib.hc_morison_end(h.ctx, _dp(np.empty(h.D_local)))
+            raise
+        return begun
+
+    def _morison_end(self, check=True):
+        out = np.empty(self.D)
+        rcs = []
+        for h in self.shards:
+            part = np.empty(h.D_local)
+            rcs.append((h, self.lib.hc_morison_end(h.ctx, _dp(part))))
+            out[6 * h.b0:6 * h.b1] = part
+        for h, rc in rcs:
+            if check:
+                h._chk(rc)
         return out
+
+    def compute_morison(self, t, pos, rpy, linvel, angvel):
+        n3 = 3 * self.N
+        a = [_arr(x, n3) for x in (pos, rpy, linvel, angvel)]
+        self._morison_begin(t, a)
+        return self._morison_end()
+
+    def morison(self):
+        m = self.__dict__.get("_morison_last")
+        return np.zeros(self.D) if m is None or not any(h.__dict__.get("_morison_any") for h in self.shards) else m.copy()
 
     def add_waves_irregular_eta(self, t, eta, simulation_dt, num_bodies=None):
         # every shard takes the whole record

@@ -137,6 +137,12 @@ struct HydroProfileStats {  // include/hydroc/hydro_forces.h:153-160
     int hydrostatics_calls = 0, radiation_calls = 0, waves_calls = 0;
 };
 
+// A Morison drag / inertia element of a body (not in the reference; hc_morison_element): position in the body frame, Cd_i A_i [m^2]
+// and Cm_i V [m^3] per body axis.
+struct MorisonElement {
+    std::array<double, 3> r{0, 0, 0}, cd_area{0, 0, 0}, cm_vol{0, 0, 0};
+};
+
 // ---------------------------------------------------------------------------------------------------------------
 // TestHydro
 // ---------------------------------------------------------------------------------------------------------------
@@ -255,6 +261,42 @@ class TestHydro {
         for (hc_ctx* c : ctxs_) check(c, hc_compute_waves(c, bodies_[0]->GetChTime(), out.data() + row0(c)));
         return out;
     }
+    // Morison elements (not in the reference; include/hydrochrono_amd.h: hc_set_morison_elements).  Once a body carries elements,
+    // CoordinateFuncForBody returns total + Morison term: hc_morison_begin on every shard, the step, hc_morison_end on every shard,
+    // one elementwise add.  The body index is 1-based, as everywhere in this class; an empty vector clears the list.
+    void SetMorisonElements(int body_index_1_based, const std::vector<MorisonElement>& elements) {
+        if (body_index_1_based < 1 || body_index_1_based > num_bodies_) throw std::out_of_range("SetMorisonElements: body index out of range");
+        std::vector<hc_morison_element> raw(elements.size());
+        for (size_t e = 0; e < elements.size(); ++e)
+            for (int k = 0; k < 3; ++k) {
+                raw[e].r[k]       = elements[e].r[k];
+                raw[e].cd_area[k] = elements[e].cd_area[k];
+                raw[e].cm_vol[k]  = elements[e].cm_vol[k];
+            }
+        for (hc_ctx* c : ctxs_) check(c, hc_set_morison_elements(c, body_index_1_based - 1, raw.data(), static_cast<int>(raw.size())));
+        morison_count_.resize(static_cast<size_t>(num_bodies_), 0);
+        morison_count_[static_cast<size_t>(body_index_1_based - 1)] = raw.size();
+        have_morison_ = std::any_of(morison_count_.begin(), morison_count_.end(), [](size_t n) { return n != 0; });
+        have_time_    = false;  // the cached total belongs to the lists before
+    }
+    // mwl, regular phase and stretching of the kinematics the elements see (those of WaveBase::GetVelocity & co.)
+    void SetMorisonOptions(double mwl = 0.0, double regular_phase = 0.0, bool wave_stretching = true) {
+        hc_wave_kinematics_opts o;
+        hc_wave_kinematics_opts_default(&o);
+        o.mwl             = mwl;
+        o.regular_phase   = regular_phase;
+        o.wave_stretching = wave_stretching ? 1 : 0;
+        for (hc_ctx* c : ctxs_) check(c, hc_set_morison_options(c, &o));
+        have_time_ = false;
+    }
+    std::vector<double> ComputeForceMorison() {
+        gather_state();
+        std::vector<double> out(6 * static_cast<size_t>(num_bodies_));
+        morison_begin(bodies_[0]->GetChTime());
+        morison_end(out.data());
+        return out;
+    }
+
     // src/hydro_forces.cpp:693-711: the radiation IRF value the convolution uses (rho-scaled; the processed kernel in
     // TaperedDirect mode).  Reads one value back from the GPU -- a debugging accessor, as in the reference.
     double GetRIRFval(int row, int col, int st) {
@@ -277,8 +319,20 @@ class TestHydro {
             prev_time_ = t;
             have_time_ = true;
             gather_state();
-            if (ctxs_.size() == 1) check(ctx_, hc_step(ctx_, t, pos_.data(), rpy_.data(), lin_.data(), ang_.data(), total_force_.data()));
-            else check(ctx_, hc_step_multi(ctxs_.data(), static_cast<int>(ctxs_.size()), t, pos_.data(), rpy_.data(), lin_.data(), ang_.data(), total_force_.data()));
+            if (have_morison_) morison_begin(t);
+            const int rc = ctxs_.size() == 1 ? hc_step(ctx_, t, pos_.data(), rpy_.data(), lin_.data(), ang_.data(), total_force_.data())
+                                             : hc_step_multi(ctxs_.data(), static_cast<int>(ctxs_.size()), t, pos_.data(), rpy_.data(), lin_.data(),
+                                                             ang_.data(), total_force_.data());
+            if (have_morison_) {
+                morison_force_.resize(total_force_.size());
+                if (rc != HC_OK) {
+                    for (hc_ctx* c : ctxs_) (void)hc_morison_end(c, morison_force_.data() + row0(c));  // nothing stays pending
+                } else {
+                    morison_end(morison_force_.data());
+                    for (size_t i = 0; i < total_force_.size(); ++i) total_force_[i] += morison_force_[i];
+                }
+            }
+            check(ctx_, rc);
         }
         return total_force_[6 * static_cast<size_t>(b - 1) + dof_index];
     }
@@ -370,6 +424,28 @@ class TestHydro {
             }
         }
     }
+    void morison_begin(double t) {
+        for (size_t g = 0; g < ctxs_.size(); ++g) {
+            const int rc = hc_morison_begin(ctxs_[g], t, pos_.data(), rpy_.data(), lin_.data(), ang_.data());
+            if (rc != HC_OK) {
+                std::vector<double> drop(6 * static_cast<size_t>(num_bodies_));
+                for (size_t h = 0; h < g; ++h) (void)hc_morison_end(ctxs_[h], drop.data());
+                check(ctxs_[g], rc);
+            }
+        }
+    }
+    void morison_end(double* out) {  // every shard is ended, then the first failure is reported
+        int rc = HC_OK;
+        hc_ctx* failed = nullptr;
+        for (hc_ctx* c : ctxs_) {
+            const int r = hc_morison_end(c, out + row0(c));
+            if (r != HC_OK && rc == HC_OK) {
+                rc     = r;
+                failed = c;
+            }
+        }
+        if (failed) check(failed, rc);
+    }
     static int row0(hc_ctx* c) {  // first output row of a shard context
         int b0 = 0;
         check(c, hc_get_shard(c, &b0, nullptr));
@@ -382,6 +458,9 @@ class TestHydro {
     hc_ctx* ctx_ = nullptr;      // ctxs_[0]
     std::shared_ptr<WaveBase> user_waves_;
     std::vector<double> total_force_, pos_, rpy_, lin_, ang_;
+    std::vector<double> morison_force_;  // the Morison term of the last evaluation
+    std::vector<size_t> morison_count_;  // elements per body
+    bool have_morison_ = false;
     std::array<double, 3> gravity_{0.0, 0.0, -9.81};
     bool have_time_   = false;
     double prev_time_ = -1.0;

@@ -512,6 +512,47 @@ int hc_wave_kinematics(hc_ctx* ctx, const hc_wave_kinematics_opts* o, int n_poin
                        int n_times, const double* t, double* eta, double* vel, double* acc);
 
 /* ------------------------------------------------------------------------------------------------
+ * Morison drag and inertia elements (not in the reference, which has none: src/hydro_types.h:34): an opt-in additional force
+ * term on the wave kinematics above.  Element e of a body: position r in the body frame (relative to the point pos[b] locates),
+ * cd_area_i = Cd_i A_i [m^2] and cm_vol_i = Cm_i V [m^3] per BODY axis (1 + Ca for a member outside the BEM mesh, 0 for drag only).
+ * With the state of hc_step:
+ *     R = Rx(rpy0) Ry(rpy1) Rz(rpy2) (Cardan XYZ),  d = R r,  p = pos + d,  v_e = linvel + angvel x d
+ *     eta, u_f, a_f = hc_wave_kinematics at p and t with the Morison options; for the two synthesised irregular models u_f and a_f
+ *         are multiplied by the ramp of hc_set_wave_irregular_spectral (ramp_duration > 0 and t < ramp_duration: 0 for t <= 0, else
+ *         t / ramp_duration; its derivative is not added); a regular wave is not ramped; NoWave, no model or an imported eta
+ *         record: still water (eta = u_f = a_f = 0)
+ *     wet when p.z - mwl <= eta; a dry element contributes nothing
+ *     u = R^T (u_f - v_e),  a = R^T a_f,  F_body,i = 1/2 rho cd_area_i |u_i| u_i + rho cm_vol_i a_i,  F = R F_body,  M = d x F
+ * A body's 6-vector is the sum of (F, M) over its elements in element index order: world frame, at the body reference, the sign of
+ * an applied force.  Its bits depend on that body's state and elements, the wave model, t and the options only -- not on the number
+ * of bodies, on other bodies' elements, or on the shard context that computes it.  The body-acceleration term of Morison's equation
+ * is not included (the step inputs carry no acceleration).
+ *
+ * The term is NOT part of hc_step & co., hc_get_force_components or hc_compute_*: a caller adds it to the total (the HydroForces /
+ * TestHydro layers do).  It runs on a stream of its own, beside the steps, and touches no step state: hc_morison_begin may be
+ * followed by hc_step and then hc_morison_end.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct hc_morison_element {
+    double r[3];
+    double cd_area[3];
+    double cm_vol[3];
+} hc_morison_element;
+/* Replaces the list of `body` (0-based, any body of the system; a shard context computes those of its own bodies); n = 0 clears
+ * it.  Before or after hc_finalize, between steps.  HC_ERR_INVALID: body out of range, n < 0, a null list with n > 0, a non-finite
+ * value, a negative coefficient, more than 4096 elements, or a hc_morison_begin without its end. */
+int hc_set_morison_elements(hc_ctx* ctx, int body, const hc_morison_element* elems, int n);
+int hc_get_morison_count(hc_ctx* ctx, int body, int* n);
+/* mwl, regular_phase, wave_stretching of the kinematics the elements see; NULL = the defaults */
+int hc_set_morison_options(hc_ctx* ctx, const hc_wave_kinematics_opts* o);
+/* begin enqueues (state as for hc_step: [3N] each), end waits and copies the 6 * n_local values of the owned bodies; exactly one
+ * end per begin.  Needs hc_finalize.  HC_ERR_INVALID on a non-finite state or t, on a second begin, on an end without a begin;
+ * nothing stays pending after a failure.  With no element on any owned body: zeros, no launch. */
+int hc_morison_begin(hc_ctx* ctx, double t, const double* pos, const double* rpy, const double* linvel, const double* angvel);
+int hc_morison_end(hc_ctx* ctx, double* out_Dlocal);
+int hc_compute_morison(hc_ctx* ctx, double t, const double* pos, const double* rpy, const double* linvel, const double* angvel,
+                       double* out_Dlocal);
+
+/* ------------------------------------------------------------------------------------------------
  * Synthetic many-body inputs generated directly in HBM (benchmark configurations C3/C4 of SURVEY 8d;
  * not part of the reference).  Fills K, K_hs, A_inf, excitation IRF for all local bodies from a
  * counter-based generator so that a 77 GB kernel never exists on the host.  hc_finalize still applies.
