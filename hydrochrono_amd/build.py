@@ -6,8 +6,9 @@
                                               neither flavour of the main library
   hydrochrono_amd/lib/libhydrochrono_amd_tuning.so + hc_kernels_tuning.co
                                               the same sources with -DHC_TUNING: the sweep / A-B / fault-injection switches (HC_TUNE_INT
-                                              in csrc/hc_internal.hpp) and the kernel variants that were measured and not taken
-                                              (EXPERIMENTS.md).  The tests that need such a switch load this one (capi.use_flavor).
+                                              in csrc/hc_internal.hpp), the step kernel's stage clock and the depth-64 pass, the one
+                                              kernel variant that was measured, not taken and is still compiled (EXPERIMENTS.md).  The
+                                              tests that need such a switch load this one (capi.use_flavor).
 """
 import os
 import shutil
@@ -25,9 +26,8 @@ BEMIO_LIB = os.path.join(LIBDIR, "libhc_bemio.so")
 SOURCES = ["hc_kernels.hip", "hc_runtime.cpp", "hc_step.cpp", "hc_pass.cpp", "hc_setup.cpp", "hc_query.cpp", "hc_direct.cpp", "hc_host_math.cpp", "hc_yaml.cpp",
            "hc_eta_fft.cpp", "hc_wave_kin.hip", "hc_eta_record.cpp", "hc_morison.hip"]
 # kernel-argument preload: the leading scalar / pointer arguments of a kernel arrive in scalar registers with the wave (up to 16 words:
-# added_mass_mv_tagged_kernel starts without a single argument load; the finalize_pre_kernel experiment of the tuning build, EXPERIMENTS.md
-# round 6); kernels whose first argument is a struct -- the step path's -- are unaffected.  The code object only: the library's embedded
-# copies go through HIP launches.
+# added_mass_mv_tagged_kernel starts without a single argument load); kernels whose first argument is a struct -- the step path's -- are
+# unaffected.  The code object only: the library's embedded copies go through HIP launches.
 PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
 KERNEL_CO = os.path.join(LIBDIR, "hc_kernels.co")  # the same kernels as a stand-alone code object, for the direct AQL dispatch (hc_direct.hpp)
 TUNING_CO = os.path.join(LIBDIR, "hc_kernels_tuning.co")

@@ -170,8 +170,6 @@ struct hc_ctx {
     std::string direct_how = "direct AQL dispatch";  // ... or how it is (where the runtime put the packet ring, hc_dispatch_mode_reason)
     int path            = 0;
     hc::DirectKernel dk_finalize_slot;  // finalize_kernel<4, true>: the body state behind the argument block (hc_step.cpp: HostState)
-    hc::DirectKernel dk_finalize_pre;   // finalize_pre_kernel<4>: the same with its first loads' addresses preloaded into scalar registers
-    bool step_preload = false;          // ... in use for this context (tuning build, HC_STEP_PRELOAD=1: measured and not taken, EXPERIMENTS.md)
     hc::DirectKernel dk_step_hot[2];    // step_hot_kernel<1>, <2>: the common block step with a compact argument block (hc_kernels.hpp: StepHotArgs)
     bool step_hot = false;              // ... in use for this context
     int step_halves = 1;                // 2: two workgroups per row tile in step_hot_kernel (systems of kStepHalvesMinColumns columns or more)
@@ -281,8 +279,7 @@ struct hc_ctx {
     int chunk_gp_ex_block = 32, nchunks_ex_block = 0;  // excitation chunks of the look-ahead launch
     int mt_mini = 2;                                    // row tiles per workgroup of the short passes (two-level form)
     int mt_narrow = 2;                                  // ... of their narrow form (16 step columns)
-    int mt_block64 = 3;                                 // ... of the experimental depth-64 pass (HC_BLOCK64_MT: 3, 4 or 6)
-    int mt_block = 4, mt_block_design = 6;              // row tiles per workgroup of the look-ahead launch (1, 2, 4, 6 or 12)
+    int mt_block = 4, mt_block_design = 6;              // row tiles per workgroup of the look-ahead launch (1, 2, 4 or 6; depth 64: hc::kBlock64MT)
     int num_cus  = 256;                                 // compute units of the device (grid rounds of the look-ahead launch)
     int lookahead = 0;  // 0: off, else 16, 32 (kDepthDefault) or 64 (experimental, hc_set_lookahead)
     hc::Plan plan;

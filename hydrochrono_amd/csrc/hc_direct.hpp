@@ -50,11 +50,8 @@ class DirectQueue {
     // argument, so it can request what the host put there together with its arguments instead of after them (the step kernel's body
     // state, hc_step.cpp).
     using FillExtra = void (*)(char* extra, void* user);
-    // no_acquire (tuning experiment, EXPERIMENTS.md round 6): the packet carries no acquire fence (the caches are not invalidated in
-    // front of the kernel); the release fence stays.
     void dispatch(const DirectKernel& k, uint32_t workgroups, uint32_t wg_size, uint32_t dyn_lds, const void* args, size_t arg_bytes,
-                  int timed_tag = -1, double timed_aux = 0.0, int lane = 0, FillExtra fill_extra = nullptr, void* fill_user = nullptr,
-                  bool no_acquire = false);
+                  int timed_tag = -1, double timed_aux = 0.0, int lane = 0, FillExtra fill_extra = nullptr, void* fill_user = nullptr);
     // Parks the lane's packet processor on a barrier packet that waits for a signal; the next dispatch() releases it right after
     // its packet is in the queue.  A queue that has sat EMPTY for more than a few tens of microseconds takes about 6 us longer from
     // doorbell to kernel start (12.2 against 6.0 us launch-to-result for a small kernel after >= 100 us of idle,

@@ -86,7 +86,7 @@ int env_int(const char* name, int fallback);
 // Environment switches.  The RELEASE library reads the operational ones only (env_int: HC_DIRECT, HC_ARM, HC_PASS_AHEAD,
 // HC_PASS_AHEAD_GAP_US, HC_PASS_CONCURRENT, HC_DEVICE_SHARED, HC_MULTI_THREADS, HC_MULTI_SPIN_US; HC_STEP_TIMEOUT_S in hc_step.cpp --
 // INTEGRATION.md lists them; tests/test_capi_exports.py checks the list against the strings of the built library).  Everything that
-// exists for sweeps, A/B runs and fault injection -- tile counts, chunk lengths, kernel variants, the canary switch -- is read by the
+// exists for sweeps, A/B runs and fault injection -- tile counts, chunk lengths, path-forcing switches, the canary switch -- is read by the
 // TUNING build only (-DHC_TUNING: libhydrochrono_amd_tuning.so + hc_kernels_tuning.co, which the tests that need a knob load);
 // in the release build the macro is its default and the name does not exist.
 #ifdef HC_TUNING

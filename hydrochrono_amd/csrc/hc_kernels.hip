@@ -349,38 +349,24 @@ __global__ void __launch_bounds__(kConvThreads) conv_step_kernel(StepArgs a) {
 }
 
 template <int MT>
-static void launch_conv_step_mt(const StepArgs& a, int unroll, int nblocks, size_t smem, hipStream_t stream) {
-#ifdef HC_TUNING  // (unroll factors 1 and 3: sweeps only)
-    if (unroll == 1) { hipLaunchKernelGGL((conv_step_kernel<MT, 1>), dim3(nblocks), dim3(kConvThreads), smem, stream, a); return; }
-    if (unroll == 3) { hipLaunchKernelGGL((conv_step_kernel<MT, 3>), dim3(nblocks), dim3(kConvThreads), smem, stream, a); return; }
-#endif
-    (void)unroll;
-    hipLaunchKernelGGL((conv_step_kernel<MT, 2>), dim3(nblocks), dim3(kConvThreads), smem, stream, a);
+static void launch_conv_step_mt(const StepArgs& a, int nblocks, size_t smem, hipStream_t stream) {
+    hipLaunchKernelGGL((conv_step_kernel<MT, StepLaunch::U>), dim3(nblocks), dim3(kConvThreads), smem, stream, a);
 }
 
 StepLaunch step_launch_config(const StepArgs& a, int mt) {
     StepLaunch l;
     l.nblocks = ((a.nchunks_rad + a.nchunks_ex + 7) >> 3) * 8 * a.ngroups;  // octets of chunks (kernel's block mapping)
-#ifdef HC_TUNING
-    static const int unroll = [] {
-        const char* e = std::getenv("HC_CONV_UNROLL");
-        return e ? std::atoi(e) : 2;
-    }();
-#else
-    constexpr int unroll = 2;
-#endif
     l.smem = (size_t)a.rhs_capacity * sizeof(double) + (size_t)max(1, a.max_steps_per_chunk) * (sizeof(Bracket) + sizeof(double));
     l.MT   = (mt == 4 || mt == 2) ? mt : 1;
-    l.U    = (unroll == 1 || unroll == 3) ? unroll : 2;
     return l;
 }
 
 void launch_conv_step(const StepArgs& a, int mt, hipStream_t stream) {
     const StepLaunch l = step_launch_config(a, mt);
     if (l.nblocks <= 0) return;
-    if (l.MT == 4) launch_conv_step_mt<4>(a, l.U, l.nblocks, l.smem, stream);
-    else if (l.MT == 2) launch_conv_step_mt<2>(a, l.U, l.nblocks, l.smem, stream);
-    else launch_conv_step_mt<1>(a, l.U, l.nblocks, l.smem, stream);
+    if (l.MT == 4) launch_conv_step_mt<4>(a, l.nblocks, l.smem, stream);
+    else if (l.MT == 2) launch_conv_step_mt<2>(a, l.nblocks, l.smem, stream);
+    else launch_conv_step_mt<1>(a, l.nblocks, l.smem, stream);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -918,169 +904,7 @@ __device__ __forceinline__ void block_rad_stream_uni(const BlockArgs& a, const i
     }
 }
 
-#ifdef HC_TUNING
-// Depth 64, second form (tuning build; EXPERIMENTS.md): the first form above issues the MT + 2*NB loads of a fragment and their address
-// arithmetic in one run behind the fragment's 8*MT MFMAs, and a wave alone on its SIMD issues in order -- the counters of profiles/r05 show
-// that run (about 600 cycles per fragment of 3072 matrix-pipe cycles) exposed, not hidden: only what is issued within the 64 cycles of
-// the last MFMA runs in its shadow.  Here the loads of the fragment NS - 1 ahead go out one at a time BETWEEN the MFMAs of the fragment
-// being consumed (one load behind every MT/2 MFMAs), into a register slot that is not being read (NS slots, NS - 1 fragments in flight).
-template <int MT, int NS, int NB, int VAR = 0>
-__device__ __forceinline__ void block_rad_stream_il(const BlockArgs& a, const int chunk, const int grp, double* red, double* t_wo, double* t_wn,
-                                                    int* t_oo, int* t_on) {
-    constexpr int L = 16 * NB;
-    static_assert(MT % 2 == 0 && MT + 2 * NB <= 4 * NB, "one load behind every half group of MFMAs");
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int kk = lane >> 4, jstep = lane & 15;
-    const int D = a.hist.D;
-    const int gp0 = chunk * a.chunk_gp;
-    const int gp1 = min((a.F + 7) >> 3, gp0 + a.chunk_gp);
-    const int s0  = (gp0 * 8) / D;
-    const int ns  = (min(a.F, gp1 * 8) - 1) / D - s0 + 1;
-    const int s_live = a.F / D;
-    const int Hc     = a.hist.HcapT;
-
-    dvec4 acc[NB][MT];
-#pragma unroll
-    for (int tb = 0; tb < NB; ++tb)
-#pragma unroll
-        for (int m = 0; m < MT; ++m) acc[tb][m] = dvec4{0.0, 0.0, 0.0, 0.0};
-    const char* __restrict__ kb    = reinterpret_cast<const char*>(a.K.base) + ((size_t)(grp * MT) * a.K.ngp) * 1024;
-    const size_t tile_bytes        = (size_t)a.K.ngp * 1024;
-    const unsigned lane16          = (unsigned)lane * 16u;
-    const char* __restrict__ ringb = reinterpret_cast<const char*>(a.hist.ring_vT);
-    const unsigned col_bytes       = (unsigned)Hc * 8u;
-
-    dvec2 kv[NS][MT];
-    dvec2u von[NS][2][NB];
-
-    build_block_table<L, true>(a, chunk, s0, ns, s_live, t_wo, t_wn, t_oo, t_on);
-    __syncthreads();
-
-    // ---- issue side ----
-    int gp_i = gp0 + wave;
-    int s_i = (gp_i * 8) / D, cb_i = gp_i * 8 - s_i * D;
-    unsigned cby = (unsigned)(cb_i + kk) * col_bytes;
-    const unsigned cby0 = cby;
-    unsigned boo[NB];
-    auto load_offsets = [&]() {
-        const int ks  = s_i - s0;
-        const bool in = ks >= 0 && ks < ns;
-#pragma unroll
-        for (int tb = 0; tb < NB; ++tb) boo[tb] = (unsigned)t_oo[(in ? ks : 0) * L + 16 * tb + jstep];
-    };
-    load_offsets();
-    // load number k of the fragment at the issue-side trackers: K tiles first (the long latency), then the gathers
-    // VAR > 0 (timing bounds of EXPERIMENTS.md, results wrong): 1 = the loop issues no gathers, 2 = no loads at all, 3 = MFMAs only
-    auto issue_part = [&](const int slot, const int k, const char* __restrict__ kg, const bool in_loop = false) {
-        if (in_loop && (VAR == 2 || VAR == 3)) return;
-        if (in_loop && VAR == 1 && k >= MT) return;
-        // VAR 4: the gathers stay on the chunk's first 8 columns (cache hits); 5: K loads without the non-temporal hint; 6: the K loads of a
-        // fragment from 6 KB in a row (one stream per wave instead of MT) -- timing bounds as well
-        if (k < MT) {
-            if constexpr (VAR == 5) kv[slot][k] = *reinterpret_cast<const dvec2*>(kg + k * tile_bytes + lane16);
-            else if constexpr (VAR == 6) kv[slot][k] = __builtin_nontemporal_load(reinterpret_cast<const dvec2*>(kb + ((size_t)(kg - kb) * MT + k * 1024 + lane16)));
-            else kv[slot][k] = __builtin_nontemporal_load(reinterpret_cast<const dvec2*>(kg + k * tile_bytes + lane16));
-        } else if (k < MT + 2 * NB) {
-            const int q = k - MT, h = q / NB, tb = q % NB;
-            von[slot][h][tb] = *reinterpret_cast<const dvec2u*>(ringb + ((VAR == 4 ? cby0 : cby) + (unsigned)(4 * h) * col_bytes + boo[tb]));
-        }
-    };
-    auto issue_advance = [&]() {
-        gp_i += 4;
-        cb_i += 32;
-        cby += 32u * col_bytes;
-        if (cb_i >= D) {
-            do {
-                cb_i -= D;
-                cby -= (unsigned)D * col_bytes;
-                ++s_i;
-            } while (cb_i >= D);
-            load_offsets();
-        }
-    };
-
-    // ---- consume side ----
-    int gp_c = gp0 + wave;
-    int s_c = (gp_c * 8) / D, cb_c = gp_c * 8 - s_c * D;
-    double cwo[NB], cwn[NB];
-    auto load_weights = [&]() {
-        const int ks  = s_c - s0;
-        const bool in = ks >= 0 && ks < ns;
-#pragma unroll
-        for (int tb = 0; tb < NB; ++tb) {
-            const int k = (in ? ks : 0) * L + 16 * tb + jstep;
-            cwo[tb]     = in ? t_wo[k] : 0.0;
-            cwn[tb]     = in ? t_wn[k] : 0.0;
-        }
-    };
-    load_weights();
-
-    const int nfrag = (gp1 - gp0 - wave + 3) / 4;
-#pragma unroll
-    for (int r = 0; r < NS - 1; ++r) {
-        const char* __restrict__ kg = kb + (size_t)min(gp_i, gp1 - 1) * 1024;
-#pragma unroll
-        for (int k = 0; k < MT + 2 * NB; ++k) issue_part(r, k, kg);
-        issue_advance();
-    }
-    for (int i = 0; i < nfrag; i += NS) {
-#pragma unroll
-        for (int r = 0; r < NS; ++r) {
-            constexpr int H = MT / 2;
-            const int is = (r + NS - 1) % NS;  // free: consumed in the step before
-            const char* __restrict__ kg = kb + (size_t)min(gp_i, gp1 - 1) * 1024;  // past the end of the chunk: the last column group again (never consumed)
-            if (gp_c < gp1) {
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int h = 0; h < 2; ++h)
-#pragma unroll
-                    for (int tb = 0; tb < NB; ++tb) {
-                        const double u = VAR == 3 ? cwo[tb] : fma(cwo[tb], von[r][h][tb].x, cwn[tb] * von[r][h][tb].y);  // (the expression of the other depths: rounds alike)
-#pragma unroll
-                        for (int m = 0; m < H; ++m) acc[tb][m] = __builtin_amdgcn_mfma_f64_16x16x4f64(h == 0 ? kv[r][m].x : kv[r][m].y, u, acc[tb][m], 0, 0, 0);
-                        issue_part(is, 2 * (h * NB + tb), kg, true);
-                        __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                        for (int m = H; m < MT; ++m) acc[tb][m] = __builtin_amdgcn_mfma_f64_16x16x4f64(h == 0 ? kv[r][m].x : kv[r][m].y, u, acc[tb][m], 0, 0, 0);
-                        issue_part(is, 2 * (h * NB + tb) + 1, kg, true);
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-            } else {
-#pragma unroll
-                for (int k = 0; k < MT + 2 * NB; ++k) issue_part(is, k, kg, true);
-            }
-            issue_advance();
-            gp_c += 4;
-            cb_c += 32;
-            if (cb_c >= D) {
-                do {
-                    cb_c -= D;
-                    ++s_c;
-                } while (cb_c >= D);
-                load_weights();
-            }
-        }
-    }
-
-#pragma unroll
-    for (int tb = 0; tb < NB; ++tb) {
-        __syncthreads();
-#pragma unroll
-        for (int m = 0; m < MT; ++m)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) red[((size_t)wave * MT + m) * 256 + (kk + 4 * r) * 16 + jstep] = acc[tb][m][r];
-        __syncthreads();
-        for (int idx = tid; idx < MT * 256; idx += kConvThreads) {
-            const int m = idx >> 8, el = idx & 255, row = el >> 4, j = el & 15;
-            const double v = ((red[(0 * MT + m) * 256 + el] + red[(1 * MT + m) * 256 + el]) + red[(2 * MT + m) * 256 + el]) + red[(3 * MT + m) * 256 + el];
-            a.partials[((size_t)chunk * L + 16 * tb + j) * a.Dpad + (grp * MT + m) * 16 + row] = v;
-        }
-    }
-}
-#endif
-
-template <int MT, int R, int NB, int WPS = ((NB == 1 && MT <= 6) ? 2 : 1)>
+template <int MT, int R, int NB, int WPS = (NB == 1 ? 2 : 1)>
 __global__ void __launch_bounds__(kConvThreads, WPS) conv_block_kernel(BlockArgs a) {
     // dynamic LDS: [front: cross-wave reduction buffer / U tiles of the excitation items][bracket table, SoA: wo', wn', off_older, off_newer]
     extern __shared__ __align__(16) unsigned char smem_raw[];
@@ -1102,11 +926,6 @@ __global__ void __launch_bounds__(kConvThreads, WPS) conv_block_kernel(BlockArgs
     // the per-DoF ring must be addressable with 32-bit byte offsets for the scalar-base form (4 GB: far beyond any real history)
     if constexpr (NB > 2) {
         // depth 64 (experimental): the uniform form only -- the host selects this depth for D % 8 == 0 systems
-#ifdef HC_TUNING
-        if constexpr (R >= 13 && MT % 2 == 0) block_rad_stream_il<MT, 3, NB, R - 12>(a, chunk, grp, front, t_wo, t_wn, t_oo, t_on);  // R = 13 ... 18: timing bounds (wrong results)
-        else if constexpr (R >= 10 && MT % 2 == 0) block_rad_stream_il<MT, R - 8, NB>(a, chunk, grp, front, t_wo, t_wn, t_oo, t_on);  // R = 11 / 12: the interleaved form with 3 / 4 slots
-        else
-#endif
         block_rad_stream_uni<MT, R, NB>(a, chunk, grp, front, t_wo, t_wn, t_oo, t_on);
     } else {
         if ((a.hist.D & 7) == 0 && (size_t)a.hist.D * a.hist.HcapT < ((size_t)1 << 28)) block_rad_stream_uni<MT, R, NB>(a, chunk, grp, front, t_wo, t_wn, t_oo, t_on);
@@ -1114,13 +933,12 @@ __global__ void __launch_bounds__(kConvThreads, WPS) conv_block_kernel(BlockArgs
     }
     // The excitation force depends on time only: its work items over Kex (a fraction of a percent of K) for the predicted times ride
     // at the end of radiation workgroups, so the launch keeps its number of workgroups (grid rounds on the chip).  An item is
-    // (excitation chunk, block of 16 steps, group of MTE row tiles) and takes about 8 us of dependent loads (free-surface table
+    // (excitation chunk, block of 16 steps, group of MT row tiles) and takes about 8 us of dependent loads (free-surface table
     // -> LDS -> MFMA).  Workgroups take items from a counter as they finish their radiation chunk: the radiation chunks end
     // over a span of 10-15 us (HBM channels are not perfectly even), so the early finishers absorb the items and the launch
     // ends with its slowest radiation chunk.  (Stacked on the first 16 workgroups the items were a 28 us tail at C3; dealt one
     // per workgroup, 8 us.)  Every item writes its own partials, so the result does not depend on who computes it.
-    constexpr int MTE = MT > 6 ? 6 : MT;  // row tiles per excitation work item (register budget of the LDS-staged form)
-    const int RG      = a.ngroups * (MT / MTE);
+    const int RG      = a.ngroups;
     const int n_items = a.nchunks_ex * NB * RG;
     if (n_items > 0) {
         __shared__ int s_item;
@@ -1131,7 +949,7 @@ __global__ void __launch_bounds__(kConvThreads, WPS) conv_block_kernel(BlockArgs
             const int it = s_item;
             if (it >= n_items) break;
             const int e = it / (NB * RG), rem = it - e * (NB * RG), tb = rem / RG, rg = rem - tb * RG;
-            block_exc_work<MTE>(a, rg, e, 16 * tb, front);
+            block_exc_work<MT>(a, rg, e, 16 * tb, front);
         }
     }
 }
@@ -1144,25 +962,12 @@ static void allow_dynamic_lds(KernelT kernel, size_t smem, size_t& granted) {
     }
 }
 
-template <int MT, int R, int R32 = R + 1>
+template <int MT, int R>
 static void launch_conv_block_mt(const BlockArgs& b, int nblocks, size_t smem, hipStream_t stream) {
     static size_t granted16 = 0, granted32 = 0;
     if (b.depth == 32) {
-#ifdef HC_TUNING  // variants of the depth-32 pass measured and not taken (EXPERIMENTS.md): the tuning build keeps them selectable
-        static const int v32 = [] { const char* e = std::getenv("HC_BLOCK_V32"); return e ? std::atoi(e) : 0; }();
-        if constexpr (MT == 4) {
-            if (v32 == 1) { hipLaunchKernelGGL((conv_block_kernel<4, 3, 2, 2>), dim3(nblocks), dim3(kConvThreads), smem, stream, b); return; }
-            if (v32 == 2) { hipLaunchKernelGGL((conv_block_kernel<4, 4, 2, 1>), dim3(nblocks), dim3(kConvThreads), smem, stream, b); return; }
-            if (v32 == 3) { hipLaunchKernelGGL((conv_block_kernel<4, 6, 2, 1>), dim3(nblocks), dim3(kConvThreads), smem, stream, b); return; }
-        }
-        if constexpr (MT == 6) {
-            if (v32 == 4) { hipLaunchKernelGGL((conv_block_kernel<6, 5, 2, 1>), dim3(nblocks), dim3(kConvThreads), smem, stream, b); return; }
-            if (v32 == 5) { hipLaunchKernelGGL((conv_block_kernel<6, 3, 2, 1>), dim3(nblocks), dim3(kConvThreads), smem, stream, b); return; }
-            if (v32 == 6) { hipLaunchKernelGGL((conv_block_kernel<6, 6, 2, 1>), dim3(nblocks), dim3(kConvThreads), smem, stream, b); return; }
-        }
-#endif
-        allow_dynamic_lds(conv_block_kernel<MT, R32, 2>, smem, granted32);
-        hipLaunchKernelGGL((conv_block_kernel<MT, R32, 2>), dim3(nblocks), dim3(kConvThreads), smem, stream, b);
+        allow_dynamic_lds(conv_block_kernel<MT, R + 1, 2>, smem, granted32);
+        hipLaunchKernelGGL((conv_block_kernel<MT, R + 1, 2>), dim3(nblocks), dim3(kConvThreads), smem, stream, b);
     } else {
         allow_dynamic_lds(conv_block_kernel<MT, R, 1>, smem, granted16);
         hipLaunchKernelGGL((conv_block_kernel<MT, R, 1>), dim3(nblocks), dim3(kConvThreads), smem, stream, b);
@@ -1170,38 +975,12 @@ static void launch_conv_block_mt(const BlockArgs& b, int nblocks, size_t smem, h
 }
 
 #ifdef HC_TUNING
-// depth 64 (NB = 4; tuning build only -- measured in round 5 and not taken, EXPERIMENTS.md): MT row tiles per workgroup x R fragments in
-// flight, both from the environment for the sweep of profiles/r05 (HC_BLOCK64_R; the tile count comes with the launch)
-static int block64_R() {
-    static const int r = [] { const char* e = std::getenv("HC_BLOCK64_R"); const int v = e ? std::atoi(e) : 4; return (v == 2 || v == 3 || v == 5 || (v >= 11 && v <= 18)) ? v : 4; }();
-    return r;
-}
-template <int MT>
-static void launch_conv_block64_mt(const BlockArgs& b, int nblocks, size_t smem, hipStream_t stream) {
-    static size_t granted[5] = {0, 0, 0, 0, 0};
-    const int R = block64_R();
-    if constexpr (MT == 3) {
-        // two workgroups per CU (two waves per SIMD, 256 registers each): the matrix pipe of a SIMD is fed by two instruction streams
-        static size_t g3 = 0;
-        if (R == 2) { allow_dynamic_lds(conv_block_kernel<3, 2, 4, 2>, smem, g3); hipLaunchKernelGGL((conv_block_kernel<3, 2, 4, 2>), dim3(nblocks), dim3(kConvThreads), smem, stream, b); return; }
-    }
-    if constexpr (MT % 2 == 0) {
-        if (R == 11) { allow_dynamic_lds(conv_block_kernel<MT, 11, 4, 1>, smem, granted[3]); hipLaunchKernelGGL((conv_block_kernel<MT, 11, 4, 1>), dim3(nblocks), dim3(kConvThreads), smem, stream, b); return; }
-        if (R == 12) { allow_dynamic_lds(conv_block_kernel<MT, 12, 4, 1>, smem, granted[4]); hipLaunchKernelGGL((conv_block_kernel<MT, 12, 4, 1>), dim3(nblocks), dim3(kConvThreads), smem, stream, b); return; }
-        if constexpr (MT == 6) {
-            static size_t g2[3] = {0, 0, 0};
-            if (R == 13) { allow_dynamic_lds(conv_block_kernel<MT, 13, 4, 1>, smem, g2[0]); hipLaunchKernelGGL((conv_block_kernel<MT, 13, 4, 1>), dim3(nblocks), dim3(kConvThreads), smem, stream, b); return; }
-            if (R == 14) { allow_dynamic_lds(conv_block_kernel<MT, 14, 4, 1>, smem, g2[1]); hipLaunchKernelGGL((conv_block_kernel<MT, 14, 4, 1>), dim3(nblocks), dim3(kConvThreads), smem, stream, b); return; }
-            if (R == 15) { allow_dynamic_lds(conv_block_kernel<MT, 15, 4, 1>, smem, g2[2]); hipLaunchKernelGGL((conv_block_kernel<MT, 15, 4, 1>), dim3(nblocks), dim3(kConvThreads), smem, stream, b); return; }
-            static size_t g3[3] = {0, 0, 0};
-            if (R == 16) { allow_dynamic_lds(conv_block_kernel<MT, 16, 4, 1>, smem, g3[0]); hipLaunchKernelGGL((conv_block_kernel<MT, 16, 4, 1>), dim3(nblocks), dim3(kConvThreads), smem, stream, b); return; }
-            if (R == 17) { allow_dynamic_lds(conv_block_kernel<MT, 17, 4, 1>, smem, g3[1]); hipLaunchKernelGGL((conv_block_kernel<MT, 17, 4, 1>), dim3(nblocks), dim3(kConvThreads), smem, stream, b); return; }
-            if (R == 18) { allow_dynamic_lds(conv_block_kernel<MT, 18, 4, 1>, smem, g3[2]); hipLaunchKernelGGL((conv_block_kernel<MT, 18, 4, 1>), dim3(nblocks), dim3(kConvThreads), smem, stream, b); return; }
-        }
-    }
-    if (R == 3) { allow_dynamic_lds(conv_block_kernel<MT, 3, 4, 1>, smem, granted[0]); hipLaunchKernelGGL((conv_block_kernel<MT, 3, 4, 1>), dim3(nblocks), dim3(kConvThreads), smem, stream, b); }
-    else if (R == 5) { allow_dynamic_lds(conv_block_kernel<MT, 5, 4, 1>, smem, granted[2]); hipLaunchKernelGGL((conv_block_kernel<MT, 5, 4, 1>), dim3(nblocks), dim3(kConvThreads), smem, stream, b); }
-    else { allow_dynamic_lds(conv_block_kernel<MT, 4, 4, 1>, smem, granted[1]); hipLaunchKernelGGL((conv_block_kernel<MT, 4, 4, 1>), dim3(nblocks), dim3(kConvThreads), smem, stream, b); }
+// depth 64 (NB = 4; tuning build only -- measured in round 5 and not taken, EXPERIMENTS.md): kBlock64MT row tiles per workgroup, 4 fragments
+// in flight, one workgroup per CU
+static void launch_conv_block64(const BlockArgs& b, int nblocks, size_t smem, hipStream_t stream) {
+    static size_t granted = 0;
+    allow_dynamic_lds(conv_block_kernel<kBlock64MT, 4, 4, 1>, smem, granted);
+    hipLaunchKernelGGL((conv_block_kernel<kBlock64MT, 4, 4, 1>), dim3(nblocks), dim3(kConvThreads), smem, stream, b);
 }
 #endif
 
@@ -1215,20 +994,18 @@ BlockLaunch block_launch_config(const BlockArgs& a, int mt, BlockArgs* b) {
     // template arguments of the kernel this (mt, depth) runs: conv_block_kernel<MT, R, NB, WPS>
 #ifdef HC_TUNING
     if (a.depth == 64) {
-        l.MT  = (mt == 6 || mt == 4 || mt == 3) ? mt : 3;
+        l.MT  = kBlock64MT;
         l.NB  = 4;
-        l.R   = ((block64_R() >= 10 && l.MT % 2) || (block64_R() >= 13 && l.MT != 6) || (block64_R() == 2 && l.MT != 3)) ? 4 : block64_R();
-        l.WPS = l.R == 2 ? 2 : 1;
+        l.R   = 4;
+        l.WPS = 1;
         return l;
     }
-    l.MT  = (mt == 12 || mt == 6 || mt == 4 || mt == 2) ? mt : 1;  // (12 tiles per workgroup: HC_BLOCK_MT=12, measured and not taken)
-#else
-    l.MT  = (mt == 6 || mt == 4 || mt == 2) ? mt : 1;
 #endif
-    const int R16 = (l.MT == 12 || l.MT == 6) ? 3 : 4;
+    l.MT  = (mt == 6 || mt == 4 || mt == 2) ? mt : 1;
+    const int R16 = l.MT == 6 ? 3 : 4;
     l.NB  = a.depth == 32 ? 2 : 1;
-    l.R   = a.depth == 32 ? (l.MT == 12 ? 2 : R16 + 1) : R16;
-    l.WPS = (l.NB == 1 && l.MT <= 6) ? 2 : 1;
+    l.R   = a.depth == 32 ? R16 + 1 : R16;
+    l.WPS = l.NB == 1 ? 2 : 1;
     return l;
 }
 
@@ -1239,13 +1016,7 @@ void launch_conv_block(const BlockArgs& a, int mt, hipStream_t stream) {
     const size_t smem   = l.smem;
     if (nblocks <= 0) return;
 #ifdef HC_TUNING
-    if (b.depth == 64) {
-        if (mt == 6) launch_conv_block64_mt<6>(b, nblocks, smem, stream);
-        else if (mt == 4) launch_conv_block64_mt<4>(b, nblocks, smem, stream);
-        else launch_conv_block64_mt<3>(b, nblocks, smem, stream);
-        return;
-    }
-    if (mt == 12) { launch_conv_block_mt<12, 3, 2>(b, nblocks, smem, stream); return; }
+    if (b.depth == 64) { launch_conv_block64(b, nblocks, smem, stream); return; }
 #endif
     if (mt == 6) launch_conv_block_mt<6, 3>(b, nblocks, smem, stream);
     else if (mt == 4) launch_conv_block_mt<4, 4>(b, nblocks, smem, stream);
@@ -1392,16 +1163,10 @@ __device__ __forceinline__ void push_sample(const FinalizeArgs& a, const double*
 // were written by other workgroups of this very launch, possibly on other XCDs (agent-scope atomic loads, see wide_step_kernel).
 // SLOT: the state lies behind the argument block (st) and the velocities of columns tid, tid + 256, tid + 512 were requested before the
 // first argument was looked at (ev0..ev3); 6N <= 1024 (kSlotStateMaxBodies).
-// EARLY (finalize_pre_kernel): the first K words of the wave and the scatter results were requested at kernel entry, from addresses the
-// packet processor had put into scalar registers (kernel-argument preload) -- `early` holds them.
-struct EarlyLoads {
-    dvec2 pre[12];
-    double ypre[kTermMax / 16];
-};
-template <int NW, bool COHERENT, bool SLOT, bool EARLY = false, class Mid>
+template <int NW, bool COHERENT, bool SLOT, class Mid>
 __device__ __forceinline__ void finalize_tile(const FinalizeArgs& a, const int tile, double* U, double (*red_near)[16], double (*red_term)[16], Mid&& mid,
                                               StageClock& sc, const double* __restrict__ st = nullptr, double ev0 = 0.0, double ev1 = 0.0, double ev2 = 0.0,
-                                              double ev3 = 0.0, const EarlyLoads* early = nullptr) {
+                                              double ev3 = 0.0) {
     static_assert(!SLOT || NW == 4, "the early loads assume 256 work-items");
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -1460,13 +1225,9 @@ __device__ __forceinline__ void finalize_tile(const FinalizeArgs& a, const int t
     // first wait.
     const int kk = lane >> 4;
     constexpr int PRE = 12;  // C3: all 12 column groups a wave owns of one IRF sample
-    static_assert(PRE == sizeof(EarlyLoads::pre) / sizeof(dvec2), "EarlyLoads::pre");
     dvec2 pre[PRE];
     const double* __restrict__ kbase = a.nearK.base + ((size_t)tile * a.nearK.ngp) * 128 + lane * 2;
-    if constexpr (EARLY) {
-#pragma unroll
-        for (int q = 0; q < PRE; ++q) pre[q] = early->pre[q];
-    } else if (near_on) {
+    if (near_on) {
         const int f0_0 = a.near[0].s * a.D, g0_0 = f0_0 >> 3, g1_0 = (f0_0 + a.D + 7) >> 3;
 #pragma unroll
         for (int q = 0; q < PRE; ++q) {
@@ -1478,10 +1239,7 @@ __device__ __forceinline__ void finalize_tile(const FinalizeArgs& a, const int t
     // (Yc[k][row]); thread (slice = tid >> 4, row = tid & 15) requests terms slice, slice + 16, ... here, before the first wait
     constexpr int TPRE = kTermMax / 16;
     double ypre[TPRE];
-    if constexpr (EARLY) {
-#pragma unroll
-        for (int q = 0; q < TPRE; ++q) ypre[q] = early->ypre[q];
-    } else if (term_on) {
+    if (term_on) {
         const double* __restrict__ yc = a.Yc + tile * 16 + (tid & 15);
 #pragma unroll
         for (int q = 0; q < TPRE; ++q) {
@@ -1685,74 +1443,6 @@ __global__ void __launch_bounds__(64 * NW) finalize_kernel(FinalizeArgs a) {
     finalize_tile<NW, false, SLOT>(a, (int)blockIdx.x, U, red_near, red_term, [] { return true; }, sc, st, ev0, ev1, ev2, ev3);
 }
 template __global__ void finalize_kernel<4, true>(FinalizeArgs);
-
-#ifdef HC_TUNING  // (measured in round 6 and not taken, EXPERIMENTS.md: the tuning build keeps it selectable with HC_STEP_PRELOAD=1)
-// finalize_pre_kernel: finalize_kernel<4, true> whose first dependent hop is gone.  The step kernel's chain is  arguments -> K words /
-// scatter results -> right-hand side -> contraction -> totals: two memory round trips before the first multiply, the first of them to
-// uncached memory (the argument slot the host has just written through the BAR).  The ten leading kernel arguments below are
-// PRELOADED -- the packet processor reads them from the argument block while it sets the dispatch up and the waves start with them in
-// scalar registers (-mllvm -amdgpu-kernarg-preload-count, kernel descriptor field kernarg_preload_length; a firmware that does not
-// preload runs the compiler's compatibility prologue, which loads them first) -- so the K words of the wave, the scatter results and
-// the body state are all requested by the kernel's first instructions, together with the rest of the argument block:
-//   kfirst = K's panel base + the first column group of the step's own IRF sample (near[0]); ngroups = its column groups (0: none);
-//   yc / n_terms / dpad = FinalizeArgs::Yc, n_terms (0 when the step has no radiation term), Dpad; ngp = row-tile stride in groups;
-//   ntiles = row tiles of the context (the workgroup behind them stores the sample and requests nothing).
-template <int NW>
-__global__ void __launch_bounds__(64 * NW) finalize_pre_kernel(const double* __restrict__ kfirst, const double* __restrict__ yc, int ngp, int ngroups, int n_terms,
-                                                                int dpad, int ntiles, int pad_, FinalizeArgs a) {
-    static_assert(NW == 4, "the early loads assume 256 work-items");
-    extern __shared__ __align__(16) unsigned char smem_raw[];
-    double* U = reinterpret_cast<double*>(smem_raw);
-    __shared__ double red_near[NW][16];
-    __shared__ double red_term[16][16];
-    StageClock sc;
-    HC_MARK(sc, 0);
-    const double* __restrict__ st = nullptr;
-#if defined(__HIP_DEVICE_COMPILE__)
-    st = (const double*)((const char*)__builtin_amdgcn_kernarg_segment_ptr() + kSlotArgBytes);
-#endif
-    const double ev0 = st[threadIdx.x], ev1 = st[threadIdx.x + 256], ev2 = st[threadIdx.x + 512], ev3 = st[threadIdx.x + 768];
-    EarlyLoads el;
-    {
-        const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), tile = (int)blockIdx.x;
-        const bool tile_wg = tile < ntiles;
-        const double* __restrict__ kb = kfirst + ((size_t)(tile_wg ? tile : 0) * ngp) * 128 + lane * 2;
-#pragma unroll
-        for (int q = 0; q < 12; ++q) {
-            const int gp = wave + NW * q;
-            el.pre[q]    = (tile_wg && gp < ngroups) ? *reinterpret_cast<const dvec2*>(kb + (size_t)gp * 128) : dvec2{0.0, 0.0};
-        }
-        const double* __restrict__ y = yc + (tile_wg ? tile : 0) * 16 + (tid & 15);
-#pragma unroll
-        for (int q = 0; q < kTermMax / 16; ++q) {
-            const int k = (tid >> 4) + 16 * q;
-            el.ypre[q]  = (tile_wg && k < n_terms) ? y[(size_t)k * dpad] : 0.0;
-        }
-    }
-#if defined(__HIP_DEVICE_COMPILE__)
-    __builtin_amdgcn_sched_barrier(0);  // (all of the above goes out BEFORE the first wait for an argument)
-#endif
-    touch_args<sizeof(FinalizeArgs) + 40>();
-    HC_MARK(sc, 1);
-    (void)pad_;
-    if (a.do_push && (int)blockIdx.x == a.nblocks - 1) {
-        push_sample<NW, true>(a, st);
-#ifdef HC_TUNING
-        if (HC_STAMPS(a)) {
-            HC_MARK(sc, 8);
-#if defined(__HIP_DEVICE_COMPILE__)
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#endif
-            HC_MARK(sc, 9);
-            sc.store(HC_STAMPS(a));
-        }
-#endif
-        return;
-    }
-    finalize_tile<NW, false, true, true>(a, (int)blockIdx.x, U, red_near, red_term, [] { return true; }, sc, st, ev0, ev1, ev2, ev3, &el);
-}
-template __global__ void finalize_pre_kernel<4>(const double*, const double*, int, int, int, int, int, int, FinalizeArgs);
-#endif
 
 // ------------------------------------------------------------------------------------------------
 // step_hot_kernel<NE>: the step kernel of the common block step (StepHotArgs, hc_kernels.hpp), written around what the stage clock of

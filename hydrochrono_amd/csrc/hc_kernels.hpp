@@ -237,16 +237,6 @@ struct FinalizeArgs {
 #endif
 };
 
-// finalize_pre_kernel's arguments as the kernel lays them out: ten preloaded words in front of the step kernel's argument block
-// (hc_kernels.hip; filled by hc_step.cpp: enqueue_step)
-struct FinalizePreArgs {
-    const double* kfirst;
-    const double* yc;
-    int ngp, ngroups, n_terms, dpad, ntiles, pad_;
-    FinalizeArgs a;
-};
-static_assert(offsetof(FinalizePreArgs, a) == 40, "kernarg layout of finalize_pre_kernel");
-
 // step_hot_kernel: the step kernel of the COMMON block step -- a step inside a look-ahead block of a system that is not wide, direct
 // dispatch with the body state behind the arguments, the step's own IRF samples weighted against its own velocity only (NE = 1 or 2 of
 // them), no plain partials, no spectral wave mode -- with a compact argument block of its own.  Everything finalize_kernel<4, true>
@@ -372,7 +362,8 @@ FinalizeLaunch finalize_launch_config(FinalizeArgs& a);  // also fills a.nblocks
 struct StepLaunch {
     int nblocks = 0;
     size_t smem = 0;
-    int MT = 0, U = 0;  // conv_step_kernel<MT, U>
+    int MT = 0;                 // conv_step_kernel<MT, U>
+    static constexpr int U = 2;  // unroll factor of its column loop
 };
 StepLaunch step_launch_config(const StepArgs& a, int mt);
 struct BlockLaunch {

@@ -99,7 +99,7 @@ PassSetup make_pass(hc_ctx* c, bool with_exc, bool next_block, bool head_only) {
     b.Dpad        = c->Dpad;
     b.error_flag  = c->d_err.p;
     b.item_counter = c->d_err.p + 1;
-    b.ngroups     = c->ntiles / (L == 64 ? c->mt_block64 : c->mt_block);
+    b.ngroups     = c->ntiles / (L == 64 ? hc::kBlock64MT : c->mt_block);
     // algorithmic bytes: summed over the steps of the block, step j's share of K and of the velocity vector from s_cut[j]
     // on ...; what the launch has to move once: the live part of K, Kex and the staged vectors
     double samples = 0.0;
@@ -134,7 +134,7 @@ void issue_pass_chunks(hc_ctx* c, const PassSetup& ps, int first, int last, bool
     c->prof.block_kernel_bytes_once = rad_once + exc_once;
     const double exc_share = exc_once / std::max(1.0, rad_once + exc_once);
     const int L  = c->lookahead;
-    const int mt = L == 64 ? c->mt_block64 : c->mt_block;
+    const int mt = L == 64 ? hc::kBlock64MT : c->mt_block;
     if (direct) {
         hc::BlockArgs b2;
         const hc::BlockLaunch l = hc::block_launch_config(b, mt, &b2);

@@ -331,7 +331,7 @@ void setup_panel_geometry(hc_ctx* c) {
     // the pass once K streams at the HBM rate (C3: 415 / 277 us with 4 / 6 tiles at depth 32 before the per-DoF ring).
     // The design value comes from the UNSHARDED tile count (the chunk length below must not depend on the rows owned).
     auto pick = [](int tiles, int limit) {
-        for (int m : {12, 6, 4, 2, 1})
+        for (int m : {6, 4, 2, 1})
             if (m <= limit && tiles % m == 0) return m;
         return 1;
     };
@@ -394,9 +394,9 @@ void choose_conv_config(hc_ctx* c) {
     } else {
         // row groups of the UNSHARDED system (6 tiles each): few of them (small systems) need more chunks to fill a round.
         // Two workgroups fit on a CU at depth 16, one at depth 32 (twice the accumulators).
-        const int mt_design         = c->lookahead > 32 ? c->mt_block64 : c->mt_block_design;
+        const int mt_design         = c->lookahead > 32 ? hc::kBlock64MT : c->mt_block_design;
         const long long groups_full = std::max<long long>(1, ((c->D + 15) / 16 + mt_design - 1) / mt_design);
-        const long long slots       = ((c->lookahead > 16 || c->mt_block_design > 6) ? 1LL : 2LL) * c->num_cus;
+        const long long slots       = (c->lookahead > 16 ? 1LL : 2LL) * c->num_cus;
         const long long nch_target  = std::max<long long>(slots / 4, (slots + groups_full - 1) / groups_full);
         bgps                       = (c->ngp + nch_target - 1) / nch_target;
         bgps                       = std::min<long long>(bgps, std::max<long long>(16, (16LL * c->D) / 8));  // <= 16 IRF samples per chunk
@@ -719,7 +719,6 @@ __attribute__((constructor)) static void request_device_memory_queue_rings() {
 void setup_direct(hc_ctx* c) {
     c->direct_ready = false;
     if (env_int("HC_DIRECT", 1) == 0) { c->direct_why = "disabled by HC_DIRECT=0"; return; }
-    if (HC_TUNE_INT("HC_BLOCK_V32", 0) != 0) { c->direct_why = "HC_BLOCK_V32 selects a tuning variant of the pass"; return; }
     if (!c->bar_state.host_ok || !c->bar_am.host_ok || !c->bar_selftest.host_ok) { c->direct_why = "the device's memory is not host-addressable"; return; }
     std::unique_ptr<hc::DirectQueue> q(new hc::DirectQueue);
     std::string why;
@@ -732,11 +731,6 @@ void setup_direct(hc_ctx* c) {
     if (c->dk_wide.kernarg != sizeof(hc::WideStepArgs) || c->dk_wide.priv != 0) c->dk_wide = hc::DirectKernel{};
     if (c->dk_finalize_slot.kernarg != sizeof(hc::FinalizeArgs) || c->dk_finalize_slot.priv != 0) c->dk_finalize_slot = hc::DirectKernel{};
     c->slot_state = HC_TUNE_INT("HC_SLOT_STATE", 1) != 0 && c->dk_finalize_slot.ok() && c->N <= hc::kSlotStateMaxBodies;
-#ifdef HC_TUNING
-    c->dk_finalize_pre = q->find("finalize_pre_kernelILi4EEEv");  // (the kernel-argument-preload experiment of round 6)
-    if (c->dk_finalize_pre.kernarg != sizeof(hc::FinalizePreArgs) || c->dk_finalize_pre.priv != 0) c->dk_finalize_pre = hc::DirectKernel{};
-    c->step_preload = c->slot_state && c->dk_finalize_pre.ok() && HC_TUNE_INT("HC_STEP_PRELOAD", 0) != 0;
-#endif
     c->dk_step_hot[0] = q->find("step_hot_kernelILi1EEEv");  // optional: without them the general step kernel runs every step
     c->dk_step_hot[1] = q->find("step_hot_kernelILi2EEEv");
     for (auto& k : c->dk_step_hot)
@@ -756,7 +750,7 @@ void setup_direct(hc_ctx* c) {
         a.ngroups = 1;
         const hc::StepLaunch l = hc::step_launch_config(a, c->mt);
         char frag[64];
-        std::snprintf(frag, sizeof frag, "conv_step_kernelILi%dELi%dEEEv", l.MT, l.U);
+        std::snprintf(frag, sizeof frag, "conv_step_kernelILi%dELi%dEEEv", l.MT, hc::StepLaunch::U);
         c->dk_step = q->find(frag);
         if (c->dk_step.kernarg != sizeof(hc::StepArgs) || c->dk_step.priv != 0) c->dk_step = hc::DirectKernel{};
     }
@@ -782,7 +776,7 @@ void setup_direct(hc_ctx* c) {
         hc::BlockArgs a{}, b{};
         a.depth   = 64;
         a.ngroups = 1;
-        const hc::BlockLaunch l = hc::block_launch_config(a, c->mt_block64, &b);
+        const hc::BlockLaunch l = hc::block_launch_config(a, hc::kBlock64MT, &b);
         char frag[96];
         std::snprintf(frag, sizeof frag, "conv_block_kernelILi%dELi%dELi%dELi%dEEEv", l.MT, l.R, l.NB, l.WPS);
         c->dk_block64 = q->find(frag);

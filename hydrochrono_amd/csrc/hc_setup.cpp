@@ -523,8 +523,6 @@ int hc_finalize(hc_ctx* c) {
     {
         const int want = HC_TUNE_INT("HC_LOOKAHEAD", 32);
         c->lookahead   = want <= 0 ? 0 : (want <= 16 ? 16 : hc::kDepthDefault);
-        c->mt_block64  = HC_TUNE_INT("HC_BLOCK64_MT", 3);
-        if (c->mt_block64 != 3 && c->mt_block64 != 4 && c->mt_block64 != 6) c->mt_block64 = 3;
         c->pass_ahead  = default_pass_ahead(c);  // hc_set_pass_schedule
         c->pass_slices = default_pass_slices(c);
         // the gap beyond which "one block ahead" pays (profiles/r05/ahead_probe_fine_gaps.txt): C3 -- 0 - 3 us: the schedules within

@@ -203,9 +203,7 @@ void enqueue_tail(hc_ctx* c) {
             pass_lane_drain(c);
         }
     }
-    static const bool skip_scatter = HC_TUNE_INT("HC_SKIP_SCATTER", 0) != 0;  // (tuning build: timing bound only -- the forces are wrong)
-    if (scatter_now && skip_scatter) {
-    } else if (scatter_now) {
+    if (scatter_now) {
         to_background();
         launch_scatter_of(c, m, bs, direct);
     } else if (block && c->plan.sub > 0 && m < c->lookahead && m % c->plan.sub == 0 && c->plan.mini_s_hi[m] >= 0) {
@@ -687,25 +685,9 @@ void dispatch_step_kernel(StepJob& j, hc::FinalizeArgs& z) {
         if (hot) {
             const hc::StepHotArgs h = hot_step_args(c, z);
             const size_t lds = static_cast<size_t>(z.n_near) * (c->D + 16) * sizeof(double);  // (own samples' right-hand sides between zero pads)
-            static const bool no_acquire = HC_TUNE_INT("HC_STEP_NO_ACQUIRE", 0) != 0;  // (tuning experiment: timing only, EXPERIMENTS.md round 6)
             c->dq->dispatch(c->dk_step_hot[z.n_near - 1], static_cast<uint32_t>(h.ntiles + 1), 256, static_cast<uint32_t>(lds), &h, sizeof h, direct_tag(c, hc::kEvStep), 0.0,
-                            0, fill_slot_state, &fill, no_acquire);
+                            0, fill_slot_state, &fill);
             c->prof.hot_steps += 1;
-        } else if (c->step_preload) {
-            // (tuning experiment) the addresses of the step kernel's first loads in front of its argument block, where the packet processor preloads them
-            hc::FinalizePreArgs pz{};
-            const bool near_on = z.do_rad && z.n_near > 0;
-            const int f0 = near_on ? z.near[0].s * c->D : 0, g0 = f0 >> 3, g1 = (f0 + c->D + 7) >> 3;
-            pz.kfirst  = z.nearK.base + static_cast<size_t>(near_on ? g0 : 0) * 128;
-            pz.ngroups = near_on ? g1 - g0 : 0;
-            pz.ngp     = z.nearK.ngp;
-            pz.yc      = z.Yc;
-            pz.n_terms = (z.do_rad && z.Yc) ? z.n_terms : 0;
-            pz.dpad    = c->Dpad;
-            pz.ntiles  = c->ntiles;
-            pz.a       = z;
-            c->dq->dispatch(c->dk_finalize_pre, static_cast<uint32_t>(l.grid), 256, static_cast<uint32_t>(l.smem), &pz, sizeof pz, direct_tag(c, hc::kEvStep), 0.0, 0,
-                            fill_slot_state, &fill);
         } else {
             c->dq->dispatch(c->dk_finalize_slot, static_cast<uint32_t>(l.grid), 256, static_cast<uint32_t>(l.smem), &z, sizeof z, direct_tag(c, hc::kEvStep), 0.0, 0,
                             fill_slot_state, &fill);
@@ -1355,7 +1337,7 @@ int hc_set_lookahead(hc_ctx* c, int steps) {
     if (c->lookahead == 64) c->lookahead = 32;  // (depth 64 exists in the tuning build only: measured in round 5 and not taken, EXPERIMENTS.md)
 #endif
     // depth 64 (tuning build, profiles/r05): the single-level form of D % 8 == 0 systems with the pass at block start, direct or not
-    if (c->lookahead == 64 && ((c->D & 7) != 0 || c->D < 32 || hc::near_slices_for(c->D) > 1 || c->ntiles % c->mt_block64 != 0 ||
+    if (c->lookahead == 64 && ((c->D & 7) != 0 || c->D < 32 || hc::near_slices_for(c->D) > 1 || c->ntiles % hc::kBlock64MT != 0 ||
                                (c->direct_ready && !c->dk_block64.ok()))) c->lookahead = 32;
     choose_conv_config(c);  // the pass chunking depends on the depth
     alloc_partials(c);
@@ -1408,7 +1390,7 @@ int hc_tuning_time_pass(hc_ctx* c, int depth, int reps, double* mean_us, double*
     require(c->finalized && mean_us, HC_ERR_INVALID, "bad arguments");
     require(depth == 16 || depth == 32 || depth == 64, HC_ERR_INVALID, "depth must be 16, 32 or 64");
     require(c->times.size() >= 2 && (c->D & 7) == 0, HC_ERR_INVALID, "needs a history of two samples and D % 8 == 0");
-    require(depth < 64 || c->ntiles % c->mt_block64 == 0, HC_ERR_INVALID, "row tiles not divisible by HC_BLOCK64_MT");
+    require(depth < 64 || c->ntiles % hc::kBlock64MT == 0, HC_ERR_INVALID, "row tiles not divisible by the depth-64 pass's tiles per workgroup");
     HC_HIP(hipDeviceSynchronize());
     c->lookahead = depth;
     choose_conv_config(c);
@@ -1429,7 +1411,7 @@ int hc_tuning_time_pass(hc_ctx* c, int depth, int reps, double* mean_us, double*
     hipEvent_t a, b;
     HC_HIP(hipEventCreate(&a));
     HC_HIP(hipEventCreate(&b));
-    const int mt = depth == 64 ? c->mt_block64 : c->mt_block;
+    const int mt = depth == 64 ? hc::kBlock64MT : c->mt_block;
     hc::launch_conv_block(ps.b, mt, c->stream);  // warm
     HC_HIP(hipStreamSynchronize(c->stream));
     // every launch timed on its own, with `pause` of idle GPU in front of it (HC_TUNING_PASS_PAUSE_US, default 0 = back to back): passes

@@ -82,6 +82,10 @@ OPERATIONAL_SWITCHES = {"HC_DIRECT", "HC_ARM", "HC_PASS_AHEAD", "HC_PASS_AHEAD_G
                         "HC_MULTI_SPIN_US", "HC_STEP_TIMEOUT_S", "HC_QUEUE_DEV_MEM", "HC_MULTI_PIN", "HC_HDP_FLUSH"}
 
 
+REMOVED_SWITCHES = ("HC_BLOCK_V32", "HC_CONV_UNROLL", "HC_BLOCK64_R", "HC_BLOCK64_MT", "HC_STEP_PRELOAD", "HC_STEP_NO_ACQUIRE", "HC_ARM_DEVICE_GATE",
+                    "HC_SKIP_SCATTER")
+
+
 def _hc_names(path):
     blob = open(path, "rb").read()
     return {m.decode() for m in re.findall(rb"(?<![A-Za-z0-9_])(HC_[A-Z][A-Z0-9_]+)\x00", blob)}
@@ -99,8 +103,13 @@ def test_release_library_reads_operational_switches_only():
     for n in OPERATIONAL_SWITCHES:
         assert n in doc, f"{n} is read by the release library but not documented in INTEGRATION.md"
     tuning = _hc_names(hb.TUNING_LIB)
-    for n in ("HC_SUB_BLOCK", "HC_MINI_NARROW", "HC_WIDE_FUSED", "HC_SLOT_STATE", "HC_STEP_CANARY", "HC_FAULT_STALE_STATE_AT", "HC_BLOCK_MT", "HC_BLOCK_V32"):
+    for n in ("HC_SUB_BLOCK", "HC_MINI_NARROW", "HC_WIDE_FUSED", "HC_SLOT_STATE", "HC_STEP_CANARY", "HC_FAULT_STALE_STATE_AT", "HC_BLOCK_MT"):
         assert n in tuning and n not in names, n
+    # the switches of the experiments whose code was removed (EXPERIMENTS.md) are in neither library, in any string
+    blobs = {lib: open(lib, "rb").read() for lib in (hb.MAIN_LIB, hb.TUNING_LIB)}
+    for n in REMOVED_SWITCHES:
+        for lib, blob in blobs.items():
+            assert n.encode() not in blob, (n, os.path.basename(lib))
 
 
 def _kernel_notes(path):
@@ -119,7 +128,8 @@ def _kernel_notes(path):
 def test_release_code_object_has_no_spills_no_scratch_and_no_rejected_variants():
     """Every kernel of the shipped code object keeps its registers (no spilled VGPR, no scratch: a kernel with scratch cannot go to
     the direct queue at all), and the variants that were measured and not taken -- 12 row tiles per pass workgroup (148 spilled
-    VGPRs at depth 32), the depth-64 pass, the HC_BLOCK_V32 / unroll sweeps -- are not in it (they live in the tuning build)."""
+    VGPRs at depth 32), the depth-64 pass, the unroll sweep, the kernel-argument-preload step kernel -- are not in it.  Of these the
+    tuning build holds the depth-64 pass alone, in one form; the code of the others was removed (EXPERIMENTS.md)."""
     from hydrochrono_amd import build as hb
     rel = _kernel_notes(hb.KERNEL_CO)
     assert len(rel) >= 20
@@ -132,6 +142,11 @@ def test_release_code_object_has_no_spills_no_scratch_and_no_rejected_variants()
     assert sum("step_hot_kernel" in n for n in rel) == 2, "the step kernel of the common block step (one and two own IRF samples) is missing"
     tun = _kernel_notes(hb.TUNING_CO)
     assert len(tun) > len(rel) and any(re.search(r"conv_block_kernelILi\dELi\dELi4E", n) for n in tun)
+    depth64 = [n for n in tun if re.search(r"conv_block_kernelILi\d+ELi\d+ELi4E", n)]
+    assert len(depth64) == 1 and "conv_block_kernelILi3ELi4ELi4ELi1E" in depth64[0], depth64
+    assert not any("conv_block_kernelILi12E" in n for n in tun), "the 12-tile pass variant is back in the tuning build"
+    assert not any(re.search(r"conv_step_kernelILi\dELi[13]E", n) for n in tun), "an unroll-sweep variant of the plain kernel is back in the tuning build"
+    assert not any("finalize_pre_kernel" in n for n in tun), "the kernel-argument-preload variant of the step kernel is back in the tuning build"
 
 
 def test_wait_result_buffer_is_host_only():
