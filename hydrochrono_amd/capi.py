@@ -43,6 +43,11 @@ class MorisonElement(C.Structure):
     _fields_ = [("r", C.c_double * 3), ("cd_area", C.c_double * 3), ("cm_vol", C.c_double * 3)]
 
 
+class SurfacePanel(C.Structure):
+    """hc_surface_panel: centroid and area vector (outward normal times area) in the body frame."""
+    _fields_ = [("c", C.c_double * 3), ("s", C.c_double * 3)]
+
+
 class ProfileStats(C.Structure):
     _fields_ = [("hydrostatics_seconds", C.c_double), ("radiation_seconds", C.c_double), ("waves_seconds", C.c_double),
                 ("hydrostatics_calls", C.c_int), ("radiation_calls", C.c_int), ("waves_calls", C.c_int),
@@ -162,6 +167,12 @@ SIGNATURES = {
     "hc_morison_begin": (C.c_int, [C.c_void_p, C.c_double, c_double_p, c_double_p, c_double_p, c_double_p]),
     "hc_morison_end": (C.c_int, [C.c_void_p, c_double_p]),
     "hc_compute_morison": (C.c_int, [C.c_void_p, C.c_double, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
+    "hc_set_surface_panels": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(SurfacePanel), C.c_int]),
+    "hc_get_surface_panel_count": (C.c_int, [C.c_void_p, C.c_int, c_int_p]),
+    "hc_set_nonlinear_options": (C.c_int, [C.c_void_p, C.POINTER(WaveKinematicsOpts)]),
+    "hc_nonlinear_begin": (C.c_int, [C.c_void_p, C.c_double, c_double_p, c_double_p]),
+    "hc_nonlinear_end": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p]),
+    "hc_compute_nonlinear": (C.c_int, [C.c_void_p, C.c_double, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
     "hc_synth_fill": (C.c_int, [C.c_void_p, C.c_ulonglong, C.c_int, C.c_double, C.c_int, C.c_double]),
 }
 

@@ -266,6 +266,22 @@ struct hc_ctx {
     hc::DeviceBuffer<int> d_mor_body, d_mor_off;  // [items] body of an element, [nloc + 1] first element of an owned body
     hc::PinnedBuffer<double> h_mor_state, h_mor_out;
 
+    // Surface panels (hc_set_surface_panels, hc_nonlinear.hip): the lists of all bodies of the system on the host, those of the owned
+    // bodies flattened body-major on the device with their chunk map; its own stream, component table and pinned staging, nothing a
+    // step uses
+    std::vector<std::vector<hc_surface_panel>> nl_panels;  // [N]
+    hc_wave_kinematics_opts nl_opts{0.0, 0.0, 1};
+    hipStream_t stream_nl = nullptr;  // created by the first hc_set_surface_panels
+    bool nl_dirty = false;            // the lists have changed since the device copy was made
+    int nl_items = 0, nl_chunks = 0;  // panels of the owned bodies, chunks of up to 256 of one body's list
+    int nl_pending = 0;               // hc_nonlinear_begin without its hc_nonlinear_end: 1 zeros (nothing launched), 2 a launch is in flight
+    unsigned long long nl_serial = ~0ULL;
+    double nl_phase = 0.0;
+    int nl_nf = 0;
+    hc::DeviceBuffer<double> d_nl_tab, d_nl_panel, d_nl_state, d_nl_part, d_nl_out;
+    hc::DeviceBuffer<int> d_nl_chunk, d_nl_off;  // [chunks][3] (body, first panel, count), [nloc + 1] first chunk of an owned body
+    hc::PinnedBuffer<double> h_nl_state, h_nl_out;  // [6 N] pos | rpy of the last hc_nonlinear_begin, [nloc][12]
+
     // GEMV configuration + scratch
     int chunk_gp = 0, nchunks_rad = 0, chunk_gp_ex = 0, nchunks_ex = 0, ngp_ex = 0;
     int chunk_gp_block = 0, nchunks_block = 0;

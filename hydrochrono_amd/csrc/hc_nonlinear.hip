@@ -1,0 +1,368 @@
+// hc_nonlinear.hip -- nonlinear buoyancy and Froude-Krylov forces on body surface panels (include/hydrochrono_amd.h:
+// hc_set_surface_panels, hc_nonlinear_begin / hc_nonlinear_end).  Not in the reference (src/hydro_types.h:33 is a TODO).  Off the
+// step path, as hc_morison.hip: its own stream, component table, buffers and pinned staging; it reads and writes nothing a step
+// uses, so it is not ordered against the direct queue.  DESIGN.md 3.7d has the definition, the kernels and their invariants.
+#include "hc_internal.hpp"
+#include "hc_wave_kin.hpp"
+
+using namespace hc::detail;
+
+namespace hc {
+namespace {
+
+constexpr int kNlThreads = 256;      // work items per workgroup, one per panel: a chunk of one body's list
+constexpr int kNlPanelDoubles = 6;   // c, s
+constexpr int kNlOut = 12;           // buoy (F, M), fk (F, M)
+
+// This path's own component table, struct of arrays [kNlCols][nf]: the columns of hc_wave_kin.hpp the pressure needs and
+// omega^2 A / k in place of the velocity and acceleration amplitudes.
+enum NlCol { kNlAmp = 0, kNlOmega, kNlK, kNlPhase, kNlW2AoK, kNlInvSinh, kNlDeep, kNlCols };
+
+struct NlArgs {
+    const double* tab;  // [kNlCols][nf]; nf = 0: still water
+    int nf;
+    const double* panel;  // [items][6] (c, s), owned bodies one after the other
+    const int* chunk;     // [chunks][3]: body (of the system), first item, count (1 .. 256)
+    const double* state;  // [6 N] pos | rpy, [3N] each
+    int N;
+    double t, depth, mwl, rho, g;
+    double ramp;       // factor on p_d
+    int stretch;       // Wheeler stretching
+    int finite_depth;  // 0: water depth +inf
+    double* part;      // [chunks][12] per-chunk sums
+};
+
+// One workgroup per chunk of up to 256 panels of ONE body, one work item per panel.  The body's frame is derived once per item
+// from the same six state values (workgroup-uniform); every item sums the wave components in index order from the same LDS tiles
+// (the loop of wave_kinematics_kernel), so a panel's 12 values depend on its body's state, its own data, the table, t and the
+// options only.  Idle items of a partly filled chunk and dry panels contribute exact zeros.  The 12 components are then reduced over
+// the 256 lanes by a tree whose shape depends on the lane index alone, and lane 0 stores the chunk's 12-vector.
+__global__ void __launch_bounds__(kNlThreads) nl_panels_kernel(NlArgs a) {
+    __shared__ double s[kNlCols][kKinTile];
+    __shared__ double red[kNlOut][kNlThreads];
+    const int tid     = threadIdx.x;
+    const int b       = a.chunk[3 * blockIdx.x];
+    const int first   = a.chunk[3 * blockIdx.x + 1];
+    const int count   = a.chunk[3 * blockIdx.x + 2];
+    const bool active = tid < count;
+    const double* pn  = a.panel + static_cast<size_t>(kNlPanelDoubles) * (first + (active ? tid : 0));  // idle items read the chunk's first panel
+    const double* pos = a.state + 3 * b;
+    const double* rpy = pos + 3 * a.N;
+
+    // ---- R = Rx(rpy0) Ry(rpy1) Rz(rpy2), d = R c, p = pos + d, n = R s (the expressions of morison_items_kernel) ----
+    double sa, ca, sb, cb, sc, cc;
+    sincos(rpy[0], &sa, &ca);
+    sincos(rpy[1], &sb, &cb);
+    sincos(rpy[2], &sc, &cc);
+    const double r00 = cb * cc, r01 = -cb * sc, r02 = sb;
+    const double r10 = ca * sc + sa * sb * cc, r11 = ca * cc - sa * sb * sc, r12 = -sa * cb;
+    const double r20 = sa * sc - ca * sb * cc, r21 = sa * cc + ca * sb * sc, r22 = ca * cb;
+    const double d0 = r00 * pn[0] + r01 * pn[1] + r02 * pn[2];
+    const double d1 = r10 * pn[0] + r11 * pn[1] + r12 * pn[2];
+    const double d2 = r20 * pn[0] + r21 * pn[1] + r22 * pn[2];
+    const double n0 = r00 * pn[3] + r01 * pn[4] + r02 * pn[5];
+    const double n1 = r10 * pn[3] + r11 * pn[4] + r12 * pn[5];
+    const double n2 = r20 * pn[3] + r21 * pn[4] + r22 * pn[5];
+    const double x = pos[0] + d0, z = pos[2] + d2, t = a.t;
+
+    // ---- eta first under stretching (wave_kinematics_kernel) ----
+    double eta = 0.0;
+    if (a.stretch) {
+        for (int i0 = 0; i0 < a.nf; i0 += kKinTile) {
+            const int m = min(kKinTile, a.nf - i0);
+            __syncthreads();
+            for (int i = tid; i < m; i += kNlThreads) {
+                s[kNlAmp][i]   = a.tab[kNlAmp * a.nf + i0 + i];
+                s[kNlOmega][i] = a.tab[kNlOmega * a.nf + i0 + i];
+                s[kNlK][i]     = a.tab[kNlK * a.nf + i0 + i];
+                s[kNlPhase][i] = a.tab[kNlPhase * a.nf + i0 + i];
+            }
+            __syncthreads();
+            for (int i = 0; i < m; ++i) eta += s[kNlAmp][i] * cos(s[kNlK][i] * x - s[kNlOmega][i] * t + s[kNlPhase][i]);
+        }
+    }
+    double zs = z;
+    if (a.stretch) {
+        const double zr = z - a.mwl;
+        zs = a.finite_depth ? a.depth * (zr - eta) / (a.depth + eta) : zr - eta;
+    }
+    const double ze = zs - a.mwl;  // under stretching mwl is subtracted a second time, as in the reference
+
+    // ---- dynamic pressure sum (and eta without stretching) ----
+    double pd = 0.0, eta1 = 0.0;
+    for (int i0 = 0; i0 < a.nf; i0 += kKinTile) {
+        const int m = min(kKinTile, a.nf - i0);
+        __syncthreads();
+        for (int i = tid; i < m; i += kNlThreads) {
+#pragma unroll
+            for (int col = 0; col < kNlCols; ++col) s[col][i] = a.tab[col * a.nf + i0 + i];
+        }
+        __syncthreads();
+        for (int i = 0; i < m; ++i) {
+            const double k = s[kNlK][i];
+            const double cs = cos(k * x - s[kNlOmega][i] * t + s[kNlPhase][i]);
+            double px;
+            if (s[kNlDeep][i] != 0.0) {  // (the same branch for every item: no divergence)
+                px = exp(k * ze);
+            } else {
+                px = cosh(k * (ze + a.depth)) * s[kNlInvSinh][i];
+            }
+            eta1 += s[kNlAmp][i] * cs;
+            pd += s[kNlW2AoK][i] * px * cs;
+        }
+    }
+    if (!a.stretch) eta = eta1;
+
+    // ---- pressures, the panel's two 6-vectors at the body reference ----
+    const bool wet  = active && (z - a.mwl <= eta);
+    const double ps = -(a.rho * a.g) * (z - a.mwl);
+    const double pw = a.rho * pd * a.ramp;
+    double v[kNlOut];
+    v[0]  = -ps * n0;
+    v[1]  = -ps * n1;
+    v[2]  = -ps * n2;
+    v[3]  = d1 * v[2] - d2 * v[1];
+    v[4]  = d2 * v[0] - d0 * v[2];
+    v[5]  = d0 * v[1] - d1 * v[0];
+    v[6]  = -pw * n0;
+    v[7]  = -pw * n1;
+    v[8]  = -pw * n2;
+    v[9]  = d1 * v[8] - d2 * v[7];
+    v[10] = d2 * v[6] - d0 * v[8];
+    v[11] = d0 * v[7] - d1 * v[6];
+#pragma unroll
+    for (int k = 0; k < kNlOut; ++k) red[k][tid] = wet ? v[k] : 0.0;
+
+    // ---- fixed-shape tree over the 256 lanes: lane l adds lane l + h for h = 128, 64, ..., 1 ----
+    for (int h = kNlThreads / 2; h > 0; h >>= 1) {
+        __syncthreads();
+        if (tid < h) {
+#pragma unroll
+            for (int k = 0; k < kNlOut; ++k) red[k][tid] += red[k][tid + h];
+        }
+    }
+    if (tid == 0) {
+        double* out = a.part + static_cast<size_t>(kNlOut) * blockIdx.x;
+#pragma unroll
+        for (int k = 0; k < kNlOut; ++k) out[k] = red[k][0];
+    }
+}
+
+// One work item per (owned body, component): the serial sum over the body's chunk partials in chunk order.
+__global__ void __launch_bounds__(kNlThreads) nl_sum_kernel(const double* part, const int* off, int rows, double* out) {
+    const int row = blockIdx.x * kNlThreads + threadIdx.x;
+    if (row >= rows) return;
+    const int b = row / kNlOut, k = row - kNlOut * b;
+    double acc = 0.0;
+    for (int c = off[b]; c < off[b + 1]; ++c) acc += part[static_cast<size_t>(kNlOut) * c + k];
+    out[row] = acc;
+}
+
+bool all_finite(const double* v, size_t n) {
+    for (size_t i = 0; i < n; ++i)
+        if (!std::isfinite(v[i])) return false;
+    return true;
+}
+
+// the device copy of the owned bodies' lists, body-major, and the chunk map: every body's list cut into chunks of 256 in index order
+void upload_panels(hc_ctx* c) {
+    std::vector<double> panel;
+    std::vector<int> chunk, off(c->nloc + 1, 0);
+    int items = 0;
+    for (int b = c->b0; b < c->b1; ++b) {
+        const std::vector<hc_surface_panel>& list = c->nl_panels[b];
+        const int n = static_cast<int>(list.size());
+        for (const hc_surface_panel& p : list) {
+            panel.insert(panel.end(), p.c, p.c + 3);
+            panel.insert(panel.end(), p.s, p.s + 3);
+        }
+        for (int e = 0; e < n; e += kNlThreads) {
+            chunk.push_back(b);
+            chunk.push_back(items + e);
+            chunk.push_back(std::min(kNlThreads, n - e));
+        }
+        items += n;
+        off[b - c->b0 + 1] = static_cast<int>(chunk.size() / 3);
+    }
+    c->d_nl_panel.upload(panel, c->stream_nl);
+    c->d_nl_chunk.upload(chunk, c->stream_nl);
+    c->d_nl_off.upload(off, c->stream_nl);
+    c->nl_items  = items;
+    c->nl_chunks = static_cast<int>(chunk.size() / 3);
+    if (c->d_nl_part.n < static_cast<size_t>(kNlOut) * c->nl_chunks) c->d_nl_part.alloc(static_cast<size_t>(kNlOut) * c->nl_chunks);
+    c->nl_dirty = false;
+}
+
+// The component table of the wave model in force, a copy of this path's own (as hc_morison.hip: another path may rebuild its table
+// while a launch of this one is in flight).
+void nonlinear_table(hc_ctx* c) {
+    const double phase = c->nl_opts.regular_phase;
+    const bool regular = c->wave_kind == kWaveRegular;
+    if (c->nl_serial == c->wave_serial && (!regular || std::memcmp(&c->nl_phase, &phase, sizeof(double)) == 0)) return;
+    const std::vector<double> kin = kin_table_host(c, phase);
+    const int nf = static_cast<int>(kin.size() / kKinCols);
+    std::vector<double> tab(static_cast<size_t>(kNlCols) * nf);
+    const int from[kNlCols] = {kKinAmp, kKinOmega, kKinK, kKinPhase, kKinW2A, kKinInvSinh, kKinDeep};
+    for (int col = 0; col < kNlCols; ++col)
+        for (int i = 0; i < nf; ++i) tab[static_cast<size_t>(col) * nf + i] = kin[static_cast<size_t>(from[col]) * nf + i];
+    for (int i = 0; i < nf; ++i) tab[static_cast<size_t>(kNlW2AoK) * nf + i] /= kin[static_cast<size_t>(kKinK) * nf + i];
+    c->d_nl_tab.upload(tab, c->stream_nl);
+    c->nl_nf     = nf;
+    c->nl_serial = c->wave_serial;
+    c->nl_phase  = phase;
+}
+
+// (the state is in h_nl_state already: hc_nonlinear_begin)
+void nonlinear_enqueue(hc_ctx* c, double t) {
+    const size_t n3 = 3 * static_cast<size_t>(c->N);
+    const size_t n_out = static_cast<size_t>(kNlOut) * c->nloc;
+    if (c->nl_dirty) upload_panels(c);
+    nonlinear_table(c);
+    if (c->d_nl_state.n < 2 * n3) c->d_nl_state.alloc(2 * n3);
+    if (c->h_nl_out.n < n_out) c->h_nl_out.alloc(n_out);
+    if (c->d_nl_out.n < n_out) c->d_nl_out.alloc(n_out);
+    const bool synthesised = (c->wave_kind == kWaveIrregular && !c->eta_record) || c->wave_kind == kWaveSpectral;
+    const double rd = c->irr.ramp_duration;
+    NlArgs a{};
+    a.tab          = c->d_nl_tab.p;
+    a.nf           = c->nl_nf;
+    a.panel        = c->d_nl_panel.p;
+    a.chunk        = c->d_nl_chunk.p;
+    a.state        = c->d_nl_state.p;
+    a.N            = c->N;
+    a.t            = t;
+    a.depth        = c->depth;
+    a.mwl          = c->nl_opts.mwl;
+    a.rho          = c->rho;
+    a.g            = -c->gsys[2];  // gravity is (0, 0, -g): checked by hc_nonlinear_begin
+    a.ramp         = (synthesised && rd > 0.0 && t < rd) ? (t <= 0.0 ? 0.0 : t / rd) : 1.0;  // the rule of the Morison term
+    a.stretch      = (synthesised && c->nl_opts.wave_stretching) ? 1 : 0;  // RegularWave has none
+    a.finite_depth = std::isfinite(c->depth) ? 1 : 0;
+    a.part         = c->d_nl_part.p;
+    const int rows = static_cast<int>(n_out);
+    hipStream_t st = c->stream_nl;
+    HC_HIP(hipMemcpyAsync(c->d_nl_state.p, c->h_nl_state.p, 2 * n3 * sizeof(double), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(nl_panels_kernel, dim3(c->nl_chunks), dim3(kNlThreads), 0, st, a);
+    HC_HIP(hipGetLastError());
+    hipLaunchKernelGGL(nl_sum_kernel, dim3((rows + kNlThreads - 1) / kNlThreads), dim3(kNlThreads), 0, st, c->d_nl_part.p, c->d_nl_off.p, rows,
+                       c->d_nl_out.p);
+    HC_HIP(hipGetLastError());
+    HC_HIP(hipMemcpyAsync(c->h_nl_out.p, c->d_nl_out.p, n_out * sizeof(double), hipMemcpyDeviceToHost, st));
+}
+
+// The linear hydrostatic term of the owned bodies for pos, rpy (ComputeForceHydrostatics, src/hydro_forces.cpp:263-322), from the
+// context's host copies, in the expression order of the step kernels.
+void hs_linear_host(const hc_ctx* c, const double* pos, const double* rpy, double* out) {
+    const double gx = c->gsys[0], gy = c->gsys[1], gz = c->gsys[2];
+    const double glen = std::sqrt(gx * gx + gy * gy + gz * gz);
+    for (int b = c->b0; b < c->b1; ++b) {
+        const hc::BodyHost& bd = c->bodies[b];
+        double dq[6], r[3];
+        for (int j = 0; j < 3; ++j) {
+            dq[j]     = pos[3 * b + j] - bd.cg[j];
+            dq[3 + j] = rpy[3 * b + j] - 0.0;
+            r[j]      = bd.cb[j] - bd.cg[j];
+        }
+        const double V = bd.disp_vol;
+        const double fbx = c->rho * (-gx) * V, fby = c->rho * (-gy) * V, fbz = c->rho * (-gz) * V;
+        const double add[6] = {fbx, fby, fbz, r[1] * fbz - r[2] * fby, r[2] * fbx - r[0] * fbz, r[0] * fby - r[1] * fbx};
+        for (int i = 0; i < 6; ++i) {
+            double s = 0.0;
+            for (int j = 0; j < 6; ++j) s += bd.lin[6 * i + j] * dq[j];
+            double hs = -(c->rho * glen) * s;
+            hs += add[i];
+            out[6 * (b - c->b0) + i] = hs;
+        }
+    }
+}
+
+}  // namespace
+}  // namespace hc
+
+extern "C" {
+
+int hc_set_surface_panels(hc_ctx* c, int body, const hc_surface_panel* panels, int n) {
+    HC_API_BEGIN_HOT(c)
+    require(body >= 0 && body < c->N, HC_ERR_INVALID, "body index out of range");
+    require(n >= 0 && n <= hc::kSurfaceMaxPanels, HC_ERR_INVALID, "surface panel count negative or above the limit per body");
+    require(n == 0 || panels, HC_ERR_INVALID, "null surface panel list");
+    require(!c->nl_pending, HC_ERR_INVALID, "a nonlinear evaluation is in flight (hc_nonlinear_end has not been called)");
+    for (int e = 0; e < n; ++e)
+        require(hc::all_finite(panels[e].c, 3) && hc::all_finite(panels[e].s, 3), HC_ERR_INVALID, "non-finite value in a surface panel");
+    if (!c->stream_nl) HC_HIP(hipStreamCreateWithFlags(&c->stream_nl, hipStreamNonBlocking));
+    if (c->nl_panels.empty()) c->nl_panels.resize(c->N);
+    c->nl_panels[body].assign(panels, panels + n);
+    c->nl_dirty = true;
+    HC_API_END(c)
+}
+
+int hc_get_surface_panel_count(hc_ctx* c, int body, int* n) {
+    HC_API_BEGIN_HOT(c)
+    require(body >= 0 && body < c->N && n, HC_ERR_INVALID, "body index out of range or null pointer");
+    *n = c->nl_panels.empty() ? 0 : static_cast<int>(c->nl_panels[body].size());
+    HC_API_END(c)
+}
+
+int hc_set_nonlinear_options(hc_ctx* c, const hc_wave_kinematics_opts* o) {
+    HC_API_BEGIN_HOT(c)
+    hc_wave_kinematics_opts v;
+    hc_wave_kinematics_opts_default(&v);
+    if (o) v = *o;
+    require(std::isfinite(v.mwl) && std::isfinite(v.regular_phase), HC_ERR_INVALID, "non-finite mwl or regular_phase");
+    require(!c->nl_pending, HC_ERR_INVALID, "a nonlinear evaluation is in flight (hc_nonlinear_end has not been called)");
+    c->nl_opts = v;
+    HC_API_END(c)
+}
+
+int hc_nonlinear_begin(hc_ctx* c, double t, const double* pos, const double* rpy) {
+    HC_API_BEGIN_HOT(c)
+    require(c->finalized, HC_ERR_INVALID, "hc_finalize has not been called");
+    require(!c->nl_pending, HC_ERR_INVALID, "hc_nonlinear_begin twice without hc_nonlinear_end");
+    require(pos && rpy, HC_ERR_INVALID, "null state");
+    const size_t n3 = 3 * static_cast<size_t>(c->N);
+    require(std::isfinite(t) && hc::all_finite(pos, n3) && hc::all_finite(rpy, n3), HC_ERR_INVALID, "non-finite time or state");
+    require(c->gsys[0] == 0.0 && c->gsys[1] == 0.0 && c->gsys[2] < 0.0, HC_ERR_INVALID,
+            "the nonlinear surface forces need gravity (0, 0, -g): z up");
+    // the host copy of the state: the kernel's source, and what hc_nonlinear_end computes hs_lin from (the caller's arrays are
+    // borrowed for this call only)
+    if (c->h_nl_state.n < 2 * n3) c->h_nl_state.alloc(2 * n3);
+    std::copy(pos, pos + n3, c->h_nl_state.p);
+    std::copy(rpy, rpy + n3, c->h_nl_state.p + n3);
+    int items = 0;
+    if (!c->nl_panels.empty())
+        for (int b = c->b0; b < c->b1; ++b) items += static_cast<int>(c->nl_panels[b].size());
+    if (items == 0) {
+        c->nl_pending = 1;
+        return HC_OK;
+    }
+    try {
+        hc::nonlinear_enqueue(c, t);
+    } catch (...) {
+        (void)hipStreamSynchronize(c->stream_nl);  // nothing stays pending
+        throw;
+    }
+    c->nl_pending = 2;
+    HC_API_END(c)
+}
+
+int hc_nonlinear_end(hc_ctx* c, double* buoy, double* fk, double* hs_lin) {
+    HC_API_BEGIN_HOT(c)
+    require(c->nl_pending != 0, HC_ERR_INVALID, "hc_nonlinear_end without hc_nonlinear_begin");
+    const int what = c->nl_pending;
+    c->nl_pending  = 0;
+    if (what == 2) HC_HIP(hipStreamSynchronize(c->stream_nl));
+    for (int bl = 0; bl < c->nloc; ++bl)
+        for (int k = 0; k < 6; ++k) {
+            if (buoy) buoy[6 * bl + k] = what == 2 ? c->h_nl_out.p[hc::kNlOut * bl + k] : 0.0;
+            if (fk) fk[6 * bl + k] = what == 2 ? c->h_nl_out.p[hc::kNlOut * bl + 6 + k] : 0.0;
+        }
+    if (hs_lin) hc::hs_linear_host(c, c->h_nl_state.p, c->h_nl_state.p + 3 * static_cast<size_t>(c->N), hs_lin);
+    HC_API_END(c)
+}
+
+int hc_compute_nonlinear(hc_ctx* c, double t, const double* pos, const double* rpy, double* buoy, double* fk, double* hs_lin) {
+    const int rc = hc_nonlinear_begin(c, t, pos, rpy);
+    return rc != HC_OK ? rc : hc_nonlinear_end(c, buoy, fk, hs_lin);
+}
+
+}  // extern "C"

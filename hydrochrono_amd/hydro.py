@@ -191,15 +191,34 @@ class HydroForces:
         a = [x if (type(x) is np.ndarray and x.dtype == np.float64 and x.size == n3 and x.flags.c_contiguous) else _arr(x, n3)
              for x in (pos, rpy, linvel, angvel)]
         out = np.empty(self.D_local)
-        if self.__dict__.get("_morison_any"):
-            # the Morison term runs on its own stream beside the step; the sum is made here (the C ABI total stays the reference's)
-            self._chk(self.lib.hc_morison_begin(self.ctx, t, _dp(a[0]), _dp(a[1]), _dp(a[2]), _dp(a[3])))
+        morison, nonlinear = self.__dict__.get("_morison_any"), self._nonlinear_on()
+        if morison or nonlinear:
+            # the side terms run on streams of their own beside the step; the composition is made here (the C ABI total stays the
+            # reference's): begin both, step, end both
+            if nonlinear:
+                self._chk(self.lib.hc_nonlinear_begin(self.ctx, t, _dp(a[0]), _dp(a[1])))
+            if morison:
+                rc_begin = self.lib.hc_morison_begin(self.ctx, t, _dp(a[0]), _dp(a[1]), _dp(a[2]), _dp(a[3]))
+                if rc_begin:
+                    if nonlinear:
+                        self.lib.hc_nonlinear_end(self.ctx, None, None, None)  # nothing stays pending
+                    self._chk(rc_begin)
             rc = capi.step_raw(self.lib)(self.ctx, t, a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, a[3].ctypes.data, out.ctypes.data)
-            mor = np.empty(self.D_local)
-            rc_end = self.lib.hc_morison_end(self.ctx, _dp(mor))
+            rc_end = 0
+            if nonlinear:
+                nl = tuple(np.empty(self.D_local) for _ in range(3))
+                rc_end = self.lib.hc_nonlinear_end(self.ctx, _dp(nl[0]), _dp(nl[1]), _dp(nl[2]))
+            if morison:
+                mor = np.empty(self.D_local)
+                rc_end = self.lib.hc_morison_end(self.ctx, _dp(mor)) or rc_end
             self._chk(rc or rc_end)
-            self._morison_last = mor
-            return out + mor
+            if nonlinear:
+                self._nonlinear_last = nl
+                out = _compose_nonlinear(out, nl, self._nonlinear_mode, self._panel_counts, self.b0, self.b1)
+            if morison:
+                self._morison_last = mor
+                out = out + mor
+            return out
         # raw addresses through a c_void_p prototype: this call sits in per-step loops
         rc = capi.step_raw(self.lib)(self.ctx, t, a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, a[3].ctypes.data, out.ctypes.data)
         if rc:
@@ -469,6 +488,95 @@ class HydroForces:
         m = self.__dict__.get("_morison_last")
         return np.zeros(self.D_local) if m is None or not self.__dict__.get("_morison_any") else m.copy()
 
+    # -- nonlinear buoyancy and Froude-Krylov forces on surface panels (an extension beyond the reference) --
+    def set_surface_panels(self, b, c, s):
+        """Replaces the panel list of body b (0-based): c, s are (n, 3) -- centroids [m] and area vectors [m^2] (area times the outward
+        normal, body into water) in the body frame; empty arrays clear it.  With set_nonlinear_mode(1 or 2) step() then replaces the
+        body's linear hydrostatic term by the pressure integral over the wetted panels."""
+        c, s = (np.ascontiguousarray(x, dtype=np.float64).reshape(-1, 3) for x in (c, s))
+        if c.shape != s.shape:
+            raise ValueError("c and s must have the same shape (n, 3)")
+        n = c.shape[0]
+        panels = (capi.SurfacePanel * max(n, 1))()
+        flat = np.concatenate([c, s], axis=1)
+        if n:
+            C.memmove(panels, flat.ctypes.data, flat.nbytes)
+        self._chk(self.lib.hc_set_surface_panels(self.ctx, int(b), panels, n))
+        self.__dict__.setdefault("_panel_counts", {})[int(b)] = n
+
+    def set_surface_mesh(self, b, triangles):
+        """Panels from triangles [n][3][3] (vertices in the body frame, counter-clockwise seen from the water):
+        c = (v0 + v1 + v2) / 3, s = 1/2 (v1 - v0) x (v2 - v0)."""
+        c, s = triangles_to_panels(triangles)
+        self.set_surface_panels(b, c, s)
+
+    def surface_panel_count(self, b):
+        n = C.c_int()
+        self._chk(self.lib.hc_get_surface_panel_count(self.ctx, int(b), C.byref(n)))
+        return n.value
+
+    def set_nonlinear_options(self, mwl=0.0, regular_phase=0.0, wave_stretching=True):
+        """mwl, regular_phase, wave_stretching of the wave kinematics the panels see (those of wave_kinematics())."""
+        o = capi.WaveKinematicsOpts(float(mwl), float(regular_phase), int(bool(wave_stretching)))
+        self._chk(self.lib.hc_set_nonlinear_options(self.ctx, C.byref(o)))
+
+    def set_nonlinear_mode(self, mode):
+        """0: off (step() as without panels); 1: a body with panels gets total - hs_lin + buoy; 2: total - hs_lin + buoy + fk (the
+        excitation data of the context should then be the scattering part only: nothing is subtracted from the wave term)."""
+        if int(mode) not in (0, 1, 2):
+            raise ValueError("nonlinear mode must be 0, 1 or 2")
+        self._nonlinear_mode = int(mode)
+
+    def _nonlinear_on(self):
+        d = self.__dict__
+        return bool(d.get("_nonlinear_mode")) and any(d.get("_panel_counts", {}).values())
+
+    def compute_nonlinear(self, t, pos, rpy):
+        """(buoy, fk, hs_lin) of the owned bodies (D_local each; world frame, at the body reference) for the given state."""
+        n3 = 3 * self.N
+        a = [_arr(x, n3) for x in (pos, rpy)]
+        out = tuple(np.empty(self.D_local) for _ in range(3))
+        self._chk(self.lib.hc_compute_nonlinear(self.ctx, float(t), _dp(a[0]), _dp(a[1]), _dp(out[0]), _dp(out[1]), _dp(out[2])))
+        return out
+
+    def nonlinear_begin(self, t, pos, rpy):
+        n3 = 3 * self.N
+        a = [_arr(x, n3) for x in (pos, rpy)]
+        self._chk(self.lib.hc_nonlinear_begin(self.ctx, float(t), _dp(a[0]), _dp(a[1])))
+
+    def nonlinear_end(self):
+        out = tuple(np.empty(self.D_local) for _ in range(3))
+        self._chk(self.lib.hc_nonlinear_end(self.ctx, _dp(out[0]), _dp(out[1]), _dp(out[2])))
+        return out
+
+    def nonlinear(self):
+        """(buoy, fk, hs_lin) of the last step() (zeros when the mode is 0 or no panel is set)."""
+        m = self.__dict__.get("_nonlinear_last")
+        if m is None or not self._nonlinear_on():
+            return tuple(np.zeros(self.D_local) for _ in range(3))
+        return tuple(x.copy() for x in m)
+
+
+def triangles_to_panels(triangles):
+    """Centroids and area vectors of triangles [n][3][3]."""
+    tri = np.ascontiguousarray(triangles, dtype=np.float64).reshape(-1, 3, 3)
+    c = (tri[:, 0] + tri[:, 1] + tri[:, 2]) / 3.0
+    s = 0.5 * np.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0])
+    return c, s
+
+
+def _compose_nonlinear(total, nl, mode, counts, b0, b1):
+    """total - hs_lin + buoy (+ fk in mode 2) on the six rows of every body of [b0, b1) that carries panels; the other rows untouched."""
+    buoy, fk, hs_lin = nl
+    out = total.copy()
+    for b, n in counts.items():
+        if n and b0 <= b < b1:
+            r = slice(6 * (b - b0), 6 * (b - b0) + 6)
+            out[r] = total[r] - hs_lin[r] + buoy[r]
+            if mode == 2:
+                out[r] = out[r] + fk[r]
+    return out
+
 
 def read_eta_file(path):
     """IrregularWaves::ReadEtaFromFile: the `time : eta` lines of an eta file as (t, eta); HydroError with the reference's message
@@ -522,14 +630,64 @@ class HydroGroup:
         a = [_arr(x, n3) for x in (pos, rpy, linvel, angvel)]
         out = np.empty(self.D)
         morison = any(h.__dict__.get("_morison_any") for h in self.shards)
+        nonlinear = self.shards[0]._nonlinear_on()  # every shard holds the lists of all bodies and the mode
+        if nonlinear:
+            self._nonlinear_begin(t, a)
         if morison:
-            self._morison_begin(t, a)
+            try:
+                self._morison_begin(t, a)
+            except HydroError:
+                if nonlinear:
+                    self._nonlinear_end(check=False)
+                raise
         rc = self._step(self._ctxs, len(self.shards), t, a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, a[3].ctypes.data, out.ctypes.data)
+        if nonlinear:
+            self._nonlinear_last = self._nonlinear_end(check=not rc)
         if morison:
             self._morison_last = self._morison_end(check=not rc)
         if rc:
             raise HydroError(rc, self.lib.hc_last_error(self.shards[0].ctx).decode())
+        if nonlinear:
+            h0 = self.shards[0]
+            out = _compose_nonlinear(out, self._nonlinear_last, h0._nonlinear_mode, h0._panel_counts, 0, self.N)
         return out + self._morison_last if morison else out
+
+    # -- surface panels: every shard holds the lists of all bodies and computes those of its own --
+    def _nonlinear_begin(self, t, a):
+        begun = []
+        try:
+            for h in self.shards:
+                h._chk(self.lib.hc_nonlinear_begin(h.ctx, float(t), _dp(a[0]), _dp(a[1])))
+                begun.append(h)
+        except HydroError:
+            for h in begun:
+                self.lib.hc_nonlinear_end(h.ctx, None, None, None)
+            raise
+
+    def _nonlinear_end(self, check=True):
+        out = tuple(np.empty(self.D) for _ in range(3))
+        rcs = []
+        for h in self.shards:
+            part = tuple(np.empty(h.D_local) for _ in range(3))
+            rcs.append((h, self.lib.hc_nonlinear_end(h.ctx, _dp(part[0]), _dp(part[1]), _dp(part[2]))))
+            for k in range(3):
+                out[k][6 * h.b0:6 * h.b1] = part[k]
+        for h, rc in rcs:
+            if check:
+                h._chk(rc)
+        return out
+
+    def compute_nonlinear(self, t, pos, rpy):
+        n3 = 3 * self.N
+        a = [_arr(x, n3) for x in (pos, rpy)]
+        self._nonlinear_begin(t, a)
+        return self._nonlinear_end()
+
+    def nonlinear(self):
+        m = self.__dict__.get("_nonlinear_last")
+        if m is None or not self.shards[0]._nonlinear_on():
+            return tuple(np.zeros(self.D) for _ in range(3))
+        return tuple(x.copy() for x in m)
 
     # -- Morison elements: every shard holds the lists of all bodies and computes those of its own --
     def _morison_begin(self, t, a):

@@ -143,6 +143,12 @@ struct MorisonElement {
     std::array<double, 3> r{0, 0, 0}, cd_area{0, 0, 0}, cm_vol{0, 0, 0};
 };
 
+// A surface panel of a body (not in the reference; hc_surface_panel): centroid [m] and area vector [m^2] (area times the outward
+// normal, body into water) in the body frame.
+struct SurfacePanel {
+    std::array<double, 3> c{0, 0, 0}, s{0, 0, 0};
+};
+
 // ---------------------------------------------------------------------------------------------------------------
 // TestHydro
 // ---------------------------------------------------------------------------------------------------------------
@@ -297,6 +303,66 @@ class TestHydro {
         return out;
     }
 
+    // Nonlinear buoyancy and Froude-Krylov forces on surface panels (not in the reference; include/hydrochrono_amd.h:
+    // hc_set_surface_panels).  With a mode > 0, CoordinateFuncForBody returns, for a body that carries panels,
+    // total - hs_lin + buoy (mode 1) or total - hs_lin + buoy + fk (mode 2: the excitation data should then be the scattering part
+    // only, nothing is subtracted from the wave term); the rows of other bodies are untouched.  The body index is 1-based; an
+    // empty vector clears the list.
+    void SetSurfacePanels(int body_index_1_based, const std::vector<SurfacePanel>& panels) {
+        if (body_index_1_based < 1 || body_index_1_based > num_bodies_) throw std::out_of_range("SetSurfacePanels: body index out of range");
+        std::vector<hc_surface_panel> raw(panels.size());
+        for (size_t e = 0; e < panels.size(); ++e)
+            for (int k = 0; k < 3; ++k) {
+                raw[e].c[k] = panels[e].c[k];
+                raw[e].s[k] = panels[e].s[k];
+            }
+        for (hc_ctx* c : ctxs_) check(c, hc_set_surface_panels(c, body_index_1_based - 1, raw.data(), static_cast<int>(raw.size())));
+        panel_count_.resize(static_cast<size_t>(num_bodies_), 0);
+        panel_count_[static_cast<size_t>(body_index_1_based - 1)] = raw.size();
+        have_time_ = false;  // the cached total belongs to the lists before
+    }
+    // triangles (three vertices each, in the body frame, counter-clockwise seen from the water):
+    // c = (v0 + v1 + v2) / 3, s = 1/2 (v1 - v0) x (v2 - v0)
+    void SetSurfaceMesh(int body_index_1_based, const std::vector<std::array<std::array<double, 3>, 3>>& triangles) {
+        std::vector<SurfacePanel> panels(triangles.size());
+        for (size_t e = 0; e < triangles.size(); ++e) {
+            const auto& v = triangles[e];
+            double a[3], b[3];
+            for (int k = 0; k < 3; ++k) {
+                panels[e].c[k] = (v[0][k] + v[1][k] + v[2][k]) / 3.0;
+                a[k]           = v[1][k] - v[0][k];
+                b[k]           = v[2][k] - v[0][k];
+            }
+            panels[e].s = {0.5 * (a[1] * b[2] - a[2] * b[1]), 0.5 * (a[2] * b[0] - a[0] * b[2]), 0.5 * (a[0] * b[1] - a[1] * b[0])};
+        }
+        SetSurfacePanels(body_index_1_based, panels);
+    }
+    // 0: off, 1: nonlinear buoyancy, 2: nonlinear buoyancy + Froude-Krylov
+    void SetNonlinearHydroMode(int mode) {
+        if (mode < 0 || mode > 2) throw std::invalid_argument("SetNonlinearHydroMode: mode must be 0, 1 or 2");
+        nonlinear_mode_ = mode;
+        have_time_      = false;
+    }
+    // mwl, regular phase and stretching of the kinematics the panels see (those of WaveBase::GetVelocity & co.)
+    void SetNonlinearHydroOptions(double mwl = 0.0, double regular_phase = 0.0, bool wave_stretching = true) {
+        hc_wave_kinematics_opts o;
+        hc_wave_kinematics_opts_default(&o);
+        o.mwl             = mwl;
+        o.regular_phase   = regular_phase;
+        o.wave_stretching = wave_stretching ? 1 : 0;
+        for (hc_ctx* c : ctxs_) check(c, hc_set_nonlinear_options(c, &o));
+        have_time_ = false;
+    }
+    // buoy | fk | hs_lin of all bodies for the bodies' present state, 6 N values each
+    std::vector<double> ComputeForceNonlinear() {
+        gather_state();
+        const size_t D = 6 * static_cast<size_t>(num_bodies_);
+        std::vector<double> out(3 * D);
+        nonlinear_begin(bodies_[0]->GetChTime());
+        nonlinear_end(out.data(), out.data() + D, out.data() + 2 * D);
+        return out;
+    }
+
     // src/hydro_forces.cpp:693-711: the radiation IRF value the convolution uses (rho-scaled; the processed kernel in
     // TaperedDirect mode).  Reads one value back from the GPU -- a debugging accessor, as in the reference.
     double GetRIRFval(int row, int col, int st) {
@@ -319,10 +385,37 @@ class TestHydro {
             prev_time_ = t;
             have_time_ = true;
             gather_state();
-            if (have_morison_) morison_begin(t);
+            const bool nonlinear = nonlinear_on();
+            if (nonlinear) nonlinear_begin(t);
+            if (have_morison_) {
+                try {
+                    morison_begin(t);
+                } catch (...) {
+                    if (nonlinear)
+                        for (hc_ctx* c : ctxs_) (void)hc_nonlinear_end(c, nullptr, nullptr, nullptr);  // nothing stays pending
+                    throw;
+                }
+            }
             const int rc = ctxs_.size() == 1 ? hc_step(ctx_, t, pos_.data(), rpy_.data(), lin_.data(), ang_.data(), total_force_.data())
                                              : hc_step_multi(ctxs_.data(), static_cast<int>(ctxs_.size()), t, pos_.data(), rpy_.data(), lin_.data(),
                                                              ang_.data(), total_force_.data());
+            if (nonlinear) {
+                const size_t D = total_force_.size();
+                nonlinear_force_.resize(3 * D);
+                double *buoy = nonlinear_force_.data(), *fk = buoy + D, *hs = fk + D;
+                if (rc != HC_OK) {
+                    for (hc_ctx* c : ctxs_) (void)hc_nonlinear_end(c, nullptr, nullptr, nullptr);  // nothing stays pending
+                } else {
+                    nonlinear_end(buoy, fk, hs);
+                    for (size_t body = 0; body < panel_count_.size(); ++body) {
+                        if (panel_count_[body] == 0) continue;
+                        for (size_t i = 6 * body; i < 6 * body + 6; ++i) {
+                            total_force_[i] = total_force_[i] - hs[i] + buoy[i];
+                            if (nonlinear_mode_ == 2) total_force_[i] = total_force_[i] + fk[i];
+                        }
+                    }
+                }
+            }
             if (have_morison_) {
                 morison_force_.resize(total_force_.size());
                 if (rc != HC_OK) {
@@ -446,6 +539,31 @@ class TestHydro {
         }
         if (failed) check(failed, rc);
     }
+    bool nonlinear_on() const {
+        return nonlinear_mode_ != 0 && std::any_of(panel_count_.begin(), panel_count_.end(), [](size_t n) { return n != 0; });
+    }
+    void nonlinear_begin(double t) {
+        for (size_t g = 0; g < ctxs_.size(); ++g) {
+            const int rc = hc_nonlinear_begin(ctxs_[g], t, pos_.data(), rpy_.data());
+            if (rc != HC_OK) {
+                for (size_t h = 0; h < g; ++h) (void)hc_nonlinear_end(ctxs_[h], nullptr, nullptr, nullptr);
+                check(ctxs_[g], rc);
+            }
+        }
+    }
+    void nonlinear_end(double* buoy, double* fk, double* hs_lin) {  // every shard is ended, then the first failure is reported
+        int rc = HC_OK;
+        hc_ctx* failed = nullptr;
+        for (hc_ctx* c : ctxs_) {
+            const int r0 = row0(c);
+            const int r  = hc_nonlinear_end(c, buoy + r0, fk + r0, hs_lin + r0);
+            if (r != HC_OK && rc == HC_OK) {
+                rc     = r;
+                failed = c;
+            }
+        }
+        if (failed) check(failed, rc);
+    }
     static int row0(hc_ctx* c) {  // first output row of a shard context
         int b0 = 0;
         check(c, hc_get_shard(c, &b0, nullptr));
@@ -461,6 +579,9 @@ class TestHydro {
     std::vector<double> morison_force_;  // the Morison term of the last evaluation
     std::vector<size_t> morison_count_;  // elements per body
     bool have_morison_ = false;
+    std::vector<double> nonlinear_force_;  // buoy | fk | hs_lin of the last evaluation
+    std::vector<size_t> panel_count_;      // surface panels per body
+    int nonlinear_mode_ = 0;               // 0 off, 1 buoyancy, 2 buoyancy + Froude-Krylov
     std::array<double, 3> gravity_{0.0, 0.0, -9.81};
     bool have_time_   = false;
     double prev_time_ = -1.0;

@@ -553,6 +553,62 @@ int hc_compute_morison(hc_ctx* ctx, double t, const double* pos, const double* r
                        double* out_Dlocal);
 
 /* ------------------------------------------------------------------------------------------------
+ * Nonlinear buoyancy and Froude-Krylov forces on body surface panels (not in the reference: src/hydro_types.h:33 is a TODO): the
+ * hydrostatic and incident-wave pressure integrated over the instantaneous wetted surface, an opt-in replacement of the linear
+ * hydrostatic term (and, with a scattering-only excitation, of the incident-wave part of the excitation).
+ *
+ * Panels.  Body b may carry n_b >= 0 panels.  A panel is a centroid c [m] and an area vector s [m^2]: |s| is the area, the
+ * direction the outward normal (body into water); both in the body frame, relative to the point pos[b] locates, as a Morison
+ * element's r.  Centroid rule, no waterline clipping: a panel is wholly wet or wholly dry by its centroid (the deliberate
+ * approximation).
+ *
+ * Per panel, with pos, rpy of hc_step and the options (mwl, regular phase, stretching) exactly as the Morison term uses them:
+ *     R = Rx(rpy0) Ry(rpy1) Rz(rpy2),  d = R c,  p = pos + d,  n = R s
+ *     theta_i = k_i p.x - w_i t + phi_i,  eta = sum_i A_i cos theta_i  (expression and component order of hc_wave_kinematics: eta
+ *         equals what it returns for that point and time, bit for bit, under the same options)
+ *     wet iff p.z - mwl <= eta; a dry panel contributes nothing
+ *     p_s = -rho g (p.z - mwl),  g = |gravity|
+ *     p_d = rho sum_i (w_i^2 A_i / k_i) px_i(z_e) cos theta_i   (-rho dphi/dt of the potential whose gradient is the velocity of
+ *         hc_wave_kinematics); px_i is its x-profile, e^{k z_e} or cosh(k (z_e + d)) / sinh(k d) per component by the reference's
+ *         profile test; z_e is exactly what the kinematics take: under Wheeler stretching the stretched z with the reference's second
+ *         mwl subtraction, otherwise p.z - mwl; the infinite-depth limit included.  p_s always uses the true p.z.
+ *     p_d is multiplied by the ramp the Morison term applies to u_f, under the same conditions (the two synthesised irregular models;
+ *         a regular wave is not ramped).  The eta of the wet test is not ramped.
+ *     NoWave, no wave model, or an imported eta record: eta = p_d = 0; the kernel still runs and gives pure nonlinear buoyancy.
+ *     buoy_e = (-p_s n, d x (-p_s n)),  fk_e = (-p_d n, d x (-p_d n)): world frame, at the body reference, the sign of an applied force.
+ * Per owned body three 6-vectors: buoy and fk, the sums over its panels (a deterministic sum: its bits depend on that body's state,
+ * its own panel list, the wave model, t and the options only -- not on the number of bodies, on other bodies' lists, or on the shard
+ * context that computes it), and hs_lin, the linear hydrostatic term of hc_step for the same pos, rpy (-rho |g| K_hs dq, the buoyancy
+ * force and the (cb - cg) x moment), computed on the host by hc_nonlinear_end so that a caller can replace the linear term without
+ * reading step state (hc_get_force_components synchronises the device and has no place in a per-step composition).
+ *
+ * The terms are NOT part of hc_step & co., hc_get_force_components, hc_compute_* or the Morison calls: a caller composes
+ * total - hs_lin + buoy (+ fk) (the HydroForces / TestHydro layers do).  The library subtracts nothing from the wave excitation: when fk
+ * is added, the excitation data handed to the context should be the scattering part only.  hc_load_bemio_h5 reads the TOTAL excitation
+ * and is not changed.  The path runs on a stream of its own, beside the steps, and touches no step state: hc_nonlinear_begin may be
+ * followed by hc_step and then hc_nonlinear_end.  The kinematics assume z up: gravity must be (0, 0, -g).
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct hc_surface_panel {
+    double c[3];
+    double s[3];
+} hc_surface_panel;
+/* Replaces the list of `body` (0-based, any body of the system; a shard context computes those of its own bodies); n = 0 clears
+ * it.  Before or after hc_finalize, between evaluations.  HC_ERR_INVALID: body out of range, n < 0, a null list with n > 0, a
+ * non-finite value, more than 1048576 panels, or a hc_nonlinear_begin without its end. */
+int hc_set_surface_panels(hc_ctx* ctx, int body, const hc_surface_panel* panels, int n);
+int hc_get_surface_panel_count(hc_ctx* ctx, int body, int* n);
+/* mwl, regular_phase, wave_stretching of the kinematics the panels see; NULL = the defaults */
+int hc_set_nonlinear_options(hc_ctx* ctx, const hc_wave_kinematics_opts* o);
+/* begin enqueues (pos, rpy as for hc_step: [3N] each), end waits and copies the 6 * n_local values of each of the three terms (any
+ * output pointer may be NULL); exactly one end per begin.  Needs hc_finalize.  HC_ERR_INVALID on a non-finite state or t, on a
+ * gravity that is not (0, 0, -g), on a second begin, on an end without a begin; nothing stays pending after a failure.  With no panel
+ * on any owned body: buoy = fk = 0, no launch. */
+int hc_nonlinear_begin(hc_ctx* ctx, double t, const double* pos, const double* rpy);
+int hc_nonlinear_end(hc_ctx* ctx, double* buoy_Dlocal, double* fk_Dlocal, double* hs_lin_Dlocal);
+int hc_compute_nonlinear(hc_ctx* ctx, double t, const double* pos, const double* rpy, double* buoy_Dlocal, double* fk_Dlocal,
+                         double* hs_lin_Dlocal);
+
+/* ------------------------------------------------------------------------------------------------
  * Synthetic many-body inputs generated directly in HBM (benchmark configurations C3/C4 of SURVEY 8d;
  * not part of the reference).  Fills K, K_hs, A_inf, excitation IRF for all local bodies from a
  * counter-based generator so that a 77 GB kernel never exists on the host.  hc_finalize still applies.
