@@ -173,6 +173,14 @@ SIGNATURES = {
     "hc_nonlinear_begin": (C.c_int, [C.c_void_p, C.c_double, c_double_p, c_double_p]),
     "hc_nonlinear_end": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p]),
     "hc_compute_nonlinear": (C.c_int, [C.c_void_p, C.c_double, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
+    "hc_set_drift_qtf": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p]),
+    "hc_get_drift_qtf_size": (C.c_int, [C.c_void_p, C.c_int, c_int_p]),
+    "hc_set_drift_mode": (C.c_int, [C.c_void_p, C.c_int]),
+    "hc_get_drift_mode": (C.c_int, [C.c_void_p, c_int_p]),
+    "hc_set_drift_options": (C.c_int, [C.c_void_p, C.POINTER(WaveKinematicsOpts)]),
+    "hc_drift_begin": (C.c_int, [C.c_void_p, C.c_double, c_double_p]),
+    "hc_drift_end": (C.c_int, [C.c_void_p, c_double_p]),
+    "hc_compute_drift": (C.c_int, [C.c_void_p, C.c_double, c_double_p, c_double_p]),
     "hc_synth_fill": (C.c_int, [C.c_void_p, C.c_ulonglong, C.c_int, C.c_double, C.c_int, C.c_double]),
 }
 

@@ -96,6 +96,13 @@ struct BarBuffer {
     void alloc(size_t count);  // hc_runtime.cpp (probes host visibility without faulting)
 };
 
+// A body's difference-frequency QTF table (hc_set_drift_qtf): nq = 0 none
+struct DriftTable {
+    int nq     = 0;
+    bool has_q = false;
+    std::vector<double> omega, P, Q;  // [nq], [6][nq][nq] each
+};
+
 struct BodyHost {
     bool have_props = false, have_lin = false, have_ainf = false, have_rirf = false, have_rao = false, have_exirf = false;
     double disp_vol = 0.0, cg[3] = {0, 0, 0}, cb[3] = {0, 0, 0};
@@ -281,6 +288,25 @@ struct hc_ctx {
     hc::DeviceBuffer<double> d_nl_tab, d_nl_panel, d_nl_state, d_nl_part, d_nl_out;
     hc::DeviceBuffer<int> d_nl_chunk, d_nl_off;  // [chunks][3] (body, first panel, count), [nloc + 1] first chunk of an owned body
     hc::PinnedBuffer<double> h_nl_state, h_nl_out;  // [6 N] pos | rpy of the last hc_nonlinear_begin, [nloc][12]
+
+    // Wave drift forces (hc_set_drift_qtf, hc_drift.hip): the tables of all bodies of the system on the host, those of the owned bodies
+    // one after the other on the device with the bin -> (component, weight) map of the component table in force; its own stream,
+    // component table and pinned staging, nothing a step uses
+    std::vector<hc::DriftTable> drift_tabs;  // [N]
+    int drift_mode = 0;                      // 0 off, 1 mean drift, 2 Newman, 3 full QTF
+    double drift_phase_opt = 0.0;            // regular_phase of hc_set_drift_options
+    hipStream_t stream_drift = nullptr;      // created by the first hc_set_drift_qtf
+    bool drift_dirty = false;                // a table has changed since the device copy was made
+    int drift_pending = 0;                   // hc_drift_begin without its hc_drift_end: 1 zeros (nothing launched), 2 a launch is in flight
+    unsigned long long drift_serial = ~0ULL;
+    double drift_phase = 0.0;
+    int drift_nf = 0;
+    std::vector<double> drift_amp, drift_omega;  // [nf] of the component table in force
+    std::vector<int> drift_slot_body;            // local body of every launched slot (owned bodies with a table, ascending)
+    hc::DeviceBuffer<double> d_drift_tab, d_drift_pq, d_drift_w, d_drift_em, d_drift_pos, d_drift_out;
+    hc::DeviceBuffer<long long> d_drift_desc;
+    hc::DeviceBuffer<int> d_drift_rowptr, d_drift_idx;
+    hc::PinnedBuffer<double> h_drift_pos, h_drift_out;
 
     // GEMV configuration + scratch
     int chunk_gp = 0, nchunks_rad = 0, chunk_gp_ex = 0, nchunks_ex = 0, ngp_ex = 0;

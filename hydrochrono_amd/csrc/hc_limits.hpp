@@ -41,6 +41,7 @@ constexpr int kSlotStateMaxBodies = 170;  // 12 N + 1 doubles fit, and 6 N <= 4 
                                           // (every system whose step is ONE launch: wide systems begin at 6 N = 1024)
 
 constexpr int kMorisonMaxElements = 4096;  // Morison elements one body may carry (hc_set_morison_elements)
+constexpr int kDriftMaxFreq = 256;  // frequencies of a body's drift QTF grid (hc_set_drift_qtf): one lane of the workgroup per bin
 constexpr int kSurfaceMaxPanels = 1 << 20;  // surface panels one body may carry (hc_set_surface_panels): 4096 chunks of 256
 
 #if defined(__HIPCC__)

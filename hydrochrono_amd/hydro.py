@@ -191,10 +191,10 @@ class HydroForces:
         a = [x if (type(x) is np.ndarray and x.dtype == np.float64 and x.size == n3 and x.flags.c_contiguous) else _arr(x, n3)
              for x in (pos, rpy, linvel, angvel)]
         out = np.empty(self.D_local)
-        morison, nonlinear = self.__dict__.get("_morison_any"), self._nonlinear_on()
-        if morison or nonlinear:
+        morison, nonlinear, drift = self.__dict__.get("_morison_any"), self._nonlinear_on(), self._drift_on()
+        if morison or nonlinear or drift:
             # the side terms run on streams of their own beside the step; the composition is made here (the C ABI total stays the
-            # reference's): begin both, step, end both
+            # reference's): begin all, step, end all
             if nonlinear:
                 self._chk(self.lib.hc_nonlinear_begin(self.ctx, t, _dp(a[0]), _dp(a[1])))
             if morison:
@@ -202,6 +202,14 @@ class HydroForces:
                 if rc_begin:
                     if nonlinear:
                         self.lib.hc_nonlinear_end(self.ctx, None, None, None)  # nothing stays pending
+                    self._chk(rc_begin)
+            if drift:
+                rc_begin = self.lib.hc_drift_begin(self.ctx, t, _dp(a[0]))
+                if rc_begin:
+                    if nonlinear:
+                        self.lib.hc_nonlinear_end(self.ctx, None, None, None)
+                    if morison:
+                        self.lib.hc_morison_end(self.ctx, _dp(np.empty(self.D_local)))
                     self._chk(rc_begin)
             rc = capi.step_raw(self.lib)(self.ctx, t, a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, a[3].ctypes.data, out.ctypes.data)
             rc_end = 0
@@ -211,6 +219,9 @@ class HydroForces:
             if morison:
                 mor = np.empty(self.D_local)
                 rc_end = self.lib.hc_morison_end(self.ctx, _dp(mor)) or rc_end
+            if drift:
+                dr = np.empty(self.D_local)
+                rc_end = self.lib.hc_drift_end(self.ctx, _dp(dr)) or rc_end
             self._chk(rc or rc_end)
             if nonlinear:
                 self._nonlinear_last = nl
@@ -218,6 +229,9 @@ class HydroForces:
             if morison:
                 self._morison_last = mor
                 out = out + mor
+            if drift:
+                self._drift_last = dr
+                out = out + dr
             return out
         # raw addresses through a c_void_p prototype: this call sits in per-step loops
         rc = capi.step_raw(self.lib)(self.ctx, t, a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, a[3].ctypes.data, out.ctypes.data)
@@ -556,6 +570,76 @@ class HydroForces:
             return tuple(np.zeros(self.D_local) for _ in range(3))
         return tuple(x.copy() for x in m)
 
+    # -- second-order wave drift forces from QTF tables (an extension beyond the reference) --
+    def set_drift_qtf(self, b, omega, P, Q=None):
+        """Replaces the difference-frequency QTF table of body b (0-based): omega [nq] rad/s, strictly increasing, 2 <= nq <= 256;
+        P, Q [6][nq][nq] real and imaginary part, force (moment) per squared amplitude, dimensional; Q=None means zeros; an empty
+        omega clears the table.  With set_drift_mode(1, 2 or 3) step() then returns total + drift term."""
+        omega = np.ascontiguousarray(omega, dtype=np.float64).reshape(-1)
+        nq = omega.size
+        if nq == 0:
+            self._chk(self.lib.hc_set_drift_qtf(self.ctx, int(b), 0, None, None, None))
+        else:
+            P = np.ascontiguousarray(P, dtype=np.float64)
+            if P.size != 6 * nq * nq or (Q is not None and np.size(Q) != 6 * nq * nq):
+                raise ValueError("P and Q must have shape (6, nq, nq)")
+            Q = None if Q is None else np.ascontiguousarray(Q, dtype=np.float64)
+            self._chk(self.lib.hc_set_drift_qtf(self.ctx, int(b), nq, _dp(omega), _dp(P), None if Q is None else _dp(Q)))
+        self.__dict__.setdefault("_drift_sizes", {})[int(b)] = nq
+
+    def set_drift_mean(self, b, omega, D):
+        """Mean-drift coefficients D [6][nq] on omega [nq]: a table with D on the diagonal and zeros elsewhere, for modes 1 and 2
+        (mode 3 needs a full table: it would take the zeros off the diagonal as data)."""
+        omega = np.ascontiguousarray(omega, dtype=np.float64).reshape(-1)
+        nq = omega.size
+        D = np.ascontiguousarray(D, dtype=np.float64)
+        if D.shape != (6, nq):
+            raise ValueError("D must have shape (6, nq)")
+        P = np.zeros((6, nq, nq))
+        P[:, np.arange(nq), np.arange(nq)] = D
+        self.set_drift_qtf(b, omega, P)
+
+    def drift_qtf_size(self, b):
+        n = C.c_int()
+        self._chk(self.lib.hc_get_drift_qtf_size(self.ctx, int(b), C.byref(n)))
+        return n.value
+
+    def set_drift_mode(self, mode):
+        """0: off; 1: mean drift; 2: Newman's approximation; 3: full QTF."""
+        self._chk(self.lib.hc_set_drift_mode(self.ctx, int(mode)))
+        self._drift_mode = int(mode)
+
+    def set_drift_options(self, regular_phase=0.0):
+        """The phase of a regular wave as the drift term sees it (that of wave_kinematics())."""
+        o = capi.WaveKinematicsOpts(0.0, float(regular_phase), 1)
+        self._chk(self.lib.hc_set_drift_options(self.ctx, C.byref(o)))
+
+    def _drift_on(self):
+        d = self.__dict__
+        return bool(d.get("_drift_mode")) and any(d.get("_drift_sizes", {}).values())
+
+    def compute_drift(self, t, pos):
+        """The drift 6-vectors of the owned bodies (world frame, at the body reference) at time t and positions pos; zeros with
+        mode 0, without a table, and without wave components."""
+        a = _arr(pos, 3 * self.N)
+        out = np.empty(self.D_local)
+        self._chk(self.lib.hc_compute_drift(self.ctx, float(t), _dp(a), _dp(out)))
+        return out
+
+    def drift_begin(self, t, pos):
+        a = _arr(pos, 3 * self.N)
+        self._chk(self.lib.hc_drift_begin(self.ctx, float(t), _dp(a)))
+
+    def drift_end(self):
+        out = np.empty(self.D_local)
+        self._chk(self.lib.hc_drift_end(self.ctx, _dp(out)))
+        return out
+
+    def drift(self):
+        """The drift term of the last step() (zeros when the mode is 0 or no table is set)."""
+        m = self.__dict__.get("_drift_last")
+        return np.zeros(self.D_local) if m is None or not self._drift_on() else m.copy()
+
 
 def triangles_to_panels(triangles):
     """Centroids and area vectors of triangles [n][3][3]."""
@@ -631,6 +715,7 @@ class HydroGroup:
         out = np.empty(self.D)
         morison = any(h.__dict__.get("_morison_any") for h in self.shards)
         nonlinear = self.shards[0]._nonlinear_on()  # every shard holds the lists of all bodies and the mode
+        drift = self.shards[0]._drift_on()
         if nonlinear:
             self._nonlinear_begin(t, a)
         if morison:
@@ -640,17 +725,65 @@ class HydroGroup:
                 if nonlinear:
                     self._nonlinear_end(check=False)
                 raise
+        if drift:
+            try:
+                self._drift_begin(t, a[0])
+            except HydroError:
+                if nonlinear:
+                    self._nonlinear_end(check=False)
+                if morison:
+                    self._morison_end(check=False)
+                raise
         rc = self._step(self._ctxs, len(self.shards), t, a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, a[3].ctypes.data, out.ctypes.data)
         if nonlinear:
             self._nonlinear_last = self._nonlinear_end(check=not rc)
         if morison:
             self._morison_last = self._morison_end(check=not rc)
+        if drift:
+            self._drift_last = self._drift_end(check=not rc)
         if rc:
             raise HydroError(rc, self.lib.hc_last_error(self.shards[0].ctx).decode())
         if nonlinear:
             h0 = self.shards[0]
             out = _compose_nonlinear(out, self._nonlinear_last, h0._nonlinear_mode, h0._panel_counts, 0, self.N)
-        return out + self._morison_last if morison else out
+        if morison:
+            out = out + self._morison_last
+        return out + self._drift_last if drift else out
+
+    # -- drift tables: every shard holds the tables of all bodies and computes those of its own --
+    def _drift_begin(self, t, pos):
+        begun = []
+        try:
+            for h in self.shards:
+                h._chk(self.lib.hc_drift_begin(h.ctx, float(t), _dp(pos)))
+                begun.append(h)
+        except HydroError:
+            for h in begun:
+                self.lib.hc_drift_end(h.ctx, _dp(np.empty(h.D_local)))
+            raise
+
+    def _drift_end(self, check=True):
+        out = np.empty(self.D)
+        rcs = []
+        for h in self.shards:
+            part = np.empty(h.D_local)
+            rcs.append((h, self.lib.hc_drift_end(h.ctx, _dp(part))))
+            out[6 * h.b0:6 * h.b1] = part
+        for h, rc in rcs:
+            if check:
+                h._chk(rc)
+        return out
+
+    def compute_drift(self, t, pos):
+        self._drift_begin(t, _arr(pos, 3 * self.N))
+        return self._drift_end()
+
+    def drift(self):
+        m = self.__dict__.get("_drift_last")
+        return np.zeros(self.D) if m is None or not self.shards[0]._drift_on() else m.copy()
+
+    def drift_qtf_size(self, b):
+        return self.shards[0].drift_qtf_size(b)
 
     # -- surface panels: every shard holds the lists of all bodies and computes those of its own --
     def _nonlinear_begin(self, t, a):

@@ -363,6 +363,54 @@ class TestHydro {
         return out;
     }
 
+    // Second-order wave drift forces from difference-frequency QTF tables (not in the reference; include/hydrochrono_amd.h:
+    // hc_set_drift_qtf).  omega [nq] rad/s strictly increasing, P and Q [6][nq][nq] row-major (Q may be empty: zeros), force per
+    // squared amplitude, dimensional.  With a mode > 0 and at least one table CoordinateFuncForBody returns total + drift term, added
+    // after the nonlinear composition and the Morison term.  The body index is 1-based; an empty omega clears the table.
+    void SetDriftQTF(int body_index_1_based, const std::vector<double>& omega, const std::vector<double>& P, const std::vector<double>& Q = {}) {
+        if (body_index_1_based < 1 || body_index_1_based > num_bodies_) throw std::out_of_range("SetDriftQTF: body index out of range");
+        const size_t nq = omega.size(), n6 = 6 * nq * nq;
+        if (P.size() != n6 || (!Q.empty() && Q.size() != n6)) throw std::invalid_argument("SetDriftQTF: P and Q must hold 6 * nq * nq values");
+        for (hc_ctx* c : ctxs_)
+            check(c, hc_set_drift_qtf(c, body_index_1_based - 1, static_cast<int>(nq), nq ? omega.data() : nullptr, nq ? P.data() : nullptr,
+                                      Q.empty() ? nullptr : Q.data()));
+        drift_size_.resize(static_cast<size_t>(num_bodies_), 0);
+        drift_size_[static_cast<size_t>(body_index_1_based - 1)] = nq;
+        have_time_ = false;  // the cached total belongs to the tables before
+    }
+    // mean-drift coefficients D [6][nq]: a table with D on the diagonal and zeros elsewhere, for modes 1 and 2 (mode 3 needs a full
+    // table: it would take the zeros off the diagonal as data)
+    void SetMeanDriftCoefficients(int body_index_1_based, const std::vector<double>& omega, const std::vector<double>& D) {
+        const size_t nq = omega.size();
+        if (D.size() != 6 * nq) throw std::invalid_argument("SetMeanDriftCoefficients: D must hold 6 * nq values");
+        std::vector<double> P(6 * nq * nq, 0.0);
+        for (size_t d = 0; d < 6; ++d)
+            for (size_t m = 0; m < nq; ++m) P[(d * nq + m) * nq + m] = D[d * nq + m];
+        SetDriftQTF(body_index_1_based, omega, P);
+    }
+    // 0: off, 1: mean drift, 2: Newman's approximation, 3: full QTF
+    void SetDriftMode(int mode) {
+        for (hc_ctx* c : ctxs_) check(c, hc_set_drift_mode(c, mode));
+        drift_mode_ = mode;
+        have_time_  = false;
+    }
+    // the phase of a regular wave as the drift term sees it (that of WaveBase::GetElevation & co.)
+    void SetDriftOptions(double regular_phase = 0.0) {
+        hc_wave_kinematics_opts o;
+        hc_wave_kinematics_opts_default(&o);
+        o.regular_phase = regular_phase;
+        for (hc_ctx* c : ctxs_) check(c, hc_set_drift_options(c, &o));
+        have_time_ = false;
+    }
+    // the drift term of all bodies for the bodies' present positions, 6 N values
+    std::vector<double> ComputeForceDrift() {
+        gather_state();
+        std::vector<double> out(6 * static_cast<size_t>(num_bodies_));
+        drift_begin(bodies_[0]->GetChTime());
+        drift_end(out.data());
+        return out;
+    }
+
     // src/hydro_forces.cpp:693-711: the radiation IRF value the convolution uses (rho-scaled; the processed kernel in
     // TaperedDirect mode).  Reads one value back from the GPU -- a debugging accessor, as in the reference.
     double GetRIRFval(int row, int col, int st) {
@@ -396,6 +444,20 @@ class TestHydro {
                     throw;
                 }
             }
+            const bool drift = drift_on();
+            if (drift) {
+                try {
+                    drift_begin(t);
+                } catch (...) {  // nothing stays pending
+                    if (nonlinear)
+                        for (hc_ctx* c : ctxs_) (void)hc_nonlinear_end(c, nullptr, nullptr, nullptr);
+                    if (have_morison_) {
+                        morison_force_.resize(total_force_.size());
+                        for (hc_ctx* c : ctxs_) (void)hc_morison_end(c, morison_force_.data() + row0(c));
+                    }
+                    throw;
+                }
+            }
             const int rc = ctxs_.size() == 1 ? hc_step(ctx_, t, pos_.data(), rpy_.data(), lin_.data(), ang_.data(), total_force_.data())
                                              : hc_step_multi(ctxs_.data(), static_cast<int>(ctxs_.size()), t, pos_.data(), rpy_.data(), lin_.data(),
                                                              ang_.data(), total_force_.data());
@@ -423,6 +485,15 @@ class TestHydro {
                 } else {
                     morison_end(morison_force_.data());
                     for (size_t i = 0; i < total_force_.size(); ++i) total_force_[i] += morison_force_[i];
+                }
+            }
+            if (drift) {
+                drift_force_.resize(total_force_.size());
+                if (rc != HC_OK) {
+                    for (hc_ctx* c : ctxs_) (void)hc_drift_end(c, drift_force_.data() + row0(c));  // nothing stays pending
+                } else {
+                    drift_end(drift_force_.data());
+                    for (size_t i = 0; i < total_force_.size(); ++i) total_force_[i] += drift_force_[i];
                 }
             }
             check(ctx_, rc);
@@ -564,6 +635,31 @@ class TestHydro {
         }
         if (failed) check(failed, rc);
     }
+    bool drift_on() const {
+        return drift_mode_ != 0 && std::any_of(drift_size_.begin(), drift_size_.end(), [](size_t n) { return n != 0; });
+    }
+    void drift_begin(double t) {
+        for (size_t g = 0; g < ctxs_.size(); ++g) {
+            const int rc = hc_drift_begin(ctxs_[g], t, pos_.data());
+            if (rc != HC_OK) {
+                std::vector<double> drop(total_force_.size());
+                for (size_t h = 0; h < g; ++h) (void)hc_drift_end(ctxs_[h], drop.data());
+                check(ctxs_[g], rc);
+            }
+        }
+    }
+    void drift_end(double* out) {  // every shard is ended, then the first failure is reported
+        int rc = HC_OK;
+        hc_ctx* failed = nullptr;
+        for (hc_ctx* c : ctxs_) {
+            const int r = hc_drift_end(c, out + row0(c));
+            if (r != HC_OK && rc == HC_OK) {
+                rc     = r;
+                failed = c;
+            }
+        }
+        if (failed) check(failed, rc);
+    }
     static int row0(hc_ctx* c) {  // first output row of a shard context
         int b0 = 0;
         check(c, hc_get_shard(c, &b0, nullptr));
@@ -582,6 +678,9 @@ class TestHydro {
     std::vector<double> nonlinear_force_;  // buoy | fk | hs_lin of the last evaluation
     std::vector<size_t> panel_count_;      // surface panels per body
     int nonlinear_mode_ = 0;               // 0 off, 1 buoyancy, 2 buoyancy + Froude-Krylov
+    std::vector<double> drift_force_;      // the drift term of the last evaluation
+    std::vector<size_t> drift_size_;       // grid size of every body's drift table
+    int drift_mode_ = 0;                   // 0 off, 1 mean drift, 2 Newman, 3 full QTF
     std::array<double, 3> gravity_{0.0, 0.0, -9.81};
     bool have_time_   = false;
     double prev_time_ = -1.0;

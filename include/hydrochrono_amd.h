@@ -609,6 +609,65 @@ int hc_compute_nonlinear(hc_ctx* ctx, double t, const double* pos, const double*
                          double* hs_lin_Dlocal);
 
 /* ------------------------------------------------------------------------------------------------
+ * Second-order wave drift forces from difference-frequency QTF tables (not in the reference, whose wave forces are first order in
+ * the amplitude: no mean, no energy below the wave band).  Opt-in, per body, evaluated at the body's instantaneous position.
+ *
+ * Data per body: a frequency grid Omega[0..nq) [rad/s], finite and strictly increasing, 2 <= nq <= 256, and P[6][nq][nq],
+ * Q[6][nq][nq] (row-major): real and imaginary part of the difference-frequency QTF T_d(Omega_m, Omega_n) of the six body rows, in
+ * force (moment) per squared wave amplitude, already dimensional -- the library applies no rho or g.  Q may be NULL (zeros).  No
+ * Hermitian symmetry is required or enforced.
+ *
+ * Components (A_i, w_i, k_i, phi_i): those of the context's wave model, exactly as hc_wave_kinematics sees them (a regular wave: one
+ * component with the regular_phase option).  For body b, theta_i = k_i pos[b].x - w_i t + phi_i in that kernel's expression; only x
+ * enters (the reference's long-crested waves along +x); rotation, y, z, mwl and stretching do not.
+ *
+ * Interpolation: a component with w_i < Omega_0 or w_i > Omega_{nq-1} takes no part, in any mode.  Otherwise m_i is the largest m
+ * with Omega_m <= w_i, capped at nq - 2, lambda_i = (w_i - Omega_m) / (Omega_{m+1} - Omega_m), W[i][m_i] = 1 - lambda_i,
+ * W[i][m_i + 1] = lambda_i, 0 elsewhere; both ends of the grid are inside.  D_d(w) is the diagonal P_d[m][m] interpolated with W.
+ *
+ * Modes (hc_set_drift_mode; 0 = off, the default):
+ *     1  mean drift           F_d = sum_i A_i^2 D_d(w_i)
+ *     2  Newman               F_d = sum_i sum_j A_i A_j 1/2 (D_d(w_i) + D_d(w_j)) cos(theta_i - theta_j)
+ *     3  full QTF             F_d = sum_i sum_j A_i A_j [P_d(w_i, w_j) cos(theta_i - theta_j) - Q_d(w_i, w_j) sin(theta_i - theta_j)],
+ *                             P_d(w_i, w_j) = sum_mn W[i][m] W[j][n] P_d[m][n] (bilinear), Q likewise
+ * Modes 1 and 2 read the diagonal of P only.  Mode 3 on a table that holds a diagonal only (mean-drift coefficients) is the caller's
+ * mistake: the zeros off the diagonal are taken as data.
+ * The result is multiplied by ramp * ramp (second order in the amplitude), ramp being the factor the Morison term applies to u_f
+ * under the same conditions: the two synthesised irregular models are ramped, a regular wave is not.
+ * NoWave, no wave model, an imported eta record (no components), mode 0: zeros, no launch.  A body without a table: zeros.
+ * World frame, at the body reference, the sign of an applied force.  A regular wave gives the constant A^2 T(w, w).
+ * Sum-frequency QTFs and wave headings are not covered.
+ *
+ * The device evaluates the exact projected form, O(nf + nq^2) per row: with u_i = A_i cos theta_i, w_i = A_i sin theta_i,
+ * U_m = sum_i W[i][m] u_i, V_m = sum_i W[i][m] w_i,
+ *     mode 3  F_d = sum_mn P_d[m][n] (U_m U_n + V_m V_n) - Q_d[m][n] (V_m U_n - U_m V_n)
+ *     mode 2  F_d = (sum_m D_m U_m)(sum_m U_m) + (sum_m D_m V_m)(sum_m V_m)
+ *     mode 1  F_d = sum_m D_m E_m,  E_m = sum_i W[i][m] A_i^2
+ * in a fixed order: a body's bits depend on its own table, pos[b].x, t, the wave model, the mode and the regular phase only -- not
+ * on the number of bodies, on other bodies' tables, or on the shard context that computes it.
+ *
+ * The term is NOT part of hc_step & co., hc_get_force_components, hc_compute_* or the Morison and nonlinear calls; a caller adds it
+ * (the HydroForces / TestHydro layers do).  The path runs on a stream of its own, beside the steps, and touches no step state, no
+ * history and no per-time cache: hc_drift_begin may be followed by hc_step and then hc_drift_end.
+ * ---------------------------------------------------------------------------------------------- */
+/* Replaces the table of `body` (0-based, any body of the system; a shard context computes those of its own bodies); nq = 0 clears
+ * it.  Before or after hc_finalize, between evaluations.  HC_ERR_INVALID: body out of range, nq of 1, negative or above 256, a null
+ * grid or P with nq > 0, a non-finite value, a grid that is not strictly increasing, or a hc_drift_begin without its end. */
+int hc_set_drift_qtf(hc_ctx* ctx, int body, int nq, const double* omega, const double* P, const double* Q);
+int hc_get_drift_qtf_size(hc_ctx* ctx, int body, int* nq);
+/* 0 off (default), 1 mean drift, 2 Newman's approximation, 3 full QTF; HC_ERR_INVALID outside 0..3 or while a begin is pending */
+int hc_set_drift_mode(hc_ctx* ctx, int mode);
+int hc_get_drift_mode(hc_ctx* ctx, int* mode);
+/* only regular_phase is read; NULL = the defaults */
+int hc_set_drift_options(hc_ctx* ctx, const hc_wave_kinematics_opts* o);
+/* begin enqueues (pos as for hc_step: [3N]), end waits and copies the 6 * n_local values; exactly one end per begin.  Needs
+ * hc_finalize.  HC_ERR_INVALID on a non-finite t or pos, on a second begin, on an end without a begin; nothing stays pending after a
+ * failure. */
+int hc_drift_begin(hc_ctx* ctx, double t, const double* pos);
+int hc_drift_end(hc_ctx* ctx, double* out_Dlocal);
+int hc_compute_drift(hc_ctx* ctx, double t, const double* pos, double* out_Dlocal);
+
+/* ------------------------------------------------------------------------------------------------
  * Synthetic many-body inputs generated directly in HBM (benchmark configurations C3/C4 of SURVEY 8d;
  * not part of the reference).  Fills K, K_hs, A_inf, excitation IRF for all local bodies from a
  * counter-based generator so that a 77 GB kernel never exists on the host.  hc_finalize still applies.
