@@ -169,6 +169,8 @@ SIGNATURES = {
     "hc_compute_morison": (C.c_int, [C.c_void_p, C.c_double, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
     "hc_set_surface_panels": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(SurfacePanel), C.c_int]),
     "hc_get_surface_panel_count": (C.c_int, [C.c_void_p, C.c_int, c_int_p]),
+    "hc_set_surface_triangles": (C.c_int, [C.c_void_p, C.c_int, c_double_p, C.c_int]),
+    "hc_get_surface_triangle_count": (C.c_int, [C.c_void_p, C.c_int, c_int_p]),
     "hc_set_nonlinear_options": (C.c_int, [C.c_void_p, C.POINTER(WaveKinematicsOpts)]),
     "hc_nonlinear_begin": (C.c_int, [C.c_void_p, C.c_double, c_double_p, c_double_p]),
     "hc_nonlinear_end": (C.c_int, [C.c_void_p, c_double_p, c_double_p, c_double_p]),

@@ -277,16 +277,20 @@ struct hc_ctx {
     // bodies flattened body-major on the device with their chunk map; its own stream, component table and pinned staging, nothing a
     // step uses
     std::vector<std::vector<hc_surface_panel>> nl_panels;  // [N]
+    // Surface triangles (hc_set_surface_triangles): [N] lists of 9 doubles per triangle, clipped at the free surface by nl_tris_kernel.
+    // A body carries panels or triangles; both kinds share the stream, the table, the chunk map and the partial buffer.
+    std::vector<std::vector<double>> nl_tris;
     hc_wave_kinematics_opts nl_opts{0.0, 0.0, 1};
     hipStream_t stream_nl = nullptr;  // created by the first hc_set_surface_panels
     bool nl_dirty = false;            // the lists have changed since the device copy was made
-    int nl_items = 0, nl_chunks = 0;  // panels of the owned bodies, chunks of up to 256 of one body's list
+    int nl_items = 0, nl_chunks = 0;  // panels and triangles of the owned bodies, chunks of up to 256 of one body's list
+    std::vector<int> nl_runs;         // [runs][3] (kind 0 panels / 1 triangles, first chunk, chunks): one launch per run of consecutive chunks of a kind
     int nl_pending = 0;               // hc_nonlinear_begin without its hc_nonlinear_end: 1 zeros (nothing launched), 2 a launch is in flight
     unsigned long long nl_serial = ~0ULL;
     double nl_phase = 0.0;
     int nl_nf = 0;
-    hc::DeviceBuffer<double> d_nl_tab, d_nl_panel, d_nl_state, d_nl_part, d_nl_out;
-    hc::DeviceBuffer<int> d_nl_chunk, d_nl_off;  // [chunks][3] (body, first panel, count), [nloc + 1] first chunk of an owned body
+    hc::DeviceBuffer<double> d_nl_tab, d_nl_panel, d_nl_tri, d_nl_state, d_nl_part, d_nl_out;
+    hc::DeviceBuffer<int> d_nl_chunk, d_nl_off;  // [chunks][3] (body, first panel or triangle, count), [nloc + 1] first chunk of an owned body
     hc::PinnedBuffer<double> h_nl_state, h_nl_out;  // [6 N] pos | rpy of the last hc_nonlinear_begin, [nloc][12]
 
     // Wave drift forces (hc_set_drift_qtf, hc_drift.hip): the tables of all bodies of the system on the host, those of the owned bodies

@@ -1,7 +1,7 @@
-// hc_nonlinear.hip -- nonlinear buoyancy and Froude-Krylov forces on body surface panels (include/hydrochrono_amd.h:
-// hc_set_surface_panels, hc_nonlinear_begin / hc_nonlinear_end).  Not in the reference (src/hydro_types.h:33 is a TODO).  Off the
+// hc_nonlinear.hip -- nonlinear buoyancy and Froude-Krylov forces on body surface panels and on triangles clipped at the free surface
+// (include/hydrochrono_amd.h: hc_set_surface_panels, hc_set_surface_triangles, hc_nonlinear_begin / hc_nonlinear_end).  Not in the reference (src/hydro_types.h:33 is a TODO).  Off the
 // step path, as hc_morison.hip: its own stream, component table, buffers and pinned staging; it reads and writes nothing a step
-// uses, so it is not ordered against the direct queue.  DESIGN.md 3.7d has the definition, the kernels and their invariants.
+// uses, so it is not ordered against the direct queue.  DESIGN.md 3.7d and 3.7d' have the definitions, the kernels and their invariants.
 #include "hc_internal.hpp"
 #include "hc_wave_kin.hpp"
 
@@ -21,8 +21,8 @@ enum NlCol { kNlAmp = 0, kNlOmega, kNlK, kNlPhase, kNlW2AoK, kNlInvSinh, kNlDeep
 struct NlArgs {
     const double* tab;  // [kNlCols][nf]; nf = 0: still water
     int nf;
-    const double* panel;  // [items][6] (c, s), owned bodies one after the other
-    const int* chunk;     // [chunks][3]: body (of the system), first item, count (1 .. 256)
+    const double* panel;  // nl_panels_kernel: [items][6] (c, s); nl_tris_kernel: [items][9] (v[3][3]); owned bodies one after the other
+    const int* chunk;     // [chunks][3]: body (of the system), first item of its kind, count (1 .. 256); from the launch's first chunk on
     const double* state;  // [6 N] pos | rpy, [3N] each
     int N;
     double t, depth, mwl, rho, g;
@@ -158,36 +158,259 @@ __global__ void __launch_bounds__(kNlThreads) nl_sum_kernel(const double* part, 
     out[row] = acc;
 }
 
+// ---- triangles clipped at the instantaneous free surface (hc_set_surface_triangles; DESIGN.md 3.7d') ----
+constexpr int kNlTriDoubles = 9;  // v[3][3]
+
+// a vertex of a triangle or of its wet part: lever from the body reference (world axes) and the two pressures there
+struct NlVertex {
+    double d0, d1, d2, ps, pd;
+};
+
+// the point of edge x -> y where h = 0, h taken as linear along it; x is the wet end: h_x <= 0 < h_y, so the denominator is positive
+__device__ __forceinline__ NlVertex nl_cut(const NlVertex& x, const NlVertex& y, double hx, double hy) {
+    const double s = hx / (hx - hy);
+    return NlVertex{x.d0 + s * (y.d0 - x.d0), x.d1 + s * (y.d1 - x.d1), x.d2 + s * (y.d2 - x.d2), x.ps + s * (y.ps - x.ps), x.pd + s * (y.pd - x.pd)};
+}
+
+// one edge midpoint of a sub-triangle: -p_m S / 3 and its moment, for p_s into v[0..6) and for p_d into v[6..12)
+__device__ __forceinline__ void nl_midpoint(const NlVertex& a, const NlVertex& b, double t0, double t1, double t2, double (&v)[kNlOut]) {
+    const double m0 = 0.5 * (a.d0 + b.d0), m1 = 0.5 * (a.d1 + b.d1), m2 = 0.5 * (a.d2 + b.d2);
+    const double ps = 0.5 * (a.ps + b.ps), pd = 0.5 * (a.pd + b.pd);
+    const double f0 = -ps * t0, f1 = -ps * t1, f2 = -ps * t2;
+    const double w0 = -pd * t0, w1 = -pd * t1, w2 = -pd * t2;
+    v[0] += f0;
+    v[1] += f1;
+    v[2] += f2;
+    v[3] += m1 * f2 - m2 * f1;
+    v[4] += m2 * f0 - m0 * f2;
+    v[5] += m0 * f1 - m1 * f0;
+    v[6] += w0;
+    v[7] += w1;
+    v[8] += w2;
+    v[9] += m1 * w2 - m2 * w1;
+    v[10] += m2 * w0 - m0 * w2;
+    v[11] += m0 * w1 - m1 * w0;
+}
+
+// sub-triangle (q0, q1, q2): S = 1/2 (q1 - q0) x (q2 - q0), the three edge midpoints with the mean of the two end pressures -- exact for
+// a pressure linear in space, the moment included
+__device__ __forceinline__ void nl_sub_triangle(const NlVertex& q0, const NlVertex& q1, const NlVertex& q2, double (&v)[kNlOut]) {
+    const double a0 = q1.d0 - q0.d0, a1 = q1.d1 - q0.d1, a2 = q1.d2 - q0.d2;
+    const double b0 = q2.d0 - q0.d0, b1 = q2.d1 - q0.d1, b2 = q2.d2 - q0.d2;
+    const double t0 = 0.5 * (a1 * b2 - a2 * b1) / 3.0, t1 = 0.5 * (a2 * b0 - a0 * b2) / 3.0, t2 = 0.5 * (a0 * b1 - a1 * b0) / 3.0;
+    nl_midpoint(q0, q1, t0, t1, t2, v);
+    nl_midpoint(q1, q2, t0, t1, t2, v);
+    nl_midpoint(q2, q0, t0, t1, t2, v);
+}
+
+// nl_panels_kernel's shape for triangles: one workgroup per chunk of up to 256 triangles of ONE body, one work item per triangle
+// (a.panel is the triangle list, [items][9]).  Each item evaluates eta, p_s and p_d at its three vertices -- three independent
+// accumulator sets over the same staged components, each vertex in the expressions and the component order of nl_panels_kernel, so a
+// vertex's eta is what hc_wave_kinematics returns there -- takes h = z - mwl - eta and the pressures as linear over the triangle, cuts
+// the triangle at h = 0 and integrates over the wet part.  Idle items of a partly filled chunk evaluate the chunk's first triangle and
+// contribute exact zeros, as dry triangles do.  Then the fixed tree; lane 0 stores the chunk's 12-vector.
+__global__ void __launch_bounds__(kNlThreads) nl_tris_kernel(NlArgs a) {
+    __shared__ double s[kNlCols][kKinTile];
+    __shared__ double red[kNlOut][kNlThreads];
+    const int tid     = threadIdx.x;
+    const int b       = a.chunk[3 * blockIdx.x];
+    const int first   = a.chunk[3 * blockIdx.x + 1];
+    const int count   = a.chunk[3 * blockIdx.x + 2];
+    const bool active = tid < count;
+    const double* tv  = a.panel + static_cast<size_t>(kNlTriDoubles) * (first + (active ? tid : 0));
+    const double* pos = a.state + 3 * b;
+    const double* rpy = pos + 3 * a.N;
+
+    // ---- R = Rx(rpy0) Ry(rpy1) Rz(rpy2), d_j = R v_j, P_j = pos + d_j (the expressions of nl_panels_kernel) ----
+    double sa, ca, sb, cb, sc, cc;
+    sincos(rpy[0], &sa, &ca);
+    sincos(rpy[1], &sb, &cb);
+    sincos(rpy[2], &sc, &cc);
+    const double r00 = cb * cc, r01 = -cb * sc, r02 = sb;
+    const double r10 = ca * sc + sa * sb * cc, r11 = ca * cc - sa * sb * sc, r12 = -sa * cb;
+    const double r20 = sa * sc - ca * sb * cc, r21 = sa * cc + ca * sb * sc, r22 = ca * cb;
+    NlVertex q0, q1, q2;
+    q0.d0 = r00 * tv[0] + r01 * tv[1] + r02 * tv[2];
+    q0.d1 = r10 * tv[0] + r11 * tv[1] + r12 * tv[2];
+    q0.d2 = r20 * tv[0] + r21 * tv[1] + r22 * tv[2];
+    q1.d0 = r00 * tv[3] + r01 * tv[4] + r02 * tv[5];
+    q1.d1 = r10 * tv[3] + r11 * tv[4] + r12 * tv[5];
+    q1.d2 = r20 * tv[3] + r21 * tv[4] + r22 * tv[5];
+    q2.d0 = r00 * tv[6] + r01 * tv[7] + r02 * tv[8];
+    q2.d1 = r10 * tv[6] + r11 * tv[7] + r12 * tv[8];
+    q2.d2 = r20 * tv[6] + r21 * tv[7] + r22 * tv[8];
+    const double x0 = pos[0] + q0.d0, x1 = pos[0] + q1.d0, x2 = pos[0] + q2.d0;
+    const double z0 = pos[2] + q0.d2, z1 = pos[2] + q1.d2, z2 = pos[2] + q2.d2;
+    const double t = a.t;
+
+    // ---- eta first under stretching ----
+    double eta0 = 0.0, eta1 = 0.0, eta2 = 0.0;
+    if (a.stretch) {
+        for (int i0 = 0; i0 < a.nf; i0 += kKinTile) {
+            const int m = min(kKinTile, a.nf - i0);
+            __syncthreads();
+            for (int i = tid; i < m; i += kNlThreads) {
+                s[kNlAmp][i]   = a.tab[kNlAmp * a.nf + i0 + i];
+                s[kNlOmega][i] = a.tab[kNlOmega * a.nf + i0 + i];
+                s[kNlK][i]     = a.tab[kNlK * a.nf + i0 + i];
+                s[kNlPhase][i] = a.tab[kNlPhase * a.nf + i0 + i];
+            }
+            __syncthreads();
+            for (int i = 0; i < m; ++i) {
+                eta0 += s[kNlAmp][i] * cos(s[kNlK][i] * x0 - s[kNlOmega][i] * t + s[kNlPhase][i]);
+                eta1 += s[kNlAmp][i] * cos(s[kNlK][i] * x1 - s[kNlOmega][i] * t + s[kNlPhase][i]);
+                eta2 += s[kNlAmp][i] * cos(s[kNlK][i] * x2 - s[kNlOmega][i] * t + s[kNlPhase][i]);
+            }
+        }
+    }
+    double zs0 = z0, zs1 = z1, zs2 = z2;
+    if (a.stretch) {
+        const double zr0 = z0 - a.mwl, zr1 = z1 - a.mwl, zr2 = z2 - a.mwl;
+        zs0 = a.finite_depth ? a.depth * (zr0 - eta0) / (a.depth + eta0) : zr0 - eta0;
+        zs1 = a.finite_depth ? a.depth * (zr1 - eta1) / (a.depth + eta1) : zr1 - eta1;
+        zs2 = a.finite_depth ? a.depth * (zr2 - eta2) / (a.depth + eta2) : zr2 - eta2;
+    }
+    const double ze0 = zs0 - a.mwl, ze1 = zs1 - a.mwl, ze2 = zs2 - a.mwl;  // the second mwl subtraction under stretching
+
+    // ---- dynamic pressure sums (and eta without stretching): three independent chains per component ----
+    double pd0 = 0.0, pd1 = 0.0, pd2 = 0.0, e0 = 0.0, e1 = 0.0, e2 = 0.0;
+    for (int i0 = 0; i0 < a.nf; i0 += kKinTile) {
+        const int m = min(kKinTile, a.nf - i0);
+        __syncthreads();
+        for (int i = tid; i < m; i += kNlThreads) {
+#pragma unroll
+            for (int col = 0; col < kNlCols; ++col) s[col][i] = a.tab[col * a.nf + i0 + i];
+        }
+        __syncthreads();
+        for (int i = 0; i < m; ++i) {
+            const double k   = s[kNlK][i];
+            const double cs0 = cos(k * x0 - s[kNlOmega][i] * t + s[kNlPhase][i]);
+            const double cs1 = cos(k * x1 - s[kNlOmega][i] * t + s[kNlPhase][i]);
+            const double cs2 = cos(k * x2 - s[kNlOmega][i] * t + s[kNlPhase][i]);
+            double px0, px1, px2;
+            if (s[kNlDeep][i] != 0.0) {  // (the same branch for every item: no divergence)
+                px0 = exp(k * ze0);
+                px1 = exp(k * ze1);
+                px2 = exp(k * ze2);
+            } else {
+                px0 = cosh(k * (ze0 + a.depth)) * s[kNlInvSinh][i];
+                px1 = cosh(k * (ze1 + a.depth)) * s[kNlInvSinh][i];
+                px2 = cosh(k * (ze2 + a.depth)) * s[kNlInvSinh][i];
+            }
+            e0 += s[kNlAmp][i] * cs0;
+            e1 += s[kNlAmp][i] * cs1;
+            e2 += s[kNlAmp][i] * cs2;
+            pd0 += s[kNlW2AoK][i] * px0 * cs0;
+            pd1 += s[kNlW2AoK][i] * px1 * cs1;
+            pd2 += s[kNlW2AoK][i] * px2 * cs2;
+        }
+    }
+    if (!a.stretch) {
+        eta0 = e0;
+        eta1 = e1;
+        eta2 = e2;
+    }
+
+    // ---- h and the pressures at the vertices; a vertex is wet iff h <= 0 ----
+    const double h0 = z0 - a.mwl - eta0, h1 = z1 - a.mwl - eta1, h2 = z2 - a.mwl - eta2;
+    q0.ps = -(a.rho * a.g) * (z0 - a.mwl);
+    q1.ps = -(a.rho * a.g) * (z1 - a.mwl);
+    q2.ps = -(a.rho * a.g) * (z2 - a.mwl);
+    q0.pd = a.rho * pd0 * a.ramp;
+    q1.pd = a.rho * pd1 * a.ramp;
+    q2.pd = a.rho * pd2 * a.ramp;
+    const bool w0 = h0 <= 0.0, w1 = h1 <= 0.0, w2 = h2 <= 0.0;
+    const int nw = active ? static_cast<int>(w0) + static_cast<int>(w1) + static_cast<int>(w2) : 0;
+
+    // ---- the case table: (A, B, C) is the triangle turned so that A is the one wet vertex, or C the one dry vertex ----
+    int r = 0;
+    if (nw == 1) r = w0 ? 0 : (w1 ? 1 : 2);
+    if (nw == 2) r = !w0 ? 1 : (!w1 ? 2 : 0);
+    const NlVertex A = r == 0 ? q0 : (r == 1 ? q1 : q2);
+    const NlVertex B = r == 0 ? q1 : (r == 1 ? q2 : q0);
+    const NlVertex C = r == 0 ? q2 : (r == 1 ? q0 : q1);
+    const double hA = r == 0 ? h0 : (r == 1 ? h1 : h2);
+    const double hB = r == 0 ? h1 : (r == 1 ? h2 : h0);
+    const double hC = r == 0 ? h2 : (r == 1 ? h0 : h1);
+    double v[kNlOut];
+#pragma unroll
+    for (int k = 0; k < kNlOut; ++k) v[k] = 0.0;
+    if (nw == 3) {
+        nl_sub_triangle(A, B, C, v);
+    } else if (nw == 2) {  // (a, b, bc) and (a, bc, ca)
+        const NlVertex bc = nl_cut(B, C, hB, hC), ca = nl_cut(A, C, hA, hC);
+        nl_sub_triangle(A, B, bc, v);
+        nl_sub_triangle(A, bc, ca, v);
+    } else if (nw == 1) {  // (a, ab, ac)
+        const NlVertex ab = nl_cut(A, B, hA, hB), ac = nl_cut(A, C, hA, hC);
+        nl_sub_triangle(A, ab, ac, v);
+    }
+#pragma unroll
+    for (int k = 0; k < kNlOut; ++k) red[k][tid] = v[k];
+
+    // ---- fixed-shape tree over the 256 lanes: lane l adds lane l + h for h = 128, 64, ..., 1 (nl_panels_kernel) ----
+    for (int h = kNlThreads / 2; h > 0; h >>= 1) {
+        __syncthreads();
+        if (tid < h) {
+#pragma unroll
+            for (int k = 0; k < kNlOut; ++k) red[k][tid] += red[k][tid + h];
+        }
+    }
+    if (tid == 0) {
+        double* out = a.part + static_cast<size_t>(kNlOut) * blockIdx.x;
+#pragma unroll
+        for (int k = 0; k < kNlOut; ++k) out[k] = red[k][0];
+    }
+}
+
 bool all_finite(const double* v, size_t n) {
     for (size_t i = 0; i < n; ++i)
         if (!std::isfinite(v[i])) return false;
     return true;
 }
 
-// the device copy of the owned bodies' lists, body-major, and the chunk map: every body's list cut into chunks of 256 in index order
+// the device copy of the owned bodies' lists, body-major, and the chunk map: every body's list (panels or triangles, a body has one kind)
+// cut into chunks of 256 in index order.  Both kinds share the map and the partial buffer; consecutive chunks of one kind are a run,
+// one launch of that kind's kernel (a system with one kind: one run, one launch)
 void upload_panels(hc_ctx* c) {
-    std::vector<double> panel;
+    std::vector<double> panel, tri;
     std::vector<int> chunk, off(c->nloc + 1, 0);
-    int items = 0;
+    c->nl_runs.clear();
+    int items = 0, tris = 0;
     for (int b = c->b0; b < c->b1; ++b) {
-        const std::vector<hc_surface_panel>& list = c->nl_panels[b];
-        const int n = static_cast<int>(list.size());
-        for (const hc_surface_panel& p : list) {
-            panel.insert(panel.end(), p.c, p.c + 3);
-            panel.insert(panel.end(), p.s, p.s + 3);
+        const int n  = c->nl_panels.empty() ? 0 : static_cast<int>(c->nl_panels[b].size());
+        const int nt = (n || c->nl_tris.empty()) ? 0 : static_cast<int>(c->nl_tris[b].size() / kNlTriDoubles);  // (the setters keep one kind)
+        if (n) {
+            for (const hc_surface_panel& p : c->nl_panels[b]) {
+                panel.insert(panel.end(), p.c, p.c + 3);
+                panel.insert(panel.end(), p.s, p.s + 3);
+            }
+        } else if (nt) {
+            tri.insert(tri.end(), c->nl_tris[b].begin(), c->nl_tris[b].end());
         }
-        for (int e = 0; e < n; e += kNlThreads) {
+        const int kind = n ? 0 : 1, len = n ? n : nt, at = n ? items : tris;
+        const int chunk0 = static_cast<int>(chunk.size() / 3);
+        for (int e = 0; e < len; e += kNlThreads) {
             chunk.push_back(b);
-            chunk.push_back(items + e);
-            chunk.push_back(std::min(kNlThreads, n - e));
+            chunk.push_back(at + e);
+            chunk.push_back(std::min(kNlThreads, len - e));
+        }
+        const int chunk1 = static_cast<int>(chunk.size() / 3);
+        if (chunk1 > chunk0) {
+            if (!c->nl_runs.empty() && c->nl_runs[c->nl_runs.size() - 3] == kind)
+                c->nl_runs.back() += chunk1 - chunk0;
+            else
+                c->nl_runs.insert(c->nl_runs.end(), {kind, chunk0, chunk1 - chunk0});
         }
         items += n;
-        off[b - c->b0 + 1] = static_cast<int>(chunk.size() / 3);
+        tris += nt;
+        off[b - c->b0 + 1] = chunk1;
     }
     c->d_nl_panel.upload(panel, c->stream_nl);
+    c->d_nl_tri.upload(tri, c->stream_nl);
     c->d_nl_chunk.upload(chunk, c->stream_nl);
     c->d_nl_off.upload(off, c->stream_nl);
-    c->nl_items  = items;
+    c->nl_items  = items + tris;
     c->nl_chunks = static_cast<int>(chunk.size() / 3);
     if (c->d_nl_part.n < static_cast<size_t>(kNlOut) * c->nl_chunks) c->d_nl_part.alloc(static_cast<size_t>(kNlOut) * c->nl_chunks);
     c->nl_dirty = false;
@@ -242,8 +465,18 @@ void nonlinear_enqueue(hc_ctx* c, double t) {
     const int rows = static_cast<int>(n_out);
     hipStream_t st = c->stream_nl;
     HC_HIP(hipMemcpyAsync(c->d_nl_state.p, c->h_nl_state.p, 2 * n3 * sizeof(double), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(nl_panels_kernel, dim3(c->nl_chunks), dim3(kNlThreads), 0, st, a);
-    HC_HIP(hipGetLastError());
+    for (size_t r = 0; r < c->nl_runs.size(); r += 3) {  // a run's chunk map and partials start at its first chunk: blockIdx.x counts from there
+        const int kind = c->nl_runs[r], chunk0 = c->nl_runs[r + 1], chunks = c->nl_runs[r + 2];
+        NlArgs ar = a;
+        ar.panel  = kind ? c->d_nl_tri.p : c->d_nl_panel.p;
+        ar.chunk  = c->d_nl_chunk.p + 3 * static_cast<size_t>(chunk0);
+        ar.part   = c->d_nl_part.p + static_cast<size_t>(kNlOut) * chunk0;
+        if (kind)
+            hipLaunchKernelGGL(nl_tris_kernel, dim3(chunks), dim3(kNlThreads), 0, st, ar);
+        else
+            hipLaunchKernelGGL(nl_panels_kernel, dim3(chunks), dim3(kNlThreads), 0, st, ar);
+        HC_HIP(hipGetLastError());
+    }
     hipLaunchKernelGGL(nl_sum_kernel, dim3((rows + kNlThreads - 1) / kNlThreads), dim3(kNlThreads), 0, st, c->d_nl_part.p, c->d_nl_off.p, rows,
                        c->d_nl_out.p);
     HC_HIP(hipGetLastError());
@@ -292,6 +525,7 @@ int hc_set_surface_panels(hc_ctx* c, int body, const hc_surface_panel* panels, i
     if (!c->stream_nl) HC_HIP(hipStreamCreateWithFlags(&c->stream_nl, hipStreamNonBlocking));
     if (c->nl_panels.empty()) c->nl_panels.resize(c->N);
     c->nl_panels[body].assign(panels, panels + n);
+    if (!c->nl_tris.empty()) c->nl_tris[body].clear();  // a body carries panels or triangles
     c->nl_dirty = true;
     HC_API_END(c)
 }
@@ -300,6 +534,29 @@ int hc_get_surface_panel_count(hc_ctx* c, int body, int* n) {
     HC_API_BEGIN_HOT(c)
     require(body >= 0 && body < c->N && n, HC_ERR_INVALID, "body index out of range or null pointer");
     *n = c->nl_panels.empty() ? 0 : static_cast<int>(c->nl_panels[body].size());
+    HC_API_END(c)
+}
+
+int hc_set_surface_triangles(hc_ctx* c, int body, const double* tri, int n) {
+    HC_API_BEGIN_HOT(c)
+    require(body >= 0 && body < c->N, HC_ERR_INVALID, "body index out of range");
+    require(n >= 0 && n <= hc::kSurfaceMaxPanels, HC_ERR_INVALID, "surface triangle count negative or above the limit per body");
+    require(n == 0 || tri, HC_ERR_INVALID, "null surface triangle list");
+    require(!c->nl_pending, HC_ERR_INVALID, "a nonlinear evaluation is in flight (hc_nonlinear_end has not been called)");
+    const size_t len = static_cast<size_t>(hc::kNlTriDoubles) * static_cast<size_t>(n);
+    require(hc::all_finite(tri, len), HC_ERR_INVALID, "non-finite value in a surface triangle");
+    if (!c->stream_nl) HC_HIP(hipStreamCreateWithFlags(&c->stream_nl, hipStreamNonBlocking));
+    if (c->nl_tris.empty()) c->nl_tris.resize(c->N);
+    c->nl_tris[body].assign(tri, tri + len);
+    if (!c->nl_panels.empty()) c->nl_panels[body].clear();  // a body carries panels or triangles
+    c->nl_dirty = true;
+    HC_API_END(c)
+}
+
+int hc_get_surface_triangle_count(hc_ctx* c, int body, int* n) {
+    HC_API_BEGIN_HOT(c)
+    require(body >= 0 && body < c->N && n, HC_ERR_INVALID, "body index out of range or null pointer");
+    *n = c->nl_tris.empty() ? 0 : static_cast<int>(c->nl_tris[body].size() / hc::kNlTriDoubles);
     HC_API_END(c)
 }
 
@@ -331,6 +588,8 @@ int hc_nonlinear_begin(hc_ctx* c, double t, const double* pos, const double* rpy
     int items = 0;
     if (!c->nl_panels.empty())
         for (int b = c->b0; b < c->b1; ++b) items += static_cast<int>(c->nl_panels[b].size());
+    if (!c->nl_tris.empty())
+        for (int b = c->b0; b < c->b1; ++b) items += static_cast<int>(c->nl_tris[b].size() / hc::kNlTriDoubles);
     if (items == 0) {
         c->nl_pending = 1;
         return HC_OK;

@@ -518,15 +518,28 @@ class HydroForces:
         self._chk(self.lib.hc_set_surface_panels(self.ctx, int(b), panels, n))
         self.__dict__.setdefault("_panel_counts", {})[int(b)] = n
 
-    def set_surface_mesh(self, b, triangles):
+    def set_surface_mesh(self, b, triangles, clip=False):
         """Panels from triangles [n][3][3] (vertices in the body frame, counter-clockwise seen from the water):
-        c = (v0 + v1 + v2) / 3, s = 1/2 (v1 - v0) x (v2 - v0)."""
-        c, s = triangles_to_panels(triangles)
-        self.set_surface_panels(b, c, s)
+        c = (v0 + v1 + v2) / 3, s = 1/2 (v1 - v0) x (v2 - v0).  clip=True keeps the vertices instead (hc_set_surface_triangles): every
+        triangle is cut at the instantaneous free surface, so the force is continuous in the state and exact in still water.  A body
+        carries panels or triangles: either call replaces what the body carried."""
+        if not clip:
+            c, s = triangles_to_panels(triangles)
+            self.set_surface_panels(b, c, s)
+            return
+        tri = np.ascontiguousarray(triangles, dtype=np.float64).reshape(-1, 3, 3)
+        n = tri.shape[0]
+        self._chk(self.lib.hc_set_surface_triangles(self.ctx, int(b), _dp(tri if n else np.zeros(9)), n))
+        self.__dict__.setdefault("_panel_counts", {})[int(b)] = n  # the body's one list, of either kind
 
     def surface_panel_count(self, b):
         n = C.c_int()
         self._chk(self.lib.hc_get_surface_panel_count(self.ctx, int(b), C.byref(n)))
+        return n.value
+
+    def surface_triangle_count(self, b):
+        n = C.c_int()
+        self._chk(self.lib.hc_get_surface_triangle_count(self.ctx, int(b), C.byref(n)))
         return n.value
 
     def set_nonlinear_options(self, mwl=0.0, regular_phase=0.0, wave_stretching=True):
@@ -542,7 +555,7 @@ class HydroForces:
         self._nonlinear_mode = int(mode)
 
     def _nonlinear_on(self):
-        d = self.__dict__
+        d = self.__dict__  # _panel_counts: the size of every body's list, panels or triangles (a setter of one kind clears the other)
         return bool(d.get("_nonlinear_mode")) and any(d.get("_panel_counts", {}).values())
 
     def compute_nonlinear(self, t, pos, rpy):
@@ -785,7 +798,13 @@ class HydroGroup:
     def drift_qtf_size(self, b):
         return self.shards[0].drift_qtf_size(b)
 
-    # -- surface panels: every shard holds the lists of all bodies and computes those of its own --
+    # -- surface panels and triangles: every shard holds the lists of all bodies and computes those of its own --
+    def surface_panel_count(self, b):
+        return self.shards[0].surface_panel_count(b)
+
+    def surface_triangle_count(self, b):
+        return self.shards[0].surface_triangle_count(b)
+
     def _nonlinear_begin(self, t, a):
         begun = []
         try:

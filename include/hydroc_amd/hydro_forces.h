@@ -309,21 +309,31 @@ class TestHydro {
     // only, nothing is subtracted from the wave term); the rows of other bodies are untouched.  The body index is 1-based; an
     // empty vector clears the list.
     void SetSurfacePanels(int body_index_1_based, const std::vector<SurfacePanel>& panels) {
-        if (body_index_1_based < 1 || body_index_1_based > num_bodies_) throw std::out_of_range("SetSurfacePanels: body index out of range");
+        const int body = surface_body(body_index_1_based, "SetSurfacePanels");
         std::vector<hc_surface_panel> raw(panels.size());
         for (size_t e = 0; e < panels.size(); ++e)
             for (int k = 0; k < 3; ++k) {
                 raw[e].c[k] = panels[e].c[k];
                 raw[e].s[k] = panels[e].s[k];
             }
-        for (hc_ctx* c : ctxs_) check(c, hc_set_surface_panels(c, body_index_1_based - 1, raw.data(), static_cast<int>(raw.size())));
-        panel_count_.resize(static_cast<size_t>(num_bodies_), 0);
-        panel_count_[static_cast<size_t>(body_index_1_based - 1)] = raw.size();
-        have_time_ = false;  // the cached total belongs to the lists before
+        for (hc_ctx* c : ctxs_) check(c, hc_set_surface_panels(c, body, raw.data(), static_cast<int>(raw.size())));
+        surface_list_set(body, raw.size());
     }
     // triangles (three vertices each, in the body frame, counter-clockwise seen from the water):
     // c = (v0 + v1 + v2) / 3, s = 1/2 (v1 - v0) x (v2 - v0)
-    void SetSurfaceMesh(int body_index_1_based, const std::vector<std::array<std::array<double, 3>, 3>>& triangles) {
+    // clip = true keeps the vertices instead (hc_set_surface_triangles): every triangle is cut at the instantaneous free surface.  A
+    // body carries panels or triangles: either call replaces what the body carried.
+    void SetSurfaceMesh(int body_index_1_based, const std::vector<std::array<std::array<double, 3>, 3>>& triangles, bool clip = false) {
+        if (clip) {
+            const int body = surface_body(body_index_1_based, "SetSurfaceMesh");
+            std::vector<double> raw;
+            raw.reserve(9 * triangles.size());
+            for (const auto& v : triangles)
+                for (int j = 0; j < 3; ++j) raw.insert(raw.end(), v[j].begin(), v[j].end());
+            for (hc_ctx* c : ctxs_) check(c, hc_set_surface_triangles(c, body, raw.data(), static_cast<int>(triangles.size())));
+            surface_list_set(body, triangles.size());
+            return;
+        }
         std::vector<SurfacePanel> panels(triangles.size());
         for (size_t e = 0; e < triangles.size(); ++e) {
             const auto& v = triangles[e];
@@ -611,6 +621,17 @@ class TestHydro {
         }
         if (failed) check(failed, rc);
     }
+    // the 0-based index of a body a surface list is set on
+    int surface_body(int body_index_1_based, const char* who) const {
+        if (body_index_1_based < 1 || body_index_1_based > num_bodies_) throw std::out_of_range(std::string(who) + ": body index out of range");
+        return body_index_1_based - 1;
+    }
+    // after either setter of a body's surface list (panels or clipped triangles: the body carries the one set last)
+    void surface_list_set(int body, size_t n) {
+        panel_count_.resize(static_cast<size_t>(num_bodies_), 0);
+        panel_count_[static_cast<size_t>(body)] = n;
+        have_time_ = false;  // the cached total belongs to the lists before
+    }
     bool nonlinear_on() const {
         return nonlinear_mode_ != 0 && std::any_of(panel_count_.begin(), panel_count_.end(), [](size_t n) { return n != 0; });
     }
@@ -677,7 +698,7 @@ class TestHydro {
     std::vector<size_t> morison_count_;  // elements per body
     bool have_morison_ = false;
     std::vector<double> nonlinear_force_;  // buoy | fk | hs_lin of the last evaluation
-    std::vector<size_t> panel_count_;      // surface panels per body
+    std::vector<size_t> panel_count_;      // surface panels or triangles per body (a body carries one kind)
     int nonlinear_mode_ = 0;               // 0 off, 1 buoyancy, 2 buoyancy + Froude-Krylov
     std::vector<double> drift_force_;      // the drift term of the last evaluation
     std::vector<size_t> drift_size_;       // grid size of every body's drift table

@@ -597,12 +597,48 @@ typedef struct hc_surface_panel {
  * non-finite value, more than 1048576 panels, or a hc_nonlinear_begin without its end. */
 int hc_set_surface_panels(hc_ctx* ctx, int body, const hc_surface_panel* panels, int n);
 int hc_get_surface_panel_count(hc_ctx* ctx, int body, int* n);
-/* mwl, regular_phase, wave_stretching of the kinematics the panels see; NULL = the defaults */
+
+/* Triangles clipped at the instantaneous free surface: the second kind of surface list, opt-in, without the centroid rule's steps.
+ *
+ * Triangle lists.  Body b may carry n_b >= 0 triangles v[3][3] [m]: the vertices in the body frame, relative to the point pos[b]
+ * locates, counter-clockwise seen from the water (the outward normal is along (v1 - v0) x (v2 - v0)).  Degenerate (zero-area)
+ * triangles are allowed.  At most 1048576 triangles per body.  A body carries panels OR triangles: each of the two setters clears
+ * the other list of that body.
+ *
+ * Per vertex j, with pos, rpy and the options of hc_set_nonlinear_options:
+ *     R as above,  d_j = R v_j,  P_j = pos + d_j
+ *     eta_j, p_s,j, p_d,j: exactly what the panel definition above gives for a panel whose point p is P_j -- the same expressions,
+ *         component order, profile test, stretching with the second mwl subtraction, infinite-depth limit and ramp; still water for
+ *         NoWave, no model or an eta record.  eta_j equals hc_wave_kinematics at (P_j, t), bit for bit, under the same options.
+ *     h_j = P_j.z - mwl - eta_j; the vertex is wet iff h_j <= 0.
+ * Wet part.  h, p_s and p_d are taken as linear over the triangle; the wet part is {h <= 0}:
+ *     0 wet vertices   nothing
+ *     3 wet vertices   the whole triangle
+ *     1 wet vertex a, with b, c following in cyclic order:          the sub-triangle (a, ab, ac)
+ *     2 wet vertices, dry vertex c, a, b following c cyclically:    the sub-triangles (a, b, bc) and (a, bc, ca)
+ *     xy is the point of edge x -> y at s = h_x / (h_x - h_y), x being the WET end: h_x <= 0 < h_y, the denominator is never zero;
+ *     d, p_s and p_d at xy are interpolated with that same s.
+ * Per sub-triangle (q0, q1, q2): S = 1/2 (q1 - q0) x (q2 - q0); at the three edge midpoints m the pressure p_m is the mean of the two
+ * end values; F = sum_m (-p_m S / 3), M = sum_m m x (-p_m S / 3): exact for a pressure linear in space, the moment included.  buoy
+ * takes p_s, fk takes p_d: world frame, at the body reference, the sign of an applied force.  A body's buoy and fk are the sums over
+ * its triangles, deterministic as above: the bits depend on that body's state, its own list, the wave model, t and the options
+ * only -- not on the number of bodies, on other bodies' lists of either kind, or on the shard.  hs_lin is unchanged.
+ *
+ * Consequences.  In still water buoy is the exact hydrostatic force and moment of the polyhedron below the plane, at any attitude
+ * and draft, with any mesh, and it is continuous in the state.  In waves the free surface is linearised per triangle: second order
+ * in the triangle size.  The p_d of a vertex above the wave is the extrapolated profile (the centroid rule already uses the
+ * extrapolated profile above the mean level).
+ *
+ * HC_ERR_INVALID as hc_set_surface_panels: body out of range, n < 0, a null list with n > 0, a non-finite value, more than 1048576
+ * triangles, or a hc_nonlinear_begin without its end.  n = 0 clears the list. */
+int hc_set_surface_triangles(hc_ctx* ctx, int body, const double* tri /* [n][3][3] */, int n);
+int hc_get_surface_triangle_count(hc_ctx* ctx, int body, int* n);
+/* mwl, regular_phase, wave_stretching of the kinematics the panels and triangle vertices see; NULL = the defaults */
 int hc_set_nonlinear_options(hc_ctx* ctx, const hc_wave_kinematics_opts* o);
 /* begin enqueues (pos, rpy as for hc_step: [3N] each), end waits and copies the 6 * n_local values of each of the three terms (any
  * output pointer may be NULL); exactly one end per begin.  Needs hc_finalize.  HC_ERR_INVALID on a non-finite state or t, on a
- * gravity that is not (0, 0, -g), on a second begin, on an end without a begin; nothing stays pending after a failure.  With no panel
- * on any owned body: buoy = fk = 0, no launch. */
+ * gravity that is not (0, 0, -g), on a second begin, on an end without a begin; nothing stays pending after a failure.  Panels and
+ * triangles are served by one evaluation.  With no panel and no triangle on any owned body: buoy = fk = 0, no launch. */
 int hc_nonlinear_begin(hc_ctx* ctx, double t, const double* pos, const double* rpy);
 int hc_nonlinear_end(hc_ctx* ctx, double* buoy_Dlocal, double* fk_Dlocal, double* hs_lin_Dlocal);
 int hc_compute_nonlinear(hc_ctx* ctx, double t, const double* pos, const double* rpy, double* buoy_Dlocal, double* fk_Dlocal,
