@@ -38,6 +38,12 @@ class WaveKinematicsOpts(C.Structure):
     _fields_ = [("mwl", C.c_double), ("regular_phase", C.c_double), ("wave_stretching", C.c_int)]
 
 
+class WaveKinematics2Opts(C.Structure):
+    """hc_wave_kinematics2_opts: mwl and regular phase as above, the difference- and sum-frequency cut-offs [rad/s], the ramp switch."""
+    _fields_ = [("mwl", C.c_double), ("regular_phase", C.c_double), ("diff_lo", C.c_double), ("diff_hi", C.c_double),
+                ("sum_lo", C.c_double), ("sum_hi", C.c_double), ("apply_ramp", C.c_int)]
+
+
 class MorisonElement(C.Structure):
     """hc_morison_element: position in the body frame, Cd_i A_i and Cm_i V per body axis."""
     _fields_ = [("r", C.c_double * 3), ("cd_area", C.c_double * 3), ("cm_vol", C.c_double * 3)]
@@ -183,6 +189,10 @@ SIGNATURES = {
     "hc_drift_begin": (C.c_int, [C.c_void_p, C.c_double, c_double_p]),
     "hc_drift_end": (C.c_int, [C.c_void_p, c_double_p]),
     "hc_compute_drift": (C.c_int, [C.c_void_p, C.c_double, c_double_p, c_double_p]),
+    "hc_wave_kinematics2_opts_default": (None, [C.POINTER(WaveKinematics2Opts)]),
+    "hc_wave_kinematics2": (C.c_int, [C.c_void_p, C.POINTER(WaveKinematics2Opts), C.c_int, c_double_p, C.c_int, c_double_p,
+                                      c_double_p, c_double_p, c_double_p]),
+    "hc_wave_kinematics2_pair_tables": (C.c_int, [C.c_void_p, C.POINTER(WaveKinematics2Opts), c_double_p, c_double_p, c_double_p, c_double_p]),
     "hc_synth_fill": (C.c_int, [C.c_void_p, C.c_ulonglong, C.c_int, C.c_double, C.c_int, C.c_double]),
 }
 

@@ -312,6 +312,17 @@ struct hc_ctx {
     hc::DeviceBuffer<int> d_drift_rowptr, d_drift_idx;
     hc::PinnedBuffer<double> h_drift_pos, h_drift_out;
 
+    // Second-order wave kinematics (hc_wave_kinematics2, hc_wave_kin2.hip): the component table, the four pair tables and the band
+    // limits of the wave model, regular phase and cut-offs they were built for; its own stream and a grow-only buffer for points,
+    // times and outputs, nothing a step uses
+    hipStream_t stream_wk2 = nullptr;  // created by the first call
+    unsigned long long wk2_serial = ~0ULL;
+    double wk2_phase = 0.0, wk2_cut[4] = {0.0, 0.0, 0.0, 0.0};
+    int wk2_nf = 0;
+    bool wk2_any[2] = {false, false};  // some pair inside the difference / the sum band
+    hc::DeviceBuffer<double> d_wk2_tab, d_wk2_pair, d_wk2_io;  // [kKinCols][nf], [4][nf][nf] (K+, K-, B+, B-)
+    hc::DeviceBuffer<int> d_wk2_band;                          // [2][nf][2]: per sign (0 difference, 1 sum) and row, first and last column
+
     // GEMV configuration + scratch
     int chunk_gp = 0, nchunks_rad = 0, chunk_gp_ex = 0, nchunks_ex = 0, ngp_ex = 0;
     int chunk_gp_block = 0, nchunks_block = 0;

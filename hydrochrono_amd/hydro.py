@@ -452,6 +452,42 @@ class HydroForces:
                                               _dp(vel.reshape(-1)), _dp(acc.reshape(-1))))
         return eta, vel, acc
 
+    # -- second-order irregular waves (Sharma and Dean; an extension beyond the reference) --
+    def _wave2_opts(self, mwl, regular_phase, diff_band, sum_band, apply_ramp):
+        o = capi.WaveKinematics2Opts()
+        self.lib.hc_wave_kinematics2_opts_default(C.byref(o))
+        o.mwl, o.regular_phase, o.apply_ramp = float(mwl), float(regular_phase), int(bool(apply_ramp))
+        (o.diff_lo, o.diff_hi), (o.sum_lo, o.sum_hi) = map(float, diff_band), map(float, sum_band)
+        return o
+
+    def wave_kinematics2(self, points, times, mwl=0.0, regular_phase=0.0, diff_band=(0.0, float("inf")), sum_band=(0.0, float("inf")),
+                         apply_ramp=True):
+        """The second-order increments to wave_kinematics() at every point (P x 3) and time (T): eta2 (T, P), vel2 (T, P, 3),
+        acc2 (T, P, 3); the caller adds them to the first-order values.  diff_band / sum_band: (lo, hi) in rad/s of the
+        difference and sum frequencies that take part.  See hc_wave_kinematics2 in include/hydrochrono_amd.h."""
+        xyz = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
+        t = _arr(times)
+        P, T = xyz.shape[0], t.size
+        eta, vel, acc = np.empty((T, P)), np.empty((T, P, 3)), np.empty((T, P, 3))
+        o = self._wave2_opts(mwl, regular_phase, diff_band, sum_band, apply_ramp)
+        self._chk(self.lib.hc_wave_kinematics2(self.ctx, C.byref(o), P, _dp(xyz.reshape(-1)), T, _dp(t), _dp(eta.reshape(-1)),
+                                               _dp(vel.reshape(-1)), _dp(acc.reshape(-1))))
+        return eta, vel, acc
+
+    def wave_pair_tables(self, regular_phase=0.0, diff_band=(0.0, float("inf")), sum_band=(0.0, float("inf"))):
+        """The device's pair tables of wave_kinematics2(): dict of Kp, Km, Bp, Bm, (nf, nf) each, zero outside the bands."""
+        nf = self.wave_component_count()
+        out = {n: np.zeros((nf, nf)) for n in ("Kp", "Km", "Bp", "Bm")}
+        o = self._wave2_opts(0.0, regular_phase, diff_band, sum_band, True)
+        self._chk(self.lib.hc_wave_kinematics2_pair_tables(self.ctx, C.byref(o), *[_dp(out[n].reshape(-1)) for n in ("Kp", "Km", "Bp", "Bm")]))
+        return out
+
+    def wave_component_count(self):
+        """Components of the wave model in force as the kinematics see them: nf of the spectrum, 1 for a regular wave, else 0."""
+        if self.lib.hc_get_regular_coeffs(self.ctx, None, None, None) == capi.HC_OK:
+            return 1
+        return self.sizes()["nf"]
+
     # -- Morison drag and inertia elements (an extension beyond the reference) --
     def set_morison_elements(self, b, r, cd_area, cm_vol):
         """Replaces the element list of body b (0-based): r, cd_area, cm_vol are (n, 3) -- positions in the body frame, Cd_i A_i [m^2]
@@ -888,6 +924,13 @@ class HydroGroup:
     def wave_kinematics(self, points, times, **opts):
         # every shard holds the whole wave model and answers with the same bits
         return self.shards[0].wave_kinematics(points, times, **opts)
+
+    def wave_kinematics2(self, points, times, **opts):
+        # every shard holds the whole wave model: any of them answers (hc_wave_kinematics2: same bits from each)
+        return self.shards[0].wave_kinematics2(points, times, **opts)
+
+    def wave_pair_tables(self, **opts):
+        return self.shards[0].wave_pair_tables(**opts)
 
     def added_mass_mv(self, R, w, c):
         R = _arr(R).copy()

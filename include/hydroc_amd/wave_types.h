@@ -15,11 +15,13 @@
 // hc_set_wave_irregular_eta, whose defined behaviour replaces the reference's undefined one (src/wave_types.cpp:480-500 vs :784-785;
 // DESIGN.md section 3): the record is zero-extended, there is no spectrum (GetSpectrum throws the reference's message), and the
 // kinematics are zeros.  The mesh helper the irregular demos call (SetUpWaveMesh / GetMeshFile / GetWaveMeshVelocity) is there so that they
-// compile.
+// compile.  GetSecondOrderElevation / GetSecondOrderVelocity / GetSecondOrderAcceleration and the batched GetSecondOrderKinematics
+// (hc_wave_kinematics2) give the second-order increments of an irregular sea; they have no counterpart in the reference.
 #pragma once
 
 #include <algorithm>
 #include <array>
+#include <cmath>
 #include <cstdio>
 #include <memory>
 #include <stdexcept>
@@ -111,6 +113,50 @@ class WaveBase {  // :52-79
         kinematics(static_cast<int>(points.size()), points.empty() ? nullptr : points[0].data(), static_cast<int>(times.size()),
                    times.data(), eta ? eta->data() : nullptr, vel ? vel->data() : nullptr, acc ? acc->data() : nullptr);
     }
+    // Second-order increments of the long-crested sea of Sharma and Dean (hc_wave_kinematics2; not in the reference): what a caller
+    // adds to GetElevation / GetVelocity / GetAcceleration.  mwl_ and a regular wave's phase are those of the first-order calls,
+    // the cut-offs and the ramp switch are second_order_; NoWave (and an imported eta record) give zeros.
+    struct SecondOrderOptions {
+        double diff_lo = 0.0, diff_hi = HUGE_VAL, sum_lo = 0.0, sum_hi = HUGE_VAL;  // rad/s
+        bool apply_ramp = true;
+    } second_order_;
+    double GetSecondOrderElevation(const std::array<double, 3>& position, double time) {
+        double eta = 0.0;
+        kinematics2(1, position.data(), 1, &time, &eta, nullptr, nullptr);
+        return eta;
+    }
+    std::array<double, 3> GetSecondOrderVelocity(const std::array<double, 3>& position, double time) {
+        std::array<double, 3> v{};
+        kinematics2(1, position.data(), 1, &time, nullptr, v.data(), nullptr);
+        return v;
+    }
+    std::array<double, 3> GetSecondOrderAcceleration(const std::array<double, 3>& position, double time) {
+        std::array<double, 3> a{};
+        kinematics2(1, position.data(), 1, &time, nullptr, nullptr, a.data());
+        return a;
+    }
+    template <class V, class = decltype(std::declval<const V&>().x() + std::declval<const V&>().z())>
+    double GetSecondOrderElevation(const V& position, double time) {
+        return GetSecondOrderElevation(as_array(position), time);
+    }
+    template <class V, class = decltype(std::declval<const V&>().x() + std::declval<const V&>().z())>
+    std::array<double, 3> GetSecondOrderVelocity(const V& position, double time) {
+        return GetSecondOrderVelocity(as_array(position), time);
+    }
+    template <class V, class = decltype(std::declval<const V&>().x() + std::declval<const V&>().z())>
+    std::array<double, 3> GetSecondOrderAcceleration(const V& position, double time) {
+        return GetSecondOrderAcceleration(as_array(position), time);
+    }
+    // Batched, as GetKinematics: eta2 [T][P], vel2 / acc2 [T][P][3]; each value has the bits of the single-point call.
+    void GetSecondOrderKinematics(const std::vector<std::array<double, 3>>& points, const std::vector<double>& times,
+                                  std::vector<double>* eta2, std::vector<double>* vel2 = nullptr, std::vector<double>* acc2 = nullptr) {
+        const size_t n = points.size() * times.size();
+        if (eta2) eta2->assign(n, 0.0);
+        if (vel2) vel2->assign(3 * n, 0.0);
+        if (acc2) acc2->assign(3 * n, 0.0);
+        kinematics2(static_cast<int>(points.size()), points.empty() ? nullptr : points[0].data(), static_cast<int>(times.size()),
+                    times.data(), eta2 ? eta2->data() : nullptr, vel2 ? vel2->data() : nullptr, acc2 ? acc2->data() : nullptr);
+    }
     double mwl_ = 0.0, g_ = 9.81, water_depth_ = 0.0;  // public members of the reference's base class (:74-78); unused by the force path
 
   protected:
@@ -137,6 +183,20 @@ class WaveBase {  // :52-79
         if (!ctx_) throw std::runtime_error("wave model is not attached to a TestHydro");
         const hc_wave_kinematics_opts o = KinematicsOptions();
         check(ctx_, hc_wave_kinematics(ctx_, &o, n_points, xyz, n_times, t, eta, vel, acc));
+    }
+    void kinematics2(int n_points, const double* xyz, int n_times, const double* t, double* eta, double* vel, double* acc) {
+        if (!ctx_) throw std::runtime_error("wave model is not attached to a TestHydro");
+        const hc_wave_kinematics_opts first = KinematicsOptions();
+        hc_wave_kinematics2_opts o;
+        hc_wave_kinematics2_opts_default(&o);
+        o.mwl           = first.mwl;
+        o.regular_phase = first.regular_phase;
+        o.diff_lo       = second_order_.diff_lo;
+        o.diff_hi       = second_order_.diff_hi;
+        o.sum_lo        = second_order_.sum_lo;
+        o.sum_hi        = second_order_.sum_hi;
+        o.apply_ramp    = second_order_.apply_ramp ? 1 : 0;
+        check(ctx_, hc_wave_kinematics2(ctx_, &o, n_points, xyz, n_times, t, eta, vel, acc));
     }
 };
 

@@ -704,6 +704,65 @@ int hc_drift_end(hc_ctx* ctx, double* out_Dlocal);
 int hc_compute_drift(hc_ctx* ctx, double t, const double* pos, double* out_Dlocal);
 
 /* ------------------------------------------------------------------------------------------------
+ * Second-order irregular waves (not in the reference): the second-order increments of the long-crested sea of Sharma and Dean
+ * (1981) to the elevation, velocity and acceleration of hc_wave_kinematics, batched over points x times, on the GPU.  The caller
+ * adds them to the first-order values.  DESIGN.md 3.7f has the derivation checks and the kernels.
+ *
+ * Components (A_i, w_i, k_i, phi_i), i < nf: those of the context's wave model, exactly as hc_wave_kinematics sees them (a regular
+ * wave: one component with the regular_phase option); theta_i = k_i x - w_i t + phi_i in that kernel's expression; g = |g| and
+ * h = the water depth of the context.  h may be infinite (tanh -> 1, the profiles become e^{kappa z}).  The reference's
+ * "exponential profile when 2 pi / k > depth" test is deliberately NOT applied here: the second-order terms always use the true
+ * depth (the first-order part stays the reference's).
+ *     R_i = w_i^2 / g (from w, not from k tanh k h: the reference's k is on the dispersion curve to 1e-6 only),
+ *     r_i = sqrt(R_i),  b_i = A_i g / w_i
+ * For a pair (i, j) and a sign +-:  kappa = k_i +- k_j (signed),  Omega = w_i +- w_j,  Theta = theta_i +- theta_j,
+ * T(kappa) = |kappa| tanh(|kappa| h),
+ *     den+-  = (r_i +- r_j)^2 - T(kappa)
+ *     D+_ij  = [ (r_i + r_j) (r_i (k_j^2 - R_j^2) + r_j (k_i^2 - R_i^2)) + 2 (r_i + r_j)^2 (k_i k_j - R_i R_j) ] / den+
+ *     D-_ij  = [ (r_i - r_j) (r_j (k_i^2 - R_i^2) - r_i (k_j^2 - R_j^2)) + 2 (r_i - r_j)^2 (k_i k_j + R_i R_j) ] / den-
+ *     K+-_ij = (D+-_ij - (k_i k_j -+ R_i R_j)) / (r_i r_j) + (R_i + R_j)
+ *     B+-_ij = 1/4 b_i b_j D+-_ij / Omega,                 D-_ij = B-_ij = 0 where w_i == w_j
+ * With C(kappa, z) = cosh(|kappa| (z + h)) / cosh(|kappa| h), S likewise with sinh in the numerator (both e^{|kappa| z} for an
+ * infinite h), all sums over every i, every j and, where B appears, both signs:
+ *     eta2 = 1/4 sum A_i A_j [K-_ij cos(theta_i - theta_j) + K+_ij cos(theta_i + theta_j)]
+ *     u2x  = sum B kappa C cos Theta          u2z = sum B |kappa| S sin Theta            (y components 0)
+ *     a2x  = sum B kappa Omega C sin Theta    a2z = -sum B |kappa| Omega S cos Theta     (local acceleration, as first order)
+ * (the gradient and its time derivative of phi2 = sum B C sin Theta).  The profiles are taken at z2 = min(z - mwl, 0), and at -h
+ * below the bed: above the mean level the second-order fields are held at their mean-level value (the expansion is about z = 0;
+ * e^{(k_i + k_j) z} is not extrapolated upward).  No Wheeler stretching applies to these terms.
+ *
+ * Cut-offs [rad/s]: a difference term takes part when diff_lo <= |w_i - w_j| <= diff_hi, a sum term when sum_lo <= w_i + w_j <=
+ * sum_hi; the defaults 0 and +inf take everything.  They decide the cost: only the band of the pair matrix is visited, a band
+ * that excludes every pair of a sign skips that sign, and two empty bands give zeros without a launch.
+ * Ramp: with apply_ramp (the default) the increments are multiplied by ramp * ramp, ramp being the factor the Morison term applies
+ * to u_f under the same conditions (the two synthesised irregular models, ramp_duration > 0 and t < ramp_duration; a regular wave
+ * is not ramped).  hc_wave_kinematics itself is not ramped, hence the switch.
+ * NoWave, no wave model, or an imported eta record (no components): zeros, no launch.  A regular wave: the single pair i = j,
+ * which is Stokes' second-order term plus the constant set-down.  More than 4096 components: HC_ERR_UNSUPPORTED (the four pair
+ * tables take 4 nf^2 doubles of device memory: 8 MB at 512 components, 134 MB at 2048, 537 MB at 4096).
+ *
+ * Every (point, time) item is summed by one workgroup in a fixed order: its bits depend on the item, the wave model and the
+ * options only -- not on the batch it is part of, its place in it, the outputs asked for, or the shard context that answers.
+ * The Morison, surface-pressure and drift terms keep seeing the first-order field.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct hc_wave_kinematics2_opts {
+    double mwl;            /* WaveBase::mwl_ (0) */
+    double regular_phase;  /* RegularWave::regular_wave_phase_ (0) */
+    double diff_lo, diff_hi, sum_lo, sum_hi; /* cut-offs in rad/s (0, +inf, 0, +inf) */
+    int apply_ramp;        /* (1) */
+} hc_wave_kinematics2_opts;
+void hc_wave_kinematics2_opts_default(hc_wave_kinematics2_opts* o);
+/* xyz[n_points][3], t[n_times] -> eta2[T][P], vel2[T][P][3], acc2[T][P][3]: the contract of hc_wave_kinematics (any output may be
+ * NULL, o NULL = the defaults, counts >= 0, a pointer where its count is > 0, finite x, z, t, mwl and regular_phase, at most
+ * 2^31 - 256 (point, time) pairs, needs hc_finalize, synchronous, changes no force and no step state; it runs on a stream of its
+ * own).  Also HC_ERR_INVALID: a negative or NaN cut-off, or lo > hi. */
+int hc_wave_kinematics2(hc_ctx* ctx, const hc_wave_kinematics2_opts* o, int n_points, const double* xyz,
+                        int n_times, const double* t, double* eta2, double* vel2, double* acc2);
+/* The device's own pair tables K+, K-, B+, B- copied back, [nf][nf] each (row i, column j; nf from hc_get_sizes, 1 for a regular
+ * wave); entries outside their cut-off band are 0.  Any pointer may be NULL.  No components: nothing is written. */
+int hc_wave_kinematics2_pair_tables(hc_ctx* ctx, const hc_wave_kinematics2_opts* o, double* Kp, double* Km, double* Bp, double* Bm);
+
+/* ------------------------------------------------------------------------------------------------
  * Synthetic many-body inputs generated directly in HBM (benchmark configurations C3/C4 of SURVEY 8d;
  * not part of the reference).  Fills K, K_hs, A_inf, excitation IRF for all local bodies from a
  * counter-based generator so that a 77 GB kernel never exists on the host.  hc_finalize still applies.
