@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 
 #include <chrono>
+#include <cmath>
 #include <deque>
 #include <stdexcept>
 #include <string>
@@ -94,6 +95,24 @@ struct BarBuffer {
         if (p) (void)hipFree(p);
     }
     void alloc(size_t count);  // hc_runtime.cpp (probes host visibility without faulting)
+};
+
+// The device tables of the second-order pair sums (hc_wave_kin2.hip: wk2_tables) and what they were built for
+struct Wk2TableSet {
+    unsigned long long serial = ~0ULL;  // wave_serial they belong to; ~0: nothing cached
+    double phase = 0.0, cut[4] = {0.0, 0.0, 0.0, 0.0};
+    int nf = 0;
+    bool any[2] = {false, false};       // some pair inside the difference / the sum band
+    DeviceBuffer<double> d_tab, d_pair;  // [kKinCols][nf], [4][nf][nf] (K+, K-, B+, B-)
+    DeviceBuffer<int> d_band;            // [2][nf][2]: per sign (0 difference, 1 sum) and row, first and last column
+    void release() {
+        d_tab.release();
+        d_pair.release();
+        d_band.release();
+        serial = ~0ULL;
+        nf = 0;
+        any[0] = any[1] = false;
+    }
 };
 
 // A body's difference-frequency QTF table (hc_set_drift_qtf): nq = 0 none
@@ -272,6 +291,18 @@ struct hc_ctx {
     hc::DeviceBuffer<double> d_mor_tab, d_mor_elem, d_mor_state, d_mor_item, d_mor_out;
     hc::DeviceBuffer<int> d_mor_body, d_mor_off;  // [items] body of an element, [nloc + 1] first element of an owned body
     hc::PinnedBuffer<double> h_mor_state, h_mor_out;
+    // ... on the second-order sea (hc_set_morison_second_order): tables of its own, built on stream_mor (a hc_wave_kinematics2 call
+    // with other cut-offs may rebuild `wk2` while a launch of this path is in flight), the elements' points and increments
+    bool mor2_on = false;
+    double mor2_cut[4] = {0.0, HUGE_VAL, 0.0, HUGE_VAL};
+    int mor2_ramp = 1;
+    hc::Wk2TableSet mor2;
+    hc::DeviceBuffer<double> d_mor_inc;     // [items][kMorIncDoubles] p, eta2, u2x, u2z, a2x, a2z
+    hc::PinnedBuffer<double> h_mor_inc[2];  // its host copies: of the evaluation in flight and of the last completed one
+    int mor_inc_cur = 0;                    // which of the two holds the last completed one
+    bool mor_inc_flight = false;            // the evaluation in flight writes the other one
+    std::vector<int> mor_inc_off;           // [nloc + 1] first element of an owned body in it; empty: no evaluation has completed
+    std::vector<int> mor_off;               // [nloc + 1] of the device copy of the lists
 
     // Surface panels (hc_set_surface_panels, hc_nonlinear.hip): the lists of all bodies of the system on the host, those of the owned
     // bodies flattened body-major on the device with their chunk map; its own stream, component table and pinned staging, nothing a
@@ -312,16 +343,11 @@ struct hc_ctx {
     hc::DeviceBuffer<int> d_drift_rowptr, d_drift_idx;
     hc::PinnedBuffer<double> h_drift_pos, h_drift_out;
 
-    // Second-order wave kinematics (hc_wave_kinematics2, hc_wave_kin2.hip): the component table, the four pair tables and the band
-    // limits of the wave model, regular phase and cut-offs they were built for; its own stream and a grow-only buffer for points,
-    // times and outputs, nothing a step uses
+    // Second-order wave kinematics (hc_wave_kinematics2, hc_wave_kin2.hip): the tables of the wave model, regular phase and cut-offs
+    // they were built for; its own stream and a grow-only buffer for points, times and outputs, nothing a step uses
     hipStream_t stream_wk2 = nullptr;  // created by the first call
-    unsigned long long wk2_serial = ~0ULL;
-    double wk2_phase = 0.0, wk2_cut[4] = {0.0, 0.0, 0.0, 0.0};
-    int wk2_nf = 0;
-    bool wk2_any[2] = {false, false};  // some pair inside the difference / the sum band
-    hc::DeviceBuffer<double> d_wk2_tab, d_wk2_pair, d_wk2_io;  // [kKinCols][nf], [4][nf][nf] (K+, K-, B+, B-)
-    hc::DeviceBuffer<int> d_wk2_band;                          // [2][nf][2]: per sign (0 difference, 1 sum) and row, first and last column
+    hc::Wk2TableSet wk2;
+    hc::DeviceBuffer<double> d_wk2_io;
 
     // GEMV configuration + scratch
     int chunk_gp = 0, nchunks_rad = 0, chunk_gp_ex = 0, nchunks_ex = 0, ngp_ex = 0;

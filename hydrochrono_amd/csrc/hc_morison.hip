@@ -1,9 +1,12 @@
 // hc_morison.hip -- Morison drag and inertia elements on the wave kinematics (include/hydrochrono_amd.h: hc_set_morison_elements,
 // hc_morison_begin / hc_morison_end).  Not in the reference.  Off the step path: its own stream, component table, buffers and pinned
 // staging; it reads and writes nothing a step uses, so it is not ordered against the direct queue (as hc_wave_kinematics).
-// DESIGN.md 3.7c has the definition, the kernels and their invariants.
+// DESIGN.md 3.7c has the definition, the kernels and their invariants; 3.7g the elements on the second-order sea
+// (hc_set_morison_second_order): the increments of hc_wave_kinematics2 at every element, added before the wet test and the force.
 #include "hc_internal.hpp"
 #include "hc_wave_kin.hpp"
+#include "hc_wave_kin2.hpp"
+#include "hc_wave_kin2_sum.hpp"
 
 using namespace hc::detail;
 
@@ -12,6 +15,7 @@ namespace {
 
 constexpr int kMorThreads = 256;  // work items per workgroup, one per element
 constexpr int kMorElemDoubles = 9;  // r, cd_area, cm_vol
+constexpr int kMorIncDoubles = 8;   // p, eta2, u2x, u2z, a2x, a2z of an element on the second-order sea
 
 struct MorArgs {
     const double* tab;  // [kKinCols][nf] (hc_wave_kin.hpp); nf = 0: still water
@@ -26,12 +30,40 @@ struct MorArgs {
     int stretch;       // Wheeler stretching
     int finite_depth;  // 0: water depth +inf
     double* item;      // [n_items][6] (F, M) of every element
+    const double* inc; // [n_items][kMorIncDoubles] of morison2_incr_kernel (the order-2 instantiation only)
 };
+
+// R = Rx(rpy0) Ry(rpy1) Rz(rpy2), d = R r, p = pos + d (x and z: the wave travels along x): one expression for the kernel that
+// evaluates the elements and the one that sums their second-order increments, so that both see the same point bit for bit
+struct MorFrame {
+    double r00, r01, r02, r10, r11, r12, r20, r21, r22;
+    double d0, d1, d2;
+    double x, z;
+};
+
+__device__ inline MorFrame morison_frame(const double* el, const double* pos, const double* rpy) {
+    double sa, ca, sb, cb, sc, cc;
+    sincos(rpy[0], &sa, &ca);
+    sincos(rpy[1], &sb, &cb);
+    sincos(rpy[2], &sc, &cc);
+    MorFrame f;
+    f.r00 = cb * cc, f.r01 = -cb * sc, f.r02 = sb;
+    f.r10 = ca * sc + sa * sb * cc, f.r11 = ca * cc - sa * sb * sc, f.r12 = -sa * cb;
+    f.r20 = sa * sc - ca * sb * cc, f.r21 = sa * cc + ca * sb * sc, f.r22 = ca * cb;
+    f.d0 = f.r00 * el[0] + f.r01 * el[1] + f.r02 * el[2];
+    f.d1 = f.r10 * el[0] + f.r11 * el[1] + f.r12 * el[2];
+    f.d2 = f.r20 * el[0] + f.r21 * el[1] + f.r22 * el[2];
+    f.x = pos[0] + f.d0, f.z = pos[2] + f.d2;
+    return f;
+}
 
 // One work item per element.  Every item derives its body's frame from the 12 state values, sums the wave components in index
 // order from the same LDS tiles (the loop of wave_kinematics_kernel) and writes its own 6-vector: its bits depend on its body's
 // state, its own data, the table, t and the options, not on where in the grid it sits.  Without stretching eta comes out of the
 // kinematics pass (the same sincos); with stretching it is summed first.
+// ORDER2: the element's second-order increments (morison2_incr_kernel, earlier on the stream) are read after the first-order sums
+// and added before the wet test and the force; the first-order part, stretching by eta1 included, is the code of order 1.
+template <bool ORDER2>
 __global__ void __launch_bounds__(kMorThreads) morison_items_kernel(MorArgs a) {
     __shared__ double s[kKinCols][kKinTile];
     const int o       = blockIdx.x * kMorThreads + threadIdx.x;
@@ -45,17 +77,10 @@ __global__ void __launch_bounds__(kMorThreads) morison_items_kernel(MorArgs a) {
     const double* ang = lin + 3 * a.N;
 
     // ---- R = Rx(rpy0) Ry(rpy1) Rz(rpy2), d = R r, p = pos + d ----
-    double sa, ca, sb, cb, sc, cc;
-    sincos(rpy[0], &sa, &ca);
-    sincos(rpy[1], &sb, &cb);
-    sincos(rpy[2], &sc, &cc);
-    const double r00 = cb * cc, r01 = -cb * sc, r02 = sb;
-    const double r10 = ca * sc + sa * sb * cc, r11 = ca * cc - sa * sb * sc, r12 = -sa * cb;
-    const double r20 = sa * sc - ca * sb * cc, r21 = sa * cc + ca * sb * sc, r22 = ca * cb;
-    const double d0 = r00 * el[0] + r01 * el[1] + r02 * el[2];
-    const double d1 = r10 * el[0] + r11 * el[1] + r12 * el[2];
-    const double d2 = r20 * el[0] + r21 * el[1] + r22 * el[2];
-    const double x = pos[0] + d0, z = pos[2] + d2, t = a.t;
+    const MorFrame f = morison_frame(el, pos, rpy);
+    const double r00 = f.r00, r01 = f.r01, r02 = f.r02, r10 = f.r10, r11 = f.r11, r12 = f.r12, r20 = f.r20, r21 = f.r21, r22 = f.r22;
+    const double d0 = f.d0, d1 = f.d1, d2 = f.d2;
+    const double x = f.x, z = f.z, t = a.t;
 
     // ---- eta first under stretching (wave_kinematics_kernel) ----
     double eta = 0.0;
@@ -112,6 +137,12 @@ __global__ void __launch_bounds__(kMorThreads) morison_items_kernel(MorArgs a) {
     }
     if (!active) return;
     if (!a.stretch) eta = eta1;
+    double u2x = 0.0, u2z = 0.0, a2x = 0.0, a2z = 0.0;
+    if constexpr (ORDER2) {
+        const double* q = a.inc + static_cast<size_t>(kMorIncDoubles) * o;
+        eta += q[3];
+        u2x = q[4], u2z = q[5], a2x = q[6], a2z = q[7];
+    }
 
     double* out = a.item + 6 * static_cast<size_t>(o);
     if (!(z - a.mwl <= eta)) {  // dry
@@ -121,10 +152,11 @@ __global__ void __launch_bounds__(kMorThreads) morison_items_kernel(MorArgs a) {
     }
     // ---- relative flow in the body frame, force per body axis, back to the world frame ----
     const double w0 = ang[0], w1 = ang[1], w2 = ang[2];
-    const double q0 = a.ramp * ux - (lin[0] + (w1 * d2 - w2 * d1));
+    double ufx = a.ramp * ux, ufz = a.ramp * uz, afx = a.ramp * ax, afz = a.ramp * az;
+    if constexpr (ORDER2) ufx += u2x, ufz += u2z, afx += a2x, afz += a2z;
+    const double q0 = ufx - (lin[0] + (w1 * d2 - w2 * d1));
     const double q1 = -(lin[1] + (w2 * d0 - w0 * d2));
-    const double q2 = a.ramp * uz - (lin[2] + (w0 * d1 - w1 * d0));
-    const double afx = a.ramp * ax, afz = a.ramp * az;
+    const double q2 = ufz - (lin[2] + (w0 * d1 - w1 * d0));
     const double u0 = r00 * q0 + r10 * q1 + r20 * q2, a0 = r00 * afx + r20 * afz;
     const double u1 = r01 * q0 + r11 * q1 + r21 * q2, a1 = r01 * afx + r21 * afz;
     const double u2 = r02 * q0 + r12 * q1 + r22 * q2, a2 = r02 * afx + r22 * afz;
@@ -140,6 +172,43 @@ __global__ void __launch_bounds__(kMorThreads) morison_items_kernel(MorArgs a) {
     out[3] = d1 * F2 - d2 * F1;
     out[4] = d2 * F0 - d0 * F2;
     out[5] = d0 * F1 - d1 * F0;
+}
+
+struct Mor2Args {
+    Wk2Sea sea;           // the Morison path's own tables (hc_ctx::mor2), mwl of the Morison options
+    const double* elem;   // as MorArgs
+    const int* body;
+    const double* state;
+    int N;
+    double t;
+    int ramped;           // ramp * ramp applies (apply_ramp, a synthesised irregular model, ramp_duration > 0)
+    double ramp_duration;
+    double* inc;          // [n_items][kMorIncDoubles]
+};
+
+// One workgroup per element of the owned bodies: the point of morison_items_kernel (morison_frame), then the pair sum of
+// hc_wave_kinematics2 at that point and time (wk2_item_sum, with its epilogue): what it stores is what that call returns for the
+// stored point, bit for bit.
+__global__ void __launch_bounds__(kWk2Threads) morison2_incr_kernel(Mor2Args a) {
+    const int e       = blockIdx.x;  // the grid is n_items
+    const int b       = a.body[e];
+    const double* pos = a.state + 3 * b;
+    const MorFrame f  = morison_frame(a.elem + static_cast<size_t>(kMorElemDoubles) * e, pos, pos + 3 * a.N);
+    const double x = f.x, y = pos[1] + f.d1, z = f.z;
+    double sum[5];
+    wk2_item_sum<true, true>(a.sea, x, z, a.t, sum);
+    if (threadIdx.x == 0) {
+        const double ramp2 = wk2_ramp2(a.ramped != 0, a.ramp_duration, a.t);
+        double* out = a.inc + static_cast<size_t>(kMorIncDoubles) * e;
+        out[0] = x;
+        out[1] = y;
+        out[2] = z;
+        out[3] = 0.25 * sum[0] * ramp2;
+        out[4] = sum[1] * ramp2;
+        out[5] = sum[2] * ramp2;
+        out[6] = sum[3] * ramp2;
+        out[7] = sum[4] * ramp2;
+    }
 }
 
 // One work item per (owned body, component): the serial sum over the body's elements in index order.
@@ -174,6 +243,7 @@ void upload_elements(hc_ctx* c) {
     c->d_mor_elem.upload(elem, c->stream_mor);
     c->d_mor_body.upload(body, c->stream_mor);
     c->d_mor_off.upload(off, c->stream_mor);
+    c->mor_off = off;
     c->mor_items = static_cast<int>(body.size());
     if (c->d_mor_item.n < 6 * body.size()) c->d_mor_item.alloc(6 * body.size());
     c->mor_dirty = false;
@@ -223,9 +293,43 @@ void morison_enqueue(hc_ctx* c, double t, const double* pos, const double* rpy, 
     a.finite_depth = std::isfinite(c->depth) ? 1 : 0;
     a.item         = c->d_mor_item.p;
     hipStream_t st = c->stream_mor;
+    // the second-order sea: tables of this path's own, then the increments of every element.  No components (NoWave, no model, an
+    // imported eta record) or no pair inside either band: order 1, no further launch.
+    bool order2 = false;
+    if (c->mor2_on && wk2_has_components(c)) {
+        wk2_tables(c, c->mor2, st, c->mor_opts.regular_phase, c->mor2_cut, false);
+        order2 = c->mor2.any[0] || c->mor2.any[1];
+    }
+    const size_t n_inc = static_cast<size_t>(kMorIncDoubles) * a.n_items;
+    PinnedBuffer<double>& h_inc = c->h_mor_inc[c->mor_inc_cur ^ 1];
+    if (order2) {
+        if (c->d_mor_inc.n < n_inc) c->d_mor_inc.alloc(n_inc);
+        if (h_inc.n < n_inc) h_inc.alloc(n_inc);
+        a.inc = c->d_mor_inc.p;
+    }
     HC_HIP(hipMemcpyAsync(c->d_mor_state.p, c->h_mor_state.p, 4 * n3 * sizeof(double), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(morison_items_kernel, dim3((a.n_items + kMorThreads - 1) / kMorThreads), dim3(kMorThreads), 0, st, a);
+    const dim3 item_grid((a.n_items + kMorThreads - 1) / kMorThreads);
+    if (order2) {
+        Mor2Args m{};
+        m.sea           = Wk2Sea{c->mor2.d_tab.p, c->mor2.nf, c->mor2.d_pair.p, c->mor2.d_band.p, c->depth, a.mwl, a.finite_depth,
+                                 {c->mor2.any[0] ? 1 : 0, c->mor2.any[1] ? 1 : 0}};
+        m.elem          = a.elem;
+        m.body          = a.body;
+        m.state         = a.state;
+        m.N             = a.N;
+        m.t             = t;
+        m.ramped        = (c->mor2_ramp && synthesised && rd > 0.0) ? 1 : 0;  // the rule of hc_wave_kinematics2
+        m.ramp_duration = rd;
+        m.inc           = c->d_mor_inc.p;
+        hipLaunchKernelGGL(morison2_incr_kernel, dim3(a.n_items), dim3(kWk2Threads), 0, st, m);
+        HC_HIP(hipGetLastError());
+        HC_HIP(hipMemcpyAsync(h_inc.p, c->d_mor_inc.p, n_inc * sizeof(double), hipMemcpyDeviceToHost, st));
+        hipLaunchKernelGGL(morison_items_kernel<true>, item_grid, dim3(kMorThreads), 0, st, a);
+    } else {
+        hipLaunchKernelGGL(morison_items_kernel<false>, item_grid, dim3(kMorThreads), 0, st, a);
+    }
     HC_HIP(hipGetLastError());
+    c->mor_inc_flight = order2;
     hipLaunchKernelGGL(morison_sum_kernel, dim3((c->Dloc + kMorThreads - 1) / kMorThreads), dim3(kMorThreads), 0, st, c->d_mor_item.p,
                        c->d_mor_off.p, c->Dloc, c->d_mor_out.p);
     HC_HIP(hipGetLastError());
@@ -253,6 +357,7 @@ int hc_set_morison_elements(hc_ctx* c, int body, const hc_morison_element* elems
     if (c->mor_elems.empty()) c->mor_elems.resize(c->N);
     c->mor_elems[body].assign(elems, elems + n);
     c->mor_dirty = true;
+    c->mor_inc_off.clear();  // hc_get_morison_increments: the lists of the last evaluation are no longer the lists
     HC_API_END(c)
 }
 
@@ -274,6 +379,54 @@ int hc_set_morison_options(hc_ctx* c, const hc_wave_kinematics_opts* o) {
     HC_API_END(c)
 }
 
+int hc_set_morison_second_order(hc_ctx* c, int on, double diff_lo, double diff_hi, double sum_lo, double sum_hi, int apply_ramp) {
+    HC_API_BEGIN_HOT(c)
+    hc_wave_kinematics2_opts o;
+    hc_wave_kinematics2_opts_default(&o);
+    o.diff_lo = diff_lo, o.diff_hi = diff_hi, o.sum_lo = sum_lo, o.sum_hi = sum_hi;
+    const char* bad = hc::wk2_check_opts(o);
+    require(bad == nullptr, HC_ERR_INVALID, bad ? bad : "");
+    require(!c->mor_pending, HC_ERR_INVALID, "a Morison evaluation is in flight (hc_morison_end has not been called)");
+    c->mor2_on     = on != 0;
+    c->mor2_cut[0] = diff_lo, c->mor2_cut[1] = diff_hi, c->mor2_cut[2] = sum_lo, c->mor2_cut[3] = sum_hi;
+    c->mor2_ramp   = apply_ramp != 0;
+    if (!c->mor2_on) {  // the second copy of the tables goes (nothing of this path is in flight)
+        c->mor2.release();
+        c->d_mor_inc.release();
+        c->mor_inc_off.clear();
+    }
+    HC_API_END(c)
+}
+
+int hc_get_morison_second_order(hc_ctx* c, int* on, double* diff_lo, double* diff_hi, double* sum_lo, double* sum_hi, int* apply_ramp) {
+    HC_API_BEGIN_HOT(c)
+    if (on) *on = c->mor2_on ? 1 : 0;
+    if (diff_lo) *diff_lo = c->mor2_cut[0];
+    if (diff_hi) *diff_hi = c->mor2_cut[1];
+    if (sum_lo) *sum_lo = c->mor2_cut[2];
+    if (sum_hi) *sum_hi = c->mor2_cut[3];
+    if (apply_ramp) *apply_ramp = c->mor2_ramp;
+    HC_API_END(c)
+}
+
+int hc_get_morison_increments(hc_ctx* c, int body, double* p, double* eta2, double* vel2, double* acc2) {
+    HC_API_BEGIN_HOT(c)
+    require(c->mor2_on, HC_ERR_INVALID, "Morison elements on the second-order sea are switched off (hc_set_morison_second_order)");
+    require(body >= c->b0 && body < c->b1, HC_ERR_INVALID, "body not owned by this context");
+    require(!c->mor_inc_off.empty(), HC_ERR_INVALID, "no Morison evaluation with a second-order part has completed");
+    const double* q = c->h_mor_inc[c->mor_inc_cur].p;
+    const int e0 = c->mor_inc_off[body - c->b0], e1 = c->mor_inc_off[body - c->b0 + 1];
+    for (int e = e0; e < e1; ++e) {
+        const double* v = q + static_cast<size_t>(hc::kMorIncDoubles) * e;
+        const size_t i  = static_cast<size_t>(e - e0);
+        if (p) std::copy(v, v + 3, p + 3 * i);
+        if (eta2) eta2[i] = v[3];
+        if (vel2) vel2[3 * i] = v[4], vel2[3 * i + 1] = 0.0, vel2[3 * i + 2] = v[5];
+        if (acc2) acc2[3 * i] = v[6], acc2[3 * i + 1] = 0.0, acc2[3 * i + 2] = v[7];
+    }
+    HC_API_END(c)
+}
+
 int hc_morison_begin(hc_ctx* c, double t, const double* pos, const double* rpy, const double* linvel, const double* angvel) {
     HC_API_BEGIN_HOT(c)
     require(c->finalized, HC_ERR_INVALID, "hc_finalize has not been called");
@@ -282,9 +435,12 @@ int hc_morison_begin(hc_ctx* c, double t, const double* pos, const double* rpy, 
     const size_t n3 = 3 * static_cast<size_t>(c->N);
     require(std::isfinite(t) && hc::all_finite(pos, n3) && hc::all_finite(rpy, n3) && hc::all_finite(linvel, n3) && hc::all_finite(angvel, n3),
             HC_ERR_INVALID, "non-finite time or state");
+    require(!(c->mor2_on && hc::wk2_has_components(c)) || hc::wk2_component_count(c) <= hc::kWk2MaxFreq, HC_ERR_UNSUPPORTED,
+            "Morison elements on the second-order sea: more than 4096 wave components");
     int items = 0;
     if (!c->mor_elems.empty())
         for (int b = c->b0; b < c->b1; ++b) items += static_cast<int>(c->mor_elems[b].size());
+    c->mor_inc_flight = false;
     if (items == 0) {
         c->mor_pending = 1;
         return HC_OK;
@@ -304,7 +460,14 @@ int hc_morison_end(hc_ctx* c, double* out) {
     require(c->mor_pending != 0, HC_ERR_INVALID, "hc_morison_end without hc_morison_begin");
     const int what = c->mor_pending;
     c->mor_pending = 0;
+    const bool with_inc = c->mor_inc_flight;
+    c->mor_inc_flight = false;
+    c->mor_inc_off.clear();  // (stays so when the wait fails)
     if (what == 2) HC_HIP(hipStreamSynchronize(c->stream_mor));
+    if (with_inc) {  // the evaluation that has completed is the one hc_get_morison_increments answers with
+        c->mor_inc_cur ^= 1;
+        c->mor_inc_off = c->mor_off;
+    }
     require(out != nullptr, HC_ERR_INVALID, "null output");
     if (what == 2) std::copy(c->h_mor_out.p, c->h_mor_out.p + c->Dloc, out);
     else std::fill(out, out + c->Dloc, 0.0);

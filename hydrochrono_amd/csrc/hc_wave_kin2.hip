@@ -6,24 +6,20 @@
 #include "hc_internal.hpp"
 #include "hc_wave_kin.hpp"
 #include "hc_wave_kin2.hpp"
+#include "hc_wave_kin2_sum.hpp"
 
 #include <algorithm>
 #include <cstring>
 
 using namespace hc::detail;
 
-// No implicit fusing of a multiplication into an addition below: the sums are written with explicit fma() where one is wanted, so
-// that an item's bits are the same in every instantiation of the sum kernel (whatever outputs were asked for).
+// No implicit fusing of a multiplication into an addition below (the shared pair sum of hc_wave_kin2_sum.hpp switches it off for
+// itself, wherever it is compiled): the sums are written with explicit fma() where one is wanted, so that an item's bits are the
+// same in every instantiation of the sum kernel (whatever outputs were asked for).
 #pragma clang fp contract(off)
 
 namespace hc {
 namespace {
-
-constexpr int kWk2Threads = 256;  // work items per workgroup: four waves, each takes every fourth row of a tile
-constexpr int kWk2Waves   = kWk2Threads / 64;
-static_assert(kKinTile == kWk2Threads, "one lane per component of a staged tile");
-
-enum Wk2Table { kWk2Kp = 0, kWk2Km, kWk2Bp, kWk2Bm, kWk2Tables };
 
 struct Wk2PairArgs {
     const double* tab;  // [kKinCols][nf] (hc_wave_kin.hpp)
@@ -95,200 +91,83 @@ struct Wk2SumArgs {
     double* acc;         // [T][P][3] }
 };
 
-// One workgroup per (point, time) item o = j * P + p.  The upper triangle j >= i of the pair matrix is visited (the terms are
-// symmetric in (i, j): an off-diagonal pair counts twice), tile of rows by tile of columns.  Per tile pair the workgroup stages
-// cos theta, sin theta, A and -- for the kinematics -- k, w, e^{k z2} and the two finite-depth factors of both tiles in LDS, one
-// component per lane, one sincos per component.  Wave v then takes the rows v, v + 4, ... of the row tile and its lanes stride over
-// the row's band of columns: the table is read along j, the column values from consecutive LDS words, the row values by broadcast.
-// Every lane adds its terms in that fixed order into its own partial sums, and the 256 partials go through a tree whose shape
-// depends on the lane index alone: an item's bits depend on the item, the tables and the options only.
+// One workgroup per (point, time) item o = j * P + p: the shared pair sum (hc_wave_kin2_sum.hpp: wk2_item_sum) at the item's point
+// and time, then the ramp.  An item's bits depend on the item, the tables and the options only.
 template <bool ETA, bool KIN>
 __global__ void __launch_bounds__(kWk2Threads) wk2_sum_kernel(Wk2SumArgs a) {
-    constexpr int kT = kKinTile, kTK = KIN ? kKinTile : 1;
-    __shared__ double sc[2][kT], ss[2][kT], sA[2][kT];  // [0]: the tile of rows, [1]: the tile of columns
-    __shared__ double sk[2][kTK], sw[2][kTK], sE[2][kTK], sG[2][kTK], sF[2][kTK];
-    __shared__ double red[5][kWk2Threads];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int nf = a.nf;
-    const long long n2 = static_cast<long long>(nf) * nf;
-    const long long o  = blockIdx.x;
+    const long long o = blockIdx.x;
     const int p = static_cast<int>(o % a.P), jt = static_cast<int>(o / a.P);
-    const double x = a.xyz[3 * static_cast<size_t>(p)], t = a.t[jt];
-    // the second-order fields are held at their mean-level value above it, and at the bed's below it
-    double z2 = fmin(a.xyz[3 * static_cast<size_t>(p) + 2] - a.mwl, 0.0);
-    if (a.finite_depth && z2 < -a.depth) z2 = -a.depth;
-    const double zh = a.finite_depth ? z2 + a.depth : 0.0;
-    double eta = 0.0, ux = 0.0, uz = 0.0, ax = 0.0, az = 0.0;
-
-    for (int j0 = 0; j0 < nf; j0 += kT) {
-        const int mj = min(kT, nf - j0), j1 = j0 + mj - 1;
-        for (int i0 = 0; i0 <= j0; i0 += kT) {
-            const int mi = min(kT, nf - i0);
-            // does any row of the tile reach into the tile of columns?  (also the barrier that frees the LDS tiles)
-            int reach = 0;
-            if (tid < mi) {
-#pragma unroll
-                for (int s = 0; s < 2; ++s) {
-                    if (!a.sign_on[s]) continue;
-                    const int* b = a.band + 2 * (static_cast<size_t>(s) * nf + i0 + tid);
-                    reach |= max(b[0], j0) <= min(b[1], j1);
-                }
-            }
-            if (!__syncthreads_or(reach)) continue;
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int base = h ? j0 : i0, m = h ? mj : mi;
-                if (tid < m) {
-                    const int i = base + tid;
-                    const double k = a.tab[kKinK * nf + i], w = a.tab[kKinOmega * nf + i];
-                    double sn, cs;
-                    sincos(k * x - w * t + a.tab[kKinPhase * nf + i], &sn, &cs);
-                    sc[h][tid] = cs;
-                    ss[h][tid] = sn;
-                    sA[h][tid] = a.tab[kKinAmp * nf + i];
-                    if constexpr (KIN) {
-                        sk[h][tid] = k;
-                        sw[h][tid] = w;
-                        sE[h][tid] = exp(k * z2);
-                        sG[h][tid] = a.finite_depth ? exp(-2.0 * k * zh) : 0.0;
-                        sF[h][tid] = a.finite_depth ? exp(-2.0 * k * a.depth) : 0.0;
-                    }
-                }
-            }
-            __syncthreads();
-            for (int r = wave; r < mi; r += kWk2Waves) {
-                const int i = i0 + r;
-                const double ci = sc[0][r], si = ss[0][r], Ai = sA[0][r];
-                const double* row = a.pair + static_cast<size_t>(i) * nf;
-                // ---- difference terms: Theta = theta_i - theta_j, kappa = k_i - k_j, Omega = w_i - w_j ----
-                if (a.sign_on[0]) {
-                    const int* b    = a.band + 2 * static_cast<size_t>(i);
-                    const int first = max(b[0], j0), last = min(b[1], j1);
-                    for (int j = first + lane; j <= last; j += 64) {
-                        const int c     = j - j0;
-                        const double cj = sc[1][c], sj = ss[1][c];
-                        const double cm = fma(ci, cj, si * sj), sm = fma(si, cj, -(ci * sj));
-                        const double wgt = j == i ? 1.0 : 2.0;
-                        if constexpr (ETA) eta = fma(wgt * (Ai * sA[1][c]) * row[kWk2Km * n2 + j], cm, eta);
-                        if constexpr (KIN) {
-                            const double B   = wgt * row[kWk2Bm * n2 + j];
-                            const double kap = sk[0][r] - sk[1][c], ak = fabs(kap), Om = sw[0][r] - sw[1][c];
-                            const double e   = exp(ak * z2);  // (not E_i / E_j: either may have underflowed)
-                            double C = e, S = e;
-                            if (a.finite_depth) {  // (uniform over the launch)
-                                const double q = exp(-2.0 * ak * zh), d = 1.0 / (1.0 + exp(-2.0 * ak * a.depth));
-                                C = e * (1.0 + q) * d;
-                                S = e * (1.0 - q) * d;
-                            }
-                            const double bkC = B * kap * C, bkS = B * ak * S;
-                            ux = fma(bkC, cm, ux);
-                            uz = fma(bkS, sm, uz);
-                            ax = fma(bkC * Om, sm, ax);
-                            az = fma(-(bkS * Om), cm, az);
-                        }
-                    }
-                }
-                // ---- sum terms: Theta = theta_i + theta_j, kappa = k_i + k_j, Omega = w_i + w_j ----
-                if (a.sign_on[1]) {
-                    const int* b    = a.band + 2 * (static_cast<size_t>(nf) + i);
-                    const int first = max(b[0], j0), last = min(b[1], j1);
-                    for (int j = first + lane; j <= last; j += 64) {
-                        const int c     = j - j0;
-                        const double cj = sc[1][c], sj = ss[1][c];
-                        const double cp = fma(ci, cj, -(si * sj)), sp = fma(si, cj, ci * sj);
-                        const double wgt = j == i ? 1.0 : 2.0;
-                        if constexpr (ETA) eta = fma(wgt * (Ai * sA[1][c]) * row[kWk2Kp * n2 + j], cp, eta);
-                        if constexpr (KIN) {
-                            const double B   = wgt * row[kWk2Bp * n2 + j];
-                            const double kap = sk[0][r] + sk[1][c], ak = fabs(kap), Om = sw[0][r] + sw[1][c];
-                            const double e   = sE[0][r] * sE[1][c];  // e^{(k_i + k_j) z2}: 0, never NaN, where a factor has underflowed
-                            double C = e, S = e;
-                            if (a.finite_depth) {
-                                const double q = sG[0][r] * sG[1][c], d = 1.0 / (1.0 + sF[0][r] * sF[1][c]);
-                                C = e * (1.0 + q) * d;
-                                S = e * (1.0 - q) * d;
-                            }
-                            const double bkC = B * kap * C, bkS = B * ak * S;
-                            ux = fma(bkC, cp, ux);
-                            uz = fma(bkS, sp, uz);
-                            ax = fma(bkC * Om, sp, ax);
-                            az = fma(-(bkS * Om), cp, az);
-                        }
-                    }
-                }
-            }
-        }
-    }
-    red[0][tid] = eta;
-    red[1][tid] = ux;
-    red[2][tid] = uz;
-    red[3][tid] = ax;
-    red[4][tid] = az;
-    // ---- fixed-shape tree over the 256 lanes: lane l adds lane l + h for h = 128, 64, ..., 1 (drift_qtf_kernel) ----
-    for (int h = kWk2Threads / 2; h > 0; h >>= 1) {
-        __syncthreads();
-        if (tid < h) {
-#pragma unroll
-            for (int k = 0; k < 5; ++k) red[k][tid] += red[k][tid + h];
-        }
-    }
-    if (tid == 0) {
+    const double t = a.t[jt];
+    const Wk2Sea sea{a.tab, a.nf, a.pair, a.band, a.depth, a.mwl, a.finite_depth, {a.sign_on[0], a.sign_on[1]}};
+    double sum[5];
+    wk2_item_sum<ETA, KIN>(sea, a.xyz[3 * static_cast<size_t>(p)], a.xyz[3 * static_cast<size_t>(p) + 2], t, sum);
+    if (threadIdx.x == 0) {
         const double ramp2 = wk2_ramp2(a.ramped != 0, a.ramp_duration, t);  // second order in the amplitude
-        if constexpr (ETA) a.eta[o] = 0.25 * red[0][0] * ramp2;
+        if constexpr (ETA) a.eta[o] = 0.25 * sum[0] * ramp2;
         if (KIN && a.vel) {
-            a.vel[3 * o]     = red[1][0] * ramp2;
+            a.vel[3 * o]     = sum[1] * ramp2;
             a.vel[3 * o + 1] = 0.0;
-            a.vel[3 * o + 2] = red[2][0] * ramp2;
+            a.vel[3 * o + 2] = sum[2] * ramp2;
         }
         if (KIN && a.acc) {
-            a.acc[3 * o]     = red[3][0] * ramp2;
+            a.acc[3 * o]     = sum[3] * ramp2;
             a.acc[3 * o + 1] = 0.0;
-            a.acc[3 * o + 2] = red[4][0] * ramp2;
+            a.acc[3 * o + 2] = sum[4] * ramp2;
         }
     }
 }
 
-bool has_components(const hc_ctx* c) {
+}  // namespace
+
+bool wk2_has_components(const hc_ctx* c) {
     return c->wave_kind == kWaveRegular || c->wave_kind == kWaveSpectral || (c->wave_kind == kWaveIrregular && !c->eta_record);
 }
 
-int component_count(const hc_ctx* c) { return c->wave_kind == kWaveRegular ? 1 : static_cast<int>(c->spec_f.size()); }
+int wk2_component_count(const hc_ctx* c) { return c->wave_kind == kWaveRegular ? 1 : static_cast<int>(c->spec_f.size()); }
 
-// The component table, the pair tables and the band limits of the context's wave model on the device.  Rebuilt when a
-// hc_set_wave_* call has come in since (wave_serial), the regular wave's phase or a cut-off differs from the cached one.
-void wk2_tables(hc_ctx* c, const hc_wave_kinematics2_opts& o) {
+void wk2_tables(hc_ctx* c, Wk2TableSet& s, hipStream_t st, double regular_phase, const double cut[4], bool keep_empty) {
     const bool regular = c->wave_kind == kWaveRegular;
-    const double cut[4] = {o.diff_lo, o.diff_hi, o.sum_lo, o.sum_hi};
-    if (c->wk2_serial == c->wave_serial && (!regular || std::memcmp(&c->wk2_phase, &o.regular_phase, sizeof(double)) == 0) &&
-        std::memcmp(c->wk2_cut, cut, sizeof(cut)) == 0)
+    if (s.serial == c->wave_serial && (!regular || std::memcmp(&s.phase, &regular_phase, sizeof(double)) == 0) &&
+        std::memcmp(s.cut, cut, sizeof(s.cut)) == 0)
         return;
-    c->wk2_serial = ~0ULL;  // nothing is cached until all of it is in place
-    hipStream_t st = c->stream_wk2;
-    const std::vector<double> tab = kin_table_host(c, o.regular_phase);
+    s.serial = ~0ULL;  // nothing is cached until all of it is in place
+    const std::vector<double> tab = kin_table_host(c, regular_phase);
     const int nf = static_cast<int>(tab.size() / kKinCols);
-    c->d_wk2_tab.upload(tab, st);
+    s.d_tab.upload(tab, st);
     std::vector<int> band(4 * static_cast<size_t>(nf));
     const double* omega = tab.data() + static_cast<size_t>(kKinOmega) * nf;
-    c->wk2_any[0] = wk2_bands(omega, nf, 0, o.diff_lo, o.diff_hi, band.data());
-    c->wk2_any[1] = wk2_bands(omega, nf, 1, o.sum_lo, o.sum_hi, band.data() + 2 * static_cast<size_t>(nf));
-    c->d_wk2_band.upload(band, st);
+    s.any[0] = wk2_bands(omega, nf, 0, cut[0], cut[1], band.data());
+    s.any[1] = wk2_bands(omega, nf, 1, cut[2], cut[3], band.data() + 2 * static_cast<size_t>(nf));
+    s.d_band.upload(band, st);
     const size_t n2 = static_cast<size_t>(nf) * nf;
-    if (c->d_wk2_pair.n != kWk2Tables * n2) c->d_wk2_pair.alloc(kWk2Tables * n2);
-    Wk2PairArgs a{};
-    a.tab          = c->d_wk2_tab.p;
-    a.nf           = nf;
-    a.finite_depth = std::isfinite(c->depth) ? 1 : 0;
-    a.g            = std::fabs(c->g);
-    a.depth        = c->depth;
-    std::copy(cut, cut + 4, a.cut);
-    a.pair = c->d_wk2_pair.p;
-    hipLaunchKernelGGL(wk2_pair_kernel, dim3(static_cast<unsigned>((n2 + kWk2Threads - 1) / kWk2Threads)), dim3(kWk2Threads), 0, st, a);
-    HC_HIP(hipGetLastError());
-    HC_HIP(hipStreamSynchronize(st));
-    c->wk2_nf = nf;
-    c->wk2_phase = o.regular_phase;
-    std::copy(cut, cut + 4, c->wk2_cut);
-    c->wk2_serial = c->wave_serial;
+    if (!(s.any[0] || s.any[1]) && !keep_empty) {
+        s.d_pair.release();
+    } else {
+        if (s.d_pair.n != kWk2Tables * n2) s.d_pair.alloc(kWk2Tables * n2);
+        Wk2PairArgs a{};
+        a.tab          = s.d_tab.p;
+        a.nf           = nf;
+        a.finite_depth = std::isfinite(c->depth) ? 1 : 0;
+        a.g            = std::fabs(c->g);
+        a.depth        = c->depth;
+        std::copy(cut, cut + 4, a.cut);
+        a.pair = s.d_pair.p;
+        hipLaunchKernelGGL(wk2_pair_kernel, dim3(static_cast<unsigned>((n2 + kWk2Threads - 1) / kWk2Threads)), dim3(kWk2Threads), 0, st, a);
+        HC_HIP(hipGetLastError());
+        HC_HIP(hipStreamSynchronize(st));
+    }
+    s.nf = nf;
+    s.phase = regular_phase;
+    std::copy(cut, cut + 4, s.cut);
+    s.serial = c->wave_serial;
+}
+
+namespace {
+
+// the tables hc_wave_kinematics2 and hc_wave_kinematics2_pair_tables read
+void wk2_own_tables(hc_ctx* c, const hc_wave_kinematics2_opts& o) {
+    const double cut[4] = {o.diff_lo, o.diff_hi, o.sum_lo, o.sum_hi};
+    wk2_tables(c, c->wk2, c->stream_wk2, o.regular_phase, cut, true);
 }
 
 hc_wave_kinematics2_opts wk2_opts(const hc_wave_kinematics2_opts* opts) {
@@ -325,16 +204,16 @@ int hc_wave_kinematics2(hc_ctx* c, const hc_wave_kinematics2_opts* opts, int n_p
     const hc_wave_kinematics2_opts o = hc::wk2_opts(opts);
     const char* bad = hc::wk2_check_batch(n_points, xyz, n_times, t);
     require(bad == nullptr, HC_ERR_INVALID, bad ? bad : "");
-    const bool waves = hc::has_components(c);
-    require(!waves || hc::component_count(c) <= hc::kWk2MaxFreq, HC_ERR_UNSUPPORTED, "more than 4096 wave components");
+    const bool waves = hc::wk2_has_components(c);
+    require(!waves || hc::wk2_component_count(c) <= hc::kWk2MaxFreq, HC_ERR_UNSUPPORTED, "more than 4096 wave components");
     const size_t n = static_cast<size_t>(n_points) * n_times;
     if (n == 0 || !(eta || vel || acc)) return HC_OK;
     if (waves) {
         if (!c->stream_wk2) HC_HIP(hipStreamCreateWithFlags(&c->stream_wk2, hipStreamNonBlocking));
-        hc::wk2_tables(c, o);
+        hc::wk2_own_tables(c, o);
     }
     // NoWave, no model, an imported eta record (no components), or no pair inside either band: zeros, no launch
-    if (!waves || !(c->wk2_any[0] || c->wk2_any[1])) {
+    if (!waves || !(c->wk2.any[0] || c->wk2.any[1])) {
         if (eta) std::fill(eta, eta + n, 0.0);
         if (vel) std::fill(vel, vel + 3 * n, 0.0);
         if (acc) std::fill(acc, acc + 3 * n, 0.0);
@@ -349,19 +228,19 @@ int hc_wave_kinematics2(hc_ctx* c, const hc_wave_kinematics2_opts* opts, int n_p
     double* d_t   = d_xyz + 3 * static_cast<size_t>(n_points);
     double* d_out = d_t + n_times;
     hc::Wk2SumArgs a{};
-    a.tab          = c->d_wk2_tab.p;
-    a.nf           = c->wk2_nf;
+    a.tab          = c->wk2.d_tab.p;
+    a.nf           = c->wk2.nf;
     a.P            = n_points;
     a.T            = n_times;
-    a.pair         = c->d_wk2_pair.p;
-    a.band         = c->d_wk2_band.p;
+    a.pair         = c->wk2.d_pair.p;
+    a.band         = c->wk2.d_band.p;
     a.xyz          = d_xyz;
     a.t            = d_t;
     a.depth        = c->depth;
     a.mwl          = o.mwl;
     a.finite_depth = std::isfinite(c->depth) ? 1 : 0;
-    a.sign_on[0]   = c->wk2_any[0] ? 1 : 0;
-    a.sign_on[1]   = c->wk2_any[1] ? 1 : 0;
+    a.sign_on[0]   = c->wk2.any[0] ? 1 : 0;
+    a.sign_on[1]   = c->wk2.any[1] ? 1 : 0;
     const bool synthesised = (c->wave_kind == hc::kWaveIrregular && !c->eta_record) || c->wave_kind == hc::kWaveSpectral;
     a.ramped        = (o.apply_ramp && synthesised && c->irr.ramp_duration > 0.0) ? 1 : 0;  // the rule of the Morison term
     a.ramp_duration = c->irr.ramp_duration;
@@ -395,14 +274,14 @@ int hc_wave_kinematics2_pair_tables(hc_ctx* c, const hc_wave_kinematics2_opts* o
     HC_API_BEGIN_HOT(c)
     require(c->finalized, HC_ERR_INVALID, "hc_finalize has not been called");
     const hc_wave_kinematics2_opts o = hc::wk2_opts(opts);
-    if (!hc::has_components(c)) return HC_OK;
-    require(hc::component_count(c) <= hc::kWk2MaxFreq, HC_ERR_UNSUPPORTED, "more than 4096 wave components");
+    if (!hc::wk2_has_components(c)) return HC_OK;
+    require(hc::wk2_component_count(c) <= hc::kWk2MaxFreq, HC_ERR_UNSUPPORTED, "more than 4096 wave components");
     if (!c->stream_wk2) HC_HIP(hipStreamCreateWithFlags(&c->stream_wk2, hipStreamNonBlocking));
-    hc::wk2_tables(c, o);
-    const size_t n2 = static_cast<size_t>(c->wk2_nf) * c->wk2_nf;
+    hc::wk2_own_tables(c, o);
+    const size_t n2 = static_cast<size_t>(c->wk2.nf) * c->wk2.nf;
     double* out[hc::kWk2Tables] = {Kp, Km, Bp, Bm};
     for (int k = 0; k < hc::kWk2Tables; ++k)
-        if (out[k]) HC_HIP(hipMemcpyAsync(out[k], c->d_wk2_pair.p + k * n2, n2 * sizeof(double), hipMemcpyDeviceToHost, c->stream_wk2));
+        if (out[k]) HC_HIP(hipMemcpyAsync(out[k], c->wk2.d_pair.p + k * n2, n2 * sizeof(double), hipMemcpyDeviceToHost, c->stream_wk2));
     HC_HIP(hipStreamSynchronize(c->stream_wk2));
     HC_API_END(c)
 }

@@ -515,6 +515,28 @@ class HydroForces:
         o = capi.WaveKinematicsOpts(float(mwl), float(regular_phase), int(bool(wave_stretching)))
         self._chk(self.lib.hc_set_morison_options(self.ctx, C.byref(o)))
 
+    def set_morison_second_order(self, on=True, diff_band=(0.0, float("inf")), sum_band=(0.0, float("inf")), apply_ramp=True):
+        """The elements see the second-order increments of wave_kinematics2() on top of the first-order field (eta1 + eta2 in the
+        wet test, u1 + u2 and a1 + a2 in the force); diff_band / sum_band: (lo, hi) in rad/s as there, mwl and regular_phase from
+        set_morison_options().  on=False frees the tables.  See hc_set_morison_second_order in include/hydrochrono_amd.h."""
+        (dlo, dhi), (slo, shi) = map(float, diff_band), map(float, sum_band)
+        self._chk(self.lib.hc_set_morison_second_order(self.ctx, int(bool(on)), dlo, dhi, slo, shi, int(bool(apply_ramp))))
+
+    def morison_second_order(self):
+        """dict(on, diff_band, sum_band, apply_ramp) as set_morison_second_order() takes them."""
+        on, ramp = C.c_int(), C.c_int()
+        v = [C.c_double() for _ in range(4)]
+        self._chk(self.lib.hc_get_morison_second_order(self.ctx, C.byref(on), *[C.byref(x) for x in v], C.byref(ramp)))
+        return dict(on=bool(on.value), diff_band=(v[0].value, v[1].value), sum_band=(v[2].value, v[3].value), apply_ramp=bool(ramp.value))
+
+    def morison_increments(self, b):
+        """What the elements of body b (0-based, owned) saw in the last evaluation on the second-order sea: dict of p (n, 3),
+        eta2 (n), vel2 (n, 3), acc2 (n, 3)."""
+        n = self.morison_count(b)
+        out = dict(p=np.empty((n, 3)), eta2=np.empty(n), vel2=np.empty((n, 3)), acc2=np.empty((n, 3)))
+        self._chk(self.lib.hc_get_morison_increments(self.ctx, int(b), *[_dp(out[k].reshape(-1)) for k in ("p", "eta2", "vel2", "acc2")]))
+        return out
+
     def morison_begin(self, t, pos, rpy, linvel, angvel):
         n3 = 3 * self.N
         a = [_arr(x, n3) for x in (pos, rpy, linvel, angvel)]
@@ -907,6 +929,16 @@ class HydroGroup:
         a = [_arr(x, n3) for x in (pos, rpy, linvel, angvel)]
         self._morison_begin(t, a)
         return self._morison_end()
+
+    def morison_second_order(self):
+        return self.shards[0].morison_second_order()
+
+    def morison_increments(self, b):
+        # the shard that owns the body answers
+        for h in self.shards:
+            if h.b0 <= int(b) < h.b1:
+                return h.morison_increments(b)
+        raise IndexError(f"body {b} out of range")
 
     def morison(self):
         m = self.__dict__.get("_morison_last")

@@ -30,6 +30,7 @@
 #include <algorithm>
 #include <array>
 #include <cstdlib>
+#include <limits>
 #include <memory>
 #include <stdexcept>
 #include <string>
@@ -141,6 +142,13 @@ struct HydroProfileStats {  // include/hydroc/hydro_forces.h:153-160
 // and Cm_i V [m^3] per body axis.
 struct MorisonElement {
     std::array<double, 3> r{0, 0, 0}, cd_area{0, 0, 0}, cm_vol{0, 0, 0};
+};
+
+// What the Morison elements of a body saw of the second-order sea (TestHydro::GetMorisonIncrements): per element the world point
+// and the increments of WaveBase::GetSecondOrderElevation / Velocity / Acceleration there.
+struct MorisonIncrements {
+    std::vector<std::array<double, 3>> p, vel2, acc2;
+    std::vector<double> eta2;
 };
 
 // A surface panel of a body (not in the reference; hc_surface_panel): centroid [m] and area vector [m^2] (area times the outward
@@ -294,6 +302,37 @@ class TestHydro {
         o.wave_stretching = wave_stretching ? 1 : 0;
         for (hc_ctx* c : ctxs_) check(c, hc_set_morison_options(c, &o));
         have_time_ = false;
+    }
+    // The elements on the second-order sea (hc_set_morison_second_order): the increments of WaveBase::GetSecondOrder* at every
+    // element, added before the wet test and the force; the cut-offs [rad/s] are as in WaveBase::second_order_, mwl and the
+    // regular phase those of SetMorisonOptions.  Applied to every shard context; on = false frees the tables.
+    void SetMorisonSecondOrder(bool on, double diff_lo = 0.0, double diff_hi = std::numeric_limits<double>::infinity(), double sum_lo = 0.0,
+                               double sum_hi = std::numeric_limits<double>::infinity(), bool apply_ramp = true) {
+        for (hc_ctx* c : ctxs_) check(c, hc_set_morison_second_order(c, on ? 1 : 0, diff_lo, diff_hi, sum_lo, sum_hi, apply_ramp ? 1 : 0));
+        have_time_ = false;
+    }
+    // What the elements of a body saw in the last evaluation on the second-order sea (hc_get_morison_increments): one entry per
+    // element, answered by the shard that owns the body.
+    MorisonIncrements GetMorisonIncrements(int body_index_1_based) {
+        if (body_index_1_based < 1 || body_index_1_based > num_bodies_) throw std::out_of_range("GetMorisonIncrements: body index out of range");
+        const int b = body_index_1_based - 1;
+        for (hc_ctx* c : ctxs_) {
+            int b0 = 0, b1 = 0, n = 0;
+            check(c, hc_get_shard(c, &b0, &b1));
+            if (b < b0 || b >= b1) continue;
+            check(c, hc_get_morison_count(c, b, &n));
+            std::vector<double> p(3 * static_cast<size_t>(n)), vel(p.size()), acc(p.size());
+            MorisonIncrements out;
+            out.eta2.resize(static_cast<size_t>(n));
+            check(c, hc_get_morison_increments(c, b, p.data(), out.eta2.data(), vel.data(), acc.data()));
+            for (int e = 0; e < n; ++e) {
+                out.p.push_back({p[3 * e], p[3 * e + 1], p[3 * e + 2]});
+                out.vel2.push_back({vel[3 * e], vel[3 * e + 1], vel[3 * e + 2]});
+                out.acc2.push_back({acc[3 * e], acc[3 * e + 1], acc[3 * e + 2]});
+            }
+            return out;
+        }
+        throw std::out_of_range("GetMorisonIncrements: no context owns the body");
     }
     std::vector<double> ComputeForceMorison() {
         gather_state();

@@ -552,6 +552,34 @@ int hc_morison_end(hc_ctx* ctx, double* out_Dlocal);
 int hc_compute_morison(hc_ctx* ctx, double t, const double* pos, const double* rpy, const double* linvel, const double* angvel,
                        double* out_Dlocal);
 
+/* Morison elements on the second-order sea: with `on` the elements see the second-order increments of Sharma and
+ * Dean's long-crested sea (hc_wave_kinematics2, below) on top of the first-order field.  For element e, with R, d, p, v_e as above:
+ *     eta1, u1, a1 = the values above: hc_wave_kinematics at p, t with the Morison options, stretching by eta1 included, u1 and a1
+ *         times the Morison ramp
+ *     eta2, u2, a2 = hc_wave_kinematics2 at the same FP64 point p and time t, with mwl and regular_phase of the Morison options
+ *         (hc_set_morison_options) and the four cut-offs [rad/s] and apply_ramp of this call; everything else of that definition
+ *         applies as written there: fields held at z2 = min(z - mwl, 0) and at -h below the bed, no stretching, the true depth,
+ *         ramp * ramp on all three increments (eta2 included) with apply_ramp
+ *     eta = eta1 + eta2,  u_f = u1 + u2,  a_f = a1 + a2;  wet when p.z - mwl <= eta;  the force formula is unchanged
+ * NoWave, no wave model, an imported eta record, or cut-offs that leave no pair inside either band: no second-order launch, the
+ * result is that of order 1 bit for bit.  With on = 0 (the default) every Morison call makes the launches and returns the bits it
+ * did before this switch existed.  The increments of an element are those hc_wave_kinematics2 returns for its point, bit for bit;
+ * a body's bits still depend on that body's state and elements, the wave model, t and the options only.
+ * The pair tables and band limits are this path's own, built on its stream and cached on the wave model, the regular phase and the
+ * cut-offs: a second copy beside the one hc_wave_kinematics2 keeps (4 nf^2 doubles: 8 MB at 512 components, 537 MB at 4096), freed
+ * by on = 0.  HC_ERR_INVALID: a negative or NaN cut-off, lo > hi, or a hc_morison_begin without its end.  More than 4096 wave
+ * components: hc_morison_begin returns HC_ERR_UNSUPPORTED and nothing stays pending.
+ * Not included (out of scope): second-order pressure on the surface panels and triangles, which like the drift term keep seeing
+ * the first-order field, and stretching of the second-order part. */
+int hc_set_morison_second_order(hc_ctx* ctx, int on, double diff_lo, double diff_hi, double sum_lo, double sum_hi, int apply_ramp);
+int hc_get_morison_second_order(hc_ctx* ctx, int* on, double* diff_lo, double* diff_hi, double* sum_lo, double* sum_hi, int* apply_ramp);
+/* What the elements of `body` (0-based, owned by this context) saw in the last completed evaluation that had a second-order part:
+ * their points p[n][3] and the increments eta2[n], vel2[n][3], acc2[n][3] (y components 0), n = the body's element count at that
+ * evaluation.  Any pointer may be NULL.  HC_ERR_INVALID: second order is off, no such evaluation has completed yet (one without a
+ * second-order part -- no components, empty bands, no element on an owned body -- forgets the one before, and so does
+ * hc_set_morison_elements), or the body is not owned by this context. */
+int hc_get_morison_increments(hc_ctx* ctx, int body, double* p, double* eta2, double* vel2, double* acc2);
+
 /* ------------------------------------------------------------------------------------------------
  * Nonlinear buoyancy and Froude-Krylov forces on body surface panels (not in the reference: src/hydro_types.h:33 is a TODO): the
  * hydrostatic and incident-wave pressure integrated over the instantaneous wetted surface, an opt-in replacement of the linear
@@ -743,7 +771,8 @@ int hc_compute_drift(hc_ctx* ctx, double t, const double* pos, double* out_Dloca
  *
  * Every (point, time) item is summed by one workgroup in a fixed order: its bits depend on the item, the wave model and the
  * options only -- not on the batch it is part of, its place in it, the outputs asked for, or the shard context that answers.
- * The Morison, surface-pressure and drift terms keep seeing the first-order field.
+ * The surface-pressure and drift terms keep seeing the first-order field; the Morison elements see these increments once
+ * hc_set_morison_second_order switches them on.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct hc_wave_kinematics2_opts {
     double mwl;            /* WaveBase::mwl_ (0) */
