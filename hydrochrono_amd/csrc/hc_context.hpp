@@ -323,6 +323,24 @@ struct hc_ctx {
     hc::DeviceBuffer<double> d_nl_tab, d_nl_panel, d_nl_tri, d_nl_state, d_nl_part, d_nl_out;
     hc::DeviceBuffer<int> d_nl_chunk, d_nl_off;  // [chunks][3] (body, first panel or triangle, count), [nloc + 1] first chunk of an owned body
     hc::PinnedBuffer<double> h_nl_state, h_nl_out;  // [6 N] pos | rpy of the last hc_nonlinear_begin, [nloc][12]
+    // ... on the second-order sea (hc_set_nonlinear_second_order): tables of its own, built on stream_nl (as `mor2`: a
+    // hc_wave_kinematics2 call with other cut-offs may rebuild `wk2` while a launch of this path is in flight); the distinct
+    // body-frame points of the owned bodies' lists, body-major, the point of every panel and triangle vertex, and the points'
+    // world positions and increments
+    bool nl2_on = false;
+    double nl2_cut[4] = {0.0, HUGE_VAL, 0.0, HUGE_VAL};
+    int nl2_ramp = 1;
+    hc::Wk2TableSet nl2;
+    bool nl_pts_dirty = true;               // the point lists below are not those of the device copy of the lists
+    hc::DeviceBuffer<double> d_nl_pt;       // [points][3]
+    hc::DeviceBuffer<int> d_nl_pbody;       // [points] body of a point
+    hc::DeviceBuffer<int> d_nl_pidx, d_nl_tidx;  // [panels], [triangles][3]: index into the points, following d_nl_panel / d_nl_tri
+    std::vector<int> nl_pt_off;             // [nloc + 1] first point of an owned body
+    hc::DeviceBuffer<double> d_nl_inc;      // [points][5] P, eta2, q2
+    hc::PinnedBuffer<double> h_nl_inc[2];   // its host copies: of the evaluation in flight and of the last completed one
+    int nl_inc_cur = 0;                     // which of the two holds the last completed one
+    bool nl_inc_flight = false;             // the evaluation in flight writes the other one
+    std::vector<int> nl_inc_off;            // [nloc + 1] first point of an owned body in it; empty: no evaluation has completed
 
     // Wave drift forces (hc_set_drift_qtf, hc_drift.hip): the tables of all bodies of the system on the host, those of the owned bodies
     // one after the other on the device with the bin -> (component, weight) map of the component table in force; its own stream,

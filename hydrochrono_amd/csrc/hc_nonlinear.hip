@@ -1,9 +1,17 @@
 // hc_nonlinear.hip -- nonlinear buoyancy and Froude-Krylov forces on body surface panels and on triangles clipped at the free surface
 // (include/hydrochrono_amd.h: hc_set_surface_panels, hc_set_surface_triangles, hc_nonlinear_begin / hc_nonlinear_end).  Not in the reference (src/hydro_types.h:33 is a TODO).  Off the
 // step path, as hc_morison.hip: its own stream, component table, buffers and pinned staging; it reads and writes nothing a step
-// uses, so it is not ordered against the direct queue.  DESIGN.md 3.7d and 3.7d' have the definitions, the kernels and their invariants.
+// uses, so it is not ordered against the direct queue.  DESIGN.md 3.7d and 3.7d' have the definitions, the kernels and their invariants;
+// 3.7h the surface on the second-order sea (hc_set_nonlinear_second_order): eta2 and q2 = -d phi2 / dt of the pair sum at every surface
+// point, added before the wet test and the clipping, and the quadratic term -1/2 rho |grad phi1|^2.
 #include "hc_internal.hpp"
 #include "hc_wave_kin.hpp"
+#include "hc_wave_kin2.hpp"
+#include "hc_wave_kin2_sum.hpp"
+
+#include <array>
+#include <cstdint>
+#include <map>
 
 using namespace hc::detail;
 
@@ -13,6 +21,7 @@ namespace {
 constexpr int kNlThreads = 256;      // work items per workgroup, one per panel: a chunk of one body's list
 constexpr int kNlPanelDoubles = 6;   // c, s
 constexpr int kNlOut = 12;           // buoy (F, M), fk (F, M)
+constexpr int kNlIncDoubles = 5;     // P, eta2, q2 of a surface point on the second-order sea
 
 // This path's own component table, struct of arrays [kNlCols][nf]: the columns of hc_wave_kin.hpp the pressure needs and
 // omega^2 A / k in place of the velocity and acceleration amplitudes.
@@ -30,14 +39,46 @@ struct NlArgs {
     int stretch;       // Wheeler stretching
     int finite_depth;  // 0: water depth +inf
     double* part;      // [chunks][12] per-chunk sums
+    // the order-2 kernels only: the increments of nl2_incr_kernel, [points][kNlIncDoubles], and the surface point of every panel
+    // ([panels]) or triangle vertex ([triangles][3]) in it
+    const double* inc;
+    const int* pidx;
 };
+
+// R = Rx(rpy0) Ry(rpy1) Rz(rpy2) and d = R c: one expression for the kernels that evaluate the items and the one that sums the
+// second-order increments of their points, so that all see the same point P = pos + d bit for bit (as morison_frame)
+struct NlFrame {
+    double r00, r01, r02, r10, r11, r12, r20, r21, r22;
+};
+
+__device__ __forceinline__ NlFrame nl_frame(const double* rpy) {
+    double sa, ca, sb, cb, sc, cc;
+    sincos(rpy[0], &sa, &ca);
+    sincos(rpy[1], &sb, &cb);
+    sincos(rpy[2], &sc, &cc);
+    NlFrame f;
+    f.r00 = cb * cc, f.r01 = -cb * sc, f.r02 = sb;
+    f.r10 = ca * sc + sa * sb * cc, f.r11 = ca * cc - sa * sb * sc, f.r12 = -sa * cb;
+    f.r20 = sa * sc - ca * sb * cc, f.r21 = sa * cc + ca * sb * sc, f.r22 = ca * cb;
+    return f;
+}
+
+__device__ __forceinline__ void nl_rotate(const NlFrame& f, const double* c, double& d0, double& d1, double& d2) {
+    d0 = f.r00 * c[0] + f.r01 * c[1] + f.r02 * c[2];
+    d1 = f.r10 * c[0] + f.r11 * c[1] + f.r12 * c[2];
+    d2 = f.r20 * c[0] + f.r21 * c[1] + f.r22 * c[2];
+}
 
 // One workgroup per chunk of up to 256 panels of ONE body, one work item per panel.  The body's frame is derived once per item
 // from the same six state values (workgroup-uniform); every item sums the wave components in index order from the same LDS tiles
 // (the loop of wave_kinematics_kernel), so a panel's 12 values depend on its body's state, its own data, the table, t and the
 // options only.  Idle items of a partly filled chunk and dry panels contribute exact zeros.  The 12 components are then reduced over
 // the 256 lanes by a tree whose shape depends on the lane index alone, and lane 0 stores the chunk's 12-vector.
-__global__ void __launch_bounds__(kNlThreads) nl_panels_kernel(NlArgs a) {
+// ORDER2 (nl2_panels_kernel): the component loop also sums the first-order velocity u1 at the same z_e (a sincos where order 1 has
+// a cos), and the centroid's increments eta2, q2 (nl2_incr_kernel, earlier on the stream) are read after the loop: eta2 enters the
+// wet test, rho q2 - 1/2 rho ramp^2 |u1|^2 the dynamic pressure.  Everything else is the code of order 1.
+template <bool ORDER2>
+__device__ __forceinline__ void nl_panels_body(const NlArgs& a) {
     __shared__ double s[kNlCols][kKinTile];
     __shared__ double red[kNlOut][kNlThreads];
     const int tid     = threadIdx.x;
@@ -45,24 +86,16 @@ __global__ void __launch_bounds__(kNlThreads) nl_panels_kernel(NlArgs a) {
     const int first   = a.chunk[3 * blockIdx.x + 1];
     const int count   = a.chunk[3 * blockIdx.x + 2];
     const bool active = tid < count;
-    const double* pn  = a.panel + static_cast<size_t>(kNlPanelDoubles) * (first + (active ? tid : 0));  // idle items read the chunk's first panel
+    const int item    = first + (active ? tid : 0);  // idle items read the chunk's first panel
+    const double* pn  = a.panel + static_cast<size_t>(kNlPanelDoubles) * item;
     const double* pos = a.state + 3 * b;
     const double* rpy = pos + 3 * a.N;
 
     // ---- R = Rx(rpy0) Ry(rpy1) Rz(rpy2), d = R c, p = pos + d, n = R s (the expressions of morison_items_kernel) ----
-    double sa, ca, sb, cb, sc, cc;
-    sincos(rpy[0], &sa, &ca);
-    sincos(rpy[1], &sb, &cb);
-    sincos(rpy[2], &sc, &cc);
-    const double r00 = cb * cc, r01 = -cb * sc, r02 = sb;
-    const double r10 = ca * sc + sa * sb * cc, r11 = ca * cc - sa * sb * sc, r12 = -sa * cb;
-    const double r20 = sa * sc - ca * sb * cc, r21 = sa * cc + ca * sb * sc, r22 = ca * cb;
-    const double d0 = r00 * pn[0] + r01 * pn[1] + r02 * pn[2];
-    const double d1 = r10 * pn[0] + r11 * pn[1] + r12 * pn[2];
-    const double d2 = r20 * pn[0] + r21 * pn[1] + r22 * pn[2];
-    const double n0 = r00 * pn[3] + r01 * pn[4] + r02 * pn[5];
-    const double n1 = r10 * pn[3] + r11 * pn[4] + r12 * pn[5];
-    const double n2 = r20 * pn[3] + r21 * pn[4] + r22 * pn[5];
+    const NlFrame f = nl_frame(rpy);
+    double d0, d1, d2, n0, n1, n2;
+    nl_rotate(f, pn, d0, d1, d2);
+    nl_rotate(f, pn + 3, n0, n1, n2);
     const double x = pos[0] + d0, z = pos[2] + d2, t = a.t;
 
     // ---- eta first under stretching (wave_kinematics_kernel) ----
@@ -89,7 +122,7 @@ __global__ void __launch_bounds__(kNlThreads) nl_panels_kernel(NlArgs a) {
     const double ze = zs - a.mwl;  // under stretching mwl is subtracted a second time, as in the reference
 
     // ---- dynamic pressure sum (and eta without stretching) ----
-    double pd = 0.0, eta1 = 0.0;
+    double pd = 0.0, eta1 = 0.0, ux = 0.0, uz = 0.0;
     for (int i0 = 0; i0 < a.nf; i0 += kKinTile) {
         const int m = min(kKinTile, a.nf - i0);
         __syncthreads();
@@ -100,23 +133,40 @@ __global__ void __launch_bounds__(kNlThreads) nl_panels_kernel(NlArgs a) {
         __syncthreads();
         for (int i = 0; i < m; ++i) {
             const double k = s[kNlK][i];
-            const double cs = cos(k * x - s[kNlOmega][i] * t + s[kNlPhase][i]);
-            double px;
+            double sn = 0.0, cs;
+            if constexpr (ORDER2)
+                sincos(k * x - s[kNlOmega][i] * t + s[kNlPhase][i], &sn, &cs);
+            else
+                cs = cos(k * x - s[kNlOmega][i] * t + s[kNlPhase][i]);
+            double px, pz;
             if (s[kNlDeep][i] != 0.0) {  // (the same branch for every item: no divergence)
-                px = exp(k * ze);
+                px = pz = exp(k * ze);
             } else {
                 px = cosh(k * (ze + a.depth)) * s[kNlInvSinh][i];
+                pz = ORDER2 ? sinh(k * (ze + a.depth)) * s[kNlInvSinh][i] : 0.0;
             }
             eta1 += s[kNlAmp][i] * cs;
             pd += s[kNlW2AoK][i] * px * cs;
+            if constexpr (ORDER2) {  // u1 of the kinematics (omega A is the table's column there), unramped
+                const double wa = s[kNlOmega][i] * s[kNlAmp][i];
+                ux += wa * px * cs;
+                uz += wa * pz * sn;
+            }
         }
     }
     if (!a.stretch) eta = eta1;
+    double q2 = 0.0;
+    if constexpr (ORDER2) {
+        const double* q = a.inc + static_cast<size_t>(kNlIncDoubles) * a.pidx[item];
+        eta += q[3];
+        q2 = q[4];
+    }
 
     // ---- pressures, the panel's two 6-vectors at the body reference ----
     const bool wet  = active && (z - a.mwl <= eta);
     const double ps = -(a.rho * a.g) * (z - a.mwl);
-    const double pw = a.rho * pd * a.ramp;
+    double pw       = a.rho * pd * a.ramp;
+    if constexpr (ORDER2) pw = pw + a.rho * q2 - 0.5 * a.rho * (a.ramp * a.ramp) * (ux * ux + uz * uz);
     double v[kNlOut];
     v[0]  = -ps * n0;
     v[1]  = -ps * n1;
@@ -147,6 +197,9 @@ __global__ void __launch_bounds__(kNlThreads) nl_panels_kernel(NlArgs a) {
         for (int k = 0; k < kNlOut; ++k) out[k] = red[k][0];
     }
 }
+
+__global__ void __launch_bounds__(kNlThreads) nl_panels_kernel(NlArgs a) { nl_panels_body<false>(a); }
+__global__ void __launch_bounds__(kNlThreads) nl2_panels_kernel(NlArgs a) { nl_panels_body<true>(a); }
 
 // One work item per (owned body, component): the serial sum over the body's chunk partials in chunk order.
 __global__ void __launch_bounds__(kNlThreads) nl_sum_kernel(const double* part, const int* off, int rows, double* out) {
@@ -209,7 +262,10 @@ __device__ __forceinline__ void nl_sub_triangle(const NlVertex& q0, const NlVert
 // vertex's eta is what hc_wave_kinematics returns there -- takes h = z - mwl - eta and the pressures as linear over the triangle, cuts
 // the triangle at h = 0 and integrates over the wet part.  Idle items of a partly filled chunk evaluate the chunk's first triangle and
 // contribute exact zeros, as dry triangles do.  Then the fixed tree; lane 0 stores the chunk's 12-vector.
-__global__ void __launch_bounds__(kNlThreads) nl_tris_kernel(NlArgs a) {
+// ORDER2 (nl2_tris_kernel): as in the panel kernel -- u1 of every vertex in the component loop, the vertices' increments after it,
+// eta2 into h and rho q2 - 1/2 rho ramp^2 |u1|^2 into p_d before the case table, which is the one of order 1.
+template <bool ORDER2>
+__device__ __forceinline__ void nl_tris_body(const NlArgs& a) {
     __shared__ double s[kNlCols][kKinTile];
     __shared__ double red[kNlOut][kNlThreads];
     const int tid     = threadIdx.x;
@@ -217,28 +273,17 @@ __global__ void __launch_bounds__(kNlThreads) nl_tris_kernel(NlArgs a) {
     const int first   = a.chunk[3 * blockIdx.x + 1];
     const int count   = a.chunk[3 * blockIdx.x + 2];
     const bool active = tid < count;
-    const double* tv  = a.panel + static_cast<size_t>(kNlTriDoubles) * (first + (active ? tid : 0));
+    const int item    = first + (active ? tid : 0);
+    const double* tv  = a.panel + static_cast<size_t>(kNlTriDoubles) * item;
     const double* pos = a.state + 3 * b;
     const double* rpy = pos + 3 * a.N;
 
     // ---- R = Rx(rpy0) Ry(rpy1) Rz(rpy2), d_j = R v_j, P_j = pos + d_j (the expressions of nl_panels_kernel) ----
-    double sa, ca, sb, cb, sc, cc;
-    sincos(rpy[0], &sa, &ca);
-    sincos(rpy[1], &sb, &cb);
-    sincos(rpy[2], &sc, &cc);
-    const double r00 = cb * cc, r01 = -cb * sc, r02 = sb;
-    const double r10 = ca * sc + sa * sb * cc, r11 = ca * cc - sa * sb * sc, r12 = -sa * cb;
-    const double r20 = sa * sc - ca * sb * cc, r21 = sa * cc + ca * sb * sc, r22 = ca * cb;
+    const NlFrame f = nl_frame(rpy);
     NlVertex q0, q1, q2;
-    q0.d0 = r00 * tv[0] + r01 * tv[1] + r02 * tv[2];
-    q0.d1 = r10 * tv[0] + r11 * tv[1] + r12 * tv[2];
-    q0.d2 = r20 * tv[0] + r21 * tv[1] + r22 * tv[2];
-    q1.d0 = r00 * tv[3] + r01 * tv[4] + r02 * tv[5];
-    q1.d1 = r10 * tv[3] + r11 * tv[4] + r12 * tv[5];
-    q1.d2 = r20 * tv[3] + r21 * tv[4] + r22 * tv[5];
-    q2.d0 = r00 * tv[6] + r01 * tv[7] + r02 * tv[8];
-    q2.d1 = r10 * tv[6] + r11 * tv[7] + r12 * tv[8];
-    q2.d2 = r20 * tv[6] + r21 * tv[7] + r22 * tv[8];
+    nl_rotate(f, tv, q0.d0, q0.d1, q0.d2);
+    nl_rotate(f, tv + 3, q1.d0, q1.d1, q1.d2);
+    nl_rotate(f, tv + 6, q2.d0, q2.d1, q2.d2);
     const double x0 = pos[0] + q0.d0, x1 = pos[0] + q1.d0, x2 = pos[0] + q2.d0;
     const double z0 = pos[2] + q0.d2, z1 = pos[2] + q1.d2, z2 = pos[2] + q2.d2;
     const double t = a.t;
@@ -274,6 +319,7 @@ __global__ void __launch_bounds__(kNlThreads) nl_tris_kernel(NlArgs a) {
 
     // ---- dynamic pressure sums (and eta without stretching): three independent chains per component ----
     double pd0 = 0.0, pd1 = 0.0, pd2 = 0.0, e0 = 0.0, e1 = 0.0, e2 = 0.0;
+    double ux0 = 0.0, ux1 = 0.0, ux2 = 0.0, uz0 = 0.0, uz1 = 0.0, uz2 = 0.0;
     for (int i0 = 0; i0 < a.nf; i0 += kKinTile) {
         const int m = min(kKinTile, a.nf - i0);
         __syncthreads();
@@ -283,19 +329,31 @@ __global__ void __launch_bounds__(kNlThreads) nl_tris_kernel(NlArgs a) {
         }
         __syncthreads();
         for (int i = 0; i < m; ++i) {
-            const double k   = s[kNlK][i];
-            const double cs0 = cos(k * x0 - s[kNlOmega][i] * t + s[kNlPhase][i]);
-            const double cs1 = cos(k * x1 - s[kNlOmega][i] * t + s[kNlPhase][i]);
-            const double cs2 = cos(k * x2 - s[kNlOmega][i] * t + s[kNlPhase][i]);
-            double px0, px1, px2;
+            const double k = s[kNlK][i];
+            double sn0 = 0.0, sn1 = 0.0, sn2 = 0.0, cs0, cs1, cs2;
+            if constexpr (ORDER2) {
+                sincos(k * x0 - s[kNlOmega][i] * t + s[kNlPhase][i], &sn0, &cs0);
+                sincos(k * x1 - s[kNlOmega][i] * t + s[kNlPhase][i], &sn1, &cs1);
+                sincos(k * x2 - s[kNlOmega][i] * t + s[kNlPhase][i], &sn2, &cs2);
+            } else {
+                cs0 = cos(k * x0 - s[kNlOmega][i] * t + s[kNlPhase][i]);
+                cs1 = cos(k * x1 - s[kNlOmega][i] * t + s[kNlPhase][i]);
+                cs2 = cos(k * x2 - s[kNlOmega][i] * t + s[kNlPhase][i]);
+            }
+            double px0, px1, px2, pz0 = 0.0, pz1 = 0.0, pz2 = 0.0;
             if (s[kNlDeep][i] != 0.0) {  // (the same branch for every item: no divergence)
-                px0 = exp(k * ze0);
-                px1 = exp(k * ze1);
-                px2 = exp(k * ze2);
+                px0 = pz0 = exp(k * ze0);
+                px1 = pz1 = exp(k * ze1);
+                px2 = pz2 = exp(k * ze2);
             } else {
                 px0 = cosh(k * (ze0 + a.depth)) * s[kNlInvSinh][i];
                 px1 = cosh(k * (ze1 + a.depth)) * s[kNlInvSinh][i];
                 px2 = cosh(k * (ze2 + a.depth)) * s[kNlInvSinh][i];
+                if constexpr (ORDER2) {
+                    pz0 = sinh(k * (ze0 + a.depth)) * s[kNlInvSinh][i];
+                    pz1 = sinh(k * (ze1 + a.depth)) * s[kNlInvSinh][i];
+                    pz2 = sinh(k * (ze2 + a.depth)) * s[kNlInvSinh][i];
+                }
             }
             e0 += s[kNlAmp][i] * cs0;
             e1 += s[kNlAmp][i] * cs1;
@@ -303,12 +361,30 @@ __global__ void __launch_bounds__(kNlThreads) nl_tris_kernel(NlArgs a) {
             pd0 += s[kNlW2AoK][i] * px0 * cs0;
             pd1 += s[kNlW2AoK][i] * px1 * cs1;
             pd2 += s[kNlW2AoK][i] * px2 * cs2;
+            if constexpr (ORDER2) {  // u1 of the kinematics at every vertex, unramped
+                const double wa = s[kNlOmega][i] * s[kNlAmp][i];
+                ux0 += wa * px0 * cs0;
+                ux1 += wa * px1 * cs1;
+                ux2 += wa * px2 * cs2;
+                uz0 += wa * pz0 * sn0;
+                uz1 += wa * pz1 * sn1;
+                uz2 += wa * pz2 * sn2;
+            }
         }
     }
     if (!a.stretch) {
         eta0 = e0;
         eta1 = e1;
         eta2 = e2;
+    }
+    double qa = 0.0, qb = 0.0, qc = 0.0;  // q2 of the three vertices
+    if constexpr (ORDER2) {
+        const int* ix    = a.pidx + 3 * static_cast<size_t>(item);
+        const double* ia = a.inc + static_cast<size_t>(kNlIncDoubles) * ix[0];
+        const double* ib = a.inc + static_cast<size_t>(kNlIncDoubles) * ix[1];
+        const double* ic = a.inc + static_cast<size_t>(kNlIncDoubles) * ix[2];
+        eta0 += ia[3], eta1 += ib[3], eta2 += ic[3];
+        qa = ia[4], qb = ib[4], qc = ic[4];
     }
 
     // ---- h and the pressures at the vertices; a vertex is wet iff h <= 0 ----
@@ -319,6 +395,12 @@ __global__ void __launch_bounds__(kNlThreads) nl_tris_kernel(NlArgs a) {
     q0.pd = a.rho * pd0 * a.ramp;
     q1.pd = a.rho * pd1 * a.ramp;
     q2.pd = a.rho * pd2 * a.ramp;
+    if constexpr (ORDER2) {
+        const double hr2 = 0.5 * a.rho * (a.ramp * a.ramp);
+        q0.pd = q0.pd + a.rho * qa - hr2 * (ux0 * ux0 + uz0 * uz0);
+        q1.pd = q1.pd + a.rho * qb - hr2 * (ux1 * ux1 + uz1 * uz1);
+        q2.pd = q2.pd + a.rho * qc - hr2 * (ux2 * ux2 + uz2 * uz2);
+    }
     const bool w0 = h0 <= 0.0, w1 = h1 <= 0.0, w2 = h2 <= 0.0;
     const int nw = active ? static_cast<int>(w0) + static_cast<int>(w1) + static_cast<int>(w2) : 0;
 
@@ -360,6 +442,44 @@ __global__ void __launch_bounds__(kNlThreads) nl_tris_kernel(NlArgs a) {
         double* out = a.part + static_cast<size_t>(kNlOut) * blockIdx.x;
 #pragma unroll
         for (int k = 0; k < kNlOut; ++k) out[k] = red[k][0];
+    }
+}
+
+__global__ void __launch_bounds__(kNlThreads) nl_tris_kernel(NlArgs a) { nl_tris_body<false>(a); }
+__global__ void __launch_bounds__(kNlThreads) nl2_tris_kernel(NlArgs a) { nl_tris_body<true>(a); }
+
+struct Nl2Args {
+    Wk2Sea sea;           // the nonlinear path's own tables (hc_ctx::nl2), mwl of the nonlinear options
+    const double* point;  // [points][3]: the distinct body-frame points of the owned bodies' lists, body-major
+    const int* body;      // [points] body (of the system) a point belongs to
+    const double* state;  // as NlArgs
+    int N;
+    double t;
+    int ramped;           // ramp * ramp applies (apply_ramp, a synthesised irregular model, ramp_duration > 0)
+    double ramp_duration;
+    double* inc;          // [points][kNlIncDoubles]
+};
+
+// One workgroup per distinct surface point of the owned bodies: the point of the item kernels (nl_frame, nl_rotate), then the pair
+// sum of hc_wave_kinematics2 at that point and time with its epilogue (1/4 on eta2, ramp^2) -- eta2 is what that call returns for the
+// stored point, bit for bit -- and q2 = -d phi2 / dt from the same pairs.  No velocity or acceleration is computed.
+__global__ void __launch_bounds__(kWk2Threads) nl2_incr_kernel(Nl2Args a) {
+    const int e       = blockIdx.x;  // the grid is the number of points
+    const double* pos = a.state + 3 * a.body[e];
+    const NlFrame f   = nl_frame(pos + 3 * a.N);
+    double d0, d1, d2;
+    nl_rotate(f, a.point + 3 * static_cast<size_t>(e), d0, d1, d2);
+    const double x = pos[0] + d0, y = pos[1] + d1, z = pos[2] + d2;
+    double sum[6];
+    wk2_item_sum<true, false, true>(a.sea, x, z, a.t, sum);
+    if (threadIdx.x == 0) {
+        const double ramp2 = wk2_ramp2(a.ramped != 0, a.ramp_duration, a.t);
+        double* out = a.inc + static_cast<size_t>(kNlIncDoubles) * e;
+        out[0] = x;
+        out[1] = y;
+        out[2] = z;
+        out[3] = 0.25 * sum[0] * ramp2;
+        out[4] = sum[5] * ramp2;
     }
 }
 
@@ -413,7 +533,47 @@ void upload_panels(hc_ctx* c) {
     c->nl_items  = items + tris;
     c->nl_chunks = static_cast<int>(chunk.size() / 3);
     if (c->d_nl_part.n < static_cast<size_t>(kNlOut) * c->nl_chunks) c->d_nl_part.alloc(static_cast<size_t>(kNlOut) * c->nl_chunks);
-    c->nl_dirty = false;
+    c->nl_dirty     = false;
+    c->nl_pts_dirty = true;  // upload_points, once an evaluation on the second-order sea needs them
+}
+
+// The distinct body-frame points of one body's list in the order of their first use -- a panel's centroid, a triangle's vertices;
+// two points are the same when all three doubles have equal bits -- appended to `pts`, and for every panel, or triangle and vertex,
+// the index of its point counted from `base`, appended to `idx`.  Returns the number of points added.
+int unique_points(const hc_ctx* c, int b, int base, std::vector<double>* pts, std::vector<int>* idx) {
+    std::map<std::array<std::uint64_t, 3>, int> seen;
+    const auto add = [&](const double* v) {
+        std::array<std::uint64_t, 3> key;
+        std::memcpy(key.data(), v, sizeof(key));
+        const auto at = seen.emplace(key, static_cast<int>(seen.size()));
+        if (at.second && pts) pts->insert(pts->end(), v, v + 3);
+        if (idx) idx->push_back(base + at.first->second);
+    };
+    if (!c->nl_panels.empty() && !c->nl_panels[b].empty()) {
+        for (const hc_surface_panel& p : c->nl_panels[b]) add(p.c);
+    } else if (!c->nl_tris.empty()) {
+        for (size_t e = 0; e + 3 <= c->nl_tris[b].size(); e += 3) add(c->nl_tris[b].data() + e);
+    }
+    return static_cast<int>(seen.size());
+}
+
+// the surface points of the owned bodies, body-major, and the point of every panel and of every triangle vertex: the two index lists
+// follow d_nl_panel and d_nl_tri item by item
+void upload_points(hc_ctx* c) {
+    std::vector<double> pts;
+    std::vector<int> body, pidx, tidx, off(c->nloc + 1, 0);
+    for (int b = c->b0; b < c->b1; ++b) {
+        const bool panels = !c->nl_panels.empty() && !c->nl_panels[b].empty();
+        const int n = unique_points(c, b, off[b - c->b0], &pts, panels ? &pidx : &tidx);
+        body.insert(body.end(), n, b);
+        off[b - c->b0 + 1] = off[b - c->b0] + n;
+    }
+    c->d_nl_pt.upload(pts, c->stream_nl);
+    c->d_nl_pbody.upload(body, c->stream_nl);
+    c->d_nl_pidx.upload(pidx, c->stream_nl);
+    c->d_nl_tidx.upload(tidx, c->stream_nl);
+    c->nl_pt_off    = off;
+    c->nl_pts_dirty = false;
 }
 
 // The component table of the wave model in force, a copy of this path's own (as hc_morison.hip: another path may rebuild its table
@@ -464,14 +624,50 @@ void nonlinear_enqueue(hc_ctx* c, double t) {
     a.part         = c->d_nl_part.p;
     const int rows = static_cast<int>(n_out);
     hipStream_t st = c->stream_nl;
+    // the second-order sea: tables of this path's own, then the increments of every surface point.  No components (NoWave, no model,
+    // an imported eta record) or no pair inside either band: order 1, no further launch.
+    bool order2 = false;
+    if (c->nl2_on && wk2_has_components(c)) {
+        wk2_tables(c, c->nl2, st, c->nl_opts.regular_phase, c->nl2_cut, false);
+        order2 = c->nl2.any[0] || c->nl2.any[1];
+    }
     HC_HIP(hipMemcpyAsync(c->d_nl_state.p, c->h_nl_state.p, 2 * n3 * sizeof(double), hipMemcpyHostToDevice, st));
+    if (order2) {
+        if (c->nl_pts_dirty) upload_points(c);
+        const int points   = c->nl_pt_off.back();
+        const size_t n_inc = static_cast<size_t>(kNlIncDoubles) * points;
+        PinnedBuffer<double>& h_inc = c->h_nl_inc[c->nl_inc_cur ^ 1];
+        if (c->d_nl_inc.n < n_inc) c->d_nl_inc.alloc(n_inc);
+        if (h_inc.n < n_inc) h_inc.alloc(n_inc);
+        Nl2Args m{};
+        m.sea           = Wk2Sea{c->nl2.d_tab.p, c->nl2.nf, c->nl2.d_pair.p, c->nl2.d_band.p, c->depth, a.mwl, a.finite_depth,
+                                 {c->nl2.any[0] ? 1 : 0, c->nl2.any[1] ? 1 : 0}};
+        m.point         = c->d_nl_pt.p;
+        m.body          = c->d_nl_pbody.p;
+        m.state         = a.state;
+        m.N             = a.N;
+        m.t             = t;
+        m.ramped        = (c->nl2_ramp && synthesised && rd > 0.0) ? 1 : 0;  // the rule of hc_wave_kinematics2
+        m.ramp_duration = rd;
+        m.inc           = c->d_nl_inc.p;
+        hipLaunchKernelGGL(nl2_incr_kernel, dim3(points), dim3(kWk2Threads), 0, st, m);
+        HC_HIP(hipGetLastError());
+        HC_HIP(hipMemcpyAsync(h_inc.p, c->d_nl_inc.p, n_inc * sizeof(double), hipMemcpyDeviceToHost, st));
+        a.inc = c->d_nl_inc.p;
+    }
+    c->nl_inc_flight = order2;
     for (size_t r = 0; r < c->nl_runs.size(); r += 3) {  // a run's chunk map and partials start at its first chunk: blockIdx.x counts from there
         const int kind = c->nl_runs[r], chunk0 = c->nl_runs[r + 1], chunks = c->nl_runs[r + 2];
         NlArgs ar = a;
         ar.panel  = kind ? c->d_nl_tri.p : c->d_nl_panel.p;
         ar.chunk  = c->d_nl_chunk.p + 3 * static_cast<size_t>(chunk0);
         ar.part   = c->d_nl_part.p + static_cast<size_t>(kNlOut) * chunk0;
-        if (kind)
+        ar.pidx   = kind ? c->d_nl_tidx.p : c->d_nl_pidx.p;  // (indexed by the item, as the list)
+        if (order2 && kind)
+            hipLaunchKernelGGL(nl2_tris_kernel, dim3(chunks), dim3(kNlThreads), 0, st, ar);
+        else if (order2)
+            hipLaunchKernelGGL(nl2_panels_kernel, dim3(chunks), dim3(kNlThreads), 0, st, ar);
+        else if (kind)
             hipLaunchKernelGGL(nl_tris_kernel, dim3(chunks), dim3(kNlThreads), 0, st, ar);
         else
             hipLaunchKernelGGL(nl_panels_kernel, dim3(chunks), dim3(kNlThreads), 0, st, ar);
@@ -527,6 +723,7 @@ int hc_set_surface_panels(hc_ctx* c, int body, const hc_surface_panel* panels, i
     c->nl_panels[body].assign(panels, panels + n);
     if (!c->nl_tris.empty()) c->nl_tris[body].clear();  // a body carries panels or triangles
     c->nl_dirty = true;
+    c->nl_inc_off.clear();  // hc_get_nonlinear_increments: the lists of the last evaluation are no longer the lists
     HC_API_END(c)
 }
 
@@ -550,6 +747,7 @@ int hc_set_surface_triangles(hc_ctx* c, int body, const double* tri, int n) {
     c->nl_tris[body].assign(tri, tri + len);
     if (!c->nl_panels.empty()) c->nl_panels[body].clear();  // a body carries panels or triangles
     c->nl_dirty = true;
+    c->nl_inc_off.clear();
     HC_API_END(c)
 }
 
@@ -571,6 +769,66 @@ int hc_set_nonlinear_options(hc_ctx* c, const hc_wave_kinematics_opts* o) {
     HC_API_END(c)
 }
 
+int hc_set_nonlinear_second_order(hc_ctx* c, int on, double diff_lo, double diff_hi, double sum_lo, double sum_hi, int apply_ramp) {
+    HC_API_BEGIN_HOT(c)
+    hc_wave_kinematics2_opts o;
+    hc_wave_kinematics2_opts_default(&o);
+    o.diff_lo = diff_lo, o.diff_hi = diff_hi, o.sum_lo = sum_lo, o.sum_hi = sum_hi;
+    const char* bad = hc::wk2_check_opts(o);
+    require(bad == nullptr, HC_ERR_INVALID, bad ? bad : "");
+    require(!c->nl_pending, HC_ERR_INVALID, "a nonlinear evaluation is in flight (hc_nonlinear_end has not been called)");
+    c->nl2_on     = on != 0;
+    c->nl2_cut[0] = diff_lo, c->nl2_cut[1] = diff_hi, c->nl2_cut[2] = sum_lo, c->nl2_cut[3] = sum_hi;
+    c->nl2_ramp   = apply_ramp != 0;
+    if (!c->nl2_on) {  // the second copy of the tables, the points and their increments go (nothing of this path is in flight)
+        c->nl2.release();
+        c->d_nl_inc.release();
+        c->d_nl_pt.release();
+        c->d_nl_pbody.release();
+        c->d_nl_pidx.release();
+        c->d_nl_tidx.release();
+        c->nl_pts_dirty = true;
+        c->nl_inc_off.clear();
+    }
+    HC_API_END(c)
+}
+
+int hc_get_nonlinear_second_order(hc_ctx* c, int* on, double* diff_lo, double* diff_hi, double* sum_lo, double* sum_hi, int* apply_ramp) {
+    HC_API_BEGIN_HOT(c)
+    if (on) *on = c->nl2_on ? 1 : 0;
+    if (diff_lo) *diff_lo = c->nl2_cut[0];
+    if (diff_hi) *diff_hi = c->nl2_cut[1];
+    if (sum_lo) *sum_lo = c->nl2_cut[2];
+    if (sum_hi) *sum_hi = c->nl2_cut[3];
+    if (apply_ramp) *apply_ramp = c->nl2_ramp;
+    HC_API_END(c)
+}
+
+int hc_get_nonlinear_point_count(hc_ctx* c, int body, int* n) {
+    HC_API_BEGIN_HOT(c)
+    require(body >= 0 && body < c->N && n, HC_ERR_INVALID, "body index out of range or null pointer");
+    *n = hc::unique_points(c, body, 0, nullptr, nullptr);
+    HC_API_END(c)
+}
+
+int hc_get_nonlinear_increments(hc_ctx* c, int body, int n, double* p, double* eta2, double* q2) {
+    HC_API_BEGIN_HOT(c)
+    require(c->nl2_on, HC_ERR_INVALID, "the surface on the second-order sea is switched off (hc_set_nonlinear_second_order)");
+    require(body >= c->b0 && body < c->b1, HC_ERR_INVALID, "body not owned by this context");
+    require(!c->nl_inc_off.empty(), HC_ERR_INVALID, "no nonlinear evaluation with a second-order part has completed");
+    const int e0 = c->nl_inc_off[body - c->b0], e1 = c->nl_inc_off[body - c->b0 + 1];
+    require(n == e1 - e0, HC_ERR_INVALID, "n is not the body's surface point count (hc_get_nonlinear_point_count)");
+    const double* q = c->h_nl_inc[c->nl_inc_cur].p;
+    for (int e = e0; e < e1; ++e) {
+        const double* v = q + static_cast<size_t>(hc::kNlIncDoubles) * e;
+        const size_t i  = static_cast<size_t>(e - e0);
+        if (p) std::copy(v, v + 3, p + 3 * i);
+        if (eta2) eta2[i] = v[3];
+        if (q2) q2[i] = v[4];
+    }
+    HC_API_END(c)
+}
+
 int hc_nonlinear_begin(hc_ctx* c, double t, const double* pos, const double* rpy) {
     HC_API_BEGIN_HOT(c)
     require(c->finalized, HC_ERR_INVALID, "hc_finalize has not been called");
@@ -580,6 +838,8 @@ int hc_nonlinear_begin(hc_ctx* c, double t, const double* pos, const double* rpy
     require(std::isfinite(t) && hc::all_finite(pos, n3) && hc::all_finite(rpy, n3), HC_ERR_INVALID, "non-finite time or state");
     require(c->gsys[0] == 0.0 && c->gsys[1] == 0.0 && c->gsys[2] < 0.0, HC_ERR_INVALID,
             "the nonlinear surface forces need gravity (0, 0, -g): z up");
+    require(!(c->nl2_on && hc::wk2_has_components(c)) || hc::wk2_component_count(c) <= hc::kWk2MaxFreq, HC_ERR_UNSUPPORTED,
+            "the surface on the second-order sea: more than 4096 wave components");
     // the host copy of the state: the kernel's source, and what hc_nonlinear_end computes hs_lin from (the caller's arrays are
     // borrowed for this call only)
     if (c->h_nl_state.n < 2 * n3) c->h_nl_state.alloc(2 * n3);
@@ -590,6 +850,7 @@ int hc_nonlinear_begin(hc_ctx* c, double t, const double* pos, const double* rpy
         for (int b = c->b0; b < c->b1; ++b) items += static_cast<int>(c->nl_panels[b].size());
     if (!c->nl_tris.empty())
         for (int b = c->b0; b < c->b1; ++b) items += static_cast<int>(c->nl_tris[b].size() / hc::kNlTriDoubles);
+    c->nl_inc_flight = false;
     if (items == 0) {
         c->nl_pending = 1;
         return HC_OK;
@@ -609,7 +870,14 @@ int hc_nonlinear_end(hc_ctx* c, double* buoy, double* fk, double* hs_lin) {
     require(c->nl_pending != 0, HC_ERR_INVALID, "hc_nonlinear_end without hc_nonlinear_begin");
     const int what = c->nl_pending;
     c->nl_pending  = 0;
+    const bool with_inc = c->nl_inc_flight;
+    c->nl_inc_flight    = false;
+    c->nl_inc_off.clear();  // (stays so when the wait fails)
     if (what == 2) HC_HIP(hipStreamSynchronize(c->stream_nl));
+    if (with_inc) {  // the evaluation that has completed is the one hc_get_nonlinear_increments answers with
+        c->nl_inc_cur ^= 1;
+        c->nl_inc_off = c->nl_pt_off;
+    }
     for (int bl = 0; bl < c->nloc; ++bl)
         for (int k = 0; k < 6; ++k) {
             if (buoy) buoy[6 * bl + k] = what == 2 ? c->h_nl_out.p[hc::kNlOut * bl + k] : 0.0;

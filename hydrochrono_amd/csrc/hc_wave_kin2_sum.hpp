@@ -1,6 +1,6 @@
 // hc_wave_kin2_sum.hpp -- the pair sum of the second-order wave kinematics as a device function, shared by the kernels that run it
-// (hc_wave_kin2.hip: wk2_sum_kernel; hc_morison.hip: morison2_incr_kernel), and the host calls that build the tables it reads.
-// HIP only.  DESIGN.md 3.7f has the definition and the invariants, 3.7g the second user.
+// (hc_wave_kin2.hip: wk2_sum_kernel; hc_morison.hip: morison2_incr_kernel; hc_nonlinear.hip: nl2_incr_kernel), and the host calls
+// that build the tables it reads.  HIP only.  DESIGN.md 3.7f has the definition and the invariants, 3.7g and 3.7h the other users.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -35,16 +35,20 @@ struct Wk2Sea {
 // table is read along j, the column values from consecutive LDS words, the row values by broadcast.  Every lane adds its terms in
 // that fixed order into its own partial sums, and the 256 partials go through a tree whose shape depends on the lane index alone:
 // an item's bits depend on the item, the tables and the options only -- not on the kernel that asks.
-// out (work item 0 only; zeros elsewhere): 4 eta2, u2x, u2z, a2x, a2z before the ramp.
+// out (work item 0 only; zeros elsewhere): 4 eta2, u2x, u2z, a2x, a2z before the ramp, and with Q2 a sixth value
+// q2 = -d phi2 / dt = sum B Omega C cos Theta [m^2/s^2], the second-order potential's part of the pressure over rho:
+// one more accumulator over the same pairs with C as the kinematics form it, one more row of the tree.  Q2 without KIN computes
+// no velocity or acceleration; eta2 has the same bits in every instantiation.
 // No implicit fusing of a multiplication into an addition: the sums are written with explicit fma() where one is wanted, so that an
 // item's bits are the same in every instantiation and in every translation unit, whatever that unit's default is.
-template <bool ETA, bool KIN>
-__device__ inline void wk2_item_sum(const Wk2Sea& a, double x, double z, double t, double (&out)[5]) {
+template <bool ETA, bool KIN, bool Q2 = false>
+__device__ inline void wk2_item_sum(const Wk2Sea& a, double x, double z, double t, double (&out)[Q2 ? 6 : 5]) {
 #pragma clang fp contract(off)
-    constexpr int kT = kKinTile, kTK = KIN ? kKinTile : 1;
+    constexpr bool PROF = KIN || Q2;  // the depth profiles are wanted
+    constexpr int kT = kKinTile, kTK = PROF ? kKinTile : 1, kR = Q2 ? 6 : 5;
     __shared__ double sc[2][kT], ss[2][kT], sA[2][kT];  // [0]: the tile of rows, [1]: the tile of columns
     __shared__ double sk[2][kTK], sw[2][kTK], sE[2][kTK], sG[2][kTK], sF[2][kTK];
-    __shared__ double red[5][kWk2Threads];
+    __shared__ double red[kR][kWk2Threads];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int nf = a.nf;
     const long long n2 = static_cast<long long>(nf) * nf;
@@ -52,7 +56,7 @@ __device__ inline void wk2_item_sum(const Wk2Sea& a, double x, double z, double 
     double z2 = fmin(z - a.mwl, 0.0);
     if (a.finite_depth && z2 < -a.depth) z2 = -a.depth;
     const double zh = a.finite_depth ? z2 + a.depth : 0.0;
-    double eta = 0.0, ux = 0.0, uz = 0.0, ax = 0.0, az = 0.0;
+    double eta = 0.0, ux = 0.0, uz = 0.0, ax = 0.0, az = 0.0, q2 = 0.0;
 
     for (int j0 = 0; j0 < nf; j0 += kT) {
         const int mj = min(kT, nf - j0), j1 = j0 + mj - 1;
@@ -80,7 +84,7 @@ __device__ inline void wk2_item_sum(const Wk2Sea& a, double x, double z, double 
                     sc[h][tid] = cs;
                     ss[h][tid] = sn;
                     sA[h][tid] = a.tab[kKinAmp * nf + i];
-                    if constexpr (KIN) {
+                    if constexpr (PROF) {
                         sk[h][tid] = k;
                         sw[h][tid] = w;
                         sE[h][tid] = exp(k * z2);
@@ -104,7 +108,7 @@ __device__ inline void wk2_item_sum(const Wk2Sea& a, double x, double z, double 
                         const double cm = fma(ci, cj, si * sj), sm = fma(si, cj, -(ci * sj));
                         const double wgt = j == i ? 1.0 : 2.0;
                         if constexpr (ETA) eta = fma(wgt * (Ai * sA[1][c]) * row[kWk2Km * n2 + j], cm, eta);
-                        if constexpr (KIN) {
+                        if constexpr (PROF) {
                             const double B   = wgt * row[kWk2Bm * n2 + j];
                             const double kap = sk[0][r] - sk[1][c], ak = fabs(kap), Om = sw[0][r] - sw[1][c];
                             const double e   = exp(ak * z2);  // (not E_i / E_j: either may have underflowed)
@@ -114,11 +118,14 @@ __device__ inline void wk2_item_sum(const Wk2Sea& a, double x, double z, double 
                                 C = e * (1.0 + q) * d;
                                 S = e * (1.0 - q) * d;
                             }
-                            const double bkC = B * kap * C, bkS = B * ak * S;
-                            ux = fma(bkC, cm, ux);
-                            uz = fma(bkS, sm, uz);
-                            ax = fma(bkC * Om, sm, ax);
-                            az = fma(-(bkS * Om), cm, az);
+                            if constexpr (KIN) {
+                                const double bkC = B * kap * C, bkS = B * ak * S;
+                                ux = fma(bkC, cm, ux);
+                                uz = fma(bkS, sm, uz);
+                                ax = fma(bkC * Om, sm, ax);
+                                az = fma(-(bkS * Om), cm, az);
+                            }
+                            if constexpr (Q2) q2 = fma(B * C * Om, cm, q2);
                         }
                     }
                 }
@@ -132,7 +139,7 @@ __device__ inline void wk2_item_sum(const Wk2Sea& a, double x, double z, double 
                         const double cp = fma(ci, cj, -(si * sj)), sp = fma(si, cj, ci * sj);
                         const double wgt = j == i ? 1.0 : 2.0;
                         if constexpr (ETA) eta = fma(wgt * (Ai * sA[1][c]) * row[kWk2Kp * n2 + j], cp, eta);
-                        if constexpr (KIN) {
+                        if constexpr (PROF) {
                             const double B   = wgt * row[kWk2Bp * n2 + j];
                             const double kap = sk[0][r] + sk[1][c], ak = fabs(kap), Om = sw[0][r] + sw[1][c];
                             const double e   = sE[0][r] * sE[1][c];  // e^{(k_i + k_j) z2}: 0, never NaN, where a factor has underflowed
@@ -142,11 +149,14 @@ __device__ inline void wk2_item_sum(const Wk2Sea& a, double x, double z, double 
                                 C = e * (1.0 + q) * d;
                                 S = e * (1.0 - q) * d;
                             }
-                            const double bkC = B * kap * C, bkS = B * ak * S;
-                            ux = fma(bkC, cp, ux);
-                            uz = fma(bkS, sp, uz);
-                            ax = fma(bkC * Om, sp, ax);
-                            az = fma(-(bkS * Om), cp, az);
+                            if constexpr (KIN) {
+                                const double bkC = B * kap * C, bkS = B * ak * S;
+                                ux = fma(bkC, cp, ux);
+                                uz = fma(bkS, sp, uz);
+                                ax = fma(bkC * Om, sp, ax);
+                                az = fma(-(bkS * Om), cp, az);
+                            }
+                            if constexpr (Q2) q2 = fma(B * C * Om, cp, q2);
                         }
                     }
                 }
@@ -158,16 +168,17 @@ __device__ inline void wk2_item_sum(const Wk2Sea& a, double x, double z, double 
     red[2][tid] = uz;
     red[3][tid] = ax;
     red[4][tid] = az;
+    if constexpr (Q2) red[5][tid] = q2;
     // ---- fixed-shape tree over the 256 lanes: lane l adds lane l + h for h = 128, 64, ..., 1 (drift_qtf_kernel) ----
     for (int h = kWk2Threads / 2; h > 0; h >>= 1) {
         __syncthreads();
         if (tid < h) {
 #pragma unroll
-            for (int k = 0; k < 5; ++k) red[k][tid] += red[k][tid + h];
+            for (int k = 0; k < kR; ++k) red[k][tid] += red[k][tid + h];
         }
     }
 #pragma unroll
-    for (int k = 0; k < 5; ++k) out[k] = tid == 0 ? red[k][0] : 0.0;
+    for (int k = 0; k < kR; ++k) out[k] = tid == 0 ? red[k][0] : 0.0;
 }
 
 // ---- hc_wave_kin2.hip: the host side both users share ----

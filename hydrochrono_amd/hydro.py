@@ -605,6 +605,35 @@ class HydroForces:
         o = capi.WaveKinematicsOpts(float(mwl), float(regular_phase), int(bool(wave_stretching)))
         self._chk(self.lib.hc_set_nonlinear_options(self.ctx, C.byref(o)))
 
+    def set_nonlinear_second_order(self, on=True, diff_band=(0.0, float("inf")), sum_band=(0.0, float("inf")), apply_ramp=True):
+        """The panels and clipped triangles on the second-order sea: eta1 + eta2 in the wet test and the clipping height, and
+        rho q2 - 1/2 rho ramp^2 |u1|^2 added to p_d (q2 = -d phi2 / dt); diff_band / sum_band: (lo, hi) in rad/s as wave_kinematics2()
+        takes them, mwl and regular_phase from set_nonlinear_options().  on=False frees the tables.  See
+        hc_set_nonlinear_second_order in include/hydrochrono_amd.h."""
+        (dlo, dhi), (slo, shi) = map(float, diff_band), map(float, sum_band)
+        self._chk(self.lib.hc_set_nonlinear_second_order(self.ctx, int(bool(on)), dlo, dhi, slo, shi, int(bool(apply_ramp))))
+
+    def nonlinear_second_order(self):
+        """dict(on, diff_band, sum_band, apply_ramp) as set_nonlinear_second_order() takes them."""
+        on, ramp = C.c_int(), C.c_int()
+        v = [C.c_double() for _ in range(4)]
+        self._chk(self.lib.hc_get_nonlinear_second_order(self.ctx, C.byref(on), *[C.byref(x) for x in v], C.byref(ramp)))
+        return dict(on=bool(on.value), diff_band=(v[0].value, v[1].value), sum_band=(v[2].value, v[3].value), apply_ramp=bool(ramp.value))
+
+    def nonlinear_point_count(self, b):
+        """The distinct surface points of body b (0-based): panel centroids or triangle vertices, a shared vertex once."""
+        n = C.c_int()
+        self._chk(self.lib.hc_get_nonlinear_point_count(self.ctx, int(b), C.byref(n)))
+        return n.value
+
+    def nonlinear_increments(self, b):
+        """What the surface points of body b (0-based, owned) saw in the last evaluation on the second-order sea: dict of p (n, 3),
+        eta2 (n), q2 (n), one entry per distinct point in the order of its first use."""
+        n = self.nonlinear_point_count(b)
+        out = dict(p=np.empty((n, 3)), eta2=np.empty(n), q2=np.empty(n))
+        self._chk(self.lib.hc_get_nonlinear_increments(self.ctx, int(b), n, *[_dp(out[k].reshape(-1)) for k in ("p", "eta2", "q2")]))
+        return out
+
     def set_nonlinear_mode(self, mode):
         """0: off (step() as without panels); 1: a body with panels gets total - hs_lin + buoy; 2: total - hs_lin + buoy + fk (the
         excitation data of the context should then be the scattering part only: nothing is subtracted from the wave term)."""
@@ -929,6 +958,19 @@ class HydroGroup:
         a = [_arr(x, n3) for x in (pos, rpy, linvel, angvel)]
         self._morison_begin(t, a)
         return self._morison_end()
+
+    def nonlinear_second_order(self):
+        return self.shards[0].nonlinear_second_order()
+
+    def nonlinear_point_count(self, b):
+        return self.shards[0].nonlinear_point_count(b)
+
+    def nonlinear_increments(self, b):
+        # the shard that owns the body answers
+        for h in self.shards:
+            if h.b0 <= int(b) < h.b1:
+                return h.nonlinear_increments(b)
+        raise IndexError(f"body {b} out of range")
 
     def morison_second_order(self):
         return self.shards[0].morison_second_order()

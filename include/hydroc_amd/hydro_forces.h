@@ -151,6 +151,13 @@ struct MorisonIncrements {
     std::vector<double> eta2;
 };
 
+// What the surface points of a body saw of the second-order sea (TestHydro::GetNonlinearIncrements): per distinct point -- a panel's
+// centroid, a triangle's vertex -- the world position, the elevation increment and q2 = -d phi2 / dt [m^2/s^2].
+struct NonlinearIncrements {
+    std::vector<std::array<double, 3>> p;
+    std::vector<double> eta2, q2;
+};
+
 // A surface panel of a body (not in the reference; hc_surface_panel): centroid [m] and area vector [m^2] (area times the outward
 // normal, body into water) in the body frame.
 struct SurfacePanel {
@@ -401,6 +408,35 @@ class TestHydro {
         o.wave_stretching = wave_stretching ? 1 : 0;
         for (hc_ctx* c : ctxs_) check(c, hc_set_nonlinear_options(c, &o));
         have_time_ = false;
+    }
+    // The panels and clipped triangles on the second-order sea (hc_set_nonlinear_second_order): eta1 + eta2 in the wet test and the
+    // clipping height, rho q2 - 1/2 rho ramp^2 |u1|^2 added to the dynamic pressure; the cut-offs [rad/s] are as in
+    // WaveBase::second_order_, mwl and the regular phase those of SetNonlinearHydroOptions.  Applied to every shard context;
+    // on = false frees the tables.  CoordinateFuncForBody composes as before, with no further call.
+    void SetNonlinearSecondOrder(bool on, double diff_lo = 0.0, double diff_hi = std::numeric_limits<double>::infinity(), double sum_lo = 0.0,
+                                 double sum_hi = std::numeric_limits<double>::infinity(), bool apply_ramp = true) {
+        for (hc_ctx* c : ctxs_) check(c, hc_set_nonlinear_second_order(c, on ? 1 : 0, diff_lo, diff_hi, sum_lo, sum_hi, apply_ramp ? 1 : 0));
+        have_time_ = false;
+    }
+    // What the surface points of a body saw in the last evaluation on the second-order sea (hc_get_nonlinear_increments): one entry
+    // per distinct point, answered by the shard that owns the body.
+    NonlinearIncrements GetNonlinearIncrements(int body_index_1_based) {
+        if (body_index_1_based < 1 || body_index_1_based > num_bodies_) throw std::out_of_range("GetNonlinearIncrements: body index out of range");
+        const int b = body_index_1_based - 1;
+        for (hc_ctx* c : ctxs_) {
+            int b0 = 0, b1 = 0, n = 0;
+            check(c, hc_get_shard(c, &b0, &b1));
+            if (b < b0 || b >= b1) continue;
+            check(c, hc_get_nonlinear_point_count(c, b, &n));
+            std::vector<double> p(3 * static_cast<size_t>(n));
+            NonlinearIncrements out;
+            out.eta2.resize(static_cast<size_t>(n));
+            out.q2.resize(static_cast<size_t>(n));
+            check(c, hc_get_nonlinear_increments(c, b, n, p.data(), out.eta2.data(), out.q2.data()));
+            for (int e = 0; e < n; ++e) out.p.push_back({p[3 * e], p[3 * e + 1], p[3 * e + 2]});
+            return out;
+        }
+        throw std::out_of_range("GetNonlinearIncrements: no context owns the body");
     }
     // buoy | fk | hs_lin of all bodies for the bodies' present state, 6 N values each
     std::vector<double> ComputeForceNonlinear() {

@@ -569,8 +569,8 @@ int hc_compute_morison(hc_ctx* ctx, double t, const double* pos, const double* r
  * cut-offs: a second copy beside the one hc_wave_kinematics2 keeps (4 nf^2 doubles: 8 MB at 512 components, 537 MB at 4096), freed
  * by on = 0.  HC_ERR_INVALID: a negative or NaN cut-off, lo > hi, or a hc_morison_begin without its end.  More than 4096 wave
  * components: hc_morison_begin returns HC_ERR_UNSUPPORTED and nothing stays pending.
- * Not included (out of scope): second-order pressure on the surface panels and triangles, which like the drift term keep seeing
- * the first-order field, and stretching of the second-order part. */
+ * Not included (out of scope): stretching of the second-order part.  The surface panels and triangles have a switch of their own
+ * (hc_set_nonlinear_second_order); the drift term stays first order. */
 int hc_set_morison_second_order(hc_ctx* ctx, int on, double diff_lo, double diff_hi, double sum_lo, double sum_hi, int apply_ramp);
 int hc_get_morison_second_order(hc_ctx* ctx, int* on, double* diff_lo, double* diff_hi, double* sum_lo, double* sum_hi, int* apply_ramp);
 /* What the elements of `body` (0-based, owned by this context) saw in the last completed evaluation that had a second-order part:
@@ -672,6 +672,48 @@ int hc_nonlinear_end(hc_ctx* ctx, double* buoy_Dlocal, double* fk_Dlocal, double
 int hc_compute_nonlinear(hc_ctx* ctx, double t, const double* pos, const double* rpy, double* buoy_Dlocal, double* fk_Dlocal,
                          double* hs_lin_Dlocal);
 
+/* The surface on the second-order sea: with `on` the panels and the clipped triangles see Sharma and Dean's
+ * long-crested sea to second order -- the wetted surface ends at eta1 + eta2 and the pressure is Bernoulli's to second order.  A
+ * surface point is a panel's centroid or a triangle's vertex; its world position P = pos + R c is the FP64 expression above.  At
+ * every surface point:
+ *     eta2 = hc_wave_kinematics2 (below) at the same FP64 point P and time t, with mwl and regular_phase of the nonlinear options
+ *         (hc_set_nonlinear_options) and the four cut-offs [rad/s] and apply_ramp of this call -- bit for bit that call's value
+ *     q2   = -d phi2 / dt = sum_{+-} sum_i sum_j B+-_ij Omega C(kappa, z2) cos Theta  [m^2/s^2], of that definition's
+ *         phi2 = sum B C sin Theta: the same pair tables, bands, profile C, z2 = min(P.z - mwl, 0) held at the bed, and the signs of
+ *         kappa, Omega, Theta of u2x; times ramp * ramp with apply_ramp, as the other increments
+ *     u1   = (u1x, u1z), the first-order velocity of hc_wave_kinematics at P, at the z_e p_d is taken at (stretching by eta1 with
+ *         the second mwl subtraction, the reference's profile test); not ramped
+ *     panels:    wet iff P.z - mwl <= eta1 + eta2
+ *     triangles: h_j = P_j.z - mwl - (eta1_j + eta2_j)
+ *     p_s unchanged;   p_d = ramp p_d1 + rho q2 - 1/2 rho ramp^2 (u1x^2 + u1z^2),  p_d1 and ramp those of order 1 (ramp = 1 where
+ *         order 1 applies none)
+ * and everything after that -- the case table, the midpoint rule, the split into buoy and fk, hs_lin -- is unchanged.  The two added
+ * terms are what cancels the first-order pressure's second-order residue at the free surface: p_s + p_d at z = mwl + eta1 + eta2 is
+ * of third order in the amplitudes.  They enter before the wet test and the clipping, so the result cannot be composed from the
+ * other calls.
+ * NoWave, no wave model, an imported eta record, or cut-offs that leave no pair inside either band: the launches and the bits of
+ * order 1.  With on = 0 (the default) every call makes the launches and returns the bits it did before this switch existed.  A
+ * body's bits still depend on that body's state and list, the wave model, t and the options only.
+ * The pair tables are this path's own (a third copy of 4 nf^2 doubles beside those of hc_wave_kinematics2 and the Morison
+ * elements: 8 MB at 512 components, 537 MB at 4096), built on its stream, cached on the wave model, the regular phase and the
+ * cut-offs and freed by on = 0 with the point and increment buffers.  The pair sum runs once per DISTINCT body-frame point of a
+ * body's list (two points are the same when their three doubles have equal bits): a closed mesh costs about half a point per
+ * triangle.  HC_ERR_INVALID: a negative or NaN cut-off, lo > hi, or a hc_nonlinear_begin without its end.  More than 4096 wave
+ * components: hc_nonlinear_begin returns HC_ERR_UNSUPPORTED and nothing stays pending.
+ * Not included: second order in the drift term (which keeps seeing the first-order sea), stretching of the second-order part, a
+ * bound on the extrapolated first-order pressure at dry vertices. */
+int hc_set_nonlinear_second_order(hc_ctx* ctx, int on, double diff_lo, double diff_hi, double sum_lo, double sum_hi, int apply_ramp);
+int hc_get_nonlinear_second_order(hc_ctx* ctx, int* on, double* diff_lo, double* diff_hi, double* sum_lo, double* sum_hi, int* apply_ramp);
+/* The number of distinct surface points of `body` (0-based, any body of the system): of its panel centroids or its triangle
+ * vertices, in the order of their first use. */
+int hc_get_nonlinear_point_count(hc_ctx* ctx, int body, int* n);
+/* What the surface points of `body` (0-based, owned by this context) saw in the last completed evaluation that had a second-order
+ * part: their world positions p[n][3] and eta2[n], q2[n]; n = the body's point count at that evaluation.  Any pointer may be NULL.
+ * Also answered between a later hc_nonlinear_begin and its end.  HC_ERR_INVALID: the switch is off, no such evaluation has
+ * completed (one without a second-order part forgets the one before, and so do hc_set_surface_panels / _triangles), n is not
+ * the point count, or the body is not owned by this context. */
+int hc_get_nonlinear_increments(hc_ctx* ctx, int body, int n, double* p /* [n][3] */, double* eta2 /* [n] */, double* q2 /* [n] */);
+
 /* ------------------------------------------------------------------------------------------------
  * Second-order wave drift forces from difference-frequency QTF tables (not in the reference, whose wave forces are first order in
  * the amplitude: no mean, no energy below the wave band).  Opt-in, per body, evaluated at the body's instantaneous position.
@@ -771,8 +813,8 @@ int hc_compute_drift(hc_ctx* ctx, double t, const double* pos, double* out_Dloca
  *
  * Every (point, time) item is summed by one workgroup in a fixed order: its bits depend on the item, the wave model and the
  * options only -- not on the batch it is part of, its place in it, the outputs asked for, or the shard context that answers.
- * The surface-pressure and drift terms keep seeing the first-order field; the Morison elements see these increments once
- * hc_set_morison_second_order switches them on.
+ * The drift term keeps seeing the first-order field; the Morison elements and the surface panels and triangles see these
+ * increments once hc_set_morison_second_order / hc_set_nonlinear_second_order switch them on.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct hc_wave_kinematics2_opts {
     double mwl;            /* WaveBase::mwl_ (0) */
