@@ -370,7 +370,7 @@ struct hc_ctx {
     // GEMV configuration + scratch
     int chunk_gp = 0, nchunks_rad = 0, chunk_gp_ex = 0, nchunks_ex = 0, ngp_ex = 0;
     int chunk_gp_block = 0, nchunks_block = 0;
-    int chunk_gp_head = 0;  // chunk length of the head pass of the spectral tail (lags below kTailP)
+    int chunk_gp_head = 0, chunk_gp_head128 = 0;  // chunk length of the head pass of the spectral tail (lags below 256 / below 128)
     hc::DeviceBuffer<double> d_partials, d_partials_block, d_P, d_E;
     hc::DeviceBuffer<double> d_near_partials;  // [16][Dpad] slice partials of near_split_kernel (wide systems)
     hc::DeviceBuffer<int> d_tile_counter;      // [ntiles] arrival counters of wide_step_kernel (zero between launches)
@@ -398,19 +398,34 @@ struct hc_ctx {
     std::chrono::steady_clock::time_point t_multi_end{};  // (kept on the group's first context) end of the last hc_step_multi
     bool have_t_multi_end = false;
     hc::AheadPass ahead;
-    // spectral radiation tail (hc_tail.hpp, hc_pass.cpp): lags s >= kTailP of the at-start pass by partitioned FFT convolution
-    int radiation_tail = 1;  // hc_set_radiation_tail: 0 always the full pass, 1 the tail where eligible
+    // spectral radiation tail (hc_tail.hpp, hc_pass.cpp): the lags from 128 (levelled form) or 256 (uniform form) on of the at-start
+    // pass by partitioned FFT convolution
+    int radiation_tail = 1;  // hc_set_radiation_tail: 0 always the full pass; where eligible 1 the levelled form, 2 the uniform form
     struct SpectralTail {
-        bool khat_ok = false;     // d_khat holds the transform of the current K (or tapered K) and widths
-        bool active = false;      // a superblock is running: its tail rows are in d_tail_out
-        int k = 0, Q = 0;         // blocks of the superblock issued so far / per superblock
-        int cur = 0;              // half of d_tail_yfar that belongs to the running superblock
-        unsigned far_cur = 0, far_next = 0;  // far chunks done for the running / the next superblock (bit k: chunk k)
+        bool active = false;      // a top period (superblock) is running: its tail rows are in the levels' `out`
+        int form = 0;             // index into spec_form of the form the running period uses
+        int k = 0, Q = 0;         // blocks of the top period issued so far / per top period
+        int cur = 0;              // half of the top level's Y that belongs to the running period
+        unsigned far_cur = 0, far_next = 0;  // far chunks of the top level done for the running / the next period (bit k: chunk k)
         unsigned long long serial = 0;       // plan serial of the last block that took its rows from the tail
-        double t0 = 0.0, dt = 0.0;           // first step of the superblock, step
+        double t0 = 0.0, dt = 0.0;           // first step of the top period, step
     } spec;
-    hc::DeviceBuffer<double> d_khat, d_tail_xw, d_tail_yfar, d_tail_out, d_tail_tw;
-    hc::DirectKernel dk_tail_fwd, dk_tail_gemv, dk_tail_inv;
+    // one level of a form: its geometry and buffers (hc_tail.hpp: TailLevel)
+    struct SpectralLevel {
+        hc::TailLevel lv{};
+        hc::DeviceBuffer<double> khat;  // [bins][Dloc][NP * D] complex
+        hc::DeviceBuffer<double> xw;    // [bins][NP * D] complex
+        hc::DeviceBuffer<double> y;     // [2][bins][Dloc] complex: this period's half and the one the far chunks fill for the next
+        hc::DeviceBuffer<double> out;   // [P][Dpad] the level's rows of the running period
+        hc::DeviceBuffer<double> tw;    // [N][2] twiddles
+    };
+    // a slot per form; hc_set_radiation_tail releases the buffers of the form it leaves, after the GPU has drained
+    struct SpectralForm {
+        int nlev = 0, S = 0;      // levels, and the window length they were laid out for
+        bool khat_ok = false;     // every level's khat holds the transform of the current K (or tapered K) and widths
+        SpectralLevel lev[hc::kTailLevelsMax];
+    } spec_form[2];               // [0] levelled (mode 1), [1] uniform (mode 2)
+    hc::DirectKernel dk_tail_fwd[3], dk_tail_inv[3], dk_tail_gemv;  // transforms of 256, 512, 1024 points
     hc::DeviceBuffer<double> d_partials_far;  // partial sums of the pass in the making (the short passes keep d_partials_block)
     hc::DeviceBuffer<double> d_partials_next; // ... and of the short passes towards the next block when they run on the pass lane
     // The pass lane (lane 2 of the direct queue): passes in the making run there BESIDE the steps of lane 0, on a queue that leaves

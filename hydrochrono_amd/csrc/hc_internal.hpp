@@ -157,13 +157,17 @@ struct PassSetup {
     bool exc_block = false;
     double rad_once = 0.0, exc_once = 0.0, bytes_steps = 0.0;
 };
-PassSetup make_pass(hc_ctx* c, bool with_exc, bool next_block, bool head_only = false);
+PassSetup make_pass(hc_ctx* c, bool with_exc, bool next_block, int head_lags = 0);
 void issue_pass_chunks(hc_ctx* c, const PassSetup& ps, int first, int last, bool with_items, hipStream_t stream, bool direct, int lane = 0);
-void issue_pass_reduce(hc_ctx* c, const PassSetup& ps, double* P, double* E, hipStream_t stream, bool direct, int lane = 0, const double* tail = nullptr,
-                       int tail_j0 = 0);
+// rows of the spectral tail's levels for a block (largest partition first; null: no such level) and the first row of each the block takes
+struct TailRows {
+    const double* tail[hc::kTailLevelsMax] = {nullptr, nullptr, nullptr};
+    int j0[hc::kTailLevelsMax]             = {0, 0, 0};
+};
+void issue_pass_reduce(hc_ctx* c, const PassSetup& ps, double* P, double* E, hipStream_t stream, bool direct, int lane = 0, const TailRows* tail = nullptr);
 void launch_pass(hc_ctx* c, hipStream_t stream, bool with_exc, bool direct = false, bool spec_goes_on = false);
 void spec_drop(hc_ctx* c, bool k_changed);
-void spec_build_khat(hc_ctx* c);
+void spec_build_khat(hc_ctx* c, hc_ctx::SpectralLevel& lev);
 void launch_mini_pass(hc_ctx* c, int i0, hipStream_t stream, bool direct, int next_kw = 0, int lane = 0);
 void ahead_drop(hc_ctx* c);
 void ahead_issue_slice(hc_ctx* c, hipStream_t stream, bool direct);

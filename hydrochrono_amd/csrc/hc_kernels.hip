@@ -1074,7 +1074,12 @@ __global__ void __launch_bounds__(256) reduce_block_kernel(ReduceArgs a) {
             const int j = out / a.Dpad;
             if (!exc && j < a.j_cnt) a.P[out + (size_t)a.j_off * a.Dpad] += v;
         } else {
-            if (!exc && a.tail) v += a.tail[(size_t)(a.tail_j0 + out / a.Dpad) * a.Dpad + out % a.Dpad];
+            if (!exc && a.tail) {
+                const int j = out / a.Dpad, row = out % a.Dpad;
+                v += a.tail[(size_t)(a.tail_j0 + j) * a.Dpad + row];
+                if (a.tail_b) v += a.tail_b[(size_t)(a.tail_b_j0 + j) * a.Dpad + row];
+                if (a.tail_c) v += a.tail_c[(size_t)(a.tail_c_j0 + j) * a.Dpad + row];
+            }
             (exc ? a.E : a.P)[out] = v;
         }
     }

@@ -321,9 +321,13 @@ struct ReduceArgs {
     int narrow;
     int tail_j0;         // spectral radiation tail (hc_tail.hpp): row j of P gets tail[tail_j0 + j] as its last addend
     unsigned char jbase[kMiniChunks];
-    const double* tail;  // [kTailP][Dpad] (null: no tail)
+    const double* tail;  // [P][Dpad] rows of the top level (null: no tail)
+    // the lower levels of the levelled form, added after `tail` in this order (largest P first; null: none)
+    const double* tail_b;  // [P_b][Dpad]
+    const double* tail_c;  // [P_c][Dpad]
+    int tail_b_j0, tail_c_j0;
 };
-static_assert(sizeof(ReduceArgs) == 80 + kMiniChunks && kMiniChunks % 8 == 0, "kernarg layout of reduce_block_kernel");
+static_assert(sizeof(ReduceArgs) == 104 + kMiniChunks && kMiniChunks % 8 == 0, "kernarg layout of reduce_block_kernel");
 
 struct TaperArgs {
     Panel Kraw;
@@ -413,8 +417,8 @@ void launch_synth_rirf(double* d_K, int ntiles, int ngp, int Dloc, int D, int S,
 struct TailKhatArgs {
     Panel K;              // the radiation panel the pass reads (K or the tapered K)
     const double* width;  // [S]
-    const double* tw;     // [kTailN][2]
-    double* Khat;         // [kTailBins][Dloc][NP * D] complex
+    const double* tw;     // [N][2], N = the transform size of the level (the kernel's template argument)
+    double* Khat;         // [bins][Dloc][NP * D] complex
     int Dloc, D, S, NP;
 };
 
@@ -423,14 +427,14 @@ struct TailFwdArgs {
     int HcapT, Hcap, head;  // head: ring slot of the newest sample (step m0 - 1)
     int D, S, NP;
     const double* tw;
-    double* Xw;             // [kTailBins][NP * D] complex
+    double* Xw;             // [bins][NP * D] complex
 };
 
 struct TailGemvArgs {
-    const double* Khat;  // [kTailBins][Dloc][ncols] complex
-    const double* Xw;    // [kTailBins][ncols] complex
-    const double* Yin;   // [kTailBins][Dloc] complex, added first (null: nothing)
-    double* Yout;        // [kTailBins][Dloc] complex (may be Yin: each element is read and written by the same work item)
+    const double* Khat;  // [bins][Dloc][ncols] complex
+    const double* Xw;    // [bins][ncols] complex
+    const double* Yin;   // [bins][Dloc] complex, added first (null: nothing)
+    double* Yout;        // [bins][Dloc] complex (may be Yin: each element is read and written by the same work item)
     int Dloc, ncols;
     int bin_lo, bin_hi;
     int col_lo, col_hi;  // Khat columns of the sum
@@ -439,17 +443,18 @@ struct TailGemvArgs {
 };
 
 struct TailInvArgs {
-    const double* Y;  // [kTailBins][Dloc] complex
+    const double* Y;  // [bins][Dloc] complex
     const double* tw;
-    double* tail;     // [kTailP][Dpad]
+    double* tail;     // [P][Dpad]
     int Dloc, Dpad;
 };
 constexpr int kTailGemvRows = 32;  // rows of one tail_gemv workgroup (a multiple of 16: four waves of four-row batches)
 int tail_gemv_lds_bytes(const TailGemvArgs& g);
 int tail_gemv_grid(const TailGemvArgs& g);
-void launch_tail_khat(const TailKhatArgs& a, hipStream_t s);
-void launch_tail_fwd(const TailFwdArgs& a, hipStream_t s);
+// N: the transform size of the level, 256, 512 or 1024 (bins = N / 2 + 1, N / 2 work items per transform); any other: hipErrorInvalidValue
+hipError_t launch_tail_khat(const TailKhatArgs& a, int N, hipStream_t s);
+hipError_t launch_tail_fwd(const TailFwdArgs& a, int N, hipStream_t s);
 void launch_tail_gemv(const TailGemvArgs& a, hipStream_t s);
-void launch_tail_inv(const TailInvArgs& a, hipStream_t s);
+hipError_t launch_tail_inv(const TailInvArgs& a, int N, hipStream_t s);
 
 }  // namespace hc

@@ -32,9 +32,10 @@ StepViews make_views(const hc_ctx* c) {
 // next_block: the same pass for the predicted steps of the block AFTER this one (hc_plan.hpp: FarPass) -- the view of the history
 // is the same, only the query times move on by a block.
 
-// head_only (spectral tail, below): the IRF samples s < kTailP only, in chunks of their own length -- the lags from kTailP on come from
-// the tail, which reduce_block_kernel adds to the rows.
-PassSetup make_pass(hc_ctx* c, bool with_exc, bool next_block, bool head_only) {
+// head_lags > 0 (spectral tail, below): the IRF samples s < head_lags (256 or 128) only, in chunks of their own length -- the lags from
+// there on come from the tail, which reduce_block_kernel adds to the rows.
+PassSetup make_pass(hc_ctx* c, bool with_exc, bool next_block, int head_lags) {
+    const bool head_only = head_lags > 0;
     auto& pl = c->plan;
     const int L = c->lookahead;
     const int H = static_cast<int>(c->times.size());
@@ -63,9 +64,9 @@ PassSetup make_pass(hc_ctx* c, bool with_exc, bool next_block, bool head_only) {
     hc::BlockArgs& b = ps.b;
     b                     = hc::BlockArgs{};
     b.K                   = rad_panel(c);
-    b.F                   = std::min(head_only ? hc::kTailP : c->S, live_samples(c, pl.tgrid[L])) * c->D;
+    b.F                   = std::min(head_only ? head_lags : c->S, live_samples(c, pl.tgrid[L])) * c->D;
     b.depth               = L;
-    b.chunk_gp            = next_block ? far_chunk_gp(c) : (head_only ? c->chunk_gp_head : c->chunk_gp_block);  // (a pass issued in slices: shorter chunks, a full round of workgroups per slice)
+    b.chunk_gp            = next_block ? far_chunk_gp(c) : (head_only ? (head_lags < hc::kTailP ? c->chunk_gp_head128 : c->chunk_gp_head) : c->chunk_gp_block);  // (a pass issued in slices: shorter chunks, a full round of workgroups per slice)
     b.nchunks             = std::max(1, ((b.F + 7) / 8 + b.chunk_gp - 1) / b.chunk_gp);
     b.max_steps_per_chunk = (b.chunk_gp * 8) / c->D + 2;
     b.hist                = hv;
@@ -151,12 +152,18 @@ void issue_pass_chunks(hc_ctx* c, const PassSetup& ps, int first, int last, bool
     c->prof.hip_launches += 1;
 }
 
-// ... and the reduction of its chunk partials into the rows P / E of a block (tail: rows of the spectral tail, added last, or null).
-void issue_pass_reduce(hc_ctx* c, const PassSetup& ps, double* P, double* E, hipStream_t stream, bool direct, int lane, const double* tail, int tail_j0) {
+// ... and the reduction of its chunk partials into the rows P / E of a block (tail: rows of the spectral tail's levels, added last, or null).
+void issue_pass_reduce(hc_ctx* c, const PassSetup& ps, double* P, double* E, hipStream_t stream, bool direct, int lane, const TailRows* tail) {
     const hc::BlockArgs& b = ps.b;
     hc::ReduceArgs r{b.partials, b.nchunks, b.nchunks_ex, c->Dpad, c->lookahead, P, E, b.item_counter, 0, 0, 0, 0};
-    r.tail    = tail;
-    r.tail_j0 = tail_j0;
+    if (tail) {  // the levels' rows, largest partition first: the order they are added in
+        r.tail      = tail->tail[0];
+        r.tail_j0   = tail->j0[0];
+        r.tail_b    = tail->tail[1];
+        r.tail_b_j0 = tail->j0[1];
+        r.tail_c    = tail->tail[2];
+        r.tail_c_j0 = tail->j0[2];
+    }
     if (direct) {
         c->dq->dispatch(c->dk_reduce, static_cast<uint32_t>(hc::reduce_block_grid(r)), 256, 0, &r, sizeof r, -1, 0.0, lane);
         c->prof.direct_dispatches += 1;
@@ -167,41 +174,59 @@ void issue_pass_reduce(hc_ctx* c, const PassSetup& ps, double* P, double* E, hip
 }
 
 // ---- spectral radiation tail (hc_tail.hpp) ------------------------------------------------------
-// A superblock is kTailP steps = Q at-start blocks.  Its first block issues, in this order on the pass's own queue: the forward
-// transforms of the NP input windows (tail_fft_fwd), whatever far chunks of this superblock are still missing, the near partition
-// for all bins on top of them, the inverse transform into the tail rows (tail_fft_inv), then the head pass and its reduction.  Every
-// other block k of the superblock: the head pass, its reduction, and far chunk k - 1 of the NEXT superblock.  A block
-// that does not continue the superblock (plan dropped, a step back in time, hc_set_history, another schedule, ...) starts a new one.
+// A form is a set of levels (hc_tail.hpp: tail_levels), largest partition first.  The TOP level is the uniform scheme with its P: a
+// top period (superblock) is P steps = Q at-start blocks.  Its first block issues, in this order on the pass's own queue: the forward
+// transforms of the NP input windows (tail_fft_fwd), whatever far chunks of this period are still missing, the near partition for
+// all bins on top of them, the inverse transform into the level's rows (tail_fft_inv); then the lower levels that start a period of
+// theirs with this block (one window, one product over all bins, the inverse into rows of their own -- at the top period's start all
+// of them, since every period is aligned to it); then the head pass and its reduction, which adds the levels' rows in the fixed order
+// largest P first.  Every other block k of the top period: the lower levels that start a period here, the head pass, its reduction,
+// and far chunk k - 1 of the NEXT top period.  A block that does not continue the top period (plan dropped, a step back in time,
+// hc_set_history, another schedule or form, ...) starts a new one, and all levels with it.
 void spec_drop(hc_ctx* c, bool k_changed) {
     c->spec.active = false;
     c->spec.far_cur = c->spec.far_next = 0;
-    if (k_changed) c->spec.khat_ok = false;
+    if (k_changed)
+        for (auto& f : c->spec_form) f.khat_ok = false;
 }
 
 namespace {
 
+int spec_n_index(int N) { return N == 256 ? 0 : (N == 512 ? 1 : 2); }
+int spec_form_index(const hc_ctx* c) { return c->radiation_tail == hc::kTailFormUniform ? 1 : 0; }
+
 bool spec_eligible(const hc_ctx* c, bool direct) {
     const auto& pl = c->plan;
-    if (direct && !(c->dk_tail_fwd.ok() && c->dk_tail_gemv.ok() && c->dk_tail_inv.ok())) return false;  // (one queue for the whole block)
+    if (c->radiation_tail != hc::kTailFormLevelled && c->radiation_tail != hc::kTailFormUniform) return false;
+    hc::TailLevel lv[hc::kTailLevelsMax];
+    const int nlev = hc::tail_levels(c->S, c->radiation_tail, lv);
+    if (nlev < 1) return false;
+    if (direct) {  // (one queue for the whole block: the product and the transforms of the sizes this form's levels have)
+        if (!c->dk_tail_gemv.ok()) return false;
+        for (int l = 0; l < nlev; ++l)
+            if (!c->dk_tail_fwd[spec_n_index(lv[l].N)].ok() || !c->dk_tail_inv[spec_n_index(lv[l].N)].ok()) return false;
+    }
     if (c->conv_mode == 1 && !c->proc_ready) return false;
     if (c->pass_ahead == 1 || (c->pass_ahead == 2 && c->ahead_now && pass_ahead_size_ok(c))) return false;  // blocks made one block ahead keep the full pass
     const int L = c->lookahead;
     const int NP = hc::tail_partitions(c->S);
-    if (c->radiation_tail != 1 || (L != 16 && L != 32) || c->D >= 1024 || NP < 1 || NP * c->D > hc::kTailMaxCols) return false;
+    if ((L != 16 && L != 32) || c->D >= 1024 || NP < 1 || NP * c->D > hc::kTailMaxCols) return false;
     if (!pl.valid || pl.own_zero || pl.sub != 0) return false;
+    const int head = hc::tail_head_lags(lv, nlev);
     for (int j = 0; j < L; ++j)
-        if (pl.s_defer[j] >= 0 || pl.s_cut[j] >= hc::kTailP) return false;
+        if (pl.s_defer[j] >= 0 || pl.s_cut[j] >= head) return false;
     return hc::tail_grid_ok(c->times, c->tau, pl.dt, pl.tgrid[1]);
 }
 
-void spec_twiddles(hc_ctx* c) {
-    if (c->d_tail_tw.n >= 2 * hc::kTailN) return;
+void spec_twiddles(hc_ctx* c, hc_ctx::SpectralLevel& lev) {
+    const int N = lev.lv.N;
+    if (lev.tw.n == static_cast<size_t>(2 * N)) return;
     // exp(-2 pi i k / N) from the first octant by symmetry, so that the exact angles (k N/4, k N/8) come out exact
-    std::vector<double> tw(2 * hc::kTailN);
+    std::vector<double> tw(2 * static_cast<size_t>(N));
     const double pi = 3.14159265358979323846;
-    for (int k = 0; k < hc::kTailN; ++k) {
-        const int q = (4 * k) / hc::kTailN, r = k - q * (hc::kTailN / 4);  // k = q N/4 + r
-        const double cr = std::cos(2.0 * pi * r / hc::kTailN), sr = std::sin(2.0 * pi * r / hc::kTailN);
+    for (int k = 0; k < N; ++k) {
+        const int q = (4 * k) / N, r = k - q * (N / 4);  // k = q N/4 + r
+        const double cr = std::cos(2.0 * pi * r / N), sr = std::sin(2.0 * pi * r / N);
         double co = cr, si = sr;  // angle 2 pi k / N = q pi/2 + theta_r
         if (q == 1) { co = -sr; si = cr; }
         if (q == 2) { co = -cr; si = -sr; }
@@ -209,21 +234,21 @@ void spec_twiddles(hc_ctx* c) {
         tw[2 * k]     = co;
         tw[2 * k + 1] = -si;
     }
-    c->d_tail_tw.alloc(tw.size());
-    HC_HIP(hipMemcpyAsync(c->d_tail_tw.p, tw.data(), tw.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    lev.tw.alloc(tw.size());
+    HC_HIP(hipMemcpyAsync(lev.tw.p, tw.data(), tw.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HC_HIP(hipStreamSynchronize(c->stream));
 }
 
-void spec_dispatch_gemv(hc_ctx* c, hipStream_t stream, bool direct, int bin_lo, int bin_hi, int col_lo, int col_hi, int x_shift, const double* Yin,
-                        double* Yout) {
+void spec_dispatch_gemv(hc_ctx* c, const hc_ctx::SpectralLevel& lev, hipStream_t stream, bool direct, int bin_lo, int bin_hi, int col_lo, int col_hi, int x_shift,
+                        const double* Yin, double* Yout) {
     if (bin_hi <= bin_lo || col_hi <= col_lo) return;
     hc::TailGemvArgs g{};
-    g.Khat = c->d_khat.p;
-    g.Xw   = c->d_tail_xw.p;
+    g.Khat = lev.khat.p;
+    g.Xw   = lev.xw.p;
     g.Yin  = Yin;
     g.Yout = Yout;
     g.Dloc = c->Dloc;
-    g.ncols = hc::tail_partitions(c->S) * c->D;
+    g.ncols = lev.lv.NP * c->D;
     g.bin_lo = bin_lo;
     g.bin_hi = bin_hi;
     g.col_lo = col_lo;
@@ -245,10 +270,11 @@ void spec_dispatch_gemv(hc_ctx* c, hipStream_t stream, bool direct, int bin_lo, 
     c->prof.hip_launches += 1;
 }
 
-// the superblock's own tail: X-hat of the windows, the missing far chunks, the near partition, the inverse transform
-void spec_superblock_start(hc_ctx* c, hipStream_t stream, bool direct) {
+// A level's own period: X-hat of its windows, (top level) the missing far chunks, the near partition, the inverse transform
+void spec_level_start(hc_ctx* c, hc_ctx::SpectralLevel& lev, bool top, hipStream_t stream, bool direct) {
     auto& sp = c->spec;
-    const int NP = hc::tail_partitions(c->S), D = c->D;
+    const hc::TailLevel& lv = lev.lv;
+    const int NP = lv.NP, D = c->D;
     const bool dd = direct;
     hc::TailFwdArgs f{};
     f.ring_vT = c->d_ring_vT.p;
@@ -258,74 +284,91 @@ void spec_superblock_start(hc_ctx* c, hipStream_t stream, bool direct) {
     f.D       = D;
     f.S       = c->S;
     f.NP      = NP;
-    f.tw      = c->d_tail_tw.p;
-    f.Xw      = c->d_tail_xw.p;
-    c->prof.tail_bytes += 8.0 * NP * D * hc::kTailN + 16.0 * hc::kTailBins * NP * D;
+    f.tw      = lev.tw.p;
+    f.Xw      = lev.xw.p;
+    c->prof.tail_bytes += 8.0 * NP * D * lv.N + 16.0 * lv.bins * NP * D;
     c->prof.tail_launches += 1;
     if (dd) {
-        c->dq->dispatch(c->dk_tail_fwd, static_cast<uint32_t>(NP * D), hc::kTailN / 2, 0, &f, sizeof f, direct_tag(c, hc::kEvTail));
+        c->dq->dispatch(c->dk_tail_fwd[spec_n_index(lv.N)], static_cast<uint32_t>(NP * D), lv.N / 2, 0, &f, sizeof f, direct_tag(c, hc::kEvTail));
         c->prof.direct_dispatches += 1;
     } else {
         hc::EventPair* ev = ev_begin(c, hc::kEvTail, stream);
-        hc::launch_tail_fwd(f, stream);
+        HC_HIP(hc::launch_tail_fwd(f, lv.N, stream));
         ev_end(ev, stream);
         c->prof.hip_launches += 1;
     }
-    double* Y = c->d_tail_yfar.p + static_cast<size_t>(sp.cur) * 2 * hc::kTailBins * c->Dloc;
+    double* Y = lev.y.p + static_cast<size_t>(top ? sp.cur : 0) * 2 * lv.bins * c->Dloc;
     if (NP > 1) {
-        // far chunks of this superblock that its predecessor did not make: window p for partition p (x shift 0)
+        // far chunks of this period that its predecessor did not make: window p for partition p (x shift 0)
         const int nch = hc::tail_far_chunks(sp.Q);
-        if (sp.far_cur == 0) {
-            spec_dispatch_gemv(c, stream, dd, 0, hc::kTailBins, D, NP * D, hc::tail_x_shift(false, D), nullptr, Y);
+        if (!top || !hc::tail_level_far_ahead(lv) || sp.far_cur == 0) {
+            spec_dispatch_gemv(c, lev, stream, dd, 0, lv.bins, D, NP * D, hc::tail_x_shift(false, D), nullptr, Y);
         } else {
             for (int k = 0; k < nch; ++k) {
                 if (sp.far_cur & (1u << k)) continue;
                 int lo, hi;
-                hc::tail_chunk_bins(k, nch, &lo, &hi);
-                spec_dispatch_gemv(c, stream, dd, lo, hi, D, NP * D, hc::tail_x_shift(false, D), nullptr, Y);
+                hc::tail_level_chunk_bins(lv, k, nch, &lo, &hi);
+                spec_dispatch_gemv(c, lev, stream, dd, lo, hi, D, NP * D, hc::tail_x_shift(false, D), nullptr, Y);
             }
         }
     }
-    spec_dispatch_gemv(c, stream, dd, 0, hc::kTailBins, 0, D, 0, NP > 1 ? Y : nullptr, Y);  // the near partition, added last
-    hc::TailInvArgs iv{Y, c->d_tail_tw.p, c->d_tail_out.p, c->Dloc, c->Dpad};
-    c->prof.tail_bytes += 16.0 * hc::kTailBins * c->Dloc + 8.0 * hc::kTailP * c->Dloc;
+    spec_dispatch_gemv(c, lev, stream, dd, 0, lv.bins, 0, D, 0, NP > 1 ? Y : nullptr, Y);  // the near partition, added last
+    hc::TailInvArgs iv{Y, lev.tw.p, lev.out.p, c->Dloc, c->Dpad};
+    c->prof.tail_bytes += 16.0 * lv.bins * c->Dloc + 8.0 * lv.P * c->Dloc;
     c->prof.tail_launches += 1;
     if (dd) {
-        c->dq->dispatch(c->dk_tail_inv, static_cast<uint32_t>(c->Dloc), hc::kTailN / 2, 0, &iv, sizeof iv, direct_tag(c, hc::kEvTail));
+        c->dq->dispatch(c->dk_tail_inv[spec_n_index(lv.N)], static_cast<uint32_t>(c->Dloc), lv.N / 2, 0, &iv, sizeof iv, direct_tag(c, hc::kEvTail));
         c->prof.direct_dispatches += 1;
     } else {
         hc::EventPair* ev = ev_begin(c, hc::kEvTail, stream);
-        hc::launch_tail_inv(iv, stream);
+        HC_HIP(hc::launch_tail_inv(iv, lv.N, stream));
         ev_end(ev, stream);
         c->prof.hip_launches += 1;
     }
 }
 
-// Buffers and K-hat; false where they cannot be had (the full pass runs).
+// Levels, buffers and K-hat of the selected form; false where they cannot be had (the full pass runs).
 bool spec_ready(hc_ctx* c) {
-    const int NP = hc::tail_partitions(c->S);
-    const size_t ncols = static_cast<size_t>(NP) * c->D;
-    const size_t nkhat = 2 * static_cast<size_t>(hc::kTailBins) * c->Dloc * ncols;
+    auto& form = c->spec_form[spec_form_index(c)];
+    hc::TailLevel lv[hc::kTailLevelsMax];
+    const int nlev = hc::tail_levels(c->S, c->radiation_tail, lv);
+    if (nlev < 1) return false;
+    if (form.nlev != nlev || form.S != c->S) form.khat_ok = false;
+    form.nlev = nlev;
+    form.S    = c->S;
+    std::vector<hc::DeviceBuffer<double>*> fresh;  // buffers this call allocated: no kernel has seen them yet
+    auto grow = [&](hc::DeviceBuffer<double>& b, size_t n) {
+        if (b.n >= n) return false;
+        fresh.push_back(&b);
+        b.alloc(n);
+        return true;
+    };
     try {
-        if (c->d_tail_xw.n < 2 * hc::kTailBins * ncols) c->d_tail_xw.alloc(2 * hc::kTailBins * ncols);
-        if (c->d_tail_yfar.n < 4 * static_cast<size_t>(hc::kTailBins) * c->Dloc) c->d_tail_yfar.alloc(4 * static_cast<size_t>(hc::kTailBins) * c->Dloc);
-        if (c->d_tail_out.n < static_cast<size_t>(hc::kTailP) * c->Dpad) {
-            c->d_tail_out.alloc(static_cast<size_t>(hc::kTailP) * c->Dpad);
-            HC_HIP(hipMemsetAsync(c->d_tail_out.p, 0, c->d_tail_out.n * sizeof(double), c->stream));  // padding rows stay zero
-            HC_HIP(hipStreamSynchronize(c->stream));  // (the tail kernels may go to the direct queue)
-        }
-        if (c->d_khat.n < nkhat) {
-            c->d_khat.alloc(nkhat);
-            c->spec.khat_ok = false;
+        for (int l = 0; l < nlev; ++l) {
+            auto& lev = form.lev[l];
+            lev.lv = lv[l];
+            const size_t bins = static_cast<size_t>(lv[l].bins), ncols = static_cast<size_t>(lv[l].NP) * c->D;
+            grow(lev.xw, 2 * bins * ncols);
+            grow(lev.y, 4 * bins * c->Dloc);
+            if (grow(lev.out, static_cast<size_t>(lv[l].P) * c->Dpad)) {
+                HC_HIP(hipMemsetAsync(lev.out.p, 0, lev.out.n * sizeof(double), c->stream));  // padding rows stay zero
+                HC_HIP(hipStreamSynchronize(c->stream));  // (the tail kernels may go to the direct queue)
+            }
+            if (grow(lev.khat, 2 * bins * c->Dloc * ncols)) form.khat_ok = false;
         }
     } catch (const Error&) {
         (void)hipGetLastError();
+        for (auto* b : fresh) b->release();  // (what a running period may still read was there before this call and stays)
+        form.khat_ok      = false;
         c->radiation_tail = 0;  // no room for the transform of K: the full pass, as before
         return false;
     }
-    spec_twiddles(c);
-    if (!c->spec.khat_ok) spec_build_khat(c);
-    return c->spec.khat_ok;
+    for (int l = 0; l < nlev; ++l) spec_twiddles(c, form.lev[l]);
+    if (!form.khat_ok) {
+        for (int l = 0; l < nlev; ++l) spec_build_khat(c, form.lev[l]);
+        form.khat_ok = true;
+    }
+    return form.khat_ok;
 }
 
 }  // namespace
@@ -334,31 +377,32 @@ void launch_pass(hc_ctx* c, hipStream_t stream, bool with_exc, bool direct, bool
     auto& sp = c->spec;
     const auto& pl = c->plan;
     const int L = c->lookahead;
+    const int fi = spec_form_index(c);
     bool use_tail = false;
-    if (spec_goes_on && sp.active && sp.k < sp.Q && std::fabs(pl.dt - sp.dt) <= 1e-9 * sp.dt) {
+    if (spec_goes_on && sp.active && sp.form == fi && sp.k < sp.Q && std::fabs(pl.dt - sp.dt) <= 1e-9 * sp.dt) {
         const double tol = std::max(1e-9 * pl.dt, 64.0 * std::numeric_limits<double>::epsilon() * std::fabs(pl.tgrid[1]));
         use_tail = std::fabs(pl.tgrid[1] - (sp.t0 + sp.k * L * sp.dt)) <= tol;
     }
-    bool sb_start = false;
     if (!use_tail) {
-        // a new superblock: from here on if the block is eligible (else the full pass, and the next block tries again).  The far
-        // chunks made for it count only if the block continues the superblock before it.
-        const bool follows = spec_goes_on && sp.active && sp.k == sp.Q &&
+        // a new top period: from here on if the block is eligible (else the full pass, and the next block tries again).  The far
+        // chunks made for it count only if the block continues the period before it.
+        const bool follows = spec_goes_on && sp.active && sp.form == fi && sp.k == sp.Q &&
                              std::fabs(pl.tgrid[1] - (sp.t0 + sp.k * L * sp.dt)) <=
                                  std::max(1e-9 * pl.dt, 64.0 * std::numeric_limits<double>::epsilon() * std::fabs(pl.tgrid[1])) &&
                              std::fabs(pl.dt - sp.dt) <= 1e-9 * sp.dt;
         const unsigned far_made = follows ? sp.far_next : 0u;
         sp.active = false;
         if (spec_eligible(c, direct) && spec_ready(c)) {
+            sp.form     = fi;
             sp.cur      = follows ? 1 - sp.cur : sp.cur;
             sp.far_cur  = far_made;
             sp.far_next = 0;
-            sp.Q        = hc::tail_blocks_per_superblock(L);
+            sp.Q        = hc::tail_level_blocks(c->spec_form[fi].lev[0].lv, L);
             sp.k        = 0;
             sp.t0       = pl.tgrid[1];
             sp.dt       = pl.dt;
             sp.active   = true;
-            use_tail = sb_start = true;
+            use_tail = true;
         }
     }
     if (!use_tail) {
@@ -368,19 +412,28 @@ void launch_pass(hc_ctx* c, hipStream_t stream, bool with_exc, bool direct, bool
         issue_pass_reduce(c, ps, rows_P(c, false), rows_E(c, false), stream, direct);
         return;
     }
-    if (sb_start) spec_superblock_start(c, stream, direct);
-    const PassSetup ps = make_pass(c, with_exc, false, true);
+    auto& form = c->spec_form[fi];
+    const int j0 = sp.k * L;  // step offset of this block in the top period
+    TailRows rows;
+    for (int l = 0; l < form.nlev; ++l) {
+        auto& lev = form.lev[l];
+        if (hc::tail_level_starts(lev.lv, j0)) spec_level_start(c, lev, l == 0, stream, direct);  // (the top level: at j0 = 0 only)
+        rows.tail[l] = lev.out.p;
+        rows.j0[l]   = j0 % lev.lv.period;
+    }
+    const PassSetup ps = make_pass(c, with_exc, false, hc::tail_head_lags(&form.lev[form.nlev - 1].lv, 1));
     c->plan.has_exc    = ps.exc_block;
     issue_pass_chunks(c, ps, 0, ps.b.nchunks, true, stream, direct);
-    issue_pass_reduce(c, ps, rows_P(c, false), rows_E(c, false), stream, direct, 0, c->d_tail_out.p, sp.k * L);
-    // far chunk k - 1 of the NEXT superblock (blocks k >= 1): window p - 1 for partition p >= 2 (x shift -D), into the other half of Y
-    const int NP = hc::tail_partitions(c->S);
-    if (NP > 1 && sp.k >= 1) {
+    issue_pass_reduce(c, ps, rows_P(c, false), rows_E(c, false), stream, direct, 0, &rows);
+    // far chunk k - 1 of the NEXT top period (blocks k >= 1): window p - 1 for partition p >= 2 (x shift -D), into the other half of Y
+    const auto& top = form.lev[0];
+    const int NP = top.lv.NP;
+    if (hc::tail_level_far_ahead(top.lv) && sp.k >= 1) {
         const int ch = sp.k - 1, nch = hc::tail_far_chunks(sp.Q);
         int lo, hi;
-        hc::tail_chunk_bins(ch, nch, &lo, &hi);
-        spec_dispatch_gemv(c, stream, direct, lo, hi, c->D, NP * c->D, hc::tail_x_shift(true, c->D), nullptr,
-                           c->d_tail_yfar.p + static_cast<size_t>(1 - sp.cur) * 2 * hc::kTailBins * c->Dloc);
+        hc::tail_level_chunk_bins(top.lv, ch, nch, &lo, &hi);
+        spec_dispatch_gemv(c, top, stream, direct, lo, hi, c->D, NP * c->D, hc::tail_x_shift(true, c->D), nullptr,
+                           top.y.p + static_cast<size_t>(1 - sp.cur) * 2 * top.lv.bins * c->Dloc);
         sp.far_next |= 1u << ch;
     }
     sp.k += 1;

@@ -406,13 +406,13 @@ void choose_conv_config(hc_ctx* c) {
     bgps                = std::max<long long>(16, ((bgps + 15) / 16) * 16);  // whole 16-group sub-tiles
     c->chunk_gp_block   = static_cast<int>(bgps);
     c->nchunks_block    = static_cast<int>((c->ngp + bgps - 1) / bgps);
-    // The head pass of the spectral tail (hc_pass.cpp: the IRF samples below kTailP only) keeps the round of workgroups of the full pass:
-    // as many chunks over a fraction of the columns (a function of the column count only, like every chunk length).
-    {
-        const long long ngp_head = (static_cast<long long>(hc::kTailP) * c->D + 7) / 8;
+    // The head pass of the spectral tail (hc_pass.cpp: the IRF samples below 256, in the levelled form below 128, only) keeps the round of
+    // workgroups of the full pass: as many chunks over a fraction of the columns (a function of the column count only, like every chunk length).
+    for (int head_lags : {hc::kTailP, hc::kTailP / 2}) {
+        const long long ngp_head = (static_cast<long long>(head_lags) * c->D + 7) / 8;
         const long long nch      = std::max<long long>(1, c->nchunks_block);
         long long hg             = std::min<long long>((ngp_head + nch - 1) / nch, bgps);
-        c->chunk_gp_head         = static_cast<int>(std::max<long long>(16, ((hg + 15) / 16) * 16));
+        (head_lags == hc::kTailP ? c->chunk_gp_head : c->chunk_gp_head128) = static_cast<int>(std::max<long long>(16, ((hg + 15) / 16) * 16));
     }
 }
 
@@ -738,12 +738,22 @@ void setup_direct(hc_ctx* c) {
     c->step_hot = c->slot_state && c->dk_step_hot[0].ok() && c->dk_step_hot[1].ok() && HC_TUNE_INT("HC_STEP_HOT", 1) != 0;
     c->step_halves = HC_TUNE_INT("HC_STEP_HALVES", 1) == 2 ? 2 : 1;
     c->dk_reduce   = q->find("reduce_block_kernelE");
-    c->dk_tail_fwd  = q->find("tail_fft_fwdENS_11TailFwdArgsE");  // optional: without them the tail goes through HIP launches
+    // optional: without them the tail goes through HIP launches.  The transforms by size (hc_tail.hpp: the levels' N).
     c->dk_tail_gemv = q->find("tail_gemvENS_12TailGemvArgsE");
-    c->dk_tail_inv  = q->find("tail_fft_invENS_11TailInvArgsE");
-    if (c->dk_tail_fwd.kernarg != sizeof(hc::TailFwdArgs) || c->dk_tail_gemv.kernarg != sizeof(hc::TailGemvArgs) ||
-        c->dk_tail_inv.kernarg != sizeof(hc::TailInvArgs) || c->dk_tail_fwd.priv || c->dk_tail_gemv.priv || c->dk_tail_inv.priv)
-        c->dk_tail_fwd = c->dk_tail_gemv = c->dk_tail_inv = hc::DirectKernel{};
+    bool tail_ok    = c->dk_tail_gemv.kernarg == sizeof(hc::TailGemvArgs) && !c->dk_tail_gemv.priv;
+    for (int i = 0; i < 3; ++i) {
+        char frag[64];
+        std::snprintf(frag, sizeof frag, "tail_fft_fwdILi%dEEEvNS_11TailFwdArgsE", 256 << i);
+        c->dk_tail_fwd[i] = q->find(frag);
+        std::snprintf(frag, sizeof frag, "tail_fft_invILi%dEEEvNS_11TailInvArgsE", 256 << i);
+        c->dk_tail_inv[i] = q->find(frag);
+        tail_ok = tail_ok && c->dk_tail_fwd[i].kernarg == sizeof(hc::TailFwdArgs) && c->dk_tail_inv[i].kernarg == sizeof(hc::TailInvArgs) && !c->dk_tail_fwd[i].priv &&
+                  !c->dk_tail_inv[i].priv;
+    }
+    if (!tail_ok) {
+        c->dk_tail_gemv = hc::DirectKernel{};
+        for (int i = 0; i < 3; ++i) c->dk_tail_fwd[i] = c->dk_tail_inv[i] = hc::DirectKernel{};
+    }
     c->dk_added_mass = q->find("added_mass_mv_tagged_kernelE");  // optional: hc_added_mass_mv falls back to a HIP launch
     {   // the plain per-step convolution of this context's tiling; optional: without it plain steps go through HIP launches
         hc::StepArgs a{};

@@ -65,24 +65,23 @@ Spectrum build_spectrum(const hc_ctx* c, const hc_irregular_wave_params& p) {
 
 namespace hc {
 namespace detail {
-// K-hat of the spectral radiation tail (hc_tail.hpp): the transform of w_s K_s, one partition of kTailP lags at a time, of the panel the
-// pass reads (K, or the tapered K of TaperedDirect).  Made on first use and after any change of K, the taper or the mode; a few
-// milliseconds for C3 (442k transforms of 512 points, 1.8 GB written).
-void spec_build_khat(hc_ctx* c) {
+// K-hat of one level of the spectral radiation tail (hc_tail.hpp): the transform of w_s K_s, one partition of P lags at a time, of the
+// panel the pass reads (K, or the tapered K of TaperedDirect).  Made on first use and after any change of K, the taper or the mode; a
+// few milliseconds for C3 (per level 147k transforms of its partition: 2.1 GB written over the three levels).
+void spec_build_khat(hc_ctx* c, hc_ctx::SpectralLevel& lev) {
     hc::TailKhatArgs a{};
     a.K     = rad_panel(c);
     a.width = c->d_width.p;
-    a.tw    = c->d_tail_tw.p;
-    a.Khat  = c->d_khat.p;
+    a.tw    = lev.tw.p;
+    a.Khat  = lev.khat.p;
     a.Dloc  = c->Dloc;
     a.D     = c->D;
     a.S     = c->S;
-    a.NP    = hc::tail_partitions(c->S);
+    a.NP    = lev.lv.NP;
     HC_HIP(hipStreamSynchronize(c->stream));
-    hc::launch_tail_khat(a, c->stream);
+    HC_HIP(hc::launch_tail_khat(a, lev.lv.N, c->stream));
     HC_HIP(hipGetLastError());
     HC_HIP(hipStreamSynchronize(c->stream));
-    c->spec.khat_ok = true;
 }
 }  // namespace detail
 }  // namespace hc

@@ -1444,7 +1444,24 @@ int hc_tuning_time_pass(hc_ctx* c, int depth, int reps, double* mean_us, double*
 
 int hc_set_radiation_tail(hc_ctx* c, int mode) {
     HC_API_BEGIN(c)
-    require(mode == 0 || mode == 1, HC_ERR_INVALID, "mode must be 0 (full pass) or 1 (spectral tail where eligible)");
+    require(mode == 0 || mode == 1 || mode == 2, HC_ERR_INVALID, "mode must be 0 (full pass), 1 (spectral tail in levels where eligible) or 2 (uniform spectral tail)");
+    if (mode != c->radiation_tail && mode != 0) {
+        // the form that is not selected gives its K-hat and buffers back (at C3 about 2 GB), once nothing on the GPU can still read them
+        auto& other = c->spec_form[mode == hc::kTailFormUniform ? 0 : 1];
+        if (other.nlev > 0) {
+            quiesce_direct(c);
+            HC_HIP(hipDeviceSynchronize());
+            for (auto& lev : other.lev) {
+                lev.khat.release();
+                lev.xw.release();
+                lev.y.release();
+                lev.out.release();
+                lev.tw.release();
+            }
+            other.nlev    = 0;
+            other.khat_ok = false;
+        }
+    }
     c->radiation_tail = mode;
     c->spec.active    = false;
     HC_API_END(c)

@@ -51,6 +51,70 @@ inline int tail_col(int p, int col, int D) { return (p - 1) * D + col; }
 // shift from a K-hat column to the X-hat column it meets: 0 for this superblock (x_p = window p), -D for the next one (x_p = window p - 1)
 inline int tail_x_shift(bool next_superblock, int D) { return next_superblock ? -D : 0; }
 
+// ---- levels (Gardner's non-uniform partitioning, cut off at 128 lags) -------------------------------------------------------------
+// A uniform scheme streams every partition's K-hat once per P steps: 2 P / P = 2 "units" of K per step and partition, whatever P is,
+// so lags are cheapest in the LARGEST partition whose input is known in time.  A level is the uniform scheme above with its own
+// partition length P: transform size N = 2P, bins = P + 1, a period of P steps, NP partitions p = 1 .. NP over the lags
+// [pP, (p+1)P), i.e. the lags [lag_lo, lag_hi) = [P, min(S, (NP + 1) P)).  A level whose lags stop at 2P (NP = 1) leaves the lags
+// from 2P on to the level above it.  The levelled form of a window of S lags:
+//     S >= 1024:        P = 512 with NP = ceil(S / 512) - 1 (lags 512 .. S - 1),  P = 256 (lags 256 .. 511),  P = 128 (lags 128 .. 255)
+//     512 <= S < 1024:  P = 256 with NP = tail_partitions(S) (lags 256 .. S - 1, the uniform scheme as it is),  P = 128 (lags 128 .. 255)
+// and the head pass keeps the lags below 128 (below that a direct pass streams no more than a transform: P / lookahead <= 2 units at
+// P = 64).  The uniform form is the single level P = 256 with all its partitions, head pass below 256.
+// All periods start together at the start of the largest one: at step offset j of the top period the level P starts a period iff
+// j % P == 0.  Windows, the zero rule, K-hat / X-hat columns and far chunks are those above with the level's P for kTailP.
+struct TailLevel {
+    int P, N, bins;  // lags per partition, transform size 2P, bins P + 1 of a real transform
+    int lag_lo;      // first lag of the level (= P)
+    int NP;          // partitions
+    int period;      // steps between two period starts (= P)
+    int lag_hi;      // one past the last lag: min(S, (NP + 1) P)
+};
+constexpr int kTailLevelsMax = 3;
+constexpr int kTailFormLevelled = 1, kTailFormUniform = 2;  // hc_set_radiation_tail
+
+inline TailLevel tail_make_level(int P, int NP, int S) { return TailLevel{P, 2 * P, P + 1, P, NP, P, std::min(S, (NP + 1) * P)}; }
+
+// The levels of a form, largest P first; returns their number (0: no tail, the full pass).
+inline int tail_levels(int S, int form, TailLevel* lv) {
+    if (tail_partitions(S) < 1) return 0;
+    if (form == kTailFormUniform) {
+        lv[0] = tail_make_level(kTailP, tail_partitions(S), S);
+        return 1;
+    }
+    if (S >= 4 * kTailP) {
+        lv[0] = tail_make_level(2 * kTailP, (S + 2 * kTailP - 1) / (2 * kTailP) - 1, S);
+        lv[1] = tail_make_level(kTailP, 1, S);
+        lv[2] = tail_make_level(kTailP / 2, 1, S);
+        return 3;
+    }
+    lv[0] = tail_make_level(kTailP, tail_partitions(S), S);
+    lv[1] = tail_make_level(kTailP / 2, 1, S);
+    return 2;
+}
+// lags the head pass keeps: those below the smallest level
+inline int tail_head_lags(const TailLevel* lv, int n) { return n > 0 ? lv[n - 1].lag_lo : 0; }
+
+// Are the far partitions (p >= 2) of a level made during the period BEFORE the one they serve, a chunk of bins beside each of its
+// blocks (tail_far_chunks)?  Only at P = kTailP.  Far chunks keep the samples of the previous period's windows for two periods, so a
+// sample that has left the IRF window can still meet (zero-padded) taps up to 2P steps later -- rounding noise where the sum is
+// exactly zero; at P = 512 that is past the S - 1 + 2 kTailP + 2 L steps after which the radiation of a body at rest is held to be
+// exactly zero.  The far partitions of the P = 512 level are therefore made at its period start, from that period's own windows:
+// the same bytes per step, in front of one step in 512 instead of spread over the blocks.
+inline bool tail_level_far_ahead(const TailLevel& lv) { return lv.NP > 1 && lv.P <= kTailP; }
+
+inline int tail_level_blocks(const TailLevel& lv, int lookahead) { return lookahead > 0 ? lv.P / lookahead : 0; }
+inline bool tail_level_starts(const TailLevel& lv, int j) { return j % lv.period == 0; }  // j: step offset in the top period
+inline void tail_level_chunk_bins(const TailLevel& lv, int k, int nchunks, int* lo, int* hi) {
+    *lo = static_cast<int>(static_cast<long long>(k) * lv.bins / nchunks);
+    *hi = static_cast<int>(static_cast<long long>(k + 1) * lv.bins / nchunks);
+}
+inline int tail_level_window_back(const TailLevel& lv, int a, int k) { return (a + 1) * lv.P - 1 - k; }
+inline bool tail_level_window_live(const TailLevel& lv, int S, int a, int k) { return k >= 1 && tail_level_window_back(lv, a, k) <= S - 2; }
+// lag of tap r of partition p, and whether K-hat holds it (the others are zero padding)
+inline int tail_level_lag(const TailLevel& lv, int p, int r) { return p * lv.P + r; }
+inline bool tail_level_tap_live(const TailLevel& lv, int S, int p, int r) { return r < lv.P && p >= 1 && p <= lv.NP && tail_level_lag(lv, p, r) < S; }
+
 // May the blocks of a superblock that starts at the block just planned take their lags s >= P from the tail?  The history is the
 // uniform grid of the step (times[k] = times[0] - k dt, k < S: the samples the windows read), the IRF grid is that grid too (tau_s = s dt), and the history
 // reaches past the oldest query of the block (every IRF sample has an older history sample, as far_pass_allowed asks).

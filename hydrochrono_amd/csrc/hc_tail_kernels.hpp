@@ -1,7 +1,8 @@
 // hc_tail_kernels.hpp -- the kernels of the spectral radiation tail (hc_tail.hpp), included into hc_kernels.hip so that the
-// stand-alone code object of the direct dispatch carries them.  All FP64; one transform of size kTailN per workgroup, radix-2 in LDS
-// with a twiddle table made on the host; every sum in a fixed order that depends on neither the row range nor the launch geometry,
-// so that row shards stay bitwise equal to the unsharded context.
+// stand-alone code object of the direct dispatch carries them.  All FP64; one transform of size N per workgroup (N = 2P of the level,
+// hc_tail.hpp: TailLevel; instantiated for 256, 512 and 1024), radix-2 in LDS with a twiddle table made on the host per N; every sum
+// in a fixed order that depends on neither the row range nor the launch geometry, so that row shards stay bitwise equal to the
+// unsharded context.
 //   tail_khat_kernel   (init) Khat[bin][row][(p-1)D + col] = FFT_N(w_s K[row, s, col], s in partition p, zero-padded)
 //   tail_fft_fwd       (superblock start) Xw[bin][(a-1)D + col] = FFT_N(window a of DoF col, from ring_vT)
 //   tail_gemv          Y[bin][row] = Yin[bin][row] + sum_c Khat[bin][row][c] Xw[bin][c + x_shift]  over a range of bins and columns
@@ -10,20 +11,20 @@
 
 namespace hc {
 
-static constexpr int kTailThreads = 256;  // = kTailN / 2: one butterfly per work item and stage
-
-// In-place radix-2 transform of the kTailN points (re, im) in LDS, input in bit-reversed order.  tw[k] = exp(-2 pi i k / N) as
+// N / 2 work items per transform: one butterfly per work item and stage.
+// In-place radix-2 transform of the N points (re, im) in LDS, input in bit-reversed order.  tw[k] = exp(-2 pi i k / N) as
 // (cos, sin) pairs; inverse: the conjugate twiddles.  Ends with a barrier.
+template <int N>
 __device__ __forceinline__ void tail_fft_lds(double* __restrict__ re, double* __restrict__ im, const double* __restrict__ tw, bool inverse) {
     const int t = threadIdx.x;
     __syncthreads();
 #pragma unroll 1
-    for (int len = 2; len <= kTailN; len <<= 1) {
+    for (int len = 2; len <= N; len <<= 1) {
         const int half = len >> 1;
         const int pos  = t & (half - 1);
         const int i    = (t - pos) * 2 + pos;
         const int j    = i + half;
-        const int k    = pos * (kTailN / len);
+        const int k    = pos * (N / len);
         const double wr = tw[2 * k], wi = inverse ? -tw[2 * k + 1] : tw[2 * k + 1];
         const double br = re[j], bi = im[j];
         const double pr = wr * br - wi * bi, pi = wr * bi + wi * br;
@@ -36,29 +37,35 @@ __device__ __forceinline__ void tail_fft_lds(double* __restrict__ re, double* __
     }
 }
 
-__device__ __forceinline__ int tail_bitrev(int k) { return static_cast<int>(__brev(static_cast<unsigned>(k)) >> (32 - 9)); }
-static_assert(kTailN == 512, "tail_bitrev assumes a transform of 2^9 points");
+constexpr int tail_log2(int n) { return n <= 1 ? 0 : 1 + tail_log2(n >> 1); }
+template <int N>
+__device__ __forceinline__ int tail_bitrev(int k) {
+    static_assert(N >= 4 && (N & (N - 1)) == 0, "a transform of 2^b points");
+    return static_cast<int>(__brev(static_cast<unsigned>(k)) >> (32 - tail_log2(N)));
+}
 
 
-__global__ void __launch_bounds__(kTailThreads) tail_khat_kernel(TailKhatArgs a) {
-    __shared__ double re[kTailN], im[kTailN];
+template <int N>
+__global__ void __launch_bounds__(N / 2) tail_khat_kernel(TailKhatArgs a) {
+    constexpr int P = N / 2, kBins = P + 1, kThreads = N / 2;
+    __shared__ double re[N], im[N];
     const int t   = threadIdx.x;
     const int col = blockIdx.x % a.D;
     const int rp  = blockIdx.x / a.D;
     const int p   = rp % a.NP + 1;
     const int row = rp / a.NP;
-    for (int k = t; k < kTailN; k += kTailThreads) {
-        const int s = p * kTailP + k;
+    for (int k = t; k < N; k += kThreads) {
+        const int s = p * P + k;
         double g = 0.0;
-        if (k < kTailP && s < a.S) g = a.width[s] * a.K.base[panel_offset(a.K.ngp, row, s * a.D + col)];
-        const int kr = tail_bitrev(k);
+        if (k < P && s < a.S) g = a.width[s] * a.K.base[panel_offset(a.K.ngp, row, s * a.D + col)];
+        const int kr = tail_bitrev<N>(k);
         re[kr] = g;
         im[kr] = 0.0;
     }
-    tail_fft_lds(re, im, a.tw, false);
+    tail_fft_lds<N>(re, im, a.tw, false);
     const size_t ncols = static_cast<size_t>(a.NP) * a.D;
     const size_t c     = static_cast<size_t>(p - 1) * a.D + col;
-    for (int b = t; b < kTailBins; b += kTailThreads) {
+    for (int b = t; b < kBins; b += kThreads) {
         double* dst = a.Khat + 2 * ((static_cast<size_t>(b) * a.Dloc + row) * ncols + c);
         dst[0] = re[b];
         dst[1] = im[b];
@@ -66,28 +73,30 @@ __global__ void __launch_bounds__(kTailThreads) tail_khat_kernel(TailKhatArgs a)
 }
 
 
-__global__ void __launch_bounds__(kTailThreads) tail_fft_fwd(TailFwdArgs a) {
-    __shared__ double re[kTailN], im[kTailN];
+template <int N>
+__global__ void __launch_bounds__(N / 2) tail_fft_fwd(TailFwdArgs a) {
+    constexpr int P = N / 2, kBins = P + 1, kThreads = N / 2;
+    __shared__ double re[N], im[N];
     const int t   = threadIdx.x;
     const int col = blockIdx.x % a.D;
     const int w   = blockIdx.x / a.D + 1;  // window 1 .. NP
     const double* __restrict__ series = a.ring_vT + static_cast<size_t>(col) * a.HcapT;
-    for (int k = t; k < kTailN; k += kTailThreads) {
-        const int back = (w + 1) * kTailP - 1 - k;  // hc_tail.hpp: tail_window_back / tail_window_live
+    for (int k = t; k < N; k += kThreads) {
+        const int back = (w + 1) * P - 1 - k;  // hc_tail.hpp: tail_window_back / tail_window_live
         double x = 0.0;
         if (k >= 1 && back <= a.S - 2) {
             int slot = (a.head - back) % a.Hcap;
             if (slot < 0) slot += a.Hcap;
             x = series[slot];
         }
-        const int kr = tail_bitrev(k);
+        const int kr = tail_bitrev<N>(k);
         re[kr] = x;
         im[kr] = 0.0;
     }
-    tail_fft_lds(re, im, a.tw, false);
+    tail_fft_lds<N>(re, im, a.tw, false);
     const size_t ncols = static_cast<size_t>(a.NP) * a.D;
     const size_t c     = static_cast<size_t>(w - 1) * a.D + col;
-    for (int b = t; b < kTailBins; b += kTailThreads) {
+    for (int b = t; b < kBins; b += kThreads) {
         double* dst = a.Xw + 2 * (static_cast<size_t>(b) * ncols + c);
         dst[0] = re[b];
         dst[1] = im[b];
@@ -167,39 +176,63 @@ __global__ void __launch_bounds__(256) tail_gemv(TailGemvArgs a) {
     }
 }
 
-__global__ void __launch_bounds__(kTailThreads) tail_fft_inv(TailInvArgs a) {
-    __shared__ double re[kTailN], im[kTailN];
+template <int N>
+__global__ void __launch_bounds__(N / 2) tail_fft_inv(TailInvArgs a) {
+    constexpr int P = N / 2, kThreads = N / 2;
+    __shared__ double re[N], im[N];
     const int t   = threadIdx.x;
     const int row = blockIdx.x;
-    for (int k = t; k < kTailN; k += kTailThreads) {
+    for (int k = t; k < N; k += kThreads) {
         // the Hermitian extension of bins 0 .. P; bins 0 and P of a real signal's transform are real
-        const int b = k <= kTailP ? k : kTailN - k;
+        const int b = k <= P ? k : N - k;
         const double* y = a.Y + 2 * (static_cast<size_t>(b) * a.Dloc + row);
         const double yr = y[0];
-        double yi       = (b == 0 || b == kTailP) ? 0.0 : y[1];
-        if (k > kTailP) yi = -yi;
-        const int kr = tail_bitrev(k);
+        double yi       = (b == 0 || b == P) ? 0.0 : y[1];
+        if (k > P) yi = -yi;
+        const int kr = tail_bitrev<N>(k);
         re[kr] = yr;
         im[kr] = yi;
     }
-    tail_fft_lds(re, im, a.tw, true);
-    for (int j = t; j < kTailP; j += kTailThreads) a.tail[static_cast<size_t>(j) * a.Dpad + row] = re[kTailP + j] * (1.0 / kTailN);
+    tail_fft_lds<N>(re, im, a.tw, true);
+    for (int j = t; j < P; j += kThreads) a.tail[static_cast<size_t>(j) * a.Dpad + row] = re[P + j] * (1.0 / N);
 }
 
 int tail_gemv_lds_bytes(const TailGemvArgs& g) { return 16 * (g.col_hi - g.col_lo); }
 int tail_gemv_grid(const TailGemvArgs& g) { return (g.bin_hi - g.bin_lo) * ((g.Dloc + g.rows_per_wg - 1) / g.rows_per_wg); }
 
-void launch_tail_khat(const TailKhatArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(tail_khat_kernel, dim3(static_cast<unsigned>(a.Dloc) * a.NP * a.D), dim3(kTailThreads), 0, s, a);
+// The transform sizes of the levels (hc_tail.hpp: tail_levels); the direct dispatch finds these instantiations by name.
+template __global__ void tail_khat_kernel<256>(TailKhatArgs);
+template __global__ void tail_khat_kernel<512>(TailKhatArgs);
+template __global__ void tail_khat_kernel<1024>(TailKhatArgs);
+template __global__ void tail_fft_fwd<256>(TailFwdArgs);
+template __global__ void tail_fft_fwd<512>(TailFwdArgs);
+template __global__ void tail_fft_fwd<1024>(TailFwdArgs);
+template __global__ void tail_fft_inv<256>(TailInvArgs);
+template __global__ void tail_fft_inv<512>(TailInvArgs);
+template __global__ void tail_fft_inv<1024>(TailInvArgs);
+
+// (an N no level has: hipErrorInvalidValue, which the callers' HC_HIP turns into the library's error)
+#define HC_TAIL_BY_N(n, call)                                 \
+    switch (n) {                                              \
+        case 256: { constexpr int kN = 256; call; break; }    \
+        case 512: { constexpr int kN = 512; call; break; }    \
+        case 1024: { constexpr int kN = 1024; call; break; }  \
+        default: return hipErrorInvalidValue;                 \
+    }                                                         \
+    return hipSuccess;
+
+hipError_t launch_tail_khat(const TailKhatArgs& a, int N, hipStream_t s) {
+    HC_TAIL_BY_N(N, hipLaunchKernelGGL(tail_khat_kernel<kN>, dim3(static_cast<unsigned>(a.Dloc) * a.NP * a.D), dim3(kN / 2), 0, s, a))
 }
-void launch_tail_fwd(const TailFwdArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(tail_fft_fwd, dim3(static_cast<unsigned>(a.NP) * a.D), dim3(kTailThreads), 0, s, a);
+hipError_t launch_tail_fwd(const TailFwdArgs& a, int N, hipStream_t s) {
+    HC_TAIL_BY_N(N, hipLaunchKernelGGL(tail_fft_fwd<kN>, dim3(static_cast<unsigned>(a.NP) * a.D), dim3(kN / 2), 0, s, a))
 }
 void launch_tail_gemv(const TailGemvArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(tail_gemv, dim3(static_cast<unsigned>(tail_gemv_grid(a))), dim3(256), static_cast<unsigned>(tail_gemv_lds_bytes(a)), s, a);
 }
-void launch_tail_inv(const TailInvArgs& a, hipStream_t s) {
-    hipLaunchKernelGGL(tail_fft_inv, dim3(static_cast<unsigned>(a.Dloc)), dim3(kTailThreads), 0, s, a);
+hipError_t launch_tail_inv(const TailInvArgs& a, int N, hipStream_t s) {
+    HC_TAIL_BY_N(N, hipLaunchKernelGGL(tail_fft_inv<kN>, dim3(static_cast<unsigned>(a.Dloc)), dim3(kN / 2), 0, s, a))
 }
+#undef HC_TAIL_BY_N
 
 }  // namespace hc

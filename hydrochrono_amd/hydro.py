@@ -321,8 +321,9 @@ class HydroForces:
         self._chk(self.lib.hc_set_pass_schedule(self.ctx, mode, int(slices)))
 
     def set_radiation_tail(self, mode):
-        """hc_set_radiation_tail: 1 (default) = lags from 256 on by partitioned FFT convolution where eligible (step = IRF spacing,
-        full history, pass at block start, 6N < 1024, S >= 512); 0 = the full pass always."""
+        """hc_set_radiation_tail: 1 (default) = lags from 128 on by partitioned FFT convolution in levels of doubling partition length
+        where eligible (step = IRF spacing, full history, pass at block start, 6N < 1024, S >= 512); 2 = the uniform form (lags from
+        256 on, partitions of 256); 0 = the full pass always."""
         self._chk(self.lib.hc_set_radiation_tail(self.ctx, int(mode)))
 
     def schedule(self):

@@ -319,13 +319,19 @@ int hc_set_lookahead(hc_ctx* ctx, int steps);
  * REPRODUCIBILITY: with the schedule pinned (0 or 1) a run is bitwise repeatable whatever the caller's timing; under the adaptive
  * default it is repeatable to rounding ("Reproducibility"). */
 int hc_set_pass_schedule(hc_ctx* ctx, int one_block_ahead, int slices);
-/* Spectral radiation tail.  mode 1 (the default): where the step equals the IRF spacing, the history covers the IRF window on that
- * grid, the look-ahead depth is 16 or 32 and the pass of a block runs at block start, the lags from 256 on (IRF samples s >= 256) of the
- * pass come from a partitioned FFT convolution made once per 256 steps (a superblock), and the pass itself streams the first 256
- * samples of K only.  Systems with 6N >= 1024 and IRFs of fewer than 512 samples keep the full pass.  The transform of K it needs
- * (complex FP64, 2 x (S - 256) x 6N x 6N_loc x 8 bytes) is made at the first superblock and again after any change of K, the
- * taper or the convolution mode.  Results are those of mode 0 up to rounding.  mode 0: the full pass always.  Part of the
- * configuration: the row shards of one array must use the same mode. */
+/* Spectral radiation tail.  Where the step equals the IRF spacing, the history covers the IRF window on that grid, the look-ahead
+ * depth is 16 or 32 and the pass of a block runs at block start, the older lags of the pass come from partitioned FFT convolutions
+ * and the pass itself streams the first IRF samples of K only.  Systems with 6N >= 1024 and IRFs of fewer than 512 samples keep
+ * the full pass.
+ *   mode 1 (the default), in levels of doubling partition length: the lags 128 .. 255 once per 128 steps, 256 .. 511 once per 256
+ *          steps and, for IRFs of 1024 samples and more, the lags from 512 on once per 512 steps (shorter IRFs: the lags from 256 on
+ *          once per 256 steps); the pass streams the first 128 samples.  Fewest bytes per step; a step that starts a 512-step period
+ *          waits for all levels' transforms of K to be streamed once.
+ *   mode 2, uniform: the lags from 256 on once per 256 steps (a superblock), the pass streams the first 256 samples.
+ *   mode 0: the full pass always.
+ * The transform of K a mode needs (complex FP64, about 2 x S x 6N x 6N_loc x 8 bytes) is made at its first use and again after any
+ * change of K, the taper or the convolution mode.  Results are those of mode 0 up to rounding.  Part of the configuration: the row
+ * shards of one array must use the same mode. */
 int hc_set_radiation_tail(hc_ctx* ctx, int mode);
 /* What is in force: the look-ahead depth (0, 16 or 32: hc_set_lookahead clamps what it is given to what this build of the library
  * holds), the pass schedule (-1 adaptive, 0 at block start, 1 one block ahead), under the adaptive schedule the rule's current answer
@@ -417,8 +423,8 @@ typedef struct hc_profile_stats {
     long long hot_steps;           /* of slot_state_steps: block steps that went to the step kernel of the common case (step_hot_kernel: the
                                     * step's own IRF samples against its own velocity only, no plain partials, no spectral wave mode) */
     /* spectral radiation tail (hc_set_radiation_tail): launches of its kernels (forward transforms, frequency-domain products,
-     * inverse transforms), their GPU time where it was measured, the bytes they move, and the look-ahead blocks whose lags from
-     * 256 on came from it.  block_kernel_* above then count the head pass (lags below 256) alone. */
+     * inverse transforms of every level), their GPU time where it was measured, the bytes they move, and the look-ahead blocks whose
+     * older lags came from it.  block_kernel_* above then count the head pass (lags below 128, mode 2: below 256) alone. */
     long long tail_launches;
     double tail_seconds;
     double tail_bytes;
