@@ -196,6 +196,14 @@ SIGNATURES = {
     "hc_drift_begin": (C.c_int, [C.c_void_p, C.c_double, c_double_p]),
     "hc_drift_end": (C.c_int, [C.c_void_p, c_double_p]),
     "hc_compute_drift": (C.c_int, [C.c_void_p, C.c_double, c_double_p, c_double_p]),
+    "hc_set_sum_qtf": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p]),
+    "hc_get_sum_qtf_size": (C.c_int, [C.c_void_p, C.c_int, c_int_p]),
+    "hc_set_sum_mode": (C.c_int, [C.c_void_p, C.c_int]),
+    "hc_get_sum_mode": (C.c_int, [C.c_void_p, c_int_p]),
+    "hc_set_sum_options": (C.c_int, [C.c_void_p, C.POINTER(WaveKinematicsOpts)]),
+    "hc_sum_qtf_begin": (C.c_int, [C.c_void_p, C.c_double, c_double_p]),
+    "hc_sum_qtf_end": (C.c_int, [C.c_void_p, c_double_p]),
+    "hc_compute_sum_qtf": (C.c_int, [C.c_void_p, C.c_double, c_double_p, c_double_p]),
     "hc_wave_kinematics2_opts_default": (None, [C.POINTER(WaveKinematics2Opts)]),
     "hc_wave_kinematics2": (C.c_int, [C.c_void_p, C.POINTER(WaveKinematics2Opts), C.c_int, c_double_p, C.c_int, c_double_p,
                                       c_double_p, c_double_p, c_double_p]),

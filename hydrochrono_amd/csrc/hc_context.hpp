@@ -476,4 +476,23 @@ struct hc_ctx {
     size_t events_used = 0;
     bool sample_this_step = false;
     hc_profile_stats prof{};
+
+    // Sum-frequency wave forces (hc_set_sum_qtf, hc_sumfreq.hip): as the drift term, with tables, bin map, stream, component table and
+    // pinned staging of its own (a table of one kind may change while a launch of the other is in flight), nothing a step uses.
+    // Kept at the end of the context: no other member moves.
+    std::vector<hc::DriftTable> sum_tabs;  // [N]: T_s(Omega_m, Omega_n) on a grid of its own
+    int sum_mode = 0;                      // 0 off, 1 on
+    double sum_phase_opt = 0.0;            // regular_phase of hc_set_sum_options
+    hipStream_t stream_sum = nullptr;      // created by the first hc_set_sum_qtf
+    bool sum_dirty = false;                // a table has changed since the device copy was made
+    int sum_pending = 0;                   // hc_sum_qtf_begin without its end: 1 zeros (nothing launched), 2 a launch is in flight
+    unsigned long long sum_serial = ~0ULL;
+    double sum_phase = 0.0;
+    int sum_nf = 0;
+    std::vector<double> sum_omega;         // [nf] of the component table in force
+    std::vector<int> sum_slot_body;        // local body of every launched slot (owned bodies with a table, ascending)
+    hc::DeviceBuffer<double> d_sum_tab, d_sum_pq, d_sum_w, d_sum_pos, d_sum_out;
+    hc::DeviceBuffer<long long> d_sum_desc;
+    hc::DeviceBuffer<int> d_sum_rowptr, d_sum_idx;
+    hc::PinnedBuffer<double> h_sum_pos, h_sum_out;
 };

@@ -192,7 +192,8 @@ class HydroForces:
              for x in (pos, rpy, linvel, angvel)]
         out = np.empty(self.D_local)
         morison, nonlinear, drift = self.__dict__.get("_morison_any"), self._nonlinear_on(), self._drift_on()
-        if morison or nonlinear or drift:
+        sumf = self._sum_on()
+        if morison or nonlinear or drift or sumf:
             # the side terms run on streams of their own beside the step; the composition is made here (the C ABI total stays the
             # reference's): begin all, step, end all
             if nonlinear:
@@ -211,6 +212,16 @@ class HydroForces:
                     if morison:
                         self.lib.hc_morison_end(self.ctx, _dp(np.empty(self.D_local)))
                     self._chk(rc_begin)
+            if sumf:
+                rc_begin = self.lib.hc_sum_qtf_begin(self.ctx, t, _dp(a[0]))
+                if rc_begin:
+                    if nonlinear:
+                        self.lib.hc_nonlinear_end(self.ctx, None, None, None)
+                    if morison:
+                        self.lib.hc_morison_end(self.ctx, _dp(np.empty(self.D_local)))
+                    if drift:
+                        self.lib.hc_drift_end(self.ctx, _dp(np.empty(self.D_local)))
+                    self._chk(rc_begin)
             rc = capi.step_raw(self.lib)(self.ctx, t, a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, a[3].ctypes.data, out.ctypes.data)
             rc_end = 0
             if nonlinear:
@@ -222,6 +233,9 @@ class HydroForces:
             if drift:
                 dr = np.empty(self.D_local)
                 rc_end = self.lib.hc_drift_end(self.ctx, _dp(dr)) or rc_end
+            if sumf:
+                sm = np.empty(self.D_local)
+                rc_end = self.lib.hc_sum_qtf_end(self.ctx, _dp(sm)) or rc_end
             self._chk(rc or rc_end)
             if nonlinear:
                 self._nonlinear_last = nl
@@ -232,6 +246,9 @@ class HydroForces:
             if drift:
                 self._drift_last = dr
                 out = out + dr
+            if sumf:
+                self._sum_last = sm
+                out = out + sm
             return out
         # raw addresses through a c_void_p prototype: this call sits in per-step loops
         rc = capi.step_raw(self.lib)(self.ctx, t, a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, a[3].ctypes.data, out.ctypes.data)
@@ -741,6 +758,65 @@ class HydroForces:
         m = self.__dict__.get("_drift_last")
         return np.zeros(self.D_local) if m is None or not self._drift_on() else m.copy()
 
+    # -- second-order wave forces from sum-frequency QTF tables (an extension beyond the reference) --
+    def set_sum_qtf(self, b, omega, P, Q=None):
+        """Replaces the sum-frequency QTF table of body b (0-based): omega [nq] rad/s, a grid of its own, strictly increasing,
+        2 <= nq <= 256; P, Q [6][nq][nq] real and imaginary part, force (moment) per squared amplitude, dimensional; Q=None means
+        zeros; an empty omega clears the table.  Only the symmetric part of a table can contribute.  With set_sum_mode(1) step() then
+        returns total (+ drift term) + sum-frequency term."""
+        omega = np.ascontiguousarray(omega, dtype=np.float64).reshape(-1)
+        nq = omega.size
+        if nq == 0:
+            self._chk(self.lib.hc_set_sum_qtf(self.ctx, int(b), 0, None, None, None))
+        else:
+            P = np.ascontiguousarray(P, dtype=np.float64)
+            if P.size != 6 * nq * nq or (Q is not None and np.size(Q) != 6 * nq * nq):
+                raise ValueError("P and Q must have shape (6, nq, nq)")
+            Q = None if Q is None else np.ascontiguousarray(Q, dtype=np.float64)
+            self._chk(self.lib.hc_set_sum_qtf(self.ctx, int(b), nq, _dp(omega), _dp(P), None if Q is None else _dp(Q)))
+        self.__dict__.setdefault("_sum_sizes", {})[int(b)] = nq
+
+    def sum_qtf_size(self, b):
+        n = C.c_int()
+        self._chk(self.lib.hc_get_sum_qtf_size(self.ctx, int(b), C.byref(n)))
+        return n.value
+
+    def set_sum_mode(self, mode):
+        """0: off; 1: on."""
+        self._chk(self.lib.hc_set_sum_mode(self.ctx, int(mode)))
+        self._sum_mode = int(mode)
+
+    def set_sum_options(self, regular_phase=0.0):
+        """The phase of a regular wave as the sum-frequency term sees it (that of wave_kinematics())."""
+        o = capi.WaveKinematicsOpts(0.0, float(regular_phase), 1)
+        self._chk(self.lib.hc_set_sum_options(self.ctx, C.byref(o)))
+
+    def _sum_on(self):
+        d = self.__dict__
+        return bool(d.get("_sum_mode")) and any(d.get("_sum_sizes", {}).values())
+
+    def compute_sum_qtf(self, t, pos):
+        """The sum-frequency 6-vectors of the owned bodies (world frame, at the body reference) at time t and positions pos; zeros
+        with mode 0, without a table, and without wave components."""
+        a = _arr(pos, 3 * self.N)
+        out = np.empty(self.D_local)
+        self._chk(self.lib.hc_compute_sum_qtf(self.ctx, float(t), _dp(a), _dp(out)))
+        return out
+
+    def sum_qtf_begin(self, t, pos):
+        a = _arr(pos, 3 * self.N)
+        self._chk(self.lib.hc_sum_qtf_begin(self.ctx, float(t), _dp(a)))
+
+    def sum_qtf_end(self):
+        out = np.empty(self.D_local)
+        self._chk(self.lib.hc_sum_qtf_end(self.ctx, _dp(out)))
+        return out
+
+    def sum_qtf(self):
+        """The sum-frequency term of the last step() (zeros when the mode is 0 or no table is set)."""
+        m = self.__dict__.get("_sum_last")
+        return np.zeros(self.D_local) if m is None or not self._sum_on() else m.copy()
+
 
 def triangles_to_panels(triangles):
     """Centroids and area vectors of triangles [n][3][3]."""
@@ -817,6 +893,7 @@ class HydroGroup:
         morison = any(h.__dict__.get("_morison_any") for h in self.shards)
         nonlinear = self.shards[0]._nonlinear_on()  # every shard holds the lists of all bodies and the mode
         drift = self.shards[0]._drift_on()
+        sumf = self.shards[0]._sum_on()
         if nonlinear:
             self._nonlinear_begin(t, a)
         if morison:
@@ -835,6 +912,17 @@ class HydroGroup:
                 if morison:
                     self._morison_end(check=False)
                 raise
+        if sumf:
+            try:
+                self._sum_begin(t, a[0])
+            except HydroError:
+                if nonlinear:
+                    self._nonlinear_end(check=False)
+                if morison:
+                    self._morison_end(check=False)
+                if drift:
+                    self._drift_end(check=False)
+                raise
         rc = self._step(self._ctxs, len(self.shards), t, a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, a[3].ctypes.data, out.ctypes.data)
         if nonlinear:
             self._nonlinear_last = self._nonlinear_end(check=not rc)
@@ -842,6 +930,8 @@ class HydroGroup:
             self._morison_last = self._morison_end(check=not rc)
         if drift:
             self._drift_last = self._drift_end(check=not rc)
+        if sumf:
+            self._sum_last = self._sum_end(check=not rc)
         if rc:
             raise HydroError(rc, self.lib.hc_last_error(self.shards[0].ctx).decode())
         if nonlinear:
@@ -849,7 +939,9 @@ class HydroGroup:
             out = _compose_nonlinear(out, self._nonlinear_last, h0._nonlinear_mode, h0._panel_counts, 0, self.N)
         if morison:
             out = out + self._morison_last
-        return out + self._drift_last if drift else out
+        if drift:
+            out = out + self._drift_last
+        return out + self._sum_last if sumf else out
 
     # -- drift tables: every shard holds the tables of all bodies and computes those of its own --
     def _drift_begin(self, t, pos):
@@ -885,6 +977,47 @@ class HydroGroup:
 
     def drift_qtf_size(self, b):
         return self.shards[0].drift_qtf_size(b)
+
+    # -- sum-frequency tables: every shard holds the tables of all bodies and computes those of its own --
+    def _sum_begin(self, t, pos):
+        begun = []
+        try:
+            for h in self.shards:
+                h._chk(self.lib.hc_sum_qtf_begin(h.ctx, float(t), _dp(pos)))
+                begun.append(h)
+        except HydroError:
+            for h in begun:
+                self.lib.hc_sum_qtf_end(h.ctx, _dp(np.empty(h.D_local)))
+            raise
+
+    def _sum_end(self, check=True):
+        out = np.empty(self.D)
+        rcs = []
+        for h in self.shards:
+            part = np.empty(h.D_local)
+            rcs.append((h, self.lib.hc_sum_qtf_end(h.ctx, _dp(part))))
+            out[6 * h.b0:6 * h.b1] = part
+        for h, rc in rcs:
+            if check:
+                h._chk(rc)
+        return out
+
+    def compute_sum_qtf(self, t, pos):
+        self._sum_begin(t, _arr(pos, 3 * self.N))
+        return self._sum_end()
+
+    def sum_qtf_begin(self, t, pos):
+        self._sum_begin(t, _arr(pos, 3 * self.N))
+
+    def sum_qtf_end(self):
+        return self._sum_end()
+
+    def sum_qtf(self):
+        m = self.__dict__.get("_sum_last")
+        return np.zeros(self.D) if m is None or not self.shards[0]._sum_on() else m.copy()
+
+    def sum_qtf_size(self, b):
+        return self.shards[0].sum_qtf_size(b)
 
     # -- surface panels and triangles: every shard holds the lists of all bodies and computes those of its own --
     def surface_panel_count(self, b):

@@ -496,6 +496,45 @@ class TestHydro {
         return out;
     }
 
+    // Second-order wave forces from sum-frequency QTF tables (not in the reference; include/hydrochrono_amd.h: hc_set_sum_qtf).
+    // omega [nq] rad/s, a grid of its own, strictly increasing, P and Q [6][nq][nq] row-major (Q may be empty: zeros), force per
+    // squared amplitude, dimensional; only the symmetric part of a table can contribute.  With SetSumMode(1) and at least one table
+    // CoordinateFuncForBody returns total + sum-frequency term, added after the drift term.  The body index is 1-based; an empty
+    // omega clears the table.
+    void SetSumQTF(int body_index_1_based, const std::vector<double>& omega, const std::vector<double>& P, const std::vector<double>& Q = {}) {
+        if (body_index_1_based < 1 || body_index_1_based > num_bodies_) throw std::out_of_range("SetSumQTF: body index out of range");
+        const size_t nq = omega.size(), n6 = 6 * nq * nq;
+        if (P.size() != n6 || (!Q.empty() && Q.size() != n6)) throw std::invalid_argument("SetSumQTF: P and Q must hold 6 * nq * nq values");
+        for (hc_ctx* c : ctxs_)
+            check(c, hc_set_sum_qtf(c, body_index_1_based - 1, static_cast<int>(nq), nq ? omega.data() : nullptr, nq ? P.data() : nullptr,
+                                    Q.empty() ? nullptr : Q.data()));
+        sum_size_.resize(static_cast<size_t>(num_bodies_), 0);
+        sum_size_[static_cast<size_t>(body_index_1_based - 1)] = nq;
+        have_time_ = false;  // the cached total belongs to the tables before
+    }
+    // 0: off, 1: on
+    void SetSumMode(int mode) {
+        for (hc_ctx* c : ctxs_) check(c, hc_set_sum_mode(c, mode));
+        sum_mode_  = mode;
+        have_time_ = false;
+    }
+    // the phase of a regular wave as the sum-frequency term sees it (that of WaveBase::GetElevation & co.)
+    void SetSumOptions(double regular_phase = 0.0) {
+        hc_wave_kinematics_opts o;
+        hc_wave_kinematics_opts_default(&o);
+        o.regular_phase = regular_phase;
+        for (hc_ctx* c : ctxs_) check(c, hc_set_sum_options(c, &o));
+        have_time_ = false;
+    }
+    // the sum-frequency term of all bodies for the bodies' present positions, 6 N values
+    std::vector<double> ComputeForceSumQTF() {
+        gather_state();
+        std::vector<double> out(6 * static_cast<size_t>(num_bodies_));
+        sum_begin(bodies_[0]->GetChTime());
+        sum_end(out.data());
+        return out;
+    }
+
     // src/hydro_forces.cpp:693-711: the radiation IRF value the convolution uses (rho-scaled; the processed kernel in
     // TaperedDirect mode).  Reads one value back from the GPU -- a debugging accessor, as in the reference.
     double GetRIRFval(int row, int col, int st) {
@@ -542,6 +581,24 @@ class TestHydro {
                     throw;
                 }
             }
+            const bool sumf = sum_on();
+            if (sumf) {
+                try {
+                    sum_begin(t);
+                } catch (...) {  // nothing stays pending
+                    if (nonlinear)
+                        for (hc_ctx* c : ctxs_) (void)hc_nonlinear_end(c, nullptr, nullptr, nullptr);
+                    if (have_morison_) {
+                        morison_force_.resize(total_force_.size());
+                        for (hc_ctx* c : ctxs_) (void)hc_morison_end(c, morison_force_.data() + row0(c));
+                    }
+                    if (drift) {
+                        drift_force_.resize(total_force_.size());
+                        for (hc_ctx* c : ctxs_) (void)hc_drift_end(c, drift_force_.data() + row0(c));
+                    }
+                    throw;
+                }
+            }
             const int rc = ctxs_.size() == 1 ? hc_step(ctx_, t, pos_.data(), rpy_.data(), lin_.data(), ang_.data(), total_force_.data())
                                              : hc_step_multi(ctxs_.data(), static_cast<int>(ctxs_.size()), t, pos_.data(), rpy_.data(), lin_.data(),
                                                              ang_.data(), total_force_.data());
@@ -578,6 +635,15 @@ class TestHydro {
                 } else {
                     drift_end(drift_force_.data());
                     for (size_t i = 0; i < total_force_.size(); ++i) total_force_[i] += drift_force_[i];
+                }
+            }
+            if (sumf) {
+                sum_force_.resize(total_force_.size());
+                if (rc != HC_OK) {
+                    for (hc_ctx* c : ctxs_) (void)hc_sum_qtf_end(c, sum_force_.data() + row0(c));  // nothing stays pending
+                } else {
+                    sum_end(sum_force_.data());
+                    for (size_t i = 0; i < total_force_.size(); ++i) total_force_[i] += sum_force_[i];
                 }
             }
             check(ctx_, rc);
@@ -757,6 +823,31 @@ class TestHydro {
         }
         if (failed) check(failed, rc);
     }
+    bool sum_on() const {
+        return sum_mode_ != 0 && std::any_of(sum_size_.begin(), sum_size_.end(), [](size_t n) { return n != 0; });
+    }
+    void sum_begin(double t) {
+        for (size_t g = 0; g < ctxs_.size(); ++g) {
+            const int rc = hc_sum_qtf_begin(ctxs_[g], t, pos_.data());
+            if (rc != HC_OK) {
+                std::vector<double> drop(total_force_.size());
+                for (size_t h = 0; h < g; ++h) (void)hc_sum_qtf_end(ctxs_[h], drop.data());
+                check(ctxs_[g], rc);
+            }
+        }
+    }
+    void sum_end(double* out) {  // every shard is ended, then the first failure is reported
+        int rc = HC_OK;
+        hc_ctx* failed = nullptr;
+        for (hc_ctx* c : ctxs_) {
+            const int r = hc_sum_qtf_end(c, out + row0(c));
+            if (r != HC_OK && rc == HC_OK) {
+                rc     = r;
+                failed = c;
+            }
+        }
+        if (failed) check(failed, rc);
+    }
     static int row0(hc_ctx* c) {  // first output row of a shard context
         int b0 = 0;
         check(c, hc_get_shard(c, &b0, nullptr));
@@ -778,6 +869,9 @@ class TestHydro {
     std::vector<double> drift_force_;      // the drift term of the last evaluation
     std::vector<size_t> drift_size_;       // grid size of every body's drift table
     int drift_mode_ = 0;                   // 0 off, 1 mean drift, 2 Newman, 3 full QTF
+    std::vector<double> sum_force_;        // the sum-frequency term of the last evaluation
+    std::vector<size_t> sum_size_;         // grid size of every body's sum-frequency table
+    int sum_mode_ = 0;                     // 0 off, 1 on
     std::array<double, 3> gravity_{0.0, 0.0, -9.81};
     bool have_time_   = false;
     double prev_time_ = -1.0;

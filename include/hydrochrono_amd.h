@@ -748,7 +748,7 @@ int hc_get_nonlinear_increments(hc_ctx* ctx, int body, int n, double* p /* [n][3
  * under the same conditions: the two synthesised irregular models are ramped, a regular wave is not.
  * NoWave, no wave model, an imported eta record (no components), mode 0: zeros, no launch.  A body without a table: zeros.
  * World frame, at the body reference, the sign of an applied force.  A regular wave gives the constant A^2 T(w, w).
- * Sum-frequency QTFs and wave headings are not covered.
+ * Sum-frequency QTFs are a term of their own (hc_set_sum_qtf below); wave headings are not covered.
  *
  * The device evaluates the exact projected form, O(nf + nq^2) per row: with u_i = A_i cos theta_i, w_i = A_i sin theta_i,
  * U_m = sum_i W[i][m] u_i, V_m = sum_i W[i][m] w_i,
@@ -778,6 +778,55 @@ int hc_set_drift_options(hc_ctx* ctx, const hc_wave_kinematics_opts* o);
 int hc_drift_begin(hc_ctx* ctx, double t, const double* pos);
 int hc_drift_end(hc_ctx* ctx, double* out_Dlocal);
 int hc_compute_drift(hc_ctx* ctx, double t, const double* pos, double* out_Dlocal);
+
+/* ------------------------------------------------------------------------------------------------
+ * Second-order wave forces from sum-frequency QTF tables (not in the reference): the other output of a second-order diffraction
+ * run, the excitation above the wave band (springing and ringing of tendons, heave and pitch of stiff platforms).  Opt-in, per
+ * body, evaluated at the body's instantaneous position; independent of the drift term above (tables, grid, mode and options of its
+ * own).
+ *
+ * Data per body: a frequency grid Omega[0..nq) [rad/s] of its own, finite and strictly increasing, 2 <= nq <= 256, and
+ * P[6][nq][nq], Q[6][nq][nq] (row-major): real and imaginary part of the sum-frequency QTF T_s(Omega_m, Omega_n) of the six body
+ * rows, in force (moment) per squared wave amplitude, already dimensional.  Q may be NULL (zeros).  No symmetry is required or
+ * enforced; since cos and sin of theta_i + theta_j are symmetric in (i, j), only the symmetric part 1/2 (T_s[m][n] + T_s[n][m]) of a
+ * table can contribute, and a purely antisymmetric table gives zero.
+ *
+ * Components, theta_i, the inside test, the cell m_i, lambda_i and the weights W[i][m]: those of the drift term, word for word (both
+ * grid ends inside).
+ *
+ *     F_s = ramp^2 sum_i sum_j A_i A_j [P_s(w_i, w_j) cos(theta_i + theta_j) - Q_s(w_i, w_j) sin(theta_i + theta_j)],
+ *     P_s(w_i, w_j) = sum_mn W[i][m] W[j][n] P_s[m][n] (bilinear), Q likewise,
+ * i.e. Re sum_ij A_i A_j T_s(w_i, w_j) exp(i (theta_i + theta_j)).  ramp as for the drift term: the two synthesised irregular models
+ * are ramped, a regular wave is not; a regular wave gives A^2 [P_s(w, w) cos 2 theta - Q_s(w, w) sin 2 theta].
+ * NoWave, no wave model, an imported eta record (no components), mode 0: zeros, no launch.  A body without a table: zeros.
+ * World frame, at the body reference, the sign of an applied force.
+ * There is no cut-off band on w_i + w_j: a caller who wants one zeroes table entries.  Wave headings are not covered.
+ *
+ * The device evaluates the exact projected form, O(nf + nq^2) per row, with the U_m, V_m of the drift term:
+ *     F_s = sum_mn P_s[m][n] (U_m U_n - V_m V_n) - Q_s[m][n] (V_m U_n + U_m V_n)
+ * in a fixed order: a body's bits depend on its own table, pos[b].x, t, the wave model and the regular phase only -- not on the
+ * number of bodies, on other bodies' tables, or on the shard context that computes it.
+ *
+ * The term is NOT part of hc_step & co., hc_get_force_components, hc_compute_* or the Morison, nonlinear and drift calls; a caller
+ * adds it (the HydroForces / TestHydro layers do, after the drift term).  The path runs on a stream of its own, beside the steps,
+ * and touches no step state: hc_sum_qtf_begin may be followed by hc_step and then hc_sum_qtf_end.
+ * ---------------------------------------------------------------------------------------------- */
+/* As hc_set_drift_qtf: replaces the table of `body` (0-based, any body of the system); nq = 0 clears it.  HC_ERR_INVALID: body out
+ * of range, nq of 1, negative or above 256, a null grid or P with nq > 0, a non-finite value, a grid that is not strictly
+ * increasing, or a hc_sum_qtf_begin without its end. */
+int hc_set_sum_qtf(hc_ctx* ctx, int body, int nq, const double* omega, const double* P, const double* Q);
+int hc_get_sum_qtf_size(hc_ctx* ctx, int body, int* nq);
+/* 0 off (default), 1 on; HC_ERR_INVALID otherwise or while a begin is pending */
+int hc_set_sum_mode(hc_ctx* ctx, int mode);
+int hc_get_sum_mode(hc_ctx* ctx, int* mode);
+/* only regular_phase is read; NULL = the defaults */
+int hc_set_sum_options(hc_ctx* ctx, const hc_wave_kinematics_opts* o);
+/* begin enqueues (pos as for hc_step: [3N]), end waits and copies the 6 * n_local values; exactly one end per begin.  Needs
+ * hc_finalize.  HC_ERR_INVALID on a non-finite t or pos, on a second begin, on an end without a begin; nothing stays pending after a
+ * failure. */
+int hc_sum_qtf_begin(hc_ctx* ctx, double t, const double* pos);
+int hc_sum_qtf_end(hc_ctx* ctx, double* out_Dlocal);
+int hc_compute_sum_qtf(hc_ctx* ctx, double t, const double* pos, double* out_Dlocal);
 
 /* ------------------------------------------------------------------------------------------------
  * Second-order irregular waves (not in the reference): the second-order increments of the long-crested sea of Sharma and Dean
