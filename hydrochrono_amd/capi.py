@@ -168,6 +168,11 @@ SIGNATURES = {
     "hc_wave_kinematics": (C.c_int, [C.c_void_p, C.POINTER(WaveKinematicsOpts), C.c_int, c_double_p, C.c_int, c_double_p,
                                      c_double_p, c_double_p, c_double_p]),
     "hc_set_morison_elements": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(MorisonElement), C.c_int]),
+    "hc_set_wave_directions": (C.c_int, [C.c_void_p, C.c_int, c_double_p]),
+    "hc_get_wave_directions": (C.c_int, [C.c_void_p, c_int_p, c_double_p]),
+    "hc_set_excitation_rao_headings": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_double_p, c_double_p, C.c_int, c_double_p, c_double_p]),
+    "hc_get_excitation_rao_headings_size": (C.c_int, [C.c_void_p, C.c_int, c_int_p, c_int_p]),
+    "hc_wave_spreading_directions": (C.c_int, [C.c_int, C.c_double, C.c_double, C.c_int, C.c_ulonglong, c_double_p]),
     "hc_get_morison_count": (C.c_int, [C.c_void_p, C.c_int, c_int_p]),
     "hc_set_morison_options": (C.c_int, [C.c_void_p, C.POINTER(WaveKinematicsOpts)]),
     "hc_morison_begin": (C.c_int, [C.c_void_p, C.c_double, c_double_p, c_double_p, c_double_p, c_double_p]),

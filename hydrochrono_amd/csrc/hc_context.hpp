@@ -130,6 +130,11 @@ struct BodyHost {
     std::vector<double> rao_w;      // [nw]
     std::vector<double> rao_mag;    // [6][nw] rho*g-scaled
     std::vector<double> rao_phase;  // [6][nw]
+    // excitation coefficients on a grid of wave headings (hc_set_excitation_rao_headings): used when wave directions are set
+    std::vector<double> hd_dir;     // [n_dir] strictly increasing; empty: none
+    std::vector<double> hd_w;       // [nw]
+    std::vector<double> hd_mag;     // [6][n_dir][nw] rho*g-scaled
+    std::vector<double> hd_phase;   // [6][n_dir][nw]
     std::vector<double> exirf_t;    // [n]
     std::vector<double> exirf_f;    // [6][n] rho*g-scaled (local bodies only)
 };
@@ -269,6 +274,12 @@ struct hc_ctx {
     hc::DeviceBuffer<double> d_kex, d_ex_tau, d_ex_width, d_eta_t, d_eta;
     hc::DeviceBuffer<double> d_spec_mag, d_spec_phase, d_spec_amp, d_spec_omega, d_spec_phi;  // spectral (component-sum) mode
     unsigned long long wave_serial = 0;  // counts the hc_set_wave_* calls (voids the kinematics table below)
+    // Directions of the wave components (hc_set_wave_directions): theta_i per component of the model in force, empty: none (the
+    // long-crested sea along +x).  Dropped by every hc_set_wave_* call; a change counts in wave_serial as those calls do, so that
+    // every cached component table is rebuilt.  kin_dir / mor_dir / nl_dir: the cached table of that path carries the two direction
+    // columns (cos, sin) behind its own and the launch goes to the directional instantiation.
+    std::vector<double> wave_dir;
+    bool kin_dir = false, mor_dir = false, nl_dir = false;
 
     // wave kinematics (hc_wave_kinematics, hc_wave_kin.hip): the component table of the wave model it was built for (wave_serial,
     // and the phase of a regular wave), and a grow-only buffer for points, times and outputs

@@ -312,6 +312,8 @@ int hc_drift_begin(hc_ctx* c, double t, const double* pos) {
     require(!c->drift_pending, HC_ERR_INVALID, "hc_drift_begin twice without hc_drift_end");
     require(pos != nullptr, HC_ERR_INVALID, "null state");
     require(std::isfinite(t) && hc::all_finite(pos, 3 * static_cast<size_t>(c->N)), HC_ERR_INVALID, "non-finite time or position");
+    require(c->drift_mode == 0 || c->wave_dir.empty(), HC_ERR_UNSUPPORTED,
+            "the QTF tables hold one heading: wave drift forces are not available while wave directions are set (hc_set_wave_directions)");
     bool any = false;
     if (!c->drift_tabs.empty())
         for (int b = c->b0; b < c->b1; ++b) any = any || c->drift_tabs[b].nq != 0;

@@ -67,6 +67,7 @@ int hc_set_wave_irregular_eta(hc_ctx* c, const hc_irregular_wave_params* pp, con
     upload_excitation(c, ex);
     c->init.wave_upload_seconds += seconds_since(t_up);
     c->init.wave_upload_bytes += 8.0 * (2.0 * nt + 2.0 * static_cast<double>(c->Dloc) * ex.L + 2.0 * ex.L);
+    c->wave_dir.clear();  // the new model is in force from here: its component count is another (hc_set_wave_directions)
     c->irr = p;
     c->nf  = 0;
     c->nt  = nt;

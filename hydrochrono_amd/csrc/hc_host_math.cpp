@@ -205,4 +205,75 @@ std::vector<double> resample_cubic_bspline6(const std::vector<double>& vals_in, 
     return out;
 }
 
+// ---- equal-energy directions of the cos-2s spreading ----
+namespace {
+
+constexpr double kPi = 3.14159265358979323846;
+constexpr int kSpreadCells = 8192;  // cells of the cumulative table over (-pi, pi), one Simpson step each
+
+double spread_density(double phi, double s) { return std::pow(std::max(std::cos(0.5 * phi), 0.0), 2.0 * s); }
+
+// integral of the density over [a, b], a short interval inside one cell: 5-point Gauss-Legendre
+double spread_gauss5(double a, double b, double s) {
+    static const double x[5] = {0.0, -0.5384693101056831, 0.5384693101056831, -0.9061798459386640, 0.9061798459386640};
+    static const double w[5] = {0.5688888888888889, 0.4786286704993665, 0.4786286704993665, 0.2369268850561891, 0.2369268850561891};
+    const double c = 0.5 * (a + b), h = 0.5 * (b - a);
+    double sum = 0.0;
+    for (int i = 0; i < 5; ++i) sum += w[i] * spread_density(c + h * x[i], s);
+    return h * sum;
+}
+
+// splitmix64 of a counter: the stream of (seed, run, position) is a pure function of its arguments
+std::uint64_t spread_mix(std::uint64_t z) {
+    z += 0x9e3779b97f4a7c15ULL;
+    z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ULL;
+    z = (z ^ (z >> 27)) * 0x94d049bb133111ebULL;
+    return z ^ (z >> 31);
+}
+
+}  // namespace
+
+std::vector<double> spreading_directions(int nf, double heading, double s, int n_bins, std::uint64_t seed) {
+    if (nf < 0 || n_bins < 1 || !std::isfinite(heading) || std::isnan(s) || std::isinf(s))
+        throw std::invalid_argument("spreading_directions: negative count, no bin, or a non-finite heading or exponent");
+    std::vector<double> theta(static_cast<size_t>(nf), heading);
+    if (s <= 0.0 || n_bins == 1 || nf == 0) return theta;
+    // cumulative integral of the density at the cell ends, Simpson per cell
+    const double h = 2.0 * kPi / kSpreadCells;
+    std::vector<double> cum(kSpreadCells + 1, 0.0);
+    for (int j = 0; j < kSpreadCells; ++j) {
+        const double a = -kPi + j * h;
+        cum[j + 1] = cum[j] + (h / 6.0) * (spread_density(a, s) + 4.0 * spread_density(a + 0.5 * h, s) + spread_density(a + h, s));
+    }
+    const double total = cum[kSpreadCells];
+    // bin m: the offset phi with G(phi) = (m + 1/2) / n_bins.  The density is even, so the lower half is computed and mirrored: the
+    // bins are symmetric about the heading exactly.
+    std::vector<double> bin(static_cast<size_t>(n_bins), 0.0);
+    for (int m = 0; m < n_bins / 2; ++m) {
+        const double target = total * ((m + 0.5) / n_bins);
+        const int j = static_cast<int>(std::upper_bound(cum.begin(), cum.end(), target) - cum.begin()) - 1;  // cum[j] <= target < cum[j + 1]
+        const int jc = std::min(std::max(j, 0), kSpreadCells - 1);
+        const double a = -kPi + jc * h;
+        double lo = a, hi = a + h;
+        for (int it = 0; it < 64; ++it) {  // bisection inside the cell
+            const double mid = 0.5 * (lo + hi);
+            if (cum[jc] + spread_gauss5(a, mid, s) < target) lo = mid;
+            else hi = mid;
+        }
+        bin[m]              = 0.5 * (lo + hi);
+        bin[n_bins - 1 - m] = -bin[m];
+    }
+    // every run of n_bins consecutive components takes every bin once: a Fisher-Yates shuffle per run, drawn from the counter
+    std::vector<int> perm(static_cast<size_t>(n_bins));
+    for (int i0 = 0, run = 0; i0 < nf; i0 += n_bins, ++run) {
+        for (int m = 0; m < n_bins; ++m) perm[m] = m;
+        for (int m = n_bins - 1; m > 0; --m) {
+            const std::uint64_t draw = spread_mix(spread_mix(seed ^ spread_mix(static_cast<std::uint64_t>(run))) + static_cast<std::uint64_t>(m));
+            std::swap(perm[m], perm[static_cast<size_t>(draw % static_cast<std::uint64_t>(m + 1))]);
+        }
+        for (int m = 0; m < n_bins && i0 + m < nf; ++m) theta[i0 + m] = heading + bin[perm[m]];
+    }
+    return theta;
+}
+
 }  // namespace hc

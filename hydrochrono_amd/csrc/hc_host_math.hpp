@@ -31,4 +31,11 @@ double wave_number(double omega, double water_depth, double g);
 // vals_in is [6][n_old] row-major; returns [6][n_new].
 std::vector<double> resample_cubic_bspline6(const std::vector<double>& vals_in, int n_old, int n_new);
 
+// Equal-energy directions of the cos-2s spreading D(theta) ~ cos^{2s}((theta - heading) / 2) on (heading - pi, heading + pi), the
+// single-direction-per-frequency method (not in the reference): bin m of n_bins has direction heading + G^-1((m + 1/2) / n_bins), G
+// the cumulative distribution of D (Simpson per cell of a table, bisection inside the cell; no special function).  Every run of
+// n_bins consecutive components takes every bin once, in a permutation drawn from `seed` by a counter-based generator (splitmix64):
+// the same on every platform.  s <= 0 or n_bins == 1: every direction is the heading.  Throws std::invalid_argument.
+std::vector<double> spreading_directions(int nf, double heading, double s, int n_bins, std::uint64_t seed);
+
 }  // namespace hc

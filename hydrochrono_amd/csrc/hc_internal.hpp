@@ -126,6 +126,36 @@ void upload_excitation(hc_ctx* c, const ExcitationGrid& ex);  // Kex in panel la
 void commit_excitation(hc_ctx* c, ExcitationGrid& ex);  // into the context; wave_kind = irregular, launch configuration
 void drop_lookahead_excitation(hc_ctx* c);
 
+// The omega interpolators of the excitation coefficients: a BEM list of nw frequencies taken as uniform and starting at its own
+// spacing dw = w_back / nw (RegularWave, src/wave_types.cpp:329-352), value = fr * (v[k1] - v[k0]) + v[k0].
+struct RaoBracket {
+    int k0, k1;
+    double fr;
+};
+// hc_set_wave_irregular_spectral: held constant outside the list
+inline RaoBracket rao_bracket_clamped(double omega, double w_back, int nw) {
+    const double dw = w_back / static_cast<double>(nw);
+    double idx = omega / dw - 1;
+    idx        = std::min(std::max(idx, 0.0), static_cast<double>(nw - 1));
+    const int k0 = std::min(static_cast<int>(std::floor(idx)), nw - 2 >= 0 ? nw - 2 : 0);
+    const int k1 = std::min(k0 + 1, nw - 1);
+    return RaoBracket{k0, k1, idx - k0};
+}
+// hc_set_wave_regular: no clamping; the bracket of one list (body 0's serves every body there) is checked against the length of
+// every list it is applied to -- HC_ERR_OUT_OF_RANGE outside
+inline RaoBracket rao_bracket_regular(double omega, double w_back, int nw) {
+    const double dw      = w_back / static_cast<double>(nw);
+    const double idx_des = (omega / dw) - 1;
+    const int k0         = static_cast<int>(std::floor(idx_des));
+    return RaoBracket{k0, k0 + 1, idx_des - std::floor(idx_des)};
+}
+inline void rao_bracket_check(const RaoBracket& br, int nw) {
+    if (br.k0 < 0 || br.k0 + 1 >= nw) throw Error(HC_ERR_OUT_OF_RANGE, "regular wave frequency outside the BEM frequency list");
+}
+// hc_directions.cpp: the per-row tables of the first-order excitation for the directions in force (c->wave_dir), rebuilt and
+// uploaded when a relevant body has heading tables (hc_set_excitation_rao_headings) or `force`; !commit: validates only
+void apply_wave_directions(hc_ctx* c, const std::vector<double>& theta, bool commit, bool force);
+
 // ---- hc_step.cpp ----
 struct StepFlags {
     bool hs = true, rad = true, waves = true;

@@ -18,7 +18,7 @@ constexpr int kMorElemDoubles = 9;  // r, cd_area, cm_vol
 constexpr int kMorIncDoubles = 8;   // p, eta2, u2x, u2z, a2x, a2z of an element on the second-order sea
 
 struct MorArgs {
-    const double* tab;  // [kKinCols][nf] (hc_wave_kin.hpp); nf = 0: still water
+    const double* tab;  // [kKinCols][nf] (hc_wave_kin.hpp), with directions [kKinCols + kDirCols][nf]; nf = 0: still water
     int nf;
     int n_items;
     const double* elem;   // [n_items][9], owned bodies one after the other
@@ -38,7 +38,7 @@ struct MorArgs {
 struct MorFrame {
     double r00, r01, r02, r10, r11, r12, r20, r21, r22;
     double d0, d1, d2;
-    double x, z;
+    double x, y, z;
 };
 
 __device__ inline MorFrame morison_frame(const double* el, const double* pos, const double* rpy) {
@@ -53,7 +53,7 @@ __device__ inline MorFrame morison_frame(const double* el, const double* pos, co
     f.d0 = f.r00 * el[0] + f.r01 * el[1] + f.r02 * el[2];
     f.d1 = f.r10 * el[0] + f.r11 * el[1] + f.r12 * el[2];
     f.d2 = f.r20 * el[0] + f.r21 * el[1] + f.r22 * el[2];
-    f.x = pos[0] + f.d0, f.z = pos[2] + f.d2;
+    f.x = pos[0] + f.d0, f.y = pos[1] + f.d1, f.z = pos[2] + f.d2;
     return f;
 }
 
@@ -63,9 +63,13 @@ __device__ inline MorFrame morison_frame(const double* el, const double* pos, co
 // kinematics pass (the same sincos); with stretching it is summed first.
 // ORDER2: the element's second-order increments (morison2_incr_kernel, earlier on the stream) are read after the first-order sums
 // and added before the wet test and the force; the first-order part, stretching by eta1 included, is the code of order 1.
-template <bool ORDER2>
-__global__ void __launch_bounds__(kMorThreads) morison_items_kernel(MorArgs a) {
-    __shared__ double s[kKinCols][kKinTile];
+// DIR (order 1 only, morison_dir_items_kernel): the directional sea of wave_kinematics_kernel<true> -- the phase at k (x cos + y sin), the horizontal flow
+// along (cos, sin), so that u_f and a_f have a y component; the long-crested instantiations keep their arithmetic.
+template <bool ORDER2, bool DIR>
+__device__ __forceinline__ void morison_items_body(const MorArgs& a) {
+    static_assert(!(ORDER2 && DIR), "the second-order sea has no directions");
+    constexpr int kDc = kKinCols, kDs = kKinCols + 1;  // rows of the direction columns (DIR only)
+    __shared__ double s[DIR ? kKinCols + kDirCols : kKinCols][kKinTile];
     const int o       = blockIdx.x * kMorThreads + threadIdx.x;
     const bool active = o < a.n_items;
     const int e       = active ? o : 0;  // items past the end evaluate item 0 and store nothing (all take part in the staging)
@@ -80,7 +84,7 @@ __global__ void __launch_bounds__(kMorThreads) morison_items_kernel(MorArgs a) {
     const MorFrame f = morison_frame(el, pos, rpy);
     const double r00 = f.r00, r01 = f.r01, r02 = f.r02, r10 = f.r10, r11 = f.r11, r12 = f.r12, r20 = f.r20, r21 = f.r21, r22 = f.r22;
     const double d0 = f.d0, d1 = f.d1, d2 = f.d2;
-    const double x = f.x, z = f.z, t = a.t;
+    const double x = f.x, y = DIR ? f.y : 0.0, z = f.z, t = a.t;
 
     // ---- eta first under stretching (wave_kinematics_kernel) ----
     double eta = 0.0;
@@ -93,9 +97,15 @@ __global__ void __launch_bounds__(kMorThreads) morison_items_kernel(MorArgs a) {
                 s[kKinOmega][i] = a.tab[kKinOmega * a.nf + i0 + i];
                 s[kKinK][i]     = a.tab[kKinK * a.nf + i0 + i];
                 s[kKinPhase][i] = a.tab[kKinPhase * a.nf + i0 + i];
+                if constexpr (DIR) {
+                    s[kDc][i] = a.tab[kDc * a.nf + i0 + i];
+                    s[kDs][i] = a.tab[kDs * a.nf + i0 + i];
+                }
             }
             __syncthreads();
-            for (int i = 0; i < m; ++i) eta += s[kKinAmp][i] * cos(s[kKinK][i] * x - s[kKinOmega][i] * t + s[kKinPhase][i]);
+            for (int i = 0; i < m; ++i)
+                eta += s[kKinAmp][i] *
+                       cos(kin_kx<DIR>(s[kKinK][i], x, y, DIR ? s[kDc][i] : 0.0, DIR ? s[kDs][i] : 0.0) - s[kKinOmega][i] * t + s[kKinPhase][i]);
         }
     }
     double zs = z;
@@ -106,19 +116,20 @@ __global__ void __launch_bounds__(kMorThreads) morison_items_kernel(MorArgs a) {
     const double ze = zs - a.mwl;  // under stretching mwl is subtracted a second time, as in the reference
 
     // ---- velocity and acceleration (and eta without stretching) ----
-    double ux = 0.0, uz = 0.0, ax = 0.0, az = 0.0, eta1 = 0.0;
+    double ux = 0.0, uy = 0.0, uz = 0.0, ax = 0.0, ay = 0.0, az = 0.0, eta1 = 0.0;
     for (int i0 = 0; i0 < a.nf; i0 += kKinTile) {
         const int m = min(kKinTile, a.nf - i0);
         __syncthreads();
         for (int i = threadIdx.x; i < m; i += kMorThreads) {
 #pragma unroll
-            for (int col = 0; col < kKinCols; ++col) s[col][i] = a.tab[col * a.nf + i0 + i];
+            for (int col = 0; col < (DIR ? kKinCols + kDirCols : kKinCols); ++col) s[col][i] = a.tab[col * a.nf + i0 + i];
         }
         __syncthreads();
         for (int i = 0; i < m; ++i) {
             const double k = s[kKinK][i];
+            const double dc = DIR ? s[kDc][i] : 0.0, ds = DIR ? s[kDs][i] : 0.0;
             double sn, cs;
-            sincos(k * x - s[kKinOmega][i] * t + s[kKinPhase][i], &sn, &cs);
+            sincos(kin_kx<DIR>(k, x, y, dc, ds) - s[kKinOmega][i] * t + s[kKinPhase][i], &sn, &cs);
             double px, pz;
             if (s[kKinDeep][i] != 0.0) {  // (the same branch for every item: no divergence)
                 px = pz = exp(k * ze);
@@ -129,9 +140,17 @@ __global__ void __launch_bounds__(kMorThreads) morison_items_kernel(MorArgs a) {
             }
             const double wa = s[kKinWA][i], w2a = s[kKinW2A][i];
             eta1 += s[kKinAmp][i] * cs;
-            ux += wa * px * cs;
+            if constexpr (DIR) {
+                const double uh = wa * px * cs, ah = w2a * px * sn;
+                ux += uh * dc;
+                uy += uh * ds;
+                ax += ah * dc;
+                ay += ah * ds;
+            } else {
+                ux += wa * px * cs;
+                ax += w2a * px * sn;
+            }
             uz += wa * pz * sn;
-            ax += w2a * px * sn;
             az -= w2a * pz * cs;
         }
     }
@@ -155,11 +174,23 @@ __global__ void __launch_bounds__(kMorThreads) morison_items_kernel(MorArgs a) {
     double ufx = a.ramp * ux, ufz = a.ramp * uz, afx = a.ramp * ax, afz = a.ramp * az;
     if constexpr (ORDER2) ufx += u2x, ufz += u2z, afx += a2x, afz += a2z;
     const double q0 = ufx - (lin[0] + (w1 * d2 - w2 * d1));
-    const double q1 = -(lin[1] + (w2 * d0 - w0 * d2));
+    double q1, a0, a1, a2;
+    if constexpr (DIR) {
+        const double ufy = a.ramp * uy, afy = a.ramp * ay;
+        q1 = ufy - (lin[1] + (w2 * d0 - w0 * d2));
+        a0 = r00 * afx + r10 * afy + r20 * afz;
+        a1 = r01 * afx + r11 * afy + r21 * afz;
+        a2 = r02 * afx + r12 * afy + r22 * afz;
+    } else {
+        q1 = -(lin[1] + (w2 * d0 - w0 * d2));
+        a0 = r00 * afx + r20 * afz;
+        a1 = r01 * afx + r21 * afz;
+        a2 = r02 * afx + r22 * afz;
+    }
     const double q2 = ufz - (lin[2] + (w0 * d1 - w1 * d0));
-    const double u0 = r00 * q0 + r10 * q1 + r20 * q2, a0 = r00 * afx + r20 * afz;
-    const double u1 = r01 * q0 + r11 * q1 + r21 * q2, a1 = r01 * afx + r21 * afz;
-    const double u2 = r02 * q0 + r12 * q1 + r22 * q2, a2 = r02 * afx + r22 * afz;
+    const double u0 = r00 * q0 + r10 * q1 + r20 * q2;
+    const double u1 = r01 * q0 + r11 * q1 + r21 * q2;
+    const double u2 = r02 * q0 + r12 * q1 + r22 * q2;
     const double f0 = 0.5 * a.rho * el[3] * fabs(u0) * u0 + a.rho * el[6] * a0;
     const double f1 = 0.5 * a.rho * el[4] * fabs(u1) * u1 + a.rho * el[7] * a1;
     const double f2 = 0.5 * a.rho * el[5] * fabs(u2) * u2 + a.rho * el[8] * a2;
@@ -173,6 +204,12 @@ __global__ void __launch_bounds__(kMorThreads) morison_items_kernel(MorArgs a) {
     out[4] = d2 * F0 - d0 * F2;
     out[5] = d0 * F1 - d1 * F0;
 }
+
+template <bool ORDER2>
+__global__ void __launch_bounds__(kMorThreads) morison_items_kernel(MorArgs a) {
+    morison_items_body<ORDER2, false>(a);
+}
+__global__ void __launch_bounds__(kMorThreads) morison_dir_items_kernel(MorArgs a) { morison_items_body<false, true>(a); }
 
 struct Mor2Args {
     Wk2Sea sea;           // the Morison path's own tables (hc_ctx::mor2), mwl of the Morison options
@@ -255,9 +292,12 @@ void morison_table(hc_ctx* c) {
     const double phase = c->mor_opts.regular_phase;
     const bool regular = c->wave_kind == kWaveRegular;
     if (c->mor_serial == c->wave_serial && (!regular || std::memcmp(&c->mor_phase, &phase, sizeof(double)) == 0)) return;
-    const std::vector<double> tab = kin_table_host(c, phase);
+    std::vector<double> tab = kin_table_host(c, phase);
+    c->mor_nf = static_cast<int>(tab.size() / kKinCols);
+    const std::vector<double> dir = kin_dir_columns_host(c);
+    tab.insert(tab.end(), dir.begin(), dir.end());
     c->d_mor_tab.upload(tab, c->stream_mor);
-    c->mor_nf     = static_cast<int>(tab.size() / kKinCols);
+    c->mor_dir    = !dir.empty();
     c->mor_serial = c->wave_serial;
     c->mor_phase  = phase;
 }
@@ -325,6 +365,8 @@ void morison_enqueue(hc_ctx* c, double t, const double* pos, const double* rpy, 
         HC_HIP(hipGetLastError());
         HC_HIP(hipMemcpyAsync(h_inc.p, c->d_mor_inc.p, n_inc * sizeof(double), hipMemcpyDeviceToHost, st));
         hipLaunchKernelGGL(morison_items_kernel<true>, item_grid, dim3(kMorThreads), 0, st, a);
+    } else if (c->mor_dir) {
+        hipLaunchKernelGGL(morison_dir_items_kernel, item_grid, dim3(kMorThreads), 0, st, a);
     } else {
         hipLaunchKernelGGL(morison_items_kernel<false>, item_grid, dim3(kMorThreads), 0, st, a);
     }
@@ -435,6 +477,9 @@ int hc_morison_begin(hc_ctx* c, double t, const double* pos, const double* rpy, 
     const size_t n3 = 3 * static_cast<size_t>(c->N);
     require(std::isfinite(t) && hc::all_finite(pos, n3) && hc::all_finite(rpy, n3) && hc::all_finite(linvel, n3) && hc::all_finite(angvel, n3),
             HC_ERR_INVALID, "non-finite time or state");
+    require(!(c->mor2_on && !c->wave_dir.empty()), HC_ERR_UNSUPPORTED,
+            "Morison elements on the second-order sea are not available while wave directions are set (hc_set_wave_directions): clear "
+            "the directions or switch the second-order sea off");
     require(!(c->mor2_on && hc::wk2_has_components(c)) || hc::wk2_component_count(c) <= hc::kWk2MaxFreq, HC_ERR_UNSUPPORTED,
             "Morison elements on the second-order sea: more than 4096 wave components");
     int items = 0;

@@ -28,7 +28,7 @@ constexpr int kNlIncDoubles = 5;     // P, eta2, q2 of a surface point on the se
 enum NlCol { kNlAmp = 0, kNlOmega, kNlK, kNlPhase, kNlW2AoK, kNlInvSinh, kNlDeep, kNlCols };
 
 struct NlArgs {
-    const double* tab;  // [kNlCols][nf]; nf = 0: still water
+    const double* tab;  // [kNlCols][nf], with directions [kNlCols + kDirCols][nf]; nf = 0: still water
     int nf;
     const double* panel;  // nl_panels_kernel: [items][6] (c, s); nl_tris_kernel: [items][9] (v[3][3]); owned bodies one after the other
     const int* chunk;     // [chunks][3]: body (of the system), first item of its kind, count (1 .. 256); from the launch's first chunk on
@@ -77,9 +77,13 @@ __device__ __forceinline__ void nl_rotate(const NlFrame& f, const double* c, dou
 // ORDER2 (nl2_panels_kernel): the component loop also sums the first-order velocity u1 at the same z_e (a sincos where order 1 has
 // a cos), and the centroid's increments eta2, q2 (nl2_incr_kernel, earlier on the stream) are read after the loop: eta2 enters the
 // wet test, rho q2 - 1/2 rho ramp^2 |u1|^2 the dynamic pressure.  Everything else is the code of order 1.
-template <bool ORDER2>
+// DIR (order 1 only, nl_panels_dir_kernel): the directional sea of wave_kinematics_kernel<true> -- cos and sin of every component's
+// direction staged behind the other columns, the phase at k (x cos + y sin); the pressure is a scalar, so nothing else changes.
+template <bool ORDER2, bool DIR = false>
 __device__ __forceinline__ void nl_panels_body(const NlArgs& a) {
-    __shared__ double s[kNlCols][kKinTile];
+    static_assert(!(ORDER2 && DIR), "the second-order sea has no directions");
+    constexpr int kDc = kNlCols, kDs = kNlCols + 1;  // rows of the direction columns (DIR only)
+    __shared__ double s[DIR ? kNlCols + kDirCols : kNlCols][kKinTile];
     __shared__ double red[kNlOut][kNlThreads];
     const int tid     = threadIdx.x;
     const int b       = a.chunk[3 * blockIdx.x];
@@ -96,7 +100,7 @@ __device__ __forceinline__ void nl_panels_body(const NlArgs& a) {
     double d0, d1, d2, n0, n1, n2;
     nl_rotate(f, pn, d0, d1, d2);
     nl_rotate(f, pn + 3, n0, n1, n2);
-    const double x = pos[0] + d0, z = pos[2] + d2, t = a.t;
+    const double x = pos[0] + d0, y = DIR ? pos[1] + d1 : 0.0, z = pos[2] + d2, t = a.t;
 
     // ---- eta first under stretching (wave_kinematics_kernel) ----
     double eta = 0.0;
@@ -109,9 +113,15 @@ __device__ __forceinline__ void nl_panels_body(const NlArgs& a) {
                 s[kNlOmega][i] = a.tab[kNlOmega * a.nf + i0 + i];
                 s[kNlK][i]     = a.tab[kNlK * a.nf + i0 + i];
                 s[kNlPhase][i] = a.tab[kNlPhase * a.nf + i0 + i];
+                if constexpr (DIR) {
+                    s[kDc][i] = a.tab[kDc * a.nf + i0 + i];
+                    s[kDs][i] = a.tab[kDs * a.nf + i0 + i];
+                }
             }
             __syncthreads();
-            for (int i = 0; i < m; ++i) eta += s[kNlAmp][i] * cos(s[kNlK][i] * x - s[kNlOmega][i] * t + s[kNlPhase][i]);
+            for (int i = 0; i < m; ++i)
+                eta += s[kNlAmp][i] *
+                       cos(kin_kx<DIR>(s[kNlK][i], x, y, DIR ? s[kDc][i] : 0.0, DIR ? s[kDs][i] : 0.0) - s[kNlOmega][i] * t + s[kNlPhase][i]);
         }
     }
     double zs = z;
@@ -128,7 +138,7 @@ __device__ __forceinline__ void nl_panels_body(const NlArgs& a) {
         __syncthreads();
         for (int i = tid; i < m; i += kNlThreads) {
 #pragma unroll
-            for (int col = 0; col < kNlCols; ++col) s[col][i] = a.tab[col * a.nf + i0 + i];
+            for (int col = 0; col < (DIR ? kNlCols + kDirCols : kNlCols); ++col) s[col][i] = a.tab[col * a.nf + i0 + i];
         }
         __syncthreads();
         for (int i = 0; i < m; ++i) {
@@ -137,7 +147,7 @@ __device__ __forceinline__ void nl_panels_body(const NlArgs& a) {
             if constexpr (ORDER2)
                 sincos(k * x - s[kNlOmega][i] * t + s[kNlPhase][i], &sn, &cs);
             else
-                cs = cos(k * x - s[kNlOmega][i] * t + s[kNlPhase][i]);
+                cs = cos(kin_kx<DIR>(k, x, y, DIR ? s[kDc][i] : 0.0, DIR ? s[kDs][i] : 0.0) - s[kNlOmega][i] * t + s[kNlPhase][i]);
             double px, pz;
             if (s[kNlDeep][i] != 0.0) {  // (the same branch for every item: no divergence)
                 px = pz = exp(k * ze);
@@ -200,6 +210,7 @@ __device__ __forceinline__ void nl_panels_body(const NlArgs& a) {
 
 __global__ void __launch_bounds__(kNlThreads) nl_panels_kernel(NlArgs a) { nl_panels_body<false>(a); }
 __global__ void __launch_bounds__(kNlThreads) nl2_panels_kernel(NlArgs a) { nl_panels_body<true>(a); }
+__global__ void __launch_bounds__(kNlThreads) nl_panels_dir_kernel(NlArgs a) { nl_panels_body<false, true>(a); }
 
 // One work item per (owned body, component): the serial sum over the body's chunk partials in chunk order.
 __global__ void __launch_bounds__(kNlThreads) nl_sum_kernel(const double* part, const int* off, int rows, double* out) {
@@ -264,9 +275,13 @@ __device__ __forceinline__ void nl_sub_triangle(const NlVertex& q0, const NlVert
 // contribute exact zeros, as dry triangles do.  Then the fixed tree; lane 0 stores the chunk's 12-vector.
 // ORDER2 (nl2_tris_kernel): as in the panel kernel -- u1 of every vertex in the component loop, the vertices' increments after it,
 // eta2 into h and rho q2 - 1/2 rho ramp^2 |u1|^2 into p_d before the case table, which is the one of order 1.
-template <bool ORDER2>
+// DIR (order 1 only, nl_tris_dir_kernel): as in the panel kernel -- every vertex's phase at k (x cos + y sin), eta at the vertices
+// where the triangle is clipped included.
+template <bool ORDER2, bool DIR = false>
 __device__ __forceinline__ void nl_tris_body(const NlArgs& a) {
-    __shared__ double s[kNlCols][kKinTile];
+    static_assert(!(ORDER2 && DIR), "the second-order sea has no directions");
+    constexpr int kDc = kNlCols, kDs = kNlCols + 1;  // rows of the direction columns (DIR only)
+    __shared__ double s[DIR ? kNlCols + kDirCols : kNlCols][kKinTile];
     __shared__ double red[kNlOut][kNlThreads];
     const int tid     = threadIdx.x;
     const int b       = a.chunk[3 * blockIdx.x];
@@ -285,6 +300,7 @@ __device__ __forceinline__ void nl_tris_body(const NlArgs& a) {
     nl_rotate(f, tv + 3, q1.d0, q1.d1, q1.d2);
     nl_rotate(f, tv + 6, q2.d0, q2.d1, q2.d2);
     const double x0 = pos[0] + q0.d0, x1 = pos[0] + q1.d0, x2 = pos[0] + q2.d0;
+    const double y0 = DIR ? pos[1] + q0.d1 : 0.0, y1 = DIR ? pos[1] + q1.d1 : 0.0, y2 = DIR ? pos[1] + q2.d1 : 0.0;
     const double z0 = pos[2] + q0.d2, z1 = pos[2] + q1.d2, z2 = pos[2] + q2.d2;
     const double t = a.t;
 
@@ -299,12 +315,17 @@ __device__ __forceinline__ void nl_tris_body(const NlArgs& a) {
                 s[kNlOmega][i] = a.tab[kNlOmega * a.nf + i0 + i];
                 s[kNlK][i]     = a.tab[kNlK * a.nf + i0 + i];
                 s[kNlPhase][i] = a.tab[kNlPhase * a.nf + i0 + i];
+                if constexpr (DIR) {
+                    s[kDc][i] = a.tab[kDc * a.nf + i0 + i];
+                    s[kDs][i] = a.tab[kDs * a.nf + i0 + i];
+                }
             }
             __syncthreads();
             for (int i = 0; i < m; ++i) {
-                eta0 += s[kNlAmp][i] * cos(s[kNlK][i] * x0 - s[kNlOmega][i] * t + s[kNlPhase][i]);
-                eta1 += s[kNlAmp][i] * cos(s[kNlK][i] * x1 - s[kNlOmega][i] * t + s[kNlPhase][i]);
-                eta2 += s[kNlAmp][i] * cos(s[kNlK][i] * x2 - s[kNlOmega][i] * t + s[kNlPhase][i]);
+                const double dc = DIR ? s[kDc][i] : 0.0, ds = DIR ? s[kDs][i] : 0.0;
+                eta0 += s[kNlAmp][i] * cos(kin_kx<DIR>(s[kNlK][i], x0, y0, dc, ds) - s[kNlOmega][i] * t + s[kNlPhase][i]);
+                eta1 += s[kNlAmp][i] * cos(kin_kx<DIR>(s[kNlK][i], x1, y1, dc, ds) - s[kNlOmega][i] * t + s[kNlPhase][i]);
+                eta2 += s[kNlAmp][i] * cos(kin_kx<DIR>(s[kNlK][i], x2, y2, dc, ds) - s[kNlOmega][i] * t + s[kNlPhase][i]);
             }
         }
     }
@@ -325,20 +346,21 @@ __device__ __forceinline__ void nl_tris_body(const NlArgs& a) {
         __syncthreads();
         for (int i = tid; i < m; i += kNlThreads) {
 #pragma unroll
-            for (int col = 0; col < kNlCols; ++col) s[col][i] = a.tab[col * a.nf + i0 + i];
+            for (int col = 0; col < (DIR ? kNlCols + kDirCols : kNlCols); ++col) s[col][i] = a.tab[col * a.nf + i0 + i];
         }
         __syncthreads();
         for (int i = 0; i < m; ++i) {
             const double k = s[kNlK][i];
+            const double dc = DIR ? s[kDc][i] : 0.0, ds = DIR ? s[kDs][i] : 0.0;
             double sn0 = 0.0, sn1 = 0.0, sn2 = 0.0, cs0, cs1, cs2;
             if constexpr (ORDER2) {
                 sincos(k * x0 - s[kNlOmega][i] * t + s[kNlPhase][i], &sn0, &cs0);
                 sincos(k * x1 - s[kNlOmega][i] * t + s[kNlPhase][i], &sn1, &cs1);
                 sincos(k * x2 - s[kNlOmega][i] * t + s[kNlPhase][i], &sn2, &cs2);
             } else {
-                cs0 = cos(k * x0 - s[kNlOmega][i] * t + s[kNlPhase][i]);
-                cs1 = cos(k * x1 - s[kNlOmega][i] * t + s[kNlPhase][i]);
-                cs2 = cos(k * x2 - s[kNlOmega][i] * t + s[kNlPhase][i]);
+                cs0 = cos(kin_kx<DIR>(k, x0, y0, dc, ds) - s[kNlOmega][i] * t + s[kNlPhase][i]);
+                cs1 = cos(kin_kx<DIR>(k, x1, y1, dc, ds) - s[kNlOmega][i] * t + s[kNlPhase][i]);
+                cs2 = cos(kin_kx<DIR>(k, x2, y2, dc, ds) - s[kNlOmega][i] * t + s[kNlPhase][i]);
             }
             double px0, px1, px2, pz0 = 0.0, pz1 = 0.0, pz2 = 0.0;
             if (s[kNlDeep][i] != 0.0) {  // (the same branch for every item: no divergence)
@@ -447,6 +469,7 @@ __device__ __forceinline__ void nl_tris_body(const NlArgs& a) {
 
 __global__ void __launch_bounds__(kNlThreads) nl_tris_kernel(NlArgs a) { nl_tris_body<false>(a); }
 __global__ void __launch_bounds__(kNlThreads) nl2_tris_kernel(NlArgs a) { nl_tris_body<true>(a); }
+__global__ void __launch_bounds__(kNlThreads) nl_tris_dir_kernel(NlArgs a) { nl_tris_body<false, true>(a); }
 
 struct Nl2Args {
     Wk2Sea sea;           // the nonlinear path's own tables (hc_ctx::nl2), mwl of the nonlinear options
@@ -585,11 +608,14 @@ void nonlinear_table(hc_ctx* c) {
     const std::vector<double> kin = kin_table_host(c, phase);
     const int nf = static_cast<int>(kin.size() / kKinCols);
     std::vector<double> tab(static_cast<size_t>(kNlCols) * nf);
+    const std::vector<double> dir = kin_dir_columns_host(c);
     const int from[kNlCols] = {kKinAmp, kKinOmega, kKinK, kKinPhase, kKinW2A, kKinInvSinh, kKinDeep};
     for (int col = 0; col < kNlCols; ++col)
         for (int i = 0; i < nf; ++i) tab[static_cast<size_t>(col) * nf + i] = kin[static_cast<size_t>(from[col]) * nf + i];
     for (int i = 0; i < nf; ++i) tab[static_cast<size_t>(kNlW2AoK) * nf + i] /= kin[static_cast<size_t>(kKinK) * nf + i];
+    tab.insert(tab.end(), dir.begin(), dir.end());
     c->d_nl_tab.upload(tab, c->stream_nl);
+    c->nl_dir    = !dir.empty();
     c->nl_nf     = nf;
     c->nl_serial = c->wave_serial;
     c->nl_phase  = phase;
@@ -667,6 +693,10 @@ void nonlinear_enqueue(hc_ctx* c, double t) {
             hipLaunchKernelGGL(nl2_tris_kernel, dim3(chunks), dim3(kNlThreads), 0, st, ar);
         else if (order2)
             hipLaunchKernelGGL(nl2_panels_kernel, dim3(chunks), dim3(kNlThreads), 0, st, ar);
+        else if (c->nl_dir && kind)
+            hipLaunchKernelGGL(nl_tris_dir_kernel, dim3(chunks), dim3(kNlThreads), 0, st, ar);
+        else if (c->nl_dir)
+            hipLaunchKernelGGL(nl_panels_dir_kernel, dim3(chunks), dim3(kNlThreads), 0, st, ar);
         else if (kind)
             hipLaunchKernelGGL(nl_tris_kernel, dim3(chunks), dim3(kNlThreads), 0, st, ar);
         else
@@ -838,6 +868,9 @@ int hc_nonlinear_begin(hc_ctx* c, double t, const double* pos, const double* rpy
     require(std::isfinite(t) && hc::all_finite(pos, n3) && hc::all_finite(rpy, n3), HC_ERR_INVALID, "non-finite time or state");
     require(c->gsys[0] == 0.0 && c->gsys[1] == 0.0 && c->gsys[2] < 0.0, HC_ERR_INVALID,
             "the nonlinear surface forces need gravity (0, 0, -g): z up");
+    require(!(c->nl2_on && !c->wave_dir.empty()), HC_ERR_UNSUPPORTED,
+            "the surface on the second-order sea is not available while wave directions are set (hc_set_wave_directions): clear the "
+            "directions or switch the second-order sea off");
     require(!(c->nl2_on && hc::wk2_has_components(c)) || hc::wk2_component_count(c) <= hc::kWk2MaxFreq, HC_ERR_UNSUPPORTED,
             "the surface on the second-order sea: more than 4096 wave components");
     // the host copy of the state: the kernel's source, and what hc_nonlinear_end computes hs_lin from (the caller's arrays are

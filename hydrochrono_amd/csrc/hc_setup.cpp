@@ -753,6 +753,7 @@ int hc_set_wave_none(hc_ctx* c, int num_bodies_arg) {
     HC_HIP(hipDeviceSynchronize());  // the tables replaced below may be in use by steps on a caller's stream
     require(c->finalized, HC_ERR_INVALID, "hc_finalize has not been called");
     require(num_bodies_arg >= 0, HC_ERR_INVALID, "negative body count");
+    c->wave_dir.clear();  // the new model is in force from here: its component count is another (hc_set_wave_directions)
     c->wave_kind   = hc::kWaveNone;
     c->wave_nb_arg = num_bodies_arg;
     c->eta_record  = false;
@@ -769,17 +770,15 @@ int hc_set_wave_regular(hc_ctx* c, int num_bodies_arg, double amplitude, double 
     require(num_bodies_arg >= 1 && num_bodies_arg <= c->N, HC_ERR_OUT_OF_RANGE, "regular wave created for more bodies than the hydro data holds");
     for (int b = 0; b < num_bodies_arg; ++b) require(c->bodies[b].have_rao, HC_ERR_INVALID, "excitation RAO missing for a body");
     // RegularWave::AddH5Data (src/wave_types.cpp:278-299), GetOmegaDelta (:329-333), Get*Interp (:335-352)
-    const auto& w0        = c->bodies[0].rao_w;
-    const double nfreq    = static_cast<double>(w0.size());
-    const double dw       = w0.back() / nfreq;
-    const double idx_des  = (omega / dw) - 1;
-    const double frac     = idx_des - std::floor(idx_des);
-    const int k0          = static_cast<int>(std::floor(idx_des));
+    const auto& w0      = c->bodies[0].rao_w;  // body 0's list serves every body, as in the reference
+    const RaoBracket br = rao_bracket_regular(omega, w0.back(), static_cast<int>(w0.size()));
+    const double frac   = br.fr;
+    const int k0        = br.k0;
     std::vector<double> mag(c->D, 0.0), ph(c->D, 0.0);
     for (int b = 0; b < num_bodies_arg; ++b) {
         const auto& bd = c->bodies[b];
         const int nw   = static_cast<int>(bd.rao_w.size());
-        if (k0 < 0 || k0 + 1 >= nw) throw Error(HC_ERR_OUT_OF_RANGE, "regular wave frequency outside the BEM frequency list");
+        rao_bracket_check(br, nw);
         for (int r = 0; r < 6; ++r) {
             const double m0 = bd.rao_mag[static_cast<size_t>(r) * nw + k0], m1 = bd.rao_mag[static_cast<size_t>(r) * nw + k0 + 1];
             const double p0 = bd.rao_phase[static_cast<size_t>(r) * nw + k0], p1 = bd.rao_phase[static_cast<size_t>(r) * nw + k0 + 1];
@@ -788,6 +787,7 @@ int hc_set_wave_regular(hc_ctx* c, int num_bodies_arg, double amplitude, double 
         }
     }
     const double k = hc::wave_number(omega, c->depth, c->g);  // RegularWave::Initialize (:274-276)
+    c->wave_dir.clear();  // the new model is in force from here: its component count is another (hc_set_wave_directions)
     c->reg_mag = mag;
     c->reg_phase = ph;
     c->reg_amp = amplitude;
@@ -881,6 +881,7 @@ int hc_set_wave_irregular(hc_ctx* c, const hc_irregular_wave_params* pp) {
     upload_excitation(c, ex);
     c->init.wave_upload_seconds += up_s + seconds_since(t_up2);
     c->init.wave_upload_bytes += 8.0 * (3.0 * nf + 3.0 * nt + 2.0 * static_cast<double>(c->Dloc) * L + 2.0 * L);
+    c->wave_dir.clear();  // the new model is in force from here: its component count is another (hc_set_wave_directions)
     c->irr = p;
     c->nf = nf;
     c->nt = nt;
@@ -917,13 +918,10 @@ int hc_set_wave_irregular_spectral(hc_ctx* c, const hc_irregular_wave_params* pp
     for (int bl = 0; bl < c->nloc; ++bl) {
         const auto& bd  = c->bodies[c->b0 + bl];
         const int nw    = static_cast<int>(bd.rao_w.size());
-        const double dw = bd.rao_w.back() / static_cast<double>(nw);
         for (int i = 0; i < sp.nf; ++i) {
-            double idx = sp.omega[i] / dw - 1;
-            idx        = std::min(std::max(idx, 0.0), static_cast<double>(nw - 1));
-            const int k0 = std::min(static_cast<int>(std::floor(idx)), nw - 2 >= 0 ? nw - 2 : 0);
-            const int k1 = std::min(k0 + 1, nw - 1);
-            const double fr = idx - k0;
+            const RaoBracket br = rao_bracket_clamped(sp.omega[i], bd.rao_w.back(), nw);
+            const int k0 = br.k0, k1 = br.k1;
+            const double fr = br.fr;
             for (int r = 0; r < 6; ++r) {
                 const double m0 = bd.rao_mag[static_cast<size_t>(r) * nw + k0], m1 = bd.rao_mag[static_cast<size_t>(r) * nw + k1];
                 const double p0 = bd.rao_phase[static_cast<size_t>(r) * nw + k0], p1 = bd.rao_phase[static_cast<size_t>(r) * nw + k1];
@@ -937,6 +935,7 @@ int hc_set_wave_irregular_spectral(hc_ctx* c, const hc_irregular_wave_params* pp
     c->d_spec_amp.upload(sp.amp, c->stream);
     c->d_spec_omega.upload(sp.omega, c->stream);
     c->d_spec_phi.upload(sp.phase, c->stream);
+    c->wave_dir.clear();  // the new model is in force from here: its component count is another (hc_set_wave_directions)
     c->irr = p;
     c->nf  = sp.nf;
     c->L = c->Lpad = c->nt = 0;

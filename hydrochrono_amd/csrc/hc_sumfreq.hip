@@ -277,6 +277,8 @@ int hc_sum_qtf_begin(hc_ctx* c, double t, const double* pos) {
     require(!c->sum_pending, HC_ERR_INVALID, "hc_sum_qtf_begin twice without hc_sum_qtf_end");
     require(pos != nullptr, HC_ERR_INVALID, "null state");
     require(std::isfinite(t) && hc::all_finite(pos, 3 * static_cast<size_t>(c->N)), HC_ERR_INVALID, "non-finite time or position");
+    require(c->sum_mode == 0 || c->wave_dir.empty(), HC_ERR_UNSUPPORTED,
+            "the QTF tables hold one heading: sum-frequency forces are not available while wave directions are set (hc_set_wave_directions)");
     bool any = false;
     if (!c->sum_tabs.empty())
         for (int b = c->b0; b < c->b1; ++b) any = any || c->sum_tabs[b].nq != 0;

@@ -47,6 +47,16 @@ std::vector<double> kin_table_host(const hc_ctx* c, double regular_phase) {
     return tab;
 }
 
+std::vector<double> kin_dir_columns_host(const hc_ctx* c) {
+    const size_t nf = c->wave_dir.size();
+    std::vector<double> col(kDirCols * nf);
+    for (size_t i = 0; i < nf; ++i) {
+        col[i]      = std::cos(c->wave_dir[i]);
+        col[nf + i] = std::sin(c->wave_dir[i]);
+    }
+    return col;
+}
+
 namespace {
 
 constexpr int kKinThreads = 256;  // work items per workgroup, one per (point, time)
@@ -54,7 +64,7 @@ constexpr int kKinThreads = 256;  // work items per workgroup, one per (point, t
 constexpr long long kKinMaxItems = (1LL << 31) - kKinThreads;
 
 struct KinArgs {
-    const double* tab;  // [kKinCols][nf]
+    const double* tab;  // [kKinCols][nf]; the directional instantiation: [kKinCols + kDirCols][nf]
     int nf;
     int P, T;
     const double* xyz;  // [P][3]
@@ -70,14 +80,19 @@ struct KinArgs {
 // One work item per (point, time), item o = j * P + p.  Every item sums the components in index order from the same LDS tiles, so
 // its bits do not depend on P, T or where in the grid it sits.  With stretching, eta is summed first (the reference's
 // GetEtaIrregular) and the kinematics are evaluated at the stretched z in a second pass.
+// DIR: every component has a direction; its cos and sin are staged behind the other columns, the phase is taken
+// at k (x cos + y sin) and the horizontal velocity and acceleration are laid along (cos, sin).  Everything else is the code of the
+// long-crested instantiation, whose arithmetic is unchanged.
+template <bool DIR>
 __global__ void __launch_bounds__(kKinThreads) wave_kinematics_kernel(KinArgs a) {
-    __shared__ double s[kKinCols][kKinTile];
+    constexpr int kDc = kKinCols, kDs = kKinCols + 1;  // rows of the direction columns (DIR only)
+    __shared__ double s[DIR ? kKinCols + kDirCols : kKinCols][kKinTile];
     const long long n  = static_cast<long long>(a.P) * a.T;
     const long long o  = static_cast<long long>(blockIdx.x) * kKinThreads + threadIdx.x;
     const bool active  = o < n;
     const long long oc = active ? o : 0;  // items past the end evaluate item 0 and store nothing (all take part in the staging)
     const int p = static_cast<int>(oc % a.P), j = static_cast<int>(oc / a.P);
-    const double x = a.xyz[3 * p], z = a.xyz[3 * p + 2], t = a.t[j];
+    const double x = a.xyz[3 * p], y = DIR ? a.xyz[3 * p + 1] : 0.0, z = a.xyz[3 * p + 2], t = a.t[j];
     const bool want_kin = a.vel || a.acc;
 
     // ---- eta = sum_i A_i cos(k_i x - w_i t + phi_i)  (src/wave_types.cpp:14-44; the expression of eta_kernel at x = 0) ----
@@ -91,9 +106,15 @@ __global__ void __launch_bounds__(kKinThreads) wave_kinematics_kernel(KinArgs a)
                 s[kKinOmega][i] = a.tab[kKinOmega * a.nf + i0 + i];
                 s[kKinK][i]     = a.tab[kKinK * a.nf + i0 + i];
                 s[kKinPhase][i] = a.tab[kKinPhase * a.nf + i0 + i];
+                if constexpr (DIR) {
+                    s[kDc][i] = a.tab[kDc * a.nf + i0 + i];
+                    s[kDs][i] = a.tab[kDs * a.nf + i0 + i];
+                }
             }
             __syncthreads();
-            for (int i = 0; i < m; ++i) eta += s[kKinAmp][i] * cos(s[kKinK][i] * x - s[kKinOmega][i] * t + s[kKinPhase][i]);
+            for (int i = 0; i < m; ++i)
+                eta += s[kKinAmp][i] *
+                       cos(kin_kx<DIR>(s[kKinK][i], x, y, DIR ? s[kDc][i] : 0.0, DIR ? s[kDs][i] : 0.0) - s[kKinOmega][i] * t + s[kKinPhase][i]);
         }
     }
     if (!want_kin) {  // (uniform over the launch)
@@ -110,19 +131,20 @@ __global__ void __launch_bounds__(kKinThreads) wave_kinematics_kernel(KinArgs a)
     const double ze = zs - a.mwl;  // under stretching mwl is subtracted a second time, as in the reference
 
     // ---- velocity and acceleration (:61-158) ----
-    double ux = 0.0, uz = 0.0, ax = 0.0, az = 0.0;
+    double ux = 0.0, uy = 0.0, uz = 0.0, ax = 0.0, ay = 0.0, az = 0.0;
     for (int i0 = 0; i0 < a.nf; i0 += kKinTile) {
         const int m = min(kKinTile, a.nf - i0);
         __syncthreads();
         for (int i = threadIdx.x; i < m; i += kKinThreads) {
 #pragma unroll
-            for (int col = kKinOmega; col < kKinCols; ++col) s[col][i] = a.tab[col * a.nf + i0 + i];
+            for (int col = kKinOmega; col < (DIR ? kKinCols + kDirCols : kKinCols); ++col) s[col][i] = a.tab[col * a.nf + i0 + i];
         }
         __syncthreads();
         for (int i = 0; i < m; ++i) {
             const double k = s[kKinK][i];
+            const double dc = DIR ? s[kDc][i] : 0.0, ds = DIR ? s[kDs][i] : 0.0;
             double sn, cs;
-            sincos(k * x - s[kKinOmega][i] * t + s[kKinPhase][i], &sn, &cs);
+            sincos(kin_kx<DIR>(k, x, y, dc, ds) - s[kKinOmega][i] * t + s[kKinPhase][i], &sn, &cs);
             double px, pz;
             if (s[kKinDeep][i] != 0.0) {  // (the same branch for every item: no divergence)
                 px = pz = exp(k * ze);
@@ -132,9 +154,17 @@ __global__ void __launch_bounds__(kKinThreads) wave_kinematics_kernel(KinArgs a)
                 pz = sinh(q) * s[kKinInvSinh][i];
             }
             const double wa = s[kKinWA][i], w2a = s[kKinW2A][i];
-            ux += wa * px * cs;
+            if constexpr (DIR) {
+                const double uh = wa * px * cs, ah = w2a * px * sn;
+                ux += uh * dc;
+                uy += uh * ds;
+                ax += ah * dc;
+                ay += ah * ds;
+            } else {
+                ux += wa * px * cs;
+                ax += w2a * px * sn;
+            }
             uz += wa * pz * sn;
-            ax += w2a * px * sn;
             az -= w2a * pz * cs;
         }
     }
@@ -142,12 +172,12 @@ __global__ void __launch_bounds__(kKinThreads) wave_kinematics_kernel(KinArgs a)
     if (a.eta) a.eta[o] = eta;
     if (a.vel) {
         a.vel[3 * o]     = ux;
-        a.vel[3 * o + 1] = 0.0;
+        a.vel[3 * o + 1] = uy;
         a.vel[3 * o + 2] = uz;
     }
     if (a.acc) {
         a.acc[3 * o]     = ax;
-        a.acc[3 * o + 1] = 0.0;
+        a.acc[3 * o + 1] = ay;
         a.acc[3 * o + 2] = az;
     }
 }
@@ -157,9 +187,12 @@ __global__ void __launch_bounds__(kKinThreads) wave_kinematics_kernel(KinArgs a)
 void kin_table(hc_ctx* c, double regular_phase) {
     const bool regular = c->wave_kind == kWaveRegular;
     if (c->kin_serial == c->wave_serial && (!regular || std::memcmp(&c->kin_phase, &regular_phase, sizeof(double)) == 0)) return;
-    const std::vector<double> tab = kin_table_host(c, regular_phase);
+    std::vector<double> tab = kin_table_host(c, regular_phase);
+    c->kin_nf = static_cast<int>(tab.size() / kKinCols);
+    const std::vector<double> dir = kin_dir_columns_host(c);
+    tab.insert(tab.end(), dir.begin(), dir.end());
     c->d_kin_tab.upload(tab, c->stream);
-    c->kin_nf     = static_cast<int>(tab.size() / kKinCols);
+    c->kin_dir    = !dir.empty();
     c->kin_serial = c->wave_serial;
     c->kin_phase  = regular_phase;
 }
@@ -192,8 +225,10 @@ int hc_wave_kinematics(hc_ctx* c, const hc_wave_kinematics_opts* opts, int n_poi
     require(std::isfinite(o.mwl) && std::isfinite(o.regular_phase), HC_ERR_INVALID, "non-finite mwl or regular_phase");
     require(n_points >= 0 && n_times >= 0, HC_ERR_INVALID, "negative point or time count");
     require((n_points == 0 || xyz) && (n_times == 0 || t), HC_ERR_INVALID, "null points or times");
+    const bool dir = !c->wave_dir.empty();  // y enters the phase
     for (int p = 0; p < n_points; ++p)
-        require(std::isfinite(xyz[3 * p]) && std::isfinite(xyz[3 * p + 2]), HC_ERR_INVALID, "non-finite x or z of a point");
+        require(std::isfinite(xyz[3 * p]) && std::isfinite(xyz[3 * p + 2]) && (!dir || std::isfinite(xyz[3 * p + 1])), HC_ERR_INVALID,
+                dir ? "non-finite coordinate of a point" : "non-finite x or z of a point");
     for (int j = 0; j < n_times; ++j) require(std::isfinite(t[j]), HC_ERR_INVALID, "non-finite time");
     const long long n = static_cast<long long>(n_points) * n_times;
     require(n <= hc::kKinMaxItems, HC_ERR_INVALID, "too many (point, time) pairs for one call");
@@ -236,7 +271,10 @@ int hc_wave_kinematics(hc_ctx* c, const hc_wave_kinematics_opts* opts, int n_poi
     HC_HIP(hipMemcpyAsync(d_xyz, xyz, 3 * static_cast<size_t>(n_points) * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HC_HIP(hipMemcpyAsync(d_t, t, static_cast<size_t>(n_times) * sizeof(double), hipMemcpyHostToDevice, c->stream));
     const unsigned blocks = static_cast<unsigned>((n + hc::kKinThreads - 1) / hc::kKinThreads);
-    hipLaunchKernelGGL(hc::wave_kinematics_kernel, dim3(blocks), dim3(hc::kKinThreads), 0, c->stream, a);
+    if (c->kin_dir)
+        hipLaunchKernelGGL(hc::wave_kinematics_kernel<true>, dim3(blocks), dim3(hc::kKinThreads), 0, c->stream, a);
+    else
+        hipLaunchKernelGGL(hc::wave_kinematics_kernel<false>, dim3(blocks), dim3(hc::kKinThreads), 0, c->stream, a);
     HC_HIP(hipGetLastError());
     if (eta) HC_HIP(hipMemcpyAsync(eta, a.eta, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
     if (vel) HC_HIP(hipMemcpyAsync(vel, a.vel, 3 * n * sizeof(double), hipMemcpyDeviceToHost, c->stream));

@@ -27,4 +27,18 @@ enum KinCol {
 // for an imported eta record (no spectrum).
 std::vector<double> kin_table_host(const hc_ctx* c, double regular_phase);
 
+// The two direction columns [2][nf] (cos theta_i, then sin theta_i) of the directions in force (hc_set_wave_directions); empty when
+// none are set.  A path that sums the directional sea appends them behind its own table's columns.
+constexpr int kDirCols = 2;
+std::vector<double> kin_dir_columns_host(const hc_ctx* c);
+
+// k (x cos + y sin) of the directional instantiations / k x of the long-crested ones, whose expression stays the one it was
+template <bool DIR>
+__host__ __device__ __forceinline__ double kin_kx(double k, double x, double y, double dc, double ds) {
+    if constexpr (DIR)
+        return k * (x * dc + y * ds);
+    else
+        return k * x;
+}
+
 }  // namespace hc

@@ -205,6 +205,8 @@ int hc_wave_kinematics2(hc_ctx* c, const hc_wave_kinematics2_opts* opts, int n_p
     const char* bad = hc::wk2_check_batch(n_points, xyz, n_times, t);
     require(bad == nullptr, HC_ERR_INVALID, bad ? bad : "");
     const bool waves = hc::wk2_has_components(c);
+    require(c->wave_dir.empty(), HC_ERR_UNSUPPORTED,
+            "the second-order sea is long-crested: not available while wave directions are set (hc_set_wave_directions)");
     require(!waves || hc::wk2_component_count(c) <= hc::kWk2MaxFreq, HC_ERR_UNSUPPORTED, "more than 4096 wave components");
     const size_t n = static_cast<size_t>(n_points) * n_times;
     if (n == 0 || !(eta || vel || acc)) return HC_OK;

@@ -470,6 +470,41 @@ class HydroForces:
                                               _dp(vel.reshape(-1)), _dp(acc.reshape(-1))))
         return eta, vel, acc
 
+    # -- wave heading and short-crested seas (an extension beyond the reference, which ignores waves.direction) --
+    def set_wave_directions(self, theta=None):
+        """One direction [rad, 0 along +x, positive towards +y] per component of the wave model in force (1 for a regular wave, else
+        nf); None or empty clears them.  Every add_waves_* call drops them.  See hc_set_wave_directions in include/hydrochrono_amd.h."""
+        th = np.zeros(0) if theta is None else _arr(theta)
+        self._chk(self.lib.hc_set_wave_directions(self.ctx, th.size, _dp(th) if th.size else None))
+
+    def wave_directions(self):
+        """The directions in force, (n,); empty when none are set."""
+        n = C.c_int()
+        self._chk(self.lib.hc_get_wave_directions(self.ctx, C.byref(n), None))
+        th = np.empty(n.value)
+        if n.value:
+            self._chk(self.lib.hc_get_wave_directions(self.ctx, C.byref(n), _dp(th)))
+        return th
+
+    def set_wave_spreading(self, heading, s=0.0, n_bins=15, seed=1):
+        """Equal-energy directions of the cos-2s spreading about `heading` for the wave model in force (s <= 0: the uniform heading),
+        then set_wave_directions.  Returns the directions."""
+        th = wave_spreading_directions(self.wave_component_count(), heading, s, n_bins, seed, lib=self.lib)
+        self.set_wave_directions(th)
+        return th
+
+    def set_body_excitation_rao_headings(self, b, dirs, w, mag, phase):
+        """Excitation coefficients of body b on a grid of headings: dirs (n_dir,) strictly increasing [rad], w (nw,), mag and phase
+        (6, n_dir, nw), the layout of a BEMIO file; empty dirs remove them."""
+        dirs, w = _arr(dirs), _arr(w)
+        mag, phase = _arr(mag, 6 * dirs.size * w.size), _arr(phase, 6 * dirs.size * w.size)
+        self._chk(self.lib.hc_set_excitation_rao_headings(self.ctx, b, dirs.size, _dp(dirs), _dp(w), w.size, _dp(mag), _dp(phase)))
+
+    def excitation_rao_headings_size(self, b):
+        nd, nw = C.c_int(), C.c_int()
+        self._chk(self.lib.hc_get_excitation_rao_headings_size(self.ctx, b, C.byref(nd), C.byref(nw)))
+        return nd.value, nw.value
+
     # -- second-order irregular waves (Sharma and Dean; an extension beyond the reference) --
     def _wave2_opts(self, mwl, regular_phase, diff_band, sum_band, apply_ramp):
         o = capi.WaveKinematics2Opts()
@@ -818,6 +853,16 @@ class HydroForces:
         return np.zeros(self.D_local) if m is None or not self._sum_on() else m.copy()
 
 
+def wave_spreading_directions(nf, heading, s=0.0, n_bins=15, seed=1, lib=None):
+    """hc_wave_spreading_directions: nf equal-energy directions of the cos-2s spreading about `heading` (no context needed)."""
+    lib = lib or capi.load()
+    th = np.empty(int(nf))
+    rc = lib.hc_wave_spreading_directions(int(nf), float(heading), float(s), int(n_bins), int(seed), _dp(th))
+    if rc != capi.HC_OK:
+        raise HydroError(rc, "hc_wave_spreading_directions: bad arguments")
+    return th
+
+
 def triangles_to_panels(triangles):
     """Centroids and area vectors of triangles [n][3][3]."""
     tri = np.ascontiguousarray(triangles, dtype=np.float64).reshape(-1, 3, 3)
@@ -1128,6 +1173,16 @@ class HydroGroup:
     def components(self):
         parts = [h.components() for h in sorted(self.shards, key=lambda h: h.b0)]
         return tuple(np.concatenate([p[k] for p in parts]) for k in range(3))
+
+    def wave_directions(self):
+        return self.shards[0].wave_directions()
+
+    def set_wave_spreading(self, heading, s=0.0, n_bins=15, seed=1):
+        """As HydroForces.set_wave_spreading: the directions are generated once, set on every shard and returned."""
+        th = wave_spreading_directions(self.shards[0].wave_component_count(), heading, s, n_bins, seed, lib=self.lib)
+        for h in self.shards:
+            h.set_wave_directions(th)
+        return th
 
     def wave_kinematics(self, points, times, **opts):
         # every shard holds the whole wave model and answers with the same bits

@@ -310,6 +310,40 @@ class TestHydro {
         for (hc_ctx* c : ctxs_) check(c, hc_set_morison_options(c, &o));
         have_time_ = false;
     }
+    // Wave heading and short-crested seas (not in the reference; include/hydrochrono_amd.h: hc_set_wave_directions): one direction
+    // [rad] per component of the wave model in force, on every shard context; the wave object keeps them (wave_directions_) across a
+    // later AddWaves of the same object; an empty vector clears them.  The kinematics, the Morison elements, the
+    // nonlinear surface forces and -- with SetExcitationRAOHeadings -- the first-order excitation then follow the heading; the
+    // second-order terms and both QTF terms throw from CoordinateFuncForBody while directions are set.
+    void SetWaveDirections(const std::vector<double>& theta_rad) {
+        if (!user_waves_) throw std::runtime_error("SetWaveDirections: no wave model (AddWaves)");
+        for (hc_ctx* c : ctxs_)
+            check(c, hc_set_wave_directions(c, static_cast<int>(theta_rad.size()), theta_rad.empty() ? nullptr : theta_rad.data()));
+        user_waves_->wave_directions_ = theta_rad;
+        have_time_ = false;  // the cached total belongs to the sea before
+    }
+    std::vector<double> GetWaveDirections() const {
+        if (!user_waves_) return {};
+        return user_waves_->GetDirections();
+    }
+    std::vector<double> SetWaveSpreading(double heading_rad, double s = 0.0, int n_bins = 15, unsigned long long seed = 1) {
+        if (!user_waves_) throw std::runtime_error("SetWaveSpreading: no wave model (AddWaves)");
+        const std::vector<double> th = user_waves_->SpreadingDirections(heading_rad, s, n_bins, seed);
+        SetWaveDirections(th);
+        return th;
+    }
+    // Excitation coefficients of a body on a grid of headings (hc_set_excitation_rao_headings): dirs [n_dir] strictly increasing,
+    // mag / phase [6][n_dir][nw] as in a BEMIO file; empty dirs remove them.  The body index is 1-based.
+    void SetExcitationRAOHeadings(int body_index_1_based, const std::vector<double>& dirs_rad, const std::vector<double>& w,
+                                  const std::vector<double>& mag, const std::vector<double>& phase) {
+        if (body_index_1_based < 1 || body_index_1_based > num_bodies_) throw std::out_of_range("SetExcitationRAOHeadings: body index out of range");
+        const size_t len = 6 * dirs_rad.size() * w.size();
+        if (mag.size() != len || phase.size() != len) throw std::invalid_argument("SetExcitationRAOHeadings: mag and phase must hold 6 * n_dir * nw values");
+        for (hc_ctx* c : ctxs_)
+            check(c, hc_set_excitation_rao_headings(c, body_index_1_based - 1, static_cast<int>(dirs_rad.size()), dirs_rad.data(), w.data(),
+                                                    static_cast<int>(w.size()), mag.data(), phase.data()));
+        have_time_ = false;
+    }
     // The elements on the second-order sea (hc_set_morison_second_order): the increments of WaveBase::GetSecondOrder* at every
     // element, added before the wet test and the force; the cut-offs [rad/s] are as in WaveBase::second_order_, mwl and the
     // regular phase those of SetMorisonOptions.  Applied to every shard context; on = false frees the tables.

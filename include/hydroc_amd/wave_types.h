@@ -157,6 +157,36 @@ class WaveBase {  // :52-79
         kinematics2(static_cast<int>(points.size()), points.empty() ? nullptr : points[0].data(), static_cast<int>(times.size()),
                     times.data(), eta2 ? eta2->data() : nullptr, vel2 ? vel2->data() : nullptr, acc2 ? acc2->data() : nullptr);
     }
+    // Wave heading and short-crested seas (hc_set_wave_directions; not in the reference, which ignores waves.direction): one
+    // direction [rad, 0 along +x, positive towards +y] per component of the model -- 1 for a RegularWave, the number of spectrum
+    // components for IrregularWaves (whose IRF model takes a uniform heading only).  The member is applied at the end of every Attach
+    // (the library drops the directions with every new wave model); SetDirections also applies it to the context of the getters --
+    // a sharded system sets them through TestHydro::SetWaveDirections, which reaches every shard.  GetElevation / GetVelocity / GetAcceleration, the Morison elements and the nonlinear surface forces then
+    // sample the directional sea; the second-order getters throw while directions are set.  Empty: the long-crested sea along +x.
+    std::vector<double> wave_directions_;
+    void SetDirections(const std::vector<double>& theta_rad) {
+        if (ctx_)  // (an error leaves the member as it was)
+            check(ctx_, hc_set_wave_directions(ctx_, static_cast<int>(theta_rad.size()), theta_rad.empty() ? nullptr : theta_rad.data()));
+        wave_directions_ = theta_rad;
+    }
+    // the directions in force on the context of the getters (empty: none); not attached: the member
+    std::vector<double> GetDirections() const {
+        if (!ctx_) return wave_directions_;
+        int n = 0;
+        check(ctx_, hc_get_wave_directions(ctx_, &n, nullptr));
+        std::vector<double> th(static_cast<size_t>(n));
+        if (n) check(ctx_, hc_get_wave_directions(ctx_, &n, th.data()));
+        return th;
+    }
+    // equal-energy directions of the cos-2s spreading about `heading_rad` for the attached model (hc_wave_spreading_directions),
+    // for SetDirections / TestHydro::SetWaveDirections; s <= 0: the uniform heading.
+    std::vector<double> SpreadingDirections(double heading_rad, double s = 0.0, int n_bins = 15, unsigned long long seed = 1) {
+        if (!ctx_) throw std::runtime_error("wave model is not attached to a TestHydro");
+        std::vector<double> th(static_cast<size_t>(ComponentCount()));
+        if (hc_wave_spreading_directions(static_cast<int>(th.size()), heading_rad, s, n_bins, seed, th.data()) != HC_OK)
+            throw std::runtime_error("SpreadingDirections: no bin, or a non-finite heading or exponent");
+        return th;
+    }
     double mwl_ = 0.0, g_ = 9.81, water_depth_ = 0.0;  // public members of the reference's base class (:74-78); unused by the force path
 
   protected:
@@ -172,6 +202,13 @@ class WaveBase {  // :52-79
     void attached(hc_ctx* ctx) {
         ctx_ = ctx;
         check(ctx, hc_get_simulation_parameters(ctx, nullptr, &g_, &water_depth_));
+        if (!wave_directions_.empty()) check(ctx, hc_set_wave_directions(ctx, static_cast<int>(wave_directions_.size()), wave_directions_.data()));
+    }
+    // components of the attached model as the kinematics see them: the spectrum's; RegularWave 1, NoWave 0
+    virtual int ComponentCount() const {
+        int nf = 0;
+        check(ctx_, hc_get_sizes(ctx_, nullptr, nullptr, nullptr, nullptr, &nf, nullptr, nullptr, nullptr));
+        return nf;
     }
 
   private:
@@ -210,6 +247,9 @@ class NoWave : public WaveBase {  // :84-104
         attached(ctx);
     }
 
+  protected:
+    int ComponentCount() const override { return 0; }
+
   private:
     unsigned int num_bodies_;
 };
@@ -234,6 +274,7 @@ class RegularWave : public WaveBase {  // :109-158
         o.regular_phase           = regular_wave_phase_;
         return o;
     }
+    int ComponentCount() const override { return 1; }
 
   private:
     unsigned int num_bodies_;

@@ -501,7 +501,9 @@ int hc_get_simulation_parameters(hc_ctx* ctx, double* rho, double* g, double* wa
  *   z_s = depth (z' - eta) / (depth + eta) (Wheeler), from which the profile subtracts mwl once more, as the reference does; for
  *   an infinite depth (where the reference gives NaN) at the limit z_s = z' - eta.
  *   NoWave (include/hydroc/wave_types.h:103-109), or no wave model: zeros, no launch.
- * Not ramped (the eta(t) table is; kinematics are not); the wave direction is ignored (only x enters the phase).
+ * Not ramped (the eta(t) table is; kinematics are not).  Without directions (hc_set_wave_directions below) the sea runs along +x
+ * and only x enters the phase, as in the reference, which ignores waves.direction; with directions every component has its own
+ * and y enters as well.
  * ---------------------------------------------------------------------------------------------- */
 typedef struct hc_wave_kinematics_opts {
     double mwl;            /* WaveBase::mwl_ (0) */
@@ -511,11 +513,60 @@ typedef struct hc_wave_kinematics_opts {
 void hc_wave_kinematics_opts_default(hc_wave_kinematics_opts* o);
 /* xyz[n_points][3], t[n_times] -> eta[T][P], vel[T][P][3], acc[T][P][3]; any output may be NULL, o NULL = the defaults.
  * Synchronous on the context's stream; needs hc_finalize.  Counts must be >= 0 and a pointer is required where its count is > 0;
- * non-finite x, z or t, non-finite options, or more than 2^31 - 256 (point, time) pairs give HC_ERR_INVALID.  Every output sums
+ * non-finite x, z or t (and y while wave directions are set), non-finite options, or more than 2^31 - 256 (point, time) pairs give HC_ERR_INVALID.  Every output sums
  * the components in index order on its own, so its bits do not depend on the batch it is part of, nor on which shard context of
  * the system answers.  Changes no force and no step state. */
 int hc_wave_kinematics(hc_ctx* ctx, const hc_wave_kinematics_opts* o, int n_points, const double* xyz,
                        int n_times, const double* t, double* eta, double* vel, double* acc);
+
+/* ------------------------------------------------------------------------------------------------
+ * Wave heading and short-crested seas (not in the reference, which parses waves.direction and ignores it: src/wave_types.cpp:20,34):
+ * one direction per component of the wave model in force, the single-direction-per-frequency ("equal-energy") method.  Opt-in; with
+ * no directions set every result keeps the bits it had.  theta_i in radians, 0 along +x, positive towards +y.  Per component, with
+ * psi_i = k_i (x cos theta_i + y sin theta_i) - w_i t + phi_i:
+ *     eta = sum A_i cos psi_i,   u_h = w A p_x cos psi_i,   velocity = (u_h cos theta_i, u_h sin theta_i, w A p_z sin psi_i),
+ *     a_h = w^2 A p_x sin psi_i, acceleration = (a_h cos theta_i, a_h sin theta_i, -w^2 A p_z cos psi_i)
+ * with the profiles p_x, p_z, the stretching, the mwl rule, the infinite-depth limit and the ramps of the long-crested sums.
+ * hc_wave_kinematics, the Morison elements and the nonlinear surface forces (panels and clipped triangles) sample this sea.
+ *
+ * hc_set_wave_directions: n = the component count (1 for a regular wave, nf for hc_set_wave_irregular and
+ * hc_set_wave_irregular_spectral); n == 0 or theta == NULL clears the directions.  HC_ERR_INVALID: a wrong n, a non-finite angle,
+ * NoWave, no model or an imported eta record (no components), a direction outside a body's heading grid, or non-uniform directions
+ * on the spectral model while a local body has no heading tables.  HC_ERR_UNSUPPORTED: non-uniform directions on the IRF model of
+ * hc_set_wave_irregular -- its excitation is one convolution of eta(0, t), which a spread sea does not have: use
+ * hc_set_wave_irregular_spectral.  A uniform heading is accepted there; the caller's excitation IRF is then understood to be the one
+ * of that heading, and no step state is touched.  A failed call changes nothing.
+ * EVERY hc_set_wave_* call that succeeds drops the directions (the component count changes with the model): set the wave model
+ * first, then the directions.  A call that fails on its arguments leaves the model in force, its directions and the excitation
+ * tables built for them as they were.
+ * hc_get_wave_directions: *n = the count (0: none set); theta may be NULL (size query).
+ *
+ * What refuses while directions are set (HC_ERR_UNSUPPORTED from the compute / begin call, nothing stays pending; as before once
+ * they are cleared): hc_wave_kinematics2, the Morison elements and the nonlinear surface on the second-order sea
+ * (hc_set_morison_second_order / hc_set_nonlinear_second_order with `on`), hc_drift_begin with a drift mode != 0 and
+ * hc_sum_qtf_begin with a sum mode != 0: their pair sums and QTF tables are those of one long-crested heading.
+ *
+ * First-order excitation under a heading: hc_set_excitation_rao_headings gives a body its excitation coefficients on a grid of
+ * headings, dir_rad[n_dir] strictly increasing, mag / phase [6][n_dir][nw] (the layout of a BEMIO file; magnitudes per rho g as for
+ * hc_set_excitation_rao); n_dir == 0 removes them; allowed before and after hc_finalize.  While directions are set on the spectral
+ * model or on a regular wave, the per-row x per-component (magnitude, phase) table of every body with heading tables is the omega
+ * interpolation of that model at the two bracketing headings, then linear in the heading on the phases as given; a direction on a
+ * grid node has weight exactly 0 on its neighbour.  No extrapolation and no wrap-around: a caller who wants the full circle supplies
+ * both ends.  A body without heading tables keeps its {6,1,nw} table under a uniform heading.  The tables are replaced under the
+ * synchronisation of hc_set_wave_irregular_spectral (the look-ahead excitation rows are dropped).
+ *
+ * hc_wave_spreading_directions needs no context: equal-energy directions of the cos-2s spreading
+ * D(theta) ~ cos^{2s}((theta - heading) / 2) on (heading - pi, heading + pi).  Bin m of n_bins has direction
+ * heading + G^-1((m + 1/2) / n_bins), G the cumulative distribution of D; every run of n_bins consecutive components takes every
+ * bin once, in a permutation drawn from `seed` by a counter-based generator (the same output on every platform).  s <= 0 or
+ * n_bins == 1: theta_i = heading.  HC_ERR_INVALID: nf < 0, n_bins < 1, non-finite heading or s, NULL output with nf > 0.
+ * ---------------------------------------------------------------------------------------------- */
+int hc_set_wave_directions(hc_ctx* ctx, int n, const double* theta_rad);
+int hc_get_wave_directions(hc_ctx* ctx, int* n, double* theta_rad);
+int hc_set_excitation_rao_headings(hc_ctx* ctx, int body, int n_dir, const double* dir_rad, const double* w, int nw,
+                                   const double* mag_6xndirxnw, const double* phase_6xndirxnw);
+int hc_get_excitation_rao_headings_size(hc_ctx* ctx, int body, int* n_dir, int* nw);
+int hc_wave_spreading_directions(int nf, double heading_rad, double s, int n_bins, unsigned long long seed, double* theta_out);
 
 /* ------------------------------------------------------------------------------------------------
  * Morison drag and inertia elements (not in the reference, which has none: src/hydro_types.h:34): an opt-in additional force
@@ -748,7 +799,8 @@ int hc_get_nonlinear_increments(hc_ctx* ctx, int body, int n, double* p /* [n][3
  * under the same conditions: the two synthesised irregular models are ramped, a regular wave is not.
  * NoWave, no wave model, an imported eta record (no components), mode 0: zeros, no launch.  A body without a table: zeros.
  * World frame, at the body reference, the sign of an applied force.  A regular wave gives the constant A^2 T(w, w).
- * Sum-frequency QTFs are a term of their own (hc_set_sum_qtf below); wave headings are not covered.
+ * Sum-frequency QTFs are a term of their own (hc_set_sum_qtf below).  The tables hold one heading: while wave directions are set
+ * (hc_set_wave_directions) hc_drift_begin with a mode != 0 returns HC_ERR_UNSUPPORTED.
  *
  * The device evaluates the exact projected form, O(nf + nq^2) per row: with u_i = A_i cos theta_i, w_i = A_i sin theta_i,
  * U_m = sum_i W[i][m] u_i, V_m = sum_i W[i][m] w_i,
@@ -800,7 +852,8 @@ int hc_compute_drift(hc_ctx* ctx, double t, const double* pos, double* out_Dloca
  * are ramped, a regular wave is not; a regular wave gives A^2 [P_s(w, w) cos 2 theta - Q_s(w, w) sin 2 theta].
  * NoWave, no wave model, an imported eta record (no components), mode 0: zeros, no launch.  A body without a table: zeros.
  * World frame, at the body reference, the sign of an applied force.
- * There is no cut-off band on w_i + w_j: a caller who wants one zeroes table entries.  Wave headings are not covered.
+ * There is no cut-off band on w_i + w_j: a caller who wants one zeroes table entries.  The tables hold one heading: while wave
+ * directions are set (hc_set_wave_directions) hc_sum_qtf_begin with a mode != 0 returns HC_ERR_UNSUPPORTED.
  *
  * The device evaluates the exact projected form, O(nf + nq^2) per row, with the U_m, V_m of the drift term:
  *     F_s = sum_mn P_s[m][n] (U_m U_n - V_m V_n) - Q_s[m][n] (V_m U_n + U_m V_n)
