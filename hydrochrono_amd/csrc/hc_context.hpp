@@ -115,11 +115,33 @@ struct Wk2TableSet {
     }
 };
 
-// A body's difference-frequency QTF table (hc_set_drift_qtf): nq = 0 none
-struct DriftTable {
+// A body's QTF table (hc_set_drift_qtf, hc_set_sum_qtf): nq = 0 none
+struct QtfTable {
     int nq     = 0;
     bool has_q = false;
     std::vector<double> omega, P, Q;  // [nq], [6][nq][nq] each
+};
+
+// One QTF term (hc_qtf.hip; the context holds two, drift and sum): the tables of all bodies of the system on the host, those of the
+// owned bodies one after the other on the device with the bin -> (component, weight) map of the component table in force; its own
+// stream, component table and pinned staging, nothing a step uses and nothing the other term uses (a table of one kind may change
+// while a launch of the other is in flight)
+struct QtfTerm {
+    std::vector<QtfTable> tabs;    // [N], each on a grid of its own
+    int mode = 0;                  // 0 off; drift: 1 mean drift, 2 Newman, 3 full QTF; sum: 1 on
+    double phase_opt = 0.0;        // regular_phase of the term's options call
+    hipStream_t stream = nullptr;  // created by the first table set
+    bool dirty = false;            // a table has changed since the device copy was made
+    int pending = 0;               // a begin without its end: 1 zeros (nothing launched), 2 a launch is in flight
+    unsigned long long serial = ~0ULL;
+    double phase = 0.0;
+    int nf = 0;
+    std::vector<double> omega, amp;  // [nf] of the component table in force
+    std::vector<int> slot_body;      // local body of every launched slot (owned bodies with a table, ascending)
+    DeviceBuffer<double> tab, pq, w, em, pos, out;  // (em: the drift term's E_m)
+    DeviceBuffer<long long> desc;
+    DeviceBuffer<int> rowptr, idx;
+    PinnedBuffer<double> h_pos, h_out;
 };
 
 struct BodyHost {
@@ -353,24 +375,8 @@ struct hc_ctx {
     bool nl_inc_flight = false;             // the evaluation in flight writes the other one
     std::vector<int> nl_inc_off;            // [nloc + 1] first point of an owned body in it; empty: no evaluation has completed
 
-    // Wave drift forces (hc_set_drift_qtf, hc_drift.hip): the tables of all bodies of the system on the host, those of the owned bodies
-    // one after the other on the device with the bin -> (component, weight) map of the component table in force; its own stream,
-    // component table and pinned staging, nothing a step uses
-    std::vector<hc::DriftTable> drift_tabs;  // [N]
-    int drift_mode = 0;                      // 0 off, 1 mean drift, 2 Newman, 3 full QTF
-    double drift_phase_opt = 0.0;            // regular_phase of hc_set_drift_options
-    hipStream_t stream_drift = nullptr;      // created by the first hc_set_drift_qtf
-    bool drift_dirty = false;                // a table has changed since the device copy was made
-    int drift_pending = 0;                   // hc_drift_begin without its hc_drift_end: 1 zeros (nothing launched), 2 a launch is in flight
-    unsigned long long drift_serial = ~0ULL;
-    double drift_phase = 0.0;
-    int drift_nf = 0;
-    std::vector<double> drift_amp, drift_omega;  // [nf] of the component table in force
-    std::vector<int> drift_slot_body;            // local body of every launched slot (owned bodies with a table, ascending)
-    hc::DeviceBuffer<double> d_drift_tab, d_drift_pq, d_drift_w, d_drift_em, d_drift_pos, d_drift_out;
-    hc::DeviceBuffer<long long> d_drift_desc;
-    hc::DeviceBuffer<int> d_drift_rowptr, d_drift_idx;
-    hc::PinnedBuffer<double> h_drift_pos, h_drift_out;
+    // Wave drift forces (hc_set_drift_qtf) and sum-frequency wave forces (hc_set_sum_qtf): hc_qtf.hip
+    hc::QtfTerm drift, sum;
 
     // Second-order wave kinematics (hc_wave_kinematics2, hc_wave_kin2.hip): the tables of the wave model, regular phase and cut-offs
     // they were built for; its own stream and a grow-only buffer for points, times and outputs, nothing a step uses
@@ -487,23 +493,4 @@ struct hc_ctx {
     size_t events_used = 0;
     bool sample_this_step = false;
     hc_profile_stats prof{};
-
-    // Sum-frequency wave forces (hc_set_sum_qtf, hc_sumfreq.hip): as the drift term, with tables, bin map, stream, component table and
-    // pinned staging of its own (a table of one kind may change while a launch of the other is in flight), nothing a step uses.
-    // Kept at the end of the context: no other member moves.
-    std::vector<hc::DriftTable> sum_tabs;  // [N]: T_s(Omega_m, Omega_n) on a grid of its own
-    int sum_mode = 0;                      // 0 off, 1 on
-    double sum_phase_opt = 0.0;            // regular_phase of hc_set_sum_options
-    hipStream_t stream_sum = nullptr;      // created by the first hc_set_sum_qtf
-    bool sum_dirty = false;                // a table has changed since the device copy was made
-    int sum_pending = 0;                   // hc_sum_qtf_begin without its end: 1 zeros (nothing launched), 2 a launch is in flight
-    unsigned long long sum_serial = ~0ULL;
-    double sum_phase = 0.0;
-    int sum_nf = 0;
-    std::vector<double> sum_omega;         // [nf] of the component table in force
-    std::vector<int> sum_slot_body;        // local body of every launched slot (owned bodies with a table, ascending)
-    hc::DeviceBuffer<double> d_sum_tab, d_sum_pq, d_sum_w, d_sum_pos, d_sum_out;
-    hc::DeviceBuffer<long long> d_sum_desc;
-    hc::DeviceBuffer<int> d_sum_rowptr, d_sum_idx;
-    hc::PinnedBuffer<double> h_sum_pos, h_sum_out;
 };

@@ -28,6 +28,12 @@ namespace hc {
 void eta_synthesis_fft(const std::vector<double>& t, const std::vector<double>& amp, const std::vector<double>& omega,
                        const std::vector<double>& phase, double ramp, const double* d_t, double* d_eta, hipStream_t stream);
 
+inline bool all_finite(const double* v, size_t n) {
+    for (size_t i = 0; i < n; ++i)
+        if (!std::isfinite(v[i])) return false;
+    return true;
+}
+
 namespace detail {
 
 using hc::Error;

@@ -258,12 +258,6 @@ __global__ void __launch_bounds__(kMorThreads) morison_sum_kernel(const double* 
     out[row] = acc;
 }
 
-bool all_finite(const double* v, size_t n) {
-    for (size_t i = 0; i < n; ++i)
-        if (!std::isfinite(v[i])) return false;
-    return true;
-}
-
 // the device copy of the owned bodies' lists, body-major
 void upload_elements(hc_ctx* c) {
     std::vector<double> elem;
@@ -290,8 +284,7 @@ void upload_elements(hc_ctx* c) {
 // regular phase while a launch of this one is in flight).
 void morison_table(hc_ctx* c) {
     const double phase = c->mor_opts.regular_phase;
-    const bool regular = c->wave_kind == kWaveRegular;
-    if (c->mor_serial == c->wave_serial && (!regular || std::memcmp(&c->mor_phase, &phase, sizeof(double)) == 0)) return;
+    if (kin_table_current(c, c->mor_serial, c->mor_phase, phase)) return;
     std::vector<double> tab = kin_table_host(c, phase);
     c->mor_nf = static_cast<int>(tab.size() / kKinCols);
     const std::vector<double> dir = kin_dir_columns_host(c);
@@ -314,7 +307,7 @@ void morison_enqueue(hc_ctx* c, double t, const double* pos, const double* rpy, 
     std::copy(rpy, rpy + n3, c->h_mor_state.p + n3);
     std::copy(linvel, linvel + n3, c->h_mor_state.p + 2 * n3);
     std::copy(angvel, angvel + n3, c->h_mor_state.p + 3 * n3);
-    const bool synthesised = (c->wave_kind == kWaveIrregular && !c->eta_record) || c->wave_kind == kWaveSpectral;
+    const bool synthesised = kin_synthesised(c);
     const double rd = c->irr.ramp_duration;
     MorArgs a{};
     a.tab          = c->d_mor_tab.p;
@@ -328,7 +321,7 @@ void morison_enqueue(hc_ctx* c, double t, const double* pos, const double* rpy, 
     a.depth        = c->depth;
     a.mwl          = c->mor_opts.mwl;
     a.rho          = c->rho;
-    a.ramp         = (synthesised && rd > 0.0 && t < rd) ? (t <= 0.0 ? 0.0 : t / rd) : 1.0;  // the rule of the spectral excitation (hc_kernels.hip)
+    a.ramp         = kin_ramp(c, t);
     a.stretch      = (synthesised && c->mor_opts.wave_stretching) ? 1 : 0;  // RegularWave has none
     a.finite_depth = std::isfinite(c->depth) ? 1 : 0;
     a.item         = c->d_mor_item.p;
@@ -336,7 +329,7 @@ void morison_enqueue(hc_ctx* c, double t, const double* pos, const double* rpy, 
     // the second-order sea: tables of this path's own, then the increments of every element.  No components (NoWave, no model, an
     // imported eta record) or no pair inside either band: order 1, no further launch.
     bool order2 = false;
-    if (c->mor2_on && wk2_has_components(c)) {
+    if (c->mor2_on && kin_has_components(c)) {
         wk2_tables(c, c->mor2, st, c->mor_opts.regular_phase, c->mor2_cut, false);
         order2 = c->mor2.any[0] || c->mor2.any[1];
     }
@@ -358,7 +351,7 @@ void morison_enqueue(hc_ctx* c, double t, const double* pos, const double* rpy, 
         m.state         = a.state;
         m.N             = a.N;
         m.t             = t;
-        m.ramped        = (c->mor2_ramp && synthesised && rd > 0.0) ? 1 : 0;  // the rule of hc_wave_kinematics2
+        m.ramped        = (c->mor2_ramp && synthesised && rd > 0.0) ? 1 : 0;  // the switch only (wk2_ramp2)
         m.ramp_duration = rd;
         m.inc           = c->d_mor_inc.p;
         hipLaunchKernelGGL(morison2_incr_kernel, dim3(a.n_items), dim3(kWk2Threads), 0, st, m);
@@ -480,7 +473,7 @@ int hc_morison_begin(hc_ctx* c, double t, const double* pos, const double* rpy, 
     require(!(c->mor2_on && !c->wave_dir.empty()), HC_ERR_UNSUPPORTED,
             "Morison elements on the second-order sea are not available while wave directions are set (hc_set_wave_directions): clear "
             "the directions or switch the second-order sea off");
-    require(!(c->mor2_on && hc::wk2_has_components(c)) || hc::wk2_component_count(c) <= hc::kWk2MaxFreq, HC_ERR_UNSUPPORTED,
+    require(!(c->mor2_on && hc::kin_has_components(c)) || hc::wk2_component_count(c) <= hc::kWk2MaxFreq, HC_ERR_UNSUPPORTED,
             "Morison elements on the second-order sea: more than 4096 wave components");
     int items = 0;
     if (!c->mor_elems.empty())

@@ -506,12 +506,6 @@ __global__ void __launch_bounds__(kWk2Threads) nl2_incr_kernel(Nl2Args a) {
     }
 }
 
-bool all_finite(const double* v, size_t n) {
-    for (size_t i = 0; i < n; ++i)
-        if (!std::isfinite(v[i])) return false;
-    return true;
-}
-
 // the device copy of the owned bodies' lists, body-major, and the chunk map: every body's list (panels or triangles, a body has one kind)
 // cut into chunks of 256 in index order.  Both kinds share the map and the partial buffer; consecutive chunks of one kind are a run,
 // one launch of that kind's kernel (a system with one kind: one run, one launch)
@@ -603,8 +597,7 @@ void upload_points(hc_ctx* c) {
 // while a launch of this one is in flight).
 void nonlinear_table(hc_ctx* c) {
     const double phase = c->nl_opts.regular_phase;
-    const bool regular = c->wave_kind == kWaveRegular;
-    if (c->nl_serial == c->wave_serial && (!regular || std::memcmp(&c->nl_phase, &phase, sizeof(double)) == 0)) return;
+    if (kin_table_current(c, c->nl_serial, c->nl_phase, phase)) return;
     const std::vector<double> kin = kin_table_host(c, phase);
     const int nf = static_cast<int>(kin.size() / kKinCols);
     std::vector<double> tab(static_cast<size_t>(kNlCols) * nf);
@@ -630,7 +623,7 @@ void nonlinear_enqueue(hc_ctx* c, double t) {
     if (c->d_nl_state.n < 2 * n3) c->d_nl_state.alloc(2 * n3);
     if (c->h_nl_out.n < n_out) c->h_nl_out.alloc(n_out);
     if (c->d_nl_out.n < n_out) c->d_nl_out.alloc(n_out);
-    const bool synthesised = (c->wave_kind == kWaveIrregular && !c->eta_record) || c->wave_kind == kWaveSpectral;
+    const bool synthesised = kin_synthesised(c);
     const double rd = c->irr.ramp_duration;
     NlArgs a{};
     a.tab          = c->d_nl_tab.p;
@@ -644,7 +637,7 @@ void nonlinear_enqueue(hc_ctx* c, double t) {
     a.mwl          = c->nl_opts.mwl;
     a.rho          = c->rho;
     a.g            = -c->gsys[2];  // gravity is (0, 0, -g): checked by hc_nonlinear_begin
-    a.ramp         = (synthesised && rd > 0.0 && t < rd) ? (t <= 0.0 ? 0.0 : t / rd) : 1.0;  // the rule of the Morison term
+    a.ramp         = kin_ramp(c, t);
     a.stretch      = (synthesised && c->nl_opts.wave_stretching) ? 1 : 0;  // RegularWave has none
     a.finite_depth = std::isfinite(c->depth) ? 1 : 0;
     a.part         = c->d_nl_part.p;
@@ -653,7 +646,7 @@ void nonlinear_enqueue(hc_ctx* c, double t) {
     // the second-order sea: tables of this path's own, then the increments of every surface point.  No components (NoWave, no model,
     // an imported eta record) or no pair inside either band: order 1, no further launch.
     bool order2 = false;
-    if (c->nl2_on && wk2_has_components(c)) {
+    if (c->nl2_on && kin_has_components(c)) {
         wk2_tables(c, c->nl2, st, c->nl_opts.regular_phase, c->nl2_cut, false);
         order2 = c->nl2.any[0] || c->nl2.any[1];
     }
@@ -673,7 +666,7 @@ void nonlinear_enqueue(hc_ctx* c, double t) {
         m.state         = a.state;
         m.N             = a.N;
         m.t             = t;
-        m.ramped        = (c->nl2_ramp && synthesised && rd > 0.0) ? 1 : 0;  // the rule of hc_wave_kinematics2
+        m.ramped        = (c->nl2_ramp && synthesised && rd > 0.0) ? 1 : 0;  // the switch only (wk2_ramp2)
         m.ramp_duration = rd;
         m.inc           = c->d_nl_inc.p;
         hipLaunchKernelGGL(nl2_incr_kernel, dim3(points), dim3(kWk2Threads), 0, st, m);
@@ -871,7 +864,7 @@ int hc_nonlinear_begin(hc_ctx* c, double t, const double* pos, const double* rpy
     require(!(c->nl2_on && !c->wave_dir.empty()), HC_ERR_UNSUPPORTED,
             "the surface on the second-order sea is not available while wave directions are set (hc_set_wave_directions): clear the "
             "directions or switch the second-order sea off");
-    require(!(c->nl2_on && hc::wk2_has_components(c)) || hc::wk2_component_count(c) <= hc::kWk2MaxFreq, HC_ERR_UNSUPPORTED,
+    require(!(c->nl2_on && hc::kin_has_components(c)) || hc::wk2_component_count(c) <= hc::kWk2MaxFreq, HC_ERR_UNSUPPORTED,
             "the surface on the second-order sea: more than 4096 wave components");
     // the host copy of the state: the kernel's source, and what hc_nonlinear_end computes hs_lin from (the caller's arrays are
     // borrowed for this call only)

@@ -170,8 +170,8 @@ void hc_destroy(hc_ctx* ctx) {
     if (ctx->stream_am) (void)hipStreamDestroy(ctx->stream_am);
     if (ctx->stream_mor) (void)hipStreamDestroy(ctx->stream_mor);
     if (ctx->stream_nl) (void)hipStreamDestroy(ctx->stream_nl);
-    if (ctx->stream_drift) (void)hipStreamDestroy(ctx->stream_drift);
-    if (ctx->stream_sum) (void)hipStreamDestroy(ctx->stream_sum);
+    if (ctx->drift.stream) (void)hipStreamDestroy(ctx->drift.stream);
+    if (ctx->sum.stream) (void)hipStreamDestroy(ctx->sum.stream);
     if (ctx->stream_wk2) (void)hipStreamDestroy(ctx->stream_wk2);
     if (ctx->ev_fin) (void)hipEventDestroy(ctx->ev_fin);
     if (ctx->ev_bg) (void)hipEventDestroy(ctx->ev_bg);

@@ -47,6 +47,21 @@ std::vector<double> kin_table_host(const hc_ctx* c, double regular_phase) {
     return tab;
 }
 
+bool kin_has_components(const hc_ctx* c) {
+    return c->wave_kind == kWaveRegular || c->wave_kind == kWaveSpectral || (c->wave_kind == kWaveIrregular && !c->eta_record);
+}
+
+bool kin_synthesised(const hc_ctx* c) { return (c->wave_kind == kWaveIrregular && !c->eta_record) || c->wave_kind == kWaveSpectral; }
+
+double kin_ramp(const hc_ctx* c, double t) {
+    const double rd = c->irr.ramp_duration;
+    return (kin_synthesised(c) && rd > 0.0 && t < rd) ? (t <= 0.0 ? 0.0 : t / rd) : 1.0;
+}
+
+bool kin_table_current(const hc_ctx* c, unsigned long long serial, double cached_phase, double phase) {
+    return serial == c->wave_serial && (c->wave_kind != kWaveRegular || std::memcmp(&cached_phase, &phase, sizeof(double)) == 0);
+}
+
 std::vector<double> kin_dir_columns_host(const hc_ctx* c) {
     const size_t nf = c->wave_dir.size();
     std::vector<double> col(kDirCols * nf);
@@ -185,8 +200,7 @@ __global__ void __launch_bounds__(kKinThreads) wave_kinematics_kernel(KinArgs a)
 // The component table of the context's wave model on the device.  Rebuilt when a hc_set_wave_* call has come in since
 // (wave_serial) or the regular wave's phase differs from the cached one.
 void kin_table(hc_ctx* c, double regular_phase) {
-    const bool regular = c->wave_kind == kWaveRegular;
-    if (c->kin_serial == c->wave_serial && (!regular || std::memcmp(&c->kin_phase, &regular_phase, sizeof(double)) == 0)) return;
+    if (kin_table_current(c, c->kin_serial, c->kin_phase, regular_phase)) return;
     std::vector<double> tab = kin_table_host(c, regular_phase);
     c->kin_nf = static_cast<int>(tab.size() / kKinCols);
     const std::vector<double> dir = kin_dir_columns_host(c);

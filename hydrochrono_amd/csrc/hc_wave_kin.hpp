@@ -26,6 +26,16 @@ enum KinCol {
 // the context, A_i = sqrt(2 S_i df_i) and w_i = 2 pi f_i as build_spectrum / the reference compute them).  Empty for NoWave and
 // for an imported eta record (no spectrum).
 std::vector<double> kin_table_host(const hc_ctx* c, double regular_phase);
+// Some component in that table: a regular wave, or a synthesised irregular model (not NoWave, no model, an imported eta record)
+bool kin_has_components(const hc_ctx* c);
+// A synthesised irregular model (irregular without an imported eta record, or spectral): the ramp and Wheeler stretching apply to it
+bool kin_synthesised(const hc_ctx* c);
+// The ramp factor of the first-order quantities at time t (that of the spectral excitation, hc_kernels.hip): a synthesised model with
+// ramp_duration > 0 rises as max(t, 0) / ramp_duration up to ramp_duration; 1 otherwise
+double kin_ramp(const hc_ctx* c, double t);
+// A path's own copy of the table, built at wave_serial `serial` for the regular phase `cached_phase`, is still the one in force for
+// `phase`: no hc_set_wave_* call has come in since and, for a regular wave, the phase has the same bits
+bool kin_table_current(const hc_ctx* c, unsigned long long serial, double cached_phase, double phase);
 
 // The two direction columns [2][nf] (cos theta_i, then sin theta_i) of the directions in force (hc_set_wave_directions); empty when
 // none are set.  A path that sums the directional sea appends them behind its own table's columns.

@@ -1,7 +1,7 @@
 // hc_wave_kin2.hip -- second-order irregular waves (Sharma and Dean 1981): the second-order increments to the elevation, velocity
 // and acceleration of hc_wave_kinematics, batched over P points x T times (include/hydrochrono_amd.h: hc_wave_kinematics2,
 // hc_wave_kinematics2_pair_tables).  Not in the reference.  Off the step path: its own stream, component table, pair tables and
-// buffers; it reads and writes nothing a step uses, so it is not ordered against the direct queue (as hc_drift.hip).
+// buffers; it reads and writes nothing a step uses, so it is not ordered against the direct queue (as hc_qtf.hip).
 // DESIGN.md 3.7f has the definition, the checks behind it, the kernels and their invariants.
 #include "hc_internal.hpp"
 #include "hc_wave_kin.hpp"
@@ -119,17 +119,10 @@ __global__ void __launch_bounds__(kWk2Threads) wk2_sum_kernel(Wk2SumArgs a) {
 
 }  // namespace
 
-bool wk2_has_components(const hc_ctx* c) {
-    return c->wave_kind == kWaveRegular || c->wave_kind == kWaveSpectral || (c->wave_kind == kWaveIrregular && !c->eta_record);
-}
-
 int wk2_component_count(const hc_ctx* c) { return c->wave_kind == kWaveRegular ? 1 : static_cast<int>(c->spec_f.size()); }
 
 void wk2_tables(hc_ctx* c, Wk2TableSet& s, hipStream_t st, double regular_phase, const double cut[4], bool keep_empty) {
-    const bool regular = c->wave_kind == kWaveRegular;
-    if (s.serial == c->wave_serial && (!regular || std::memcmp(&s.phase, &regular_phase, sizeof(double)) == 0) &&
-        std::memcmp(s.cut, cut, sizeof(s.cut)) == 0)
-        return;
+    if (kin_table_current(c, s.serial, s.phase, regular_phase) && std::memcmp(s.cut, cut, sizeof(s.cut)) == 0) return;
     s.serial = ~0ULL;  // nothing is cached until all of it is in place
     const std::vector<double> tab = kin_table_host(c, regular_phase);
     const int nf = static_cast<int>(tab.size() / kKinCols);
@@ -204,7 +197,7 @@ int hc_wave_kinematics2(hc_ctx* c, const hc_wave_kinematics2_opts* opts, int n_p
     const hc_wave_kinematics2_opts o = hc::wk2_opts(opts);
     const char* bad = hc::wk2_check_batch(n_points, xyz, n_times, t);
     require(bad == nullptr, HC_ERR_INVALID, bad ? bad : "");
-    const bool waves = hc::wk2_has_components(c);
+    const bool waves = hc::kin_has_components(c);
     require(c->wave_dir.empty(), HC_ERR_UNSUPPORTED,
             "the second-order sea is long-crested: not available while wave directions are set (hc_set_wave_directions)");
     require(!waves || hc::wk2_component_count(c) <= hc::kWk2MaxFreq, HC_ERR_UNSUPPORTED, "more than 4096 wave components");
@@ -243,8 +236,7 @@ int hc_wave_kinematics2(hc_ctx* c, const hc_wave_kinematics2_opts* opts, int n_p
     a.finite_depth = std::isfinite(c->depth) ? 1 : 0;
     a.sign_on[0]   = c->wk2.any[0] ? 1 : 0;
     a.sign_on[1]   = c->wk2.any[1] ? 1 : 0;
-    const bool synthesised = (c->wave_kind == hc::kWaveIrregular && !c->eta_record) || c->wave_kind == hc::kWaveSpectral;
-    a.ramped        = (o.apply_ramp && synthesised && c->irr.ramp_duration > 0.0) ? 1 : 0;  // the rule of the Morison term
+    a.ramped        = (o.apply_ramp && hc::kin_synthesised(c) && c->irr.ramp_duration > 0.0) ? 1 : 0;  // the switch only (wk2_ramp2)
     a.ramp_duration = c->irr.ramp_duration;
     if (eta) {
         a.eta = d_out;
@@ -276,7 +268,7 @@ int hc_wave_kinematics2_pair_tables(hc_ctx* c, const hc_wave_kinematics2_opts* o
     HC_API_BEGIN_HOT(c)
     require(c->finalized, HC_ERR_INVALID, "hc_finalize has not been called");
     const hc_wave_kinematics2_opts o = hc::wk2_opts(opts);
-    if (!hc::wk2_has_components(c)) return HC_OK;
+    if (!hc::kin_has_components(c)) return HC_OK;
     require(hc::wk2_component_count(c) <= hc::kWk2MaxFreq, HC_ERR_UNSUPPORTED, "more than 4096 wave components");
     if (!c->stream_wk2) HC_HIP(hipStreamCreateWithFlags(&c->stream_wk2, hipStreamNonBlocking));
     hc::wk2_own_tables(c, o);

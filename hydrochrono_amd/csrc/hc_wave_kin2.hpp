@@ -75,7 +75,7 @@ inline bool wk2_bands(const double* omega, int nf, int sign, double lo, double h
     return any;
 }
 
-// ramp * ramp's switch: the rule of the Morison term (synthesised irregular model, ramp_duration > 0); the factor itself is taken per
+// ramp * ramp's switch: that of kin_ramp (hc_wave_kin.hpp: kin_synthesised, ramp_duration > 0); the factor itself is taken per
 // time: 0 for t <= 0, (t / ramp_duration)^2 for t < ramp_duration, else 1
 HC_HOST_DEVICE inline double wk2_ramp2(bool ramped, double ramp_duration, double t) {
     if (!ramped || !(t < ramp_duration)) return 1.0;

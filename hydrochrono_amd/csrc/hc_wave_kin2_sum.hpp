@@ -182,8 +182,6 @@ __device__ inline void wk2_item_sum(const Wk2Sea& a, double x, double z, double 
 }
 
 // ---- hc_wave_kin2.hip: the host side both users share ----
-// Some component to pair: a regular wave, or a synthesised irregular model (not NoWave, no model, an imported eta record)
-bool wk2_has_components(const hc_ctx* c);
 int wk2_component_count(const hc_ctx* c);
 // The component table, the pair tables and the band limits of the context's wave model in `s`, built on `st` (wk2_pair_kernel) and
 // complete when the call returns.  Rebuilt when a hc_set_wave_* call has come in since (wave_serial), the regular wave's phase or a

@@ -1,4 +1,4 @@
-"""Wave drift forces on the GPU (hc_compute_drift, csrc/hc_drift.hip): what a call costs and what it does to the step beside it.
+"""Wave drift forces on the GPU (hc_compute_drift, csrc/hc_qtf.hip): what a call costs and what it does to the step beside it.
 
   (a) hc_compute_drift per call at 64 bodies x 512 components x nq = 64 (the C3 system of bench.py), modes 1, 2 and 3, first call
       (tables uploaded, bin map built) and steady state;

@@ -1,4 +1,4 @@
-"""Sum-frequency wave forces on the GPU (hc_compute_sum_qtf, csrc/hc_sumfreq.hip): what a call costs beside the drift term's, and
+"""Sum-frequency wave forces on the GPU (hc_compute_sum_qtf, csrc/hc_qtf.hip): what a call costs beside the drift term's, and
 what the two terms do to the step beside them.
 
   (a) hc_compute_sum_qtf and hc_compute_drift (mode 3) per call at 64 bodies x 512 components x nq = 64 (the C3 system of bench.py),

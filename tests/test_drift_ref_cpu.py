@@ -1,6 +1,6 @@
 """The wave drift term without a GPU: the projected evaluation form in float64 against the direct pair sum of the
 definition in longdouble (tests/drift_ref.py), inside the derived bound; closed forms; the grid ends; and the build of the kernel
-(csrc/hc_drift.hip: no scratch, no spilled register).  The GPU side is tests/test_gpu_drift.py."""
+(csrc/hc_qtf.hip: no scratch, no spilled register).  The GPU side is tests/test_gpu_drift.py."""
 import ctypes as C
 import os
 import re
@@ -113,16 +113,18 @@ def test_kernel_builds_without_scratch_or_spills(tmp_path):
     readelf = "/opt/rocm/lib/llvm/bin/llvm-readelf"
     assert os.path.exists(readelf), "llvm-readelf not found"
     from hydrochrono_amd import build as hb
-    co = str(tmp_path / "hc_drift.co")
+    co = str(tmp_path / "hc_qtf.co")
     subprocess.run([hb._hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "--genco", "--no-gpu-bundle-output", "-Wno-unused-result",
-                    "-I", os.path.join(ROOT, "include"), os.path.join(hb.CSRC, "hc_drift.hip"), "-o", co], check=True)
+                    "-I", os.path.join(ROOT, "include"), os.path.join(hb.CSRC, "hc_qtf.hip"), "-o", co], check=True)
     txt = subprocess.run([readelf, "--notes", co], capture_output=True, text=True, check=True).stdout
-    notes = {m.group(1): (int(m.group(2)), int(m.group(3)), int(m.group(4))) for m in re.finditer(
-        r"\.name:\s+(\S+).*?\.private_segment_fixed_size:\s+(\d+).*?\.vgpr_count:\s+(\d+).*?\.vgpr_spill_count:\s+(\d+)", txt, re.S)}
+    notes = {m.group(2): (int(m.group(3)), int(m.group(4)), int(m.group(5)), int(m.group(1))) for m in re.finditer(
+        r"\.group_segment_fixed_size:\s+(\d+).*?\.name:\s+(\S+).*?\.private_segment_fixed_size:\s+(\d+).*?\.vgpr_count:\s+(\d+)"
+        r".*?\.vgpr_spill_count:\s+(\d+)", txt, re.S)}
     assert any("drift_qtf_kernel" in n for n in notes), sorted(notes)
-    for name, (scratch, vgpr, spills) in notes.items():
+    for name, (scratch, vgpr, spills, lds) in notes.items():
         assert scratch == 0 and spills == 0, (name, scratch, spills)
-    assert "hc_drift.hip" in hb.SOURCES
+        assert lds == (16384 if "drift_qtf_kernel" in name else 10240), (name, lds)  # four reduction columns against sum_qtf_kernel's one
+    assert "hc_qtf.hip" in hb.SOURCES
 
 
 def test_abi_declares_the_drift_entry_points_and_needs_a_device():

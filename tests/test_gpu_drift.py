@@ -1,4 +1,4 @@
-"""Second-order wave drift forces on the GPU (hc_set_drift_qtf, hc_drift_begin / hc_drift_end, hc_compute_drift; csrc/hc_drift.hip)
+"""Second-order wave drift forces on the GPU (hc_set_drift_qtf, hc_drift_begin / hc_drift_end, hc_compute_drift; csrc/hc_qtf.hip)
 against the direct longdouble pair sum of the definition (tests/drift_ref.py), fed the context's own spectrum / regular-wave
 coefficients.  The device evaluates the projected O(nf + nq^2) form, so the identity between the two is under test as well.
 

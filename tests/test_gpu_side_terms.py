@@ -1,4 +1,4 @@
-"""The Morison, nonlinear and drift terms TOGETHER and across wave-model changes (csrc/hc_morison.hip, hc_nonlinear.hip, hc_drift.hip and
+"""The Morison, nonlinear and drift terms TOGETHER and across wave-model changes (csrc/hc_morison.hip, hc_nonlinear.hip, hc_qtf.hip and
 the three layers that compose them: HydroForces.step, HydroGroup.step, TestHydro::CoordinateFuncForBody).  Each term alone is the
 subject of tests/test_gpu_morison.py, test_gpu_nonlinear.py and test_gpu_drift.py; here
 

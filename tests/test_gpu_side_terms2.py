@@ -1,7 +1,7 @@
 """The Morison, nonlinear, drift and sum-frequency terms TOGETHER, the first two on the second-order sea, across changes of the wave
 model, the bands and the tables: what tests/test_gpu_side_terms.py checks for three first-order terms, for the state added
 since -- clipped triangles, the three pair-table sets of csrc/hc_wave_kin2.hip (hc_wave_kinematics2's, the Morison one, the nonlinear one), the surface points
-and double-buffered increments of csrc/hc_nonlinear.hip, the bin map and slot layout of csrc/hc_sumfreq.hip, and the fourth begin
+and double-buffered increments of csrc/hc_nonlinear.hip, the bin map and slot layout of csrc/hc_qtf.hip, and the fourth begin
 of HydroForces.step, HydroGroup.step and TestHydro::CoordinateFuncForBody.  Each term alone is the subject of
 tests/test_gpu_morison2.py, test_gpu_nonlinear2.py, test_gpu_surface_clip.py, test_gpu_drift.py and test_gpu_sumfreq.py; here
 

@@ -1,6 +1,6 @@
 """The sum-frequency term without a GPU: the projected evaluation form in float64 against the direct pair sum of the
 definition in longdouble (tests/sumfreq_ref.py), inside the derived bound; the antisymmetric part of a table; the regular-wave closed
-form; and the build of the kernel (csrc/hc_sumfreq.hip: no scratch, no spilled register).  The GPU side is tests/test_gpu_sumfreq.py."""
+form; and the build of the kernel (csrc/hc_qtf.hip: no scratch, no spilled register).  The GPU side is tests/test_gpu_sumfreq.py."""
 import os
 import re
 import subprocess
@@ -129,20 +129,20 @@ def test_kernel_builds_without_scratch_or_spills_and_the_drift_kernel_is_still_t
     readelf = "/opt/rocm/lib/llvm/bin/llvm-readelf"
     assert os.path.exists(readelf), "llvm-readelf not found"
     from hydrochrono_amd import build as hb
-    assert "hc_sumfreq.hip" in hb.SOURCES and "hc_drift.hip" in hb.SOURCES
-    co = str(tmp_path / "hc_sumfreq.co")
+    assert "hc_qtf.hip" in hb.SOURCES
+    co = str(tmp_path / "hc_qtf.co")
     subprocess.run([hb._hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "--genco", "--no-gpu-bundle-output", "-Wno-unused-result",
-                    "-I", os.path.join(ROOT, "include"), os.path.join(hb.CSRC, "hc_sumfreq.hip"), "-o", co], check=True)
+                    "-I", os.path.join(ROOT, "include"), os.path.join(hb.CSRC, "hc_qtf.hip"), "-o", co], check=True)
     txt = subprocess.run([readelf, "--notes", co], capture_output=True, text=True, check=True).stdout
     notes = {}
     for m in re.finditer(r"\.group_segment_fixed_size:\s+(\d+).*?\.name:\s+(\S+).*?\.private_segment_fixed_size:\s+(\d+).*?\.vgpr_count:\s+(\d+)"
                          r".*?\.vgpr_spill_count:\s+(\d+)", txt, re.S):
         notes[m.group(2)] = (int(m.group(3)), int(m.group(4)), int(m.group(5)), int(m.group(1)))
-    assert any("sum_qtf_kernel" in n for n in notes), (sorted(notes), txt[:2000])
+    assert any("sum_qtf_kernel" in n for n in notes) and any("drift_qtf_kernel" in n for n in notes), (sorted(notes), txt[:2000])
     for name, (scratch, vgpr, spills, lds) in notes.items():
         print(f"{name}: {vgpr} VGPRs, {lds} B LDS, scratch {scratch}, spills {spills}")
         assert scratch == 0 and spills == 0, (name, scratch, spills)
-        assert lds <= 16384, (name, lds)  # that of drift_qtf_kernel or less: one reduction column
+        assert lds == (10240 if "sum_qtf_kernel" in name else 16384), (name, lds)  # one reduction column against drift_qtf_kernel's four
     # the names a HIP launch looks a kernel up by are plain strings of the built library
     blob = open(hb.MAIN_LIB, "rb").read()
     assert b"sum_qtf_kernel" in blob and b"drift_qtf_kernel" in blob
