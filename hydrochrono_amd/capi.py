@@ -195,6 +195,8 @@ SIGNATURES = {
     "hc_get_nonlinear_increments": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p]),
     "hc_set_drift_qtf": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p]),
     "hc_get_drift_qtf_size": (C.c_int, [C.c_void_p, C.c_int, c_int_p]),
+    "hc_set_drift_qtf_headings": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_double_p, C.c_int, c_double_p, c_double_p, c_double_p]),
+    "hc_get_drift_qtf_headings": (C.c_int, [C.c_void_p, C.c_int, c_int_p]),
     "hc_set_drift_mode": (C.c_int, [C.c_void_p, C.c_int]),
     "hc_get_drift_mode": (C.c_int, [C.c_void_p, c_int_p]),
     "hc_set_drift_options": (C.c_int, [C.c_void_p, C.POINTER(WaveKinematicsOpts)]),
@@ -203,6 +205,8 @@ SIGNATURES = {
     "hc_compute_drift": (C.c_int, [C.c_void_p, C.c_double, c_double_p, c_double_p]),
     "hc_set_sum_qtf": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p]),
     "hc_get_sum_qtf_size": (C.c_int, [C.c_void_p, C.c_int, c_int_p]),
+    "hc_set_sum_qtf_headings": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_double_p, C.c_int, c_double_p, c_double_p, c_double_p]),
+    "hc_get_sum_qtf_headings": (C.c_int, [C.c_void_p, C.c_int, c_int_p]),
     "hc_set_sum_mode": (C.c_int, [C.c_void_p, C.c_int]),
     "hc_get_sum_mode": (C.c_int, [C.c_void_p, c_int_p]),
     "hc_set_sum_options": (C.c_int, [C.c_void_p, C.POINTER(WaveKinematicsOpts)]),

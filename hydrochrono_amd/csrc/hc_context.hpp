@@ -115,11 +115,14 @@ struct Wk2TableSet {
     }
 };
 
-// A body's QTF table (hc_set_drift_qtf, hc_set_sum_qtf): nq = 0 none
+// A body's QTF table (hc_set_drift_qtf, hc_set_sum_qtf; on a heading grid: hc_set_drift_qtf_headings, hc_set_sum_qtf_headings):
+// nq = 0 none, nh = 0 one heading
 struct QtfTable {
     int nq     = 0;
+    int nh     = 0;
     bool has_q = false;
-    std::vector<double> omega, P, Q;  // [nq], [6][nq][nq] each
+    std::vector<double> omega, P, Q;  // [nq], [6][nq][nq] each; on a heading grid [6][nh][nh][nq][nq] as the caller gave them
+    std::vector<double> beta;         // [nh]
 };
 
 // One QTF term (hc_qtf.hip; the context holds two, drift and sum): the tables of all bodies of the system on the host, those of the
@@ -137,8 +140,12 @@ struct QtfTerm {
     double phase = 0.0;
     int nf = 0;
     std::vector<double> omega, amp;  // [nf] of the component table in force
-    std::vector<int> slot_body;      // local body of every launched slot (owned bodies with a table, ascending)
-    DeviceBuffer<double> tab, pq, w, em, pos, out;  // (em: the drift term's E_m)
+    std::vector<double> theta;       // [nf] the directions it was built with (zeros: none set)
+    std::vector<int> slot_body;      // local body of every launched slot: the owned bodies with a one-heading table, ascending, then
+                                     // those with a table on a heading grid, ascending
+    int slots_dir  = 0;              // how many of them are of the second kind (hc_qtf_dir.hip)
+    int chunks_dir = 0;              // the most chunks of 32 node rows any of those has
+    DeviceBuffer<double> tab, pq, w, em, pos, out, part;  // (em: the drift term's E_m; part: the chunk partials of hc_qtf_dir.hip)
     DeviceBuffer<long long> desc;
     DeviceBuffer<int> rowptr, idx;
     PinnedBuffer<double> h_pos, h_out;

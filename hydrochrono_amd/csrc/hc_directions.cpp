@@ -3,6 +3,7 @@
 // (src/wave_types.cpp:20,34).  Host code only: the directions are state that the component tables of the side terms pick up
 // (hc_wave_kin.hip: kin_dir_columns_host), and the excitation follows by rebuilding the per-row x per-component (magnitude, phase)
 // tables the step kernels already read -- no kernel of the step path changes.  DESIGN.md 3.7k.
+#include "hc_heading.hpp"
 #include "hc_internal.hpp"
 
 #include <algorithm>
@@ -22,20 +23,8 @@ bool uniform(const std::vector<double>& theta) {
     return true;
 }
 
-// The two grid headings around theta and the weight of the second: the largest j0 with dir[j0] <= theta, so that a theta on a grid
-// node has weight exactly 0 and the node's table comes out bit for bit.  No extrapolation, no wrap-around.
-struct HeadBracket {
-    int j0, j1;
-    double wt;
-};
-HeadBracket heading_bracket(const std::vector<double>& dir, double theta) {
-    require(theta >= dir.front() && theta <= dir.back(), HC_ERR_INVALID,
-            "a wave direction lies outside the heading grid of a body's excitation tables (no extrapolation, no wrap-around)");
-    const int n  = static_cast<int>(dir.size());
-    const int j0 = static_cast<int>(std::upper_bound(dir.begin(), dir.end(), theta) - dir.begin()) - 1;
-    if (j0 >= n - 1) return HeadBracket{n - 1, n - 1, 0.0};
-    return HeadBracket{j0, j0 + 1, (theta - dir[j0]) / (dir[j0 + 1] - dir[j0])};
-}
+const char* const kOutsideExcitationGrid =
+    "a wave direction lies outside the heading grid of a body's excitation tables (no extrapolation, no wrap-around)";
 
 // (magnitude, phase) of row r of a body at (omega bracket, heading bracket): the omega interpolation at the two headings, then
 // linear in the heading on the values as given
@@ -77,7 +66,7 @@ void apply_wave_directions(hc_ctx* c, const std::vector<double>& theta, bool com
                 for (int r = 0; r < 6; ++r) {
                     double m, p;
                     if (heads) {
-                        heading_value(bd, r, br, heading_bracket(bd.hd_dir, theta[i]), &m, &p);
+                        heading_value(bd, r, br, heading_bracket(bd.hd_dir, theta[i], kOutsideExcitationGrid), &m, &p);
                     } else {  // the expression of hc_set_wave_irregular_spectral
                         const double m0 = bd.rao_mag[static_cast<size_t>(r) * nw + br.k0], m1 = bd.rao_mag[static_cast<size_t>(r) * nw + br.k1];
                         const double p0 = bd.rao_phase[static_cast<size_t>(r) * nw + br.k0], p1 = bd.rao_phase[static_cast<size_t>(r) * nw + br.k1];
@@ -114,7 +103,7 @@ void apply_wave_directions(hc_ctx* c, const std::vector<double>& theta, bool com
             for (int r = 0; r < 6; ++r) {
                 double m, p;
                 if (heads) {
-                    heading_value(bd, r, br, heading_bracket(bd.hd_dir, theta[0]), &m, &p);
+                    heading_value(bd, r, br, heading_bracket(bd.hd_dir, theta[0], kOutsideExcitationGrid), &m, &p);
                 } else {  // the expression of hc_set_wave_regular
                     const double m0 = bd.rao_mag[static_cast<size_t>(r) * nw + br.k0], m1 = bd.rao_mag[static_cast<size_t>(r) * nw + br.k1];
                     const double p0 = bd.rao_phase[static_cast<size_t>(r) * nw + br.k0], p1 = bd.rao_phase[static_cast<size_t>(r) * nw + br.k1];

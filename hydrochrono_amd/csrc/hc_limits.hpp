@@ -42,6 +42,8 @@ constexpr int kSlotStateMaxBodies = 170;  // 12 N + 1 doubles fit, and 6 N <= 4 
 
 constexpr int kMorisonMaxElements = 4096;  // Morison elements one body may carry (hc_set_morison_elements)
 constexpr int kDriftMaxFreq = 256;  // frequencies of a body's drift QTF grid (hc_set_drift_qtf): one lane of the workgroup per bin
+constexpr int kQtfMaxHeadings = 16;  // headings of a QTF table on a heading grid (hc_set_drift_qtf_headings, hc_set_sum_qtf_headings)
+constexpr int kQtfMaxNodes = 1024;   // (heading, frequency) nodes J = nh nq of such a table: U, V [J] stay in LDS, four nodes per lane
 constexpr int kSurfaceMaxPanels = 1 << 20;  // surface panels one body may carry (hc_set_surface_panels): 4096 chunks of 256
 
 #if defined(__HIPCC__)

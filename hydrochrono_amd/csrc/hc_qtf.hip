@@ -6,7 +6,9 @@
 // its own stream, component table, table copies and pinned staging; it reads and writes nothing a step or the other term uses, so it is
 // not ordered against the direct queue (as hc_morison.hip).  DESIGN.md 3.7e and 3.7i have the definitions, the projected evaluation
 // form, the kernels and their invariants.
+#include "hc_heading.hpp"
 #include "hc_internal.hpp"
+#include "hc_qtf.hpp"
 #include "hc_wave_kin.hpp"
 
 #include <algorithm>
@@ -15,30 +17,6 @@ using namespace hc::detail;
 
 namespace hc {
 namespace {
-
-constexpr int kQtfThreads = 256;  // work items per workgroup: one per grid bin in phase 1 (kDriftMaxFreq bins at the most)
-static_assert(kDriftMaxFreq <= kQtfThreads, "one lane per bin of the frequency grid");
-static_assert(kKinTile == kQtfThreads, "one lane per component of a staged tile");
-
-// per (owned body with a table): [kDescWords] 64-bit words
-enum QtfDesc { kDescBody = 0, kDescNq, kDescRowPtr, kDescP, kDescQ, kDescE, kDescWords };
-
-enum QtfKind { kQtfDrift, kQtfSum };
-
-struct QtfArgs {
-    const double* tab;      // [kKinCols][nf] (hc_wave_kin.hpp)
-    int nf;
-    int mode;               // drift: 1 mean drift, 2 Newman, 3 full QTF (the sum kernel does not read it)
-    const long long* desc;  // [slots][kDescWords]: body, nq, first row pointer, offsets of P, Q (-1: none) and E (drift)
-    const int* rowptr;      // per slot nq + 1 entries: bin m owns the entries [rowptr[m], rowptr[m + 1])
-    const int* ent_idx;     // component index of an entry, ascending within a bin
-    const double* ent_w;    // its interpolation weight
-    const double* pq;       // the tables, [6][nq][nq] each
-    const double* em;       // drift: E_m = sum_i W[i][m] A_i^2 per slot and bin
-    const double* pos;      // [3 N]
-    double t, ramp2;
-    double* out;            // [slots][6]
-};
 
 // Phase 1: u_i = A_i cos theta_i, w_i = A_i sin theta_i tile by tile through LDS; lane m < nq adds its bin's entries in component order
 // into one accumulator pair (U_m, V_m), whatever the tiling.  Leaves them in sU, sV (zero for the lanes past the grid), visible to all.
@@ -87,36 +65,15 @@ __device__ __forceinline__ double qtf_pairs(const QtfArgs& a, const long long* d
         const double* Q = a.pq + desc[kDescQ] + static_cast<size_t>(d) * nq2;
         for (int e = tid; e < nq2; e += kQtfThreads) {
             const int m = e / nq, n = e - m * nq;
-            const double Um = sU[m], Vm = sV[m], Un = sU[n], Vn = sV[n];
-            if constexpr (KIND == kQtfDrift)
-                acc += P[e] * (Um * Un + Vm * Vn) - Q[e] * (Vm * Un - Um * Vn);
-            else
-                acc += P[e] * (Um * Un - Vm * Vn) - Q[e] * (Vm * Un + Um * Vn);
+            acc += qtf_pair_pq<KIND>(P[e], Q[e], sU[m], sV[m], sU[n], sV[n]);
         }
     } else {
         for (int e = tid; e < nq2; e += kQtfThreads) {
             const int m = e / nq, n = e - m * nq;
-            if constexpr (KIND == kQtfDrift)
-                acc += P[e] * (sU[m] * sU[n] + sV[m] * sV[n]);
-            else
-                acc += P[e] * (sU[m] * sU[n] - sV[m] * sV[n]);
+            acc += qtf_pair_p<KIND>(P[e], sU[m], sV[m], sU[n], sV[n]);
         }
     }
     return acc;
-}
-
-// Fixed-shape tree over the 256 lanes of R columns: lane l adds lane l + h for h = 128, 64, ..., 1 (nl_panels_kernel); the sums end
-// in red[k][0], for lane 0 to read
-template <int R>
-__device__ __forceinline__ void qtf_tree(double (*red)[kQtfThreads]) {
-    const int tid = threadIdx.x;
-    for (int h = kQtfThreads / 2; h > 0; h >>= 1) {
-        __syncthreads();
-        if (tid < h) {
-#pragma unroll
-            for (int k = 0; k < R; ++k) red[k][tid] += red[k][tid + h];
-        }
-    }
 }
 
 // One workgroup per (slot, row d): qtf_project, then the mode's sum over the bins (modes 1 and 2: the diagonal alone) and the tree,
@@ -184,6 +141,7 @@ __global__ void __launch_bounds__(kQtfThreads) sum_qtf_kernel(QtfArgs a) {
 struct QtfSpec {
     hc::QtfTerm hc_ctx::*term;
     void (*kernel)(QtfArgs);
+    QtfKind kind;
     bool build_em;  // E_m of the drift term's mode 1
     int mode_max;
     const char *msg_count, *msg_in_flight, *msg_table, *msg_grid, *msg_mode, *msg_twice, *msg_directions, *msg_no_begin;
@@ -191,6 +149,7 @@ struct QtfSpec {
 
 const QtfSpec kDrift = {&hc_ctx::drift,
                         drift_qtf_kernel,
+                        kQtfDrift,
                         true,
                         3,
                         "drift frequency count must be 0 or 2 .. 256",
@@ -203,6 +162,7 @@ const QtfSpec kDrift = {&hc_ctx::drift,
                         "hc_drift_end without hc_drift_begin"};
 const QtfSpec kSum   = {&hc_ctx::sum,
                         sum_qtf_kernel,
+                        kQtfSum,
                         false,
                         1,
                         "sum-frequency count must be 0 or 2 .. 256",
@@ -214,74 +174,120 @@ const QtfSpec kSum   = {&hc_ctx::sum,
                         "the QTF tables hold one heading: sum-frequency forces are not available while wave directions are set (hc_set_wave_directions)",
                         "hc_sum_qtf_end without hc_sum_qtf_begin"};
 
+const char* const kOutsideQtfGrid =
+    "a wave direction lies outside the heading grid of a body's QTF table (hc_set_drift_qtf_headings, hc_set_sum_qtf_headings: no "
+    "extrapolation, no wrap-around)";
+
+// A table on a heading grid as the kernels of hc_qtf_dir.hip read it: [6][J][J] with node p = a nq + m, from [6][nh][nh][nq][nq]
+void qtf_append_nodes(std::vector<double>& pq, const std::vector<double>& T, int nh, int nq) {
+    const size_t J = static_cast<size_t>(nh) * nq, at = pq.size();
+    pq.resize(at + 6 * J * J);
+    for (int d = 0; d < 6; ++d)
+        for (int a = 0; a < nh; ++a)
+            for (int b = 0; b < nh; ++b)
+                for (int m = 0; m < nq; ++m) {
+                    const double* src = T.data() + (((static_cast<size_t>(d) * nh + a) * nh + b) * nq + m) * nq;
+                    std::copy(src, src + nq, pq.begin() + at + (d * J + a * nq + m) * J + static_cast<size_t>(b) * nq);
+                }
+}
+
 // The device copy of the owned bodies' tables (when a table has changed) and, per owned body with a table, the map from grid bin
-// to (component, weight) and (drift) E_m for the component table in force (when a table or the wave model has changed).
+// (node, for a table on a heading grid) to (component, weight) and (drift) E_m for the component table and the directions in force
+// (when a table, the wave model or the directions have changed).  The slots of the one-heading tables come first, in every list.
 void qtf_layout(hc_ctx* c, const QtfSpec& s) {
     QtfTerm& q         = c->*s.term;
     const double phase = q.phase_opt;
     const bool same_waves = kin_table_current(c, q.serial, q.phase, phase);
     if (same_waves && !q.dirty) return;
     hipStream_t st = q.stream;
+    q.serial       = ~0ULL;  // a failure below leaves nothing that counts as current
     if (!same_waves) {
-        const std::vector<double> tab = kin_table_host(c, phase);
-        q.tab.upload(tab, st);
-        q.nf     = static_cast<int>(tab.size() / kKinCols);
-        q.serial = c->wave_serial;
-        q.phase  = phase;
+        std::vector<double> tab = kin_table_host(c, phase);
+        q.nf = static_cast<int>(tab.size() / kKinCols);
         q.amp.assign(tab.begin() + static_cast<size_t>(kKinAmp) * q.nf, tab.begin() + static_cast<size_t>(kKinAmp + 1) * q.nf);
         q.omega.assign(tab.begin() + static_cast<size_t>(kKinOmega) * q.nf, tab.begin() + static_cast<size_t>(kKinOmega + 1) * q.nf);
+        // the direction columns behind the table's own (hc_qtf_dir.hip); none set: theta_i = 0, the phase of the one-heading kernels
+        std::vector<double> dir = kin_dir_columns_host(c);
+        q.theta = c->wave_dir;
+        if (dir.empty()) {
+            dir.assign(static_cast<size_t>(kDirCols) * q.nf, 0.0);
+            std::fill(dir.begin(), dir.begin() + q.nf, 1.0);
+            q.theta.assign(q.nf, 0.0);
+        }
+        tab.insert(tab.end(), dir.begin(), dir.end());
+        q.tab.upload(tab, st);
     }
     const int nf = q.nf;
     std::vector<long long> desc;
     std::vector<int> rowptr, idx, slot_body;
     std::vector<double> wgt, em, pq;
     size_t pq_n = 0;  // doubles of the tables before this body's
-    for (int b = c->b0; b < c->b1; ++b) {
-        const QtfTable& T = q.tabs[b];
-        if (T.nq == 0) continue;
-        const int nq = T.nq;
-        const size_t n6 = 6 * static_cast<size_t>(nq) * nq;
-        // cell and weight of every component inside [Omega_0, Omega_{nq-1}] (both ends inside)
-        std::vector<std::vector<std::pair<int, double>>> bins(nq);
-        std::vector<double> E(s.build_em ? nq : 0, 0.0);
-        for (int i = 0; i < nf; ++i) {
-            const double w = q.omega[i], A = q.amp[i];
-            if (!(w >= T.omega.front() && w <= T.omega.back())) continue;
-            int m = static_cast<int>(std::upper_bound(T.omega.begin(), T.omega.end(), w) - T.omega.begin()) - 1;  // largest m with Omega_m <= w
-            m     = std::min(m, nq - 2);
-            const double lam = (w - T.omega[m]) / (T.omega[m + 1] - T.omega[m]);
-            const double w0 = 1.0 - lam, w1 = lam;
-            if (w0 != 0.0) {
-                bins[m].emplace_back(i, w0);
-                if (s.build_em) E[m] += w0 * (A * A);
+    int slots_dir = 0, chunks_dir = 0;
+    for (int pass = 0; pass < 2; ++pass)
+        for (int b = c->b0; b < c->b1; ++b) {
+            const QtfTable& T = q.tabs[b];
+            if (T.nq == 0 || (T.nh != 0) != (pass == 1)) continue;
+            const int nq = T.nq, nh = std::max(T.nh, 1), J = nh * nq;
+            const size_t n6 = 6 * static_cast<size_t>(J) * J;
+            // cell and weight of every component inside [Omega_0, Omega_{nq-1}] (both ends inside); on a heading grid times the
+            // weights of the two headings around its direction
+            std::vector<std::vector<std::pair<int, double>>> bins(J);
+            std::vector<double> E(s.build_em ? J : 0, 0.0);
+            const auto deposit = [&](int node, int i, double w, double A) {
+                if (w == 0.0) return;
+                bins[node].emplace_back(i, w);
+                if (s.build_em) E[node] += w * (A * A);
+            };
+            for (int i = 0; i < nf; ++i) {
+                const double w = q.omega[i], A = q.amp[i];
+                if (!(w >= T.omega.front() && w <= T.omega.back())) continue;
+                int m = static_cast<int>(std::upper_bound(T.omega.begin(), T.omega.end(), w) - T.omega.begin()) - 1;  // largest m with Omega_m <= w
+                m     = std::min(m, nq - 2);
+                const double lam = (w - T.omega[m]) / (T.omega[m + 1] - T.omega[m]);
+                const double w0 = 1.0 - lam, w1 = lam;
+                if (pass == 0) {
+                    deposit(m, i, w0, A);
+                    deposit(m + 1, i, w1, A);
+                } else {
+                    const HeadBracket hb = heading_bracket(T.beta, q.theta[i], kOutsideQtfGrid);
+                    const double h0 = 1.0 - hb.wt, h1 = hb.wt;
+                    deposit(hb.j0 * nq + m, i, h0 * w0, A);
+                    deposit(hb.j0 * nq + m + 1, i, h0 * w1, A);
+                    deposit(hb.j1 * nq + m, i, h1 * w0, A);  // (j1 == j0 at the last heading: h1 is 0)
+                    deposit(hb.j1 * nq + m + 1, i, h1 * w1, A);
+                }
             }
-            if (w1 != 0.0) {
-                bins[m + 1].emplace_back(i, w1);
-                if (s.build_em) E[m + 1] += w1 * (A * A);
+            desc.push_back(b);
+            desc.push_back(J);
+            desc.push_back(static_cast<long long>(rowptr.size()));
+            desc.push_back(static_cast<long long>(pq_n));
+            desc.push_back(T.has_q ? static_cast<long long>(pq_n + n6) : -1LL);
+            desc.push_back(static_cast<long long>(em.size()));
+            for (int m = 0; m < J; ++m) {
+                rowptr.push_back(static_cast<int>(idx.size()));
+                for (const auto& e : bins[m]) {
+                    idx.push_back(e.first);
+                    wgt.push_back(e.second);
+                }
             }
-        }
-        desc.push_back(b);
-        desc.push_back(nq);
-        desc.push_back(static_cast<long long>(rowptr.size()));
-        desc.push_back(static_cast<long long>(pq_n));
-        desc.push_back(T.has_q ? static_cast<long long>(pq_n + n6) : -1LL);
-        desc.push_back(static_cast<long long>(em.size()));
-        for (int m = 0; m < nq; ++m) {
             rowptr.push_back(static_cast<int>(idx.size()));
-            for (const auto& e : bins[m]) {
-                idx.push_back(e.first);
-                wgt.push_back(e.second);
+            em.insert(em.end(), E.begin(), E.end());
+            pq_n += n6 * (T.has_q ? 2 : 1);
+            if (q.dirty) {  // otherwise the device copy is in place
+                if (pass == 0) {
+                    pq.insert(pq.end(), T.P.begin(), T.P.end());
+                    if (T.has_q) pq.insert(pq.end(), T.Q.begin(), T.Q.end());
+                } else {
+                    qtf_append_nodes(pq, T.P, nh, nq);
+                    if (T.has_q) qtf_append_nodes(pq, T.Q, nh, nq);
+                }
+            }
+            slot_body.push_back(b - c->b0);
+            if (pass == 1) {
+                ++slots_dir;
+                chunks_dir = std::max(chunks_dir, (J + kQtfDirRows - 1) / kQtfDirRows);
             }
         }
-        rowptr.push_back(static_cast<int>(idx.size()));
-        em.insert(em.end(), E.begin(), E.end());
-        pq_n += n6 * (T.has_q ? 2 : 1);
-        if (q.dirty) {  // otherwise the device copy is in place
-            pq.insert(pq.end(), T.P.begin(), T.P.end());
-            if (T.has_q) pq.insert(pq.end(), T.Q.begin(), T.Q.end());
-        }
-        slot_body.push_back(b - c->b0);
-    }
     if (idx.empty()) {  // keep the pointers valid where no component falls inside a grid
         idx.push_back(0);
         wgt.push_back(0.0);
@@ -292,19 +298,25 @@ void qtf_layout(hc_ctx* c, const QtfSpec& s) {
     q.w.upload(wgt, st);
     if (s.build_em) q.em.upload(em, st);
     if (q.dirty) q.pq.upload(pq, st);
-    q.slot_body = slot_body;
-    q.dirty     = false;
+    q.slot_body  = slot_body;
+    q.slots_dir  = slots_dir;
+    q.chunks_dir = chunks_dir;
+    q.dirty      = false;
+    q.serial     = c->wave_serial;
+    q.phase      = phase;
 }
 
 void qtf_enqueue(hc_ctx* c, const QtfSpec& s, double t, const double* pos) {
     QtfTerm& q      = c->*s.term;
     const size_t n3 = 3 * static_cast<size_t>(c->N);
     qtf_layout(c, s);
-    const size_t nout = 6 * q.slot_body.size();
+    const size_t nout = 6 * q.slot_body.size(), nout_dir = 6 * static_cast<size_t>(q.slots_dir), nout_one = nout - nout_dir;
+    require(nout_dir <= 65535, HC_ERR_INVALID, "too many bodies with a QTF table on a heading grid for one launch");
     if (q.h_pos.n < n3) q.h_pos.alloc(n3);
     if (q.pos.n < n3) q.pos.alloc(n3);
     if (q.h_out.n < nout) q.h_out.alloc(nout);
     if (q.out.n < nout) q.out.alloc(nout);
+    if (q.part.n < nout_dir * kQtfDirChunks) q.part.alloc(nout_dir * kQtfDirChunks);
     std::copy(pos, pos + n3, q.h_pos.p);
     const double ramp = kin_ramp(c, t);
     QtfArgs a{};
@@ -323,42 +335,65 @@ void qtf_enqueue(hc_ctx* c, const QtfSpec& s, double t, const double* pos) {
     a.out     = q.out.p;
     hipStream_t st = q.stream;
     HC_HIP(hipMemcpyAsync(q.pos.p, q.h_pos.p, n3 * sizeof(double), hipMemcpyHostToDevice, st));
-    hipLaunchKernelGGL(s.kernel, dim3(static_cast<unsigned>(nout)), dim3(kQtfThreads), 0, st, a);
-    HC_HIP(hipGetLastError());
+    if (nout_one) {
+        hipLaunchKernelGGL(s.kernel, dim3(static_cast<unsigned>(nout_one)), dim3(kQtfThreads), 0, st, a);
+        HC_HIP(hipGetLastError());
+    }
+    if (nout_dir) {  // the slots behind those of the one-heading tables
+        QtfDirArgs g{};
+        g.a      = a;
+        g.a.desc = a.desc + kDescWords * (nout_one / 6);
+        g.a.out  = a.out + nout_one;
+        g.part   = q.part.p;
+        const bool diagonal = s.kind == kQtfDrift && q.mode != 3;
+        qtf_dir_launch(g, s.kind, q.slots_dir, diagonal ? 1 : q.chunks_dir, st);
+        HC_HIP(hipGetLastError());
+    }
     HC_HIP(hipMemcpyAsync(q.h_out.p, q.out.p, nout * sizeof(double), hipMemcpyDeviceToHost, st));
 }
 
 // ---- the entry points of a term (include/hydrochrono_amd.h): the extern "C" functions below forward to these ----
 
-int qtf_set_table(hc_ctx* c, const QtfSpec& s, int body, int nq, const double* omega, const double* P, const double* Q) {
+// nh = 0: a one-heading table (hc_set_drift_qtf, hc_set_sum_qtf); nh > 0: P, Q [6][nh][nh][nq][nq] on the heading grid beta
+int qtf_set_table(hc_ctx* c, const QtfSpec& s, int body, int nh, const double* beta, int nq, const double* omega, const double* P,
+                  const double* Q, bool headings) {
     HC_API_BEGIN_HOT(c)
     QtfTerm& q = c->*s.term;
     require(body >= 0 && body < c->N, HC_ERR_INVALID, "body index out of range");
     require(nq == 0 || (nq >= 2 && nq <= kDriftMaxFreq), HC_ERR_INVALID, s.msg_count);
-    require(nq == 0 || (omega && P), HC_ERR_INVALID, "null frequency grid or QTF table");
+    if (nq == 0 || !headings) nh = 0;
+    if (nq && headings) {
+        require(nh >= 1 && nh <= kQtfMaxHeadings, HC_ERR_INVALID, "QTF heading count must be 1 .. 16");
+        require(nh * nq <= kQtfMaxNodes, HC_ERR_INVALID, "heading count times frequency count of a QTF table must not exceed 1024 nodes");
+    }
+    require(nq == 0 || (omega && P && (!headings || beta)), HC_ERR_INVALID, "null frequency grid, heading grid or QTF table");
     require(!q.pending, HC_ERR_INVALID, s.msg_in_flight);
-    const size_t n6 = 6 * static_cast<size_t>(nq) * nq;
+    const size_t nn = static_cast<size_t>(std::max(nh, 1)) * nq, n6 = 6 * nn * nn;
     if (nq) {
         require(all_finite(omega, nq) && all_finite(P, n6) && (!Q || all_finite(Q, n6)), HC_ERR_INVALID, s.msg_table);
         for (int m = 1; m < nq; ++m) require(omega[m] > omega[m - 1], HC_ERR_INVALID, s.msg_grid);
+        require(nh == 0 || all_finite(beta, nh), HC_ERR_INVALID, "non-finite value in a QTF heading grid");
+        for (int j = 1; j < nh; ++j) require(beta[j] > beta[j - 1], HC_ERR_INVALID, "the QTF heading grid is not strictly increasing");
     }
     if (!q.stream) HC_HIP(hipStreamCreateWithFlags(&q.stream, hipStreamNonBlocking));
     if (q.tabs.empty()) q.tabs.resize(c->N);
     QtfTable& T = q.tabs[body];
     T.nq        = nq;
+    T.nh        = nh;
     T.has_q     = nq != 0 && Q != nullptr;
     T.omega.assign(omega, omega + nq);
+    T.beta.assign(beta, beta + nh);
     T.P.assign(P, P + n6);
     T.Q.assign(Q, Q + (T.has_q ? n6 : 0));
     q.dirty = true;
     HC_API_END(c)
 }
 
-int qtf_get_size(hc_ctx* c, const QtfSpec& s, int body, int* nq) {
+int qtf_get_size(hc_ctx* c, const QtfSpec& s, int body, int* nq, bool headings) {
     HC_API_BEGIN_HOT(c)
     const QtfTerm& q = c->*s.term;
     require(body >= 0 && body < c->N && nq, HC_ERR_INVALID, "body index out of range or null pointer");
-    *nq = q.tabs.empty() ? 0 : q.tabs[body].nq;
+    *nq = q.tabs.empty() ? 0 : (headings ? q.tabs[body].nh : q.tabs[body].nq);
     HC_API_END(c)
 }
 
@@ -397,7 +432,9 @@ int qtf_begin(hc_ctx* c, const QtfSpec& s, double t, const double* pos) {
     require(!q.pending, HC_ERR_INVALID, s.msg_twice);
     require(pos != nullptr, HC_ERR_INVALID, "null state");
     require(std::isfinite(t) && all_finite(pos, 3 * static_cast<size_t>(c->N)), HC_ERR_INVALID, "non-finite time or position");
-    require(q.mode == 0 || c->wave_dir.empty(), HC_ERR_UNSUPPORTED, s.msg_directions);
+    bool one_heading = false;  // of any body of the system: every shard context answers alike
+    for (const QtfTable& T : q.tabs) one_heading = one_heading || (T.nq != 0 && T.nh == 0);
+    require(q.mode == 0 || c->wave_dir.empty() || !one_heading, HC_ERR_UNSUPPORTED, s.msg_directions);
     bool any = false;
     if (!q.tabs.empty())
         for (int b = c->b0; b < c->b1; ++b) any = any || q.tabs[b].nq != 0;
@@ -436,9 +473,13 @@ int qtf_end(hc_ctx* c, const QtfSpec& s, double* out) {
 extern "C" {
 
 int hc_set_drift_qtf(hc_ctx* c, int body, int nq, const double* omega, const double* P, const double* Q) {
-    return hc::qtf_set_table(c, hc::kDrift, body, nq, omega, P, Q);
+    return hc::qtf_set_table(c, hc::kDrift, body, 0, nullptr, nq, omega, P, Q, false);
 }
-int hc_get_drift_qtf_size(hc_ctx* c, int body, int* nq) { return hc::qtf_get_size(c, hc::kDrift, body, nq); }
+int hc_set_drift_qtf_headings(hc_ctx* c, int body, int nh, const double* beta, int nq, const double* omega, const double* P, const double* Q) {
+    return hc::qtf_set_table(c, hc::kDrift, body, nh, beta, nq, omega, P, Q, true);
+}
+int hc_get_drift_qtf_size(hc_ctx* c, int body, int* nq) { return hc::qtf_get_size(c, hc::kDrift, body, nq, false); }
+int hc_get_drift_qtf_headings(hc_ctx* c, int body, int* nh) { return hc::qtf_get_size(c, hc::kDrift, body, nh, true); }
 int hc_set_drift_mode(hc_ctx* c, int mode) { return hc::qtf_set_mode(c, hc::kDrift, mode); }
 int hc_get_drift_mode(hc_ctx* c, int* mode) { return hc::qtf_get_mode(c, hc::kDrift, mode); }
 int hc_set_drift_options(hc_ctx* c, const hc_wave_kinematics_opts* o) { return hc::qtf_set_options(c, hc::kDrift, o); }
@@ -450,9 +491,13 @@ int hc_compute_drift(hc_ctx* c, double t, const double* pos, double* out) {
 }
 
 int hc_set_sum_qtf(hc_ctx* c, int body, int nq, const double* omega, const double* P, const double* Q) {
-    return hc::qtf_set_table(c, hc::kSum, body, nq, omega, P, Q);
+    return hc::qtf_set_table(c, hc::kSum, body, 0, nullptr, nq, omega, P, Q, false);
 }
-int hc_get_sum_qtf_size(hc_ctx* c, int body, int* nq) { return hc::qtf_get_size(c, hc::kSum, body, nq); }
+int hc_set_sum_qtf_headings(hc_ctx* c, int body, int nh, const double* beta, int nq, const double* omega, const double* P, const double* Q) {
+    return hc::qtf_set_table(c, hc::kSum, body, nh, beta, nq, omega, P, Q, true);
+}
+int hc_get_sum_qtf_size(hc_ctx* c, int body, int* nq) { return hc::qtf_get_size(c, hc::kSum, body, nq, false); }
+int hc_get_sum_qtf_headings(hc_ctx* c, int body, int* nh) { return hc::qtf_get_size(c, hc::kSum, body, nh, true); }
 int hc_set_sum_mode(hc_ctx* c, int mode) { return hc::qtf_set_mode(c, hc::kSum, mode); }
 int hc_get_sum_mode(hc_ctx* c, int* mode) { return hc::qtf_get_mode(c, hc::kSum, mode); }
 int hc_set_sum_options(hc_ctx* c, const hc_wave_kinematics_opts* o) { return hc::qtf_set_options(c, hc::kSum, o); }

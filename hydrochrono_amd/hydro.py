@@ -724,37 +724,65 @@ class HydroForces:
         return tuple(x.copy() for x in m)
 
     # -- second-order wave drift forces from QTF tables (an extension beyond the reference) --
-    def set_drift_qtf(self, b, omega, P, Q=None):
-        """Replaces the difference-frequency QTF table of body b (0-based): omega [nq] rad/s, strictly increasing, 2 <= nq <= 256;
-        P, Q [6][nq][nq] real and imaginary part, force (moment) per squared amplitude, dimensional; Q=None means zeros; an empty
-        omega clears the table.  With set_drift_mode(1, 2 or 3) step() then returns total + drift term."""
+    def _set_qtf(self, setter, setter_headings, b, omega, P, Q, headings):
         omega = np.ascontiguousarray(omega, dtype=np.float64).reshape(-1)
         nq = omega.size
         if nq == 0:
-            self._chk(self.lib.hc_set_drift_qtf(self.ctx, int(b), 0, None, None, None))
-        else:
-            P = np.ascontiguousarray(P, dtype=np.float64)
-            if P.size != 6 * nq * nq or (Q is not None and np.size(Q) != 6 * nq * nq):
+            self._chk(setter(self.ctx, int(b), 0, None, None, None))
+            return 0
+        P = np.ascontiguousarray(P, dtype=np.float64)
+        Q = None if Q is None else np.ascontiguousarray(Q, dtype=np.float64)
+        if headings is None:
+            if P.size != 6 * nq * nq or (Q is not None and Q.size != 6 * nq * nq):
                 raise ValueError("P and Q must have shape (6, nq, nq)")
-            Q = None if Q is None else np.ascontiguousarray(Q, dtype=np.float64)
-            self._chk(self.lib.hc_set_drift_qtf(self.ctx, int(b), nq, _dp(omega), _dp(P), None if Q is None else _dp(Q)))
+            self._chk(setter(self.ctx, int(b), nq, _dp(omega), _dp(P), None if Q is None else _dp(Q)))
+        else:
+            beta = np.ascontiguousarray(headings, dtype=np.float64).reshape(-1)
+            shape = (6, beta.size, beta.size, nq, nq)
+            if P.shape != shape or (Q is not None and Q.shape != shape):
+                raise ValueError("with headings, P and Q must have shape (6, nh, nh, nq, nq)")
+            self._chk(setter_headings(self.ctx, int(b), beta.size, _dp(beta), nq, _dp(omega), _dp(P), None if Q is None else _dp(Q)))
+        return nq
+
+    def set_drift_qtf(self, b, omega, P, Q=None, headings=None):
+        """Replaces the difference-frequency QTF table of body b (0-based): omega [nq] rad/s, strictly increasing, 2 <= nq <= 256;
+        P, Q [6][nq][nq] real and imaginary part, force (moment) per squared amplitude, dimensional; Q=None means zeros; an empty
+        omega clears the table.  With set_drift_mode(1, 2 or 3) step() then returns total + drift term.
+        headings [nh] rad (world frame, strictly increasing, nh <= 16, nh nq <= 1024): a table on a heading grid, P, Q of shape
+        (6, nh, nh, nq, nq), element (d, a, b, m, n) = T(beta_a, beta_b, Omega_m, Omega_n); the one kind of table that is evaluated
+        while wave directions are set (hc_set_drift_qtf_headings)."""
+        nq = self._set_qtf(self.lib.hc_set_drift_qtf, self.lib.hc_set_drift_qtf_headings, b, omega, P, Q, headings)
         self.__dict__.setdefault("_drift_sizes", {})[int(b)] = nq
 
-    def set_drift_mean(self, b, omega, D):
+    def set_drift_mean(self, b, omega, D, headings=None):
         """Mean-drift coefficients D [6][nq] on omega [nq]: a table with D on the diagonal and zeros elsewhere, for modes 1 and 2
-        (mode 3 needs a full table: it would take the zeros off the diagonal as data)."""
+        (mode 3 needs a full table: it would take the zeros off the diagonal as data).  With headings [nh]: D of shape (6, nh, nq)."""
         omega = np.ascontiguousarray(omega, dtype=np.float64).reshape(-1)
         nq = omega.size
         D = np.ascontiguousarray(D, dtype=np.float64)
-        if D.shape != (6, nq):
-            raise ValueError("D must have shape (6, nq)")
-        P = np.zeros((6, nq, nq))
-        P[:, np.arange(nq), np.arange(nq)] = D
-        self.set_drift_qtf(b, omega, P)
+        if headings is None:
+            if D.shape != (6, nq):
+                raise ValueError("D must have shape (6, nq)")
+            P = np.zeros((6, nq, nq))
+            P[:, np.arange(nq), np.arange(nq)] = D
+        else:
+            nh = np.size(headings)
+            if D.shape != (6, nh, nq):
+                raise ValueError("with headings, D must have shape (6, nh, nq)")
+            P = np.zeros((6, nh, nh, nq, nq))
+            for a in range(nh):
+                P[:, a, a, np.arange(nq), np.arange(nq)] = D[:, a]
+        self.set_drift_qtf(b, omega, P, headings=headings)
 
     def drift_qtf_size(self, b):
         n = C.c_int()
         self._chk(self.lib.hc_get_drift_qtf_size(self.ctx, int(b), C.byref(n)))
+        return n.value
+
+    def drift_qtf_headings(self, b):
+        """The heading count of body b's drift table: 0 for a one-heading table or none."""
+        n = C.c_int()
+        self._chk(self.lib.hc_get_drift_qtf_headings(self.ctx, int(b), C.byref(n)))
         return n.value
 
     def set_drift_mode(self, mode):
@@ -794,26 +822,23 @@ class HydroForces:
         return np.zeros(self.D_local) if m is None or not self._drift_on() else m.copy()
 
     # -- second-order wave forces from sum-frequency QTF tables (an extension beyond the reference) --
-    def set_sum_qtf(self, b, omega, P, Q=None):
+    def set_sum_qtf(self, b, omega, P, Q=None, headings=None):
         """Replaces the sum-frequency QTF table of body b (0-based): omega [nq] rad/s, a grid of its own, strictly increasing,
         2 <= nq <= 256; P, Q [6][nq][nq] real and imaginary part, force (moment) per squared amplitude, dimensional; Q=None means
         zeros; an empty omega clears the table.  Only the symmetric part of a table can contribute.  With set_sum_mode(1) step() then
-        returns total (+ drift term) + sum-frequency term."""
-        omega = np.ascontiguousarray(omega, dtype=np.float64).reshape(-1)
-        nq = omega.size
-        if nq == 0:
-            self._chk(self.lib.hc_set_sum_qtf(self.ctx, int(b), 0, None, None, None))
-        else:
-            P = np.ascontiguousarray(P, dtype=np.float64)
-            if P.size != 6 * nq * nq or (Q is not None and np.size(Q) != 6 * nq * nq):
-                raise ValueError("P and Q must have shape (6, nq, nq)")
-            Q = None if Q is None else np.ascontiguousarray(Q, dtype=np.float64)
-            self._chk(self.lib.hc_set_sum_qtf(self.ctx, int(b), nq, _dp(omega), _dp(P), None if Q is None else _dp(Q)))
+        returns total (+ drift term) + sum-frequency term.  headings: as set_drift_qtf (hc_set_sum_qtf_headings)."""
+        nq = self._set_qtf(self.lib.hc_set_sum_qtf, self.lib.hc_set_sum_qtf_headings, b, omega, P, Q, headings)
         self.__dict__.setdefault("_sum_sizes", {})[int(b)] = nq
 
     def sum_qtf_size(self, b):
         n = C.c_int()
         self._chk(self.lib.hc_get_sum_qtf_size(self.ctx, int(b), C.byref(n)))
+        return n.value
+
+    def sum_qtf_headings(self, b):
+        """The heading count of body b's sum-frequency table: 0 for a one-heading table or none."""
+        n = C.c_int()
+        self._chk(self.lib.hc_get_sum_qtf_headings(self.ctx, int(b), C.byref(n)))
         return n.value
 
     def set_sum_mode(self, mode):
@@ -1023,6 +1048,9 @@ class HydroGroup:
     def drift_qtf_size(self, b):
         return self.shards[0].drift_qtf_size(b)
 
+    def drift_qtf_headings(self, b):
+        return self.shards[0].drift_qtf_headings(b)
+
     # -- sum-frequency tables: every shard holds the tables of all bodies and computes those of its own --
     def _sum_begin(self, t, pos):
         begun = []
@@ -1063,6 +1091,9 @@ class HydroGroup:
 
     def sum_qtf_size(self, b):
         return self.shards[0].sum_qtf_size(b)
+
+    def sum_qtf_headings(self, b):
+        return self.shards[0].sum_qtf_headings(b)
 
     # -- surface panels and triangles: every shard holds the lists of all bodies and computes those of its own --
     def surface_panel_count(self, b):

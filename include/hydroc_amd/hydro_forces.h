@@ -497,6 +497,22 @@ class TestHydro {
         drift_size_[static_cast<size_t>(body_index_1_based - 1)] = nq;
         have_time_ = false;  // the cached total belongs to the tables before
     }
+    // The same on a heading grid (hc_set_drift_qtf_headings): beta [nh] rad, world frame, strictly increasing; P and Q
+    // [6][nh][nh][nq][nq] row-major, element (d, a, b, m, n) = T(beta_a, beta_b, Omega_m, Omega_n).  The one kind of table that is
+    // evaluated while wave directions are set (SetWaveDirections); it replaces a table set with SetDriftQTF, and the other way round.
+    void SetDriftQTFHeadings(int body_index_1_based, const std::vector<double>& beta, const std::vector<double>& omega,
+                             const std::vector<double>& P, const std::vector<double>& Q = {}) {
+        if (body_index_1_based < 1 || body_index_1_based > num_bodies_) throw std::out_of_range("SetDriftQTFHeadings: body index out of range");
+        const size_t nq = omega.size(), nh = beta.size(), n6 = 6 * nh * nh * nq * nq;
+        if (P.size() != n6 || (!Q.empty() && Q.size() != n6))
+            throw std::invalid_argument("SetDriftQTFHeadings: P and Q must hold 6 * nh * nh * nq * nq values");
+        for (hc_ctx* c : ctxs_)
+            check(c, hc_set_drift_qtf_headings(c, body_index_1_based - 1, static_cast<int>(nh), beta.data(), static_cast<int>(nq),
+                                               nq ? omega.data() : nullptr, nq ? P.data() : nullptr, Q.empty() ? nullptr : Q.data()));
+        drift_size_.resize(static_cast<size_t>(num_bodies_), 0);
+        drift_size_[static_cast<size_t>(body_index_1_based - 1)] = nq;
+        have_time_ = false;  // the cached total belongs to the tables before
+    }
     // mean-drift coefficients D [6][nq]: a table with D on the diagonal and zeros elsewhere, for modes 1 and 2 (mode 3 needs a full
     // table: it would take the zeros off the diagonal as data)
     void SetMeanDriftCoefficients(int body_index_1_based, const std::vector<double>& omega, const std::vector<double>& D) {
@@ -542,6 +558,20 @@ class TestHydro {
         for (hc_ctx* c : ctxs_)
             check(c, hc_set_sum_qtf(c, body_index_1_based - 1, static_cast<int>(nq), nq ? omega.data() : nullptr, nq ? P.data() : nullptr,
                                     Q.empty() ? nullptr : Q.data()));
+        sum_size_.resize(static_cast<size_t>(num_bodies_), 0);
+        sum_size_[static_cast<size_t>(body_index_1_based - 1)] = nq;
+        have_time_ = false;  // the cached total belongs to the tables before
+    }
+    // The same on a heading grid (hc_set_sum_qtf_headings), as SetDriftQTFHeadings
+    void SetSumQTFHeadings(int body_index_1_based, const std::vector<double>& beta, const std::vector<double>& omega,
+                           const std::vector<double>& P, const std::vector<double>& Q = {}) {
+        if (body_index_1_based < 1 || body_index_1_based > num_bodies_) throw std::out_of_range("SetSumQTFHeadings: body index out of range");
+        const size_t nq = omega.size(), nh = beta.size(), n6 = 6 * nh * nh * nq * nq;
+        if (P.size() != n6 || (!Q.empty() && Q.size() != n6))
+            throw std::invalid_argument("SetSumQTFHeadings: P and Q must hold 6 * nh * nh * nq * nq values");
+        for (hc_ctx* c : ctxs_)
+            check(c, hc_set_sum_qtf_headings(c, body_index_1_based - 1, static_cast<int>(nh), beta.data(), static_cast<int>(nq),
+                                             nq ? omega.data() : nullptr, nq ? P.data() : nullptr, Q.empty() ? nullptr : Q.data()));
         sum_size_.resize(static_cast<size_t>(num_bodies_), 0);
         sum_size_[static_cast<size_t>(body_index_1_based - 1)] = nq;
         have_time_ = false;  // the cached total belongs to the tables before

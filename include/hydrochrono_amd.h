@@ -543,8 +543,10 @@ int hc_wave_kinematics(hc_ctx* ctx, const hc_wave_kinematics_opts* o, int n_poin
  *
  * What refuses while directions are set (HC_ERR_UNSUPPORTED from the compute / begin call, nothing stays pending; as before once
  * they are cleared): hc_wave_kinematics2, the Morison elements and the nonlinear surface on the second-order sea
- * (hc_set_morison_second_order / hc_set_nonlinear_second_order with `on`), hc_drift_begin with a drift mode != 0 and
- * hc_sum_qtf_begin with a sum mode != 0: their pair sums and QTF tables are those of one long-crested heading.
+ * (hc_set_morison_second_order / hc_set_nonlinear_second_order with `on`), and hc_drift_begin with a drift mode != 0 /
+ * hc_sum_qtf_begin with a sum mode != 0 while some body of the system holds a one-heading table of that term (hc_set_drift_qtf,
+ * hc_set_sum_qtf): their pair sums and those tables are of one long-crested heading.  QTF tables on a heading grid
+ * (hc_set_drift_qtf_headings, hc_set_sum_qtf_headings) are evaluated.
  *
  * First-order excitation under a heading: hc_set_excitation_rao_headings gives a body its excitation coefficients on a grid of
  * headings, dir_rad[n_dir] strictly increasing, mag / phase [6][n_dir][nw] (the layout of a BEMIO file; magnitudes per rho g as for
@@ -800,7 +802,26 @@ int hc_get_nonlinear_increments(hc_ctx* ctx, int body, int n, double* p /* [n][3
  * NoWave, no wave model, an imported eta record (no components), mode 0: zeros, no launch.  A body without a table: zeros.
  * World frame, at the body reference, the sign of an applied force.  A regular wave gives the constant A^2 T(w, w).
  * Sum-frequency QTFs are a term of their own (hc_set_sum_qtf below).  The tables hold one heading: while wave directions are set
- * (hc_set_wave_directions) hc_drift_begin with a mode != 0 returns HC_ERR_UNSUPPORTED.
+ * (hc_set_wave_directions) and some body holds such a table hc_drift_begin with a mode != 0 returns HC_ERR_UNSUPPORTED.
+ *
+ * QTF tables on a heading grid (hc_set_drift_qtf_headings, hc_set_sum_qtf_headings; both terms): what is evaluated while directions
+ * are set.  Per body and term a heading grid beta[0..nh) [rad], world frame, 0 along +x as hc_set_wave_directions, finite and
+ * strictly increasing, 1 <= nh <= 16, the frequency grid Omega[0..nq) as above, J = nh nq <= 1024, and P, Q [6][nh][nh][nq][nq]
+ * (row-major, Q may be NULL): element (d, a, b, m, n) is T(beta_a, beta_b, Omega_m, Omega_n), a and m belonging to component i of a
+ * pair, b and n to component j.  Dimensional; no symmetry is required or enforced.  A body holds one table per term: either setter
+ * replaces what the other stored; nq = 0 clears.
+ * Phase: that of the directional kinematics, psi_i = k_i (x cos theta_i + y sin theta_i) - w_i t + phi_i with x, y = pos[b]; with no
+ * directions set every theta_i = 0, the theta_i of the one-heading tables.  Frequency weights: exactly those above.  Heading weights:
+ * a_i is the largest a with beta_a <= theta_i, mu_i = (theta_i - beta_a) / (beta_{a+1} - beta_a), Wh[i][a_i] = 1 - mu_i,
+ * Wh[i][a_i + 1] = mu_i; a theta on a node has weight exactly 0 on the neighbour; nh = 1 is valid for theta_i == beta_0 only; no
+ * extrapolation and no wrap-around.  A component inside the frequency grid whose theta_i lies outside [beta_0, beta_{nh-1}] makes
+ * the begin call fail with HC_ERR_INVALID, nothing pending (it is not dropped silently).  The body's yaw is NOT applied to the
+ * headings, as with the first-order heading tables.
+ * With the node weight w_i,(a,m) = Wh[i][a] Wf[i][m], T(i, j) = sum_{a,b,m,n} w_i,(a,m) w_j,(b,n) T[a][b][m][n] and
+ * D(i) = sum_{a,m} w_i,(a,m) P[a][a][m][m] take the places of P_d(w_i, w_j), Q_d(w_i, w_j) and D_d(w_i) in the modes above and in the
+ * sum-frequency term, with psi for theta; ramp^2, the zero cases, the frame and the sign are unchanged.  The device evaluates the
+ * same projected form over the nodes p = a nq + m, O(nf + J^2) per row, in a fixed order: a body's bits depend on its own table,
+ * pos[b].x, pos[b].y, t, the wave model with its directions, the mode and the regular phase only.
  *
  * The device evaluates the exact projected form, O(nf + nq^2) per row: with u_i = A_i cos theta_i, w_i = A_i sin theta_i,
  * U_m = sum_i W[i][m] u_i, V_m = sum_i W[i][m] w_i,
@@ -819,6 +840,11 @@ int hc_get_nonlinear_increments(hc_ctx* ctx, int body, int n, double* p /* [n][3
  * grid or P with nq > 0, a non-finite value, a grid that is not strictly increasing, or a hc_drift_begin without its end. */
 int hc_set_drift_qtf(hc_ctx* ctx, int body, int nq, const double* omega, const double* P, const double* Q);
 int hc_get_drift_qtf_size(hc_ctx* ctx, int body, int* nq);
+/* The same on a heading grid ("QTF tables on a heading grid" above): replaces the table of `body`, of either kind; nq = 0 clears it.
+ * HC_ERR_INVALID in addition: nh outside 1 .. 16, nh nq above 1024, a null, non-finite or not strictly increasing heading grid.
+ * *nh of the getter: 0 for a one-heading table or none.  hc_get_drift_qtf_size reports nq for both kinds. */
+int hc_set_drift_qtf_headings(hc_ctx* ctx, int body, int nh, const double* beta, int nq, const double* omega, const double* P, const double* Q);
+int hc_get_drift_qtf_headings(hc_ctx* ctx, int body, int* nh);
 /* 0 off (default), 1 mean drift, 2 Newman's approximation, 3 full QTF; HC_ERR_INVALID outside 0..3 or while a begin is pending */
 int hc_set_drift_mode(hc_ctx* ctx, int mode);
 int hc_get_drift_mode(hc_ctx* ctx, int* mode);
@@ -853,7 +879,8 @@ int hc_compute_drift(hc_ctx* ctx, double t, const double* pos, double* out_Dloca
  * NoWave, no wave model, an imported eta record (no components), mode 0: zeros, no launch.  A body without a table: zeros.
  * World frame, at the body reference, the sign of an applied force.
  * There is no cut-off band on w_i + w_j: a caller who wants one zeroes table entries.  The tables hold one heading: while wave
- * directions are set (hc_set_wave_directions) hc_sum_qtf_begin with a mode != 0 returns HC_ERR_UNSUPPORTED.
+ * directions are set (hc_set_wave_directions) and some body holds such a table hc_sum_qtf_begin with a mode != 0 returns
+ * HC_ERR_UNSUPPORTED; tables on a heading grid (hc_set_sum_qtf_headings, defined with the drift term above) are evaluated.
  *
  * The device evaluates the exact projected form, O(nf + nq^2) per row, with the U_m, V_m of the drift term:
  *     F_s = sum_mn P_s[m][n] (U_m U_n - V_m V_n) - Q_s[m][n] (V_m U_n + U_m V_n)
@@ -869,6 +896,9 @@ int hc_compute_drift(hc_ctx* ctx, double t, const double* pos, double* out_Dloca
  * increasing, or a hc_sum_qtf_begin without its end. */
 int hc_set_sum_qtf(hc_ctx* ctx, int body, int nq, const double* omega, const double* P, const double* Q);
 int hc_get_sum_qtf_size(hc_ctx* ctx, int body, int* nq);
+/* As hc_set_drift_qtf_headings / hc_get_drift_qtf_headings, for the sum-frequency table of `body` */
+int hc_set_sum_qtf_headings(hc_ctx* ctx, int body, int nh, const double* beta, int nq, const double* omega, const double* P, const double* Q);
+int hc_get_sum_qtf_headings(hc_ctx* ctx, int body, int* nh);
 /* 0 off (default), 1 on; HC_ERR_INVALID otherwise or while a begin is pending */
 int hc_set_sum_mode(hc_ctx* ctx, int mode);
 int hc_get_sum_mode(hc_ctx* ctx, int* mode);
