@@ -115,6 +115,12 @@ struct Wk2TableSet {
     }
 };
 
+}  // namespace hc
+
+#include "hc_side.hpp"  // KinTableCopy, SideLane, Order2Part: made of the types above
+
+namespace hc {
+
 // A body's QTF table (hc_set_drift_qtf, hc_set_sum_qtf; on a heading grid: hc_set_drift_qtf_headings, hc_set_sum_qtf_headings):
 // nq = 0 none, nh = 0 one heading
 struct QtfTable {
@@ -126,29 +132,53 @@ struct QtfTable {
 };
 
 // One QTF term (hc_qtf.hip; the context holds two, drift and sum): the tables of all bodies of the system on the host, those of the
-// owned bodies one after the other on the device with the bin -> (component, weight) map of the component table in force; its own
-// stream, component table and pinned staging, nothing a step uses and nothing the other term uses (a table of one kind may change
-// while a launch of the other is in flight)
+// owned bodies one after the other on the device with the bin -> (component, weight) map of the component table in force; a lane of
+// its own (hc_side.hpp) and its own pinned staging, nothing a step uses and nothing the other term uses (a table of one kind may
+// change while a launch of the other is in flight)
 struct QtfTerm {
     std::vector<QtfTable> tabs;    // [N], each on a grid of its own
     int mode = 0;                  // 0 off; drift: 1 mean drift, 2 Newman, 3 full QTF; sum: 1 on
-    double phase_opt = 0.0;        // regular_phase of the term's options call
-    hipStream_t stream = nullptr;  // created by the first table set
-    bool dirty = false;            // a table has changed since the device copy was made
-    int pending = 0;               // a begin without its end: 1 zeros (nothing launched), 2 a launch is in flight
-    unsigned long long serial = ~0ULL;
-    double phase = 0.0;
-    int nf = 0;
+    SideLane lane;                 // (opts: the regular_phase of the term's options call; dirty: a table has changed)
     std::vector<double> omega, amp;  // [nf] of the component table in force
     std::vector<double> theta;       // [nf] the directions it was built with (zeros: none set)
     std::vector<int> slot_body;      // local body of every launched slot: the owned bodies with a one-heading table, ascending, then
                                      // those with a table on a heading grid, ascending
     int slots_dir  = 0;              // how many of them are of the second kind (hc_qtf_dir.hip)
     int chunks_dir = 0;              // the most chunks of 32 node rows any of those has
-    DeviceBuffer<double> tab, pq, w, em, pos, out, part;  // (em: the drift term's E_m; part: the chunk partials of hc_qtf_dir.hip)
+    DeviceBuffer<double> pq, w, em, pos, out, part;  // (em: the drift term's E_m; part: the chunk partials of hc_qtf_dir.hip)
     DeviceBuffer<long long> desc;
     DeviceBuffer<int> rowptr, idx;
     PinnedBuffer<double> h_pos, h_out;
+};
+
+// Morison elements (hc_set_morison_elements, hc_morison.hip): the lists of all bodies of the system on the host, those of the owned
+// bodies flattened body-major on the device, and the pinned staging
+struct MorisonData {
+    std::vector<std::vector<hc_morison_element>> elems;  // [N]
+    int items = 0;                                       // elements of the owned bodies
+    DeviceBuffer<double> elem, state, item, out;
+    DeviceBuffer<int> body, off;  // [items] body of an element, [nloc + 1] first element of an owned body
+    PinnedBuffer<double> h_state, h_out;
+};
+
+// Surface panels and triangles (hc_set_surface_panels, hc_set_surface_triangles, hc_nonlinear.hip): the lists of all bodies of the
+// system on the host, those of the owned bodies flattened body-major on the device with their chunk map, and the pinned staging.  A
+// body carries panels or triangles ([N] lists of 9 doubles per triangle, clipped at the free surface by nl_tris_kernel); both kinds
+// share the lane, the chunk map and the partial buffer.
+struct SurfaceData {
+    std::vector<std::vector<hc_surface_panel>> panels;  // [N]
+    std::vector<std::vector<double>> tris;              // [N]
+    int items = 0, chunks = 0;  // panels and triangles of the owned bodies, chunks of up to 256 of one body's list
+    std::vector<int> runs;      // [runs][3] (kind 0 panels / 1 triangles, first chunk, chunks): one launch per run of consecutive chunks of a kind
+    DeviceBuffer<double> panel, tri, state, part, out;
+    DeviceBuffer<int> chunk, off;         // [chunks][3] (body, first panel or triangle, count), [nloc + 1] first chunk of an owned body
+    PinnedBuffer<double> h_state, h_out;  // [6 N] pos | rpy of the last hc_nonlinear_begin, [nloc][12]
+    // on the second-order sea: the distinct body-frame points of the owned bodies' lists, body-major (Order2Part::off: the first
+    // point of an owned body), and the point of every panel and triangle vertex
+    bool pts_dirty = true;            // the point lists below are not those of the device copy of the lists
+    DeviceBuffer<double> pt;          // [points][3]
+    DeviceBuffer<int> pbody;          // [points] body of a point
+    DeviceBuffer<int> pidx, tidx;     // [panels], [triangles][3]: index into the points, following `panel` / `tri`
 };
 
 struct BodyHost {
@@ -305,82 +335,21 @@ struct hc_ctx {
     unsigned long long wave_serial = 0;  // counts the hc_set_wave_* calls (voids the kinematics table below)
     // Directions of the wave components (hc_set_wave_directions): theta_i per component of the model in force, empty: none (the
     // long-crested sea along +x).  Dropped by every hc_set_wave_* call; a change counts in wave_serial as those calls do, so that
-    // every cached component table is rebuilt.  kin_dir / mor_dir / nl_dir: the cached table of that path carries the two direction
-    // columns (cos, sin) behind its own and the launch goes to the directional instantiation.
+    // every cached component table is rebuilt.
     std::vector<double> wave_dir;
-    bool kin_dir = false, mor_dir = false, nl_dir = false;
 
-    // wave kinematics (hc_wave_kinematics, hc_wave_kin.hip): the component table of the wave model it was built for (wave_serial,
-    // and the phase of a regular wave), and a grow-only buffer for points, times and outputs
-    unsigned long long kin_serial = ~0ULL;
-    double kin_phase = 0.0;
-    int kin_nf = 0;
-    hc::DeviceBuffer<double> d_kin_tab, d_kin_io;
+    // wave kinematics (hc_wave_kinematics, hc_wave_kin.hip): the component table of the wave model it was built for, and a grow-only
+    // buffer for points, times and outputs
+    hc::KinTableCopy kin;
+    hc::DeviceBuffer<double> d_kin_io;
 
-    // Morison elements (hc_set_morison_elements, hc_morison.hip): the lists of all bodies of the system on the host, those of the
-    // owned bodies flattened body-major on the device; its own stream, component table and pinned staging, nothing a step uses
-    std::vector<std::vector<hc_morison_element>> mor_elems;  // [N]
-    hc_wave_kinematics_opts mor_opts{0.0, 0.0, 1};
-    hipStream_t stream_mor = nullptr;  // created by the first hc_set_morison_elements
-    bool mor_dirty = false;            // the lists have changed since the device copy was made
-    int mor_items = 0;                 // elements of the owned bodies
-    int mor_pending = 0;               // hc_morison_begin without its hc_morison_end: 1 zeros (nothing launched), 2 a launch is in flight
-    unsigned long long mor_serial = ~0ULL;
-    double mor_phase = 0.0;
-    int mor_nf = 0;
-    hc::DeviceBuffer<double> d_mor_tab, d_mor_elem, d_mor_state, d_mor_item, d_mor_out;
-    hc::DeviceBuffer<int> d_mor_body, d_mor_off;  // [items] body of an element, [nloc + 1] first element of an owned body
-    hc::PinnedBuffer<double> h_mor_state, h_mor_out;
-    // ... on the second-order sea (hc_set_morison_second_order): tables of its own, built on stream_mor (a hc_wave_kinematics2 call
-    // with other cut-offs may rebuild `wk2` while a launch of this path is in flight), the elements' points and increments
-    bool mor2_on = false;
-    double mor2_cut[4] = {0.0, HUGE_VAL, 0.0, HUGE_VAL};
-    int mor2_ramp = 1;
-    hc::Wk2TableSet mor2;
-    hc::DeviceBuffer<double> d_mor_inc;     // [items][kMorIncDoubles] p, eta2, u2x, u2z, a2x, a2z
-    hc::PinnedBuffer<double> h_mor_inc[2];  // its host copies: of the evaluation in flight and of the last completed one
-    int mor_inc_cur = 0;                    // which of the two holds the last completed one
-    bool mor_inc_flight = false;            // the evaluation in flight writes the other one
-    std::vector<int> mor_inc_off;           // [nloc + 1] first element of an owned body in it; empty: no evaluation has completed
-    std::vector<int> mor_off;               // [nloc + 1] of the device copy of the lists
-
-    // Surface panels (hc_set_surface_panels, hc_nonlinear.hip): the lists of all bodies of the system on the host, those of the owned
-    // bodies flattened body-major on the device with their chunk map; its own stream, component table and pinned staging, nothing a
-    // step uses
-    std::vector<std::vector<hc_surface_panel>> nl_panels;  // [N]
-    // Surface triangles (hc_set_surface_triangles): [N] lists of 9 doubles per triangle, clipped at the free surface by nl_tris_kernel.
-    // A body carries panels or triangles; both kinds share the stream, the table, the chunk map and the partial buffer.
-    std::vector<std::vector<double>> nl_tris;
-    hc_wave_kinematics_opts nl_opts{0.0, 0.0, 1};
-    hipStream_t stream_nl = nullptr;  // created by the first hc_set_surface_panels
-    bool nl_dirty = false;            // the lists have changed since the device copy was made
-    int nl_items = 0, nl_chunks = 0;  // panels and triangles of the owned bodies, chunks of up to 256 of one body's list
-    std::vector<int> nl_runs;         // [runs][3] (kind 0 panels / 1 triangles, first chunk, chunks): one launch per run of consecutive chunks of a kind
-    int nl_pending = 0;               // hc_nonlinear_begin without its hc_nonlinear_end: 1 zeros (nothing launched), 2 a launch is in flight
-    unsigned long long nl_serial = ~0ULL;
-    double nl_phase = 0.0;
-    int nl_nf = 0;
-    hc::DeviceBuffer<double> d_nl_tab, d_nl_panel, d_nl_tri, d_nl_state, d_nl_part, d_nl_out;
-    hc::DeviceBuffer<int> d_nl_chunk, d_nl_off;  // [chunks][3] (body, first panel or triangle, count), [nloc + 1] first chunk of an owned body
-    hc::PinnedBuffer<double> h_nl_state, h_nl_out;  // [6 N] pos | rpy of the last hc_nonlinear_begin, [nloc][12]
-    // ... on the second-order sea (hc_set_nonlinear_second_order): tables of its own, built on stream_nl (as `mor2`: a
-    // hc_wave_kinematics2 call with other cut-offs may rebuild `wk2` while a launch of this path is in flight); the distinct
-    // body-frame points of the owned bodies' lists, body-major, the point of every panel and triangle vertex, and the points'
-    // world positions and increments
-    bool nl2_on = false;
-    double nl2_cut[4] = {0.0, HUGE_VAL, 0.0, HUGE_VAL};
-    int nl2_ramp = 1;
-    hc::Wk2TableSet nl2;
-    bool nl_pts_dirty = true;               // the point lists below are not those of the device copy of the lists
-    hc::DeviceBuffer<double> d_nl_pt;       // [points][3]
-    hc::DeviceBuffer<int> d_nl_pbody;       // [points] body of a point
-    hc::DeviceBuffer<int> d_nl_pidx, d_nl_tidx;  // [panels], [triangles][3]: index into the points, following d_nl_panel / d_nl_tri
-    std::vector<int> nl_pt_off;             // [nloc + 1] first point of an owned body
-    hc::DeviceBuffer<double> d_nl_inc;      // [points][5] P, eta2, q2
-    hc::PinnedBuffer<double> h_nl_inc[2];   // its host copies: of the evaluation in flight and of the last completed one
-    int nl_inc_cur = 0;                     // which of the two holds the last completed one
-    bool nl_inc_flight = false;             // the evaluation in flight writes the other one
-    std::vector<int> nl_inc_off;            // [nloc + 1] first point of an owned body in it; empty: no evaluation has completed
+    // The terms beside the step (hc_side.hpp): Morison elements and the nonlinear surface pressure, each with a lane
+    // of its own, its second-order sea (increments [items][8] p, eta2, u2x, u2z, a2x, a2z of the elements; [points][5] p, eta2, q2
+    // of the surface points) and its lists
+    hc::SideLane mor, nl;
+    hc::Order2Part mor2, nl2;
+    hc::MorisonData morison;
+    hc::SurfaceData surface;
 
     // Wave drift forces (hc_set_drift_qtf) and sum-frequency wave forces (hc_set_sum_qtf): hc_qtf.hip
     hc::QtfTerm drift, sum;

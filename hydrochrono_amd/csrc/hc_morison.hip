@@ -1,6 +1,7 @@
 // hc_morison.hip -- Morison drag and inertia elements on the wave kinematics (include/hydrochrono_amd.h: hc_set_morison_elements,
-// hc_morison_begin / hc_morison_end).  Not in the reference.  Off the step path: its own stream, component table, buffers and pinned
-// staging; it reads and writes nothing a step uses, so it is not ordered against the direct queue (as hc_wave_kinematics).
+// hc_morison_begin / hc_morison_end).  Not in the reference.  Off the step path: a lane of its own (hc_side.hpp: stream, component table, begin / end
+// protocol), its own buffers and pinned staging; it reads and writes nothing a step uses, so it is not ordered against the direct queue
+// (as hc_wave_kinematics).
 // DESIGN.md 3.7c has the definition, the kernels and their invariants; 3.7g the elements on the second-order sea
 // (hc_set_morison_second_order): the increments of hc_wave_kinematics2 at every element, added before the wet test and the force.
 #include "hc_internal.hpp"
@@ -260,10 +261,11 @@ __global__ void __launch_bounds__(kMorThreads) morison_sum_kernel(const double* 
 
 // the device copy of the owned bodies' lists, body-major
 void upload_elements(hc_ctx* c) {
+    MorisonData& d = c->morison;
     std::vector<double> elem;
     std::vector<int> body, off(c->nloc + 1, 0);
     for (int b = c->b0; b < c->b1; ++b) {
-        for (const hc_morison_element& m : c->mor_elems[b]) {
+        for (const hc_morison_element& m : d.elems[b]) {
             elem.insert(elem.end(), m.r, m.r + 3);
             elem.insert(elem.end(), m.cd_area, m.cd_area + 3);
             elem.insert(elem.end(), m.cm_vol, m.cm_vol + 3);
@@ -271,105 +273,80 @@ void upload_elements(hc_ctx* c) {
         }
         off[b - c->b0 + 1] = static_cast<int>(body.size());
     }
-    c->d_mor_elem.upload(elem, c->stream_mor);
-    c->d_mor_body.upload(body, c->stream_mor);
-    c->d_mor_off.upload(off, c->stream_mor);
-    c->mor_off = off;
-    c->mor_items = static_cast<int>(body.size());
-    if (c->d_mor_item.n < 6 * body.size()) c->d_mor_item.alloc(6 * body.size());
-    c->mor_dirty = false;
-}
-
-// The component table of the wave model in force, a copy of this path's own (hc_wave_kinematics may rebuild its table for another
-// regular phase while a launch of this one is in flight).
-void morison_table(hc_ctx* c) {
-    const double phase = c->mor_opts.regular_phase;
-    if (kin_table_current(c, c->mor_serial, c->mor_phase, phase)) return;
-    std::vector<double> tab = kin_table_host(c, phase);
-    c->mor_nf = static_cast<int>(tab.size() / kKinCols);
-    const std::vector<double> dir = kin_dir_columns_host(c);
-    tab.insert(tab.end(), dir.begin(), dir.end());
-    c->d_mor_tab.upload(tab, c->stream_mor);
-    c->mor_dir    = !dir.empty();
-    c->mor_serial = c->wave_serial;
-    c->mor_phase  = phase;
+    d.elem.upload(elem, c->mor.stream);
+    d.body.upload(body, c->mor.stream);
+    d.off.upload(off, c->mor.stream);
+    c->mor2.off = off;
+    d.items     = static_cast<int>(body.size());
+    if (d.item.n < 6 * body.size()) d.item.alloc(6 * body.size());
+    c->mor.dirty = false;
 }
 
 void morison_enqueue(hc_ctx* c, double t, const double* pos, const double* rpy, const double* linvel, const double* angvel) {
+    MorisonData& d  = c->morison;
     const size_t n3 = 3 * static_cast<size_t>(c->N);
-    if (c->mor_dirty) upload_elements(c);
-    morison_table(c);
-    if (c->h_mor_state.n < 4 * n3) c->h_mor_state.alloc(4 * n3);
-    if (c->d_mor_state.n < 4 * n3) c->d_mor_state.alloc(4 * n3);
-    if (c->h_mor_out.n < static_cast<size_t>(c->Dloc)) c->h_mor_out.alloc(c->Dloc);
-    if (c->d_mor_out.n < static_cast<size_t>(c->Dloc)) c->d_mor_out.alloc(c->Dloc);
-    std::copy(pos, pos + n3, c->h_mor_state.p);
-    std::copy(rpy, rpy + n3, c->h_mor_state.p + n3);
-    std::copy(linvel, linvel + n3, c->h_mor_state.p + 2 * n3);
-    std::copy(angvel, angvel + n3, c->h_mor_state.p + 3 * n3);
-    const bool synthesised = kin_synthesised(c);
-    const double rd = c->irr.ramp_duration;
+    hipStream_t st  = c->mor.stream;
+    if (c->mor.dirty) upload_elements(c);
+    c->mor.kin.refresh(c, c->mor.opts.regular_phase, st);
+    if (d.h_state.n < 4 * n3) d.h_state.alloc(4 * n3);
+    if (d.state.n < 4 * n3) d.state.alloc(4 * n3);
+    if (d.h_out.n < static_cast<size_t>(c->Dloc)) d.h_out.alloc(c->Dloc);
+    if (d.out.n < static_cast<size_t>(c->Dloc)) d.out.alloc(c->Dloc);
+    std::copy(pos, pos + n3, d.h_state.p);
+    std::copy(rpy, rpy + n3, d.h_state.p + n3);
+    std::copy(linvel, linvel + n3, d.h_state.p + 2 * n3);
+    std::copy(angvel, angvel + n3, d.h_state.p + 3 * n3);
     MorArgs a{};
-    a.tab          = c->d_mor_tab.p;
-    a.nf           = c->mor_nf;
-    a.n_items      = c->mor_items;
-    a.elem         = c->d_mor_elem.p;
-    a.body         = c->d_mor_body.p;
-    a.state        = c->d_mor_state.p;
+    a.tab          = c->mor.kin.tab.p;
+    a.nf           = c->mor.kin.nf;
+    a.n_items      = d.items;
+    a.elem         = d.elem.p;
+    a.body         = d.body.p;
+    a.state        = d.state.p;
     a.N            = c->N;
     a.t            = t;
     a.depth        = c->depth;
-    a.mwl          = c->mor_opts.mwl;
+    a.mwl          = c->mor.opts.mwl;
     a.rho          = c->rho;
     a.ramp         = kin_ramp(c, t);
-    a.stretch      = (synthesised && c->mor_opts.wave_stretching) ? 1 : 0;  // RegularWave has none
+    a.stretch      = (kin_synthesised(c) && c->mor.opts.wave_stretching) ? 1 : 0;  // RegularWave has none
     a.finite_depth = std::isfinite(c->depth) ? 1 : 0;
-    a.item         = c->d_mor_item.p;
-    hipStream_t st = c->stream_mor;
-    // the second-order sea: tables of this path's own, then the increments of every element.  No components (NoWave, no model, an
-    // imported eta record) or no pair inside either band: order 1, no further launch.
-    bool order2 = false;
-    if (c->mor2_on && kin_has_components(c)) {
-        wk2_tables(c, c->mor2, st, c->mor_opts.regular_phase, c->mor2_cut, false);
-        order2 = c->mor2.any[0] || c->mor2.any[1];
-    }
+    a.item         = d.item.p;
+    // the second-order sea: tables of this path's own, then the increments of every element
+    const bool order2  = c->mor2.prepare(c, c->mor);
     const size_t n_inc = static_cast<size_t>(kMorIncDoubles) * a.n_items;
-    PinnedBuffer<double>& h_inc = c->h_mor_inc[c->mor_inc_cur ^ 1];
-    if (order2) {
-        if (c->d_mor_inc.n < n_inc) c->d_mor_inc.alloc(n_inc);
-        if (h_inc.n < n_inc) h_inc.alloc(n_inc);
-        a.inc = c->d_mor_inc.p;
-    }
-    HC_HIP(hipMemcpyAsync(c->d_mor_state.p, c->h_mor_state.p, 4 * n3 * sizeof(double), hipMemcpyHostToDevice, st));
+    double* h_inc      = order2 ? c->mor2.stage(n_inc) : nullptr;
+    if (order2) a.inc = c->mor2.d_inc.p;
+    HC_HIP(hipMemcpyAsync(d.state.p, d.h_state.p, 4 * n3 * sizeof(double), hipMemcpyHostToDevice, st));
     const dim3 item_grid((a.n_items + kMorThreads - 1) / kMorThreads);
     if (order2) {
         Mor2Args m{};
-        m.sea           = Wk2Sea{c->mor2.d_tab.p, c->mor2.nf, c->mor2.d_pair.p, c->mor2.d_band.p, c->depth, a.mwl, a.finite_depth,
-                                 {c->mor2.any[0] ? 1 : 0, c->mor2.any[1] ? 1 : 0}};
+        m.sea           = c->mor2.sea(c, a.mwl);
         m.elem          = a.elem;
         m.body          = a.body;
         m.state         = a.state;
         m.N             = a.N;
         m.t             = t;
-        m.ramped        = (c->mor2_ramp && synthesised && rd > 0.0) ? 1 : 0;  // the switch only (wk2_ramp2)
-        m.ramp_duration = rd;
-        m.inc           = c->d_mor_inc.p;
+        m.ramped        = c->mor2.ramped(c);
+        m.ramp_duration = c->irr.ramp_duration;
+        m.inc           = c->mor2.d_inc.p;
         hipLaunchKernelGGL(morison2_incr_kernel, dim3(a.n_items), dim3(kWk2Threads), 0, st, m);
         HC_HIP(hipGetLastError());
-        HC_HIP(hipMemcpyAsync(h_inc.p, c->d_mor_inc.p, n_inc * sizeof(double), hipMemcpyDeviceToHost, st));
+        HC_HIP(hipMemcpyAsync(h_inc, c->mor2.d_inc.p, n_inc * sizeof(double), hipMemcpyDeviceToHost, st));
         hipLaunchKernelGGL(morison_items_kernel<true>, item_grid, dim3(kMorThreads), 0, st, a);
-    } else if (c->mor_dir) {
+    } else if (c->mor.kin.dir) {
         hipLaunchKernelGGL(morison_dir_items_kernel, item_grid, dim3(kMorThreads), 0, st, a);
     } else {
         hipLaunchKernelGGL(morison_items_kernel<false>, item_grid, dim3(kMorThreads), 0, st, a);
     }
     HC_HIP(hipGetLastError());
-    c->mor_inc_flight = order2;
-    hipLaunchKernelGGL(morison_sum_kernel, dim3((c->Dloc + kMorThreads - 1) / kMorThreads), dim3(kMorThreads), 0, st, c->d_mor_item.p,
-                       c->d_mor_off.p, c->Dloc, c->d_mor_out.p);
+    hipLaunchKernelGGL(morison_sum_kernel, dim3((c->Dloc + kMorThreads - 1) / kMorThreads), dim3(kMorThreads), 0, st, d.item.p, d.off.p,
+                       c->Dloc, d.out.p);
     HC_HIP(hipGetLastError());
-    HC_HIP(hipMemcpyAsync(c->h_mor_out.p, c->d_mor_out.p, static_cast<size_t>(c->Dloc) * sizeof(double), hipMemcpyDeviceToHost, st));
+    HC_HIP(hipMemcpyAsync(d.h_out.p, d.out.p, static_cast<size_t>(c->Dloc) * sizeof(double), hipMemcpyDeviceToHost, st));
 }
+
+const char* const kMorInFlight = "a Morison evaluation is in flight (hc_morison_end has not been called)";
 
 }  // namespace
 }  // namespace hc
@@ -381,76 +358,53 @@ int hc_set_morison_elements(hc_ctx* c, int body, const hc_morison_element* elems
     require(body >= 0 && body < c->N, HC_ERR_INVALID, "body index out of range");
     require(n >= 0 && n <= hc::kMorisonMaxElements, HC_ERR_INVALID, "element count negative or above the limit per body");
     require(n == 0 || elems, HC_ERR_INVALID, "null element list");
-    require(!c->mor_pending, HC_ERR_INVALID, "a Morison evaluation is in flight (hc_morison_end has not been called)");
+    c->mor.require_idle(hc::kMorInFlight);
     for (int e = 0; e < n; ++e) {
         const hc_morison_element& m = elems[e];
         require(hc::all_finite(m.r, 3) && hc::all_finite(m.cd_area, 3) && hc::all_finite(m.cm_vol, 3), HC_ERR_INVALID,
                 "non-finite value in a Morison element");
         for (int k = 0; k < 3; ++k) require(m.cd_area[k] >= 0.0 && m.cm_vol[k] >= 0.0, HC_ERR_INVALID, "negative Morison coefficient");
     }
-    if (!c->stream_mor) HC_HIP(hipStreamCreateWithFlags(&c->stream_mor, hipStreamNonBlocking));
-    if (c->mor_elems.empty()) c->mor_elems.resize(c->N);
-    c->mor_elems[body].assign(elems, elems + n);
-    c->mor_dirty = true;
-    c->mor_inc_off.clear();  // hc_get_morison_increments: the lists of the last evaluation are no longer the lists
+    c->mor.open();
+    if (c->morison.elems.empty()) c->morison.elems.resize(c->N);
+    c->morison.elems[body].assign(elems, elems + n);
+    c->mor.dirty = true;
+    c->mor2.done.clear();  // hc_get_morison_increments: the lists of the last evaluation are no longer the lists
     HC_API_END(c)
 }
 
 int hc_get_morison_count(hc_ctx* c, int body, int* n) {
     HC_API_BEGIN_HOT(c)
     require(body >= 0 && body < c->N && n, HC_ERR_INVALID, "body index out of range or null pointer");
-    *n = c->mor_elems.empty() ? 0 : static_cast<int>(c->mor_elems[body].size());
+    *n = c->morison.elems.empty() ? 0 : static_cast<int>(c->morison.elems[body].size());
     HC_API_END(c)
 }
 
 int hc_set_morison_options(hc_ctx* c, const hc_wave_kinematics_opts* o) {
     HC_API_BEGIN_HOT(c)
-    hc_wave_kinematics_opts v;
-    hc_wave_kinematics_opts_default(&v);
-    if (o) v = *o;
-    require(std::isfinite(v.mwl) && std::isfinite(v.regular_phase), HC_ERR_INVALID, "non-finite mwl or regular_phase");
-    require(!c->mor_pending, HC_ERR_INVALID, "a Morison evaluation is in flight (hc_morison_end has not been called)");
-    c->mor_opts = v;
+    c->mor.set_options(o, true, "non-finite mwl or regular_phase", hc::kMorInFlight);
     HC_API_END(c)
 }
 
 int hc_set_morison_second_order(hc_ctx* c, int on, double diff_lo, double diff_hi, double sum_lo, double sum_hi, int apply_ramp) {
     HC_API_BEGIN_HOT(c)
-    hc_wave_kinematics2_opts o;
-    hc_wave_kinematics2_opts_default(&o);
-    o.diff_lo = diff_lo, o.diff_hi = diff_hi, o.sum_lo = sum_lo, o.sum_hi = sum_hi;
-    const char* bad = hc::wk2_check_opts(o);
-    require(bad == nullptr, HC_ERR_INVALID, bad ? bad : "");
-    require(!c->mor_pending, HC_ERR_INVALID, "a Morison evaluation is in flight (hc_morison_end has not been called)");
-    c->mor2_on     = on != 0;
-    c->mor2_cut[0] = diff_lo, c->mor2_cut[1] = diff_hi, c->mor2_cut[2] = sum_lo, c->mor2_cut[3] = sum_hi;
-    c->mor2_ramp   = apply_ramp != 0;
-    if (!c->mor2_on) {  // the second copy of the tables goes (nothing of this path is in flight)
-        c->mor2.release();
-        c->d_mor_inc.release();
-        c->mor_inc_off.clear();
-    }
+    c->mor2.set(c->mor, hc::kMorInFlight, on, diff_lo, diff_hi, sum_lo, sum_hi, apply_ramp);
     HC_API_END(c)
 }
 
 int hc_get_morison_second_order(hc_ctx* c, int* on, double* diff_lo, double* diff_hi, double* sum_lo, double* sum_hi, int* apply_ramp) {
     HC_API_BEGIN_HOT(c)
-    if (on) *on = c->mor2_on ? 1 : 0;
-    if (diff_lo) *diff_lo = c->mor2_cut[0];
-    if (diff_hi) *diff_hi = c->mor2_cut[1];
-    if (sum_lo) *sum_lo = c->mor2_cut[2];
-    if (sum_hi) *sum_hi = c->mor2_cut[3];
-    if (apply_ramp) *apply_ramp = c->mor2_ramp;
+    c->mor2.get(on, diff_lo, diff_hi, sum_lo, sum_hi, apply_ramp);
     HC_API_END(c)
 }
 
 int hc_get_morison_increments(hc_ctx* c, int body, double* p, double* eta2, double* vel2, double* acc2) {
     HC_API_BEGIN_HOT(c)
-    require(c->mor2_on, HC_ERR_INVALID, "Morison elements on the second-order sea are switched off (hc_set_morison_second_order)");
+    require(c->mor2.on, HC_ERR_INVALID, "Morison elements on the second-order sea are switched off (hc_set_morison_second_order)");
     require(body >= c->b0 && body < c->b1, HC_ERR_INVALID, "body not owned by this context");
-    require(!c->mor_inc_off.empty(), HC_ERR_INVALID, "no Morison evaluation with a second-order part has completed");
-    const double* q = c->h_mor_inc[c->mor_inc_cur].p;
-    const int e0 = c->mor_inc_off[body - c->b0], e1 = c->mor_inc_off[body - c->b0 + 1];
+    require(!c->mor2.done.empty(), HC_ERR_INVALID, "no Morison evaluation with a second-order part has completed");
+    const double* q = c->mor2.last();
+    const int e0 = c->mor2.done[body - c->b0], e1 = c->mor2.done[body - c->b0 + 1];
     for (int e = e0; e < e1; ++e) {
         const double* v = q + static_cast<size_t>(hc::kMorIncDoubles) * e;
         const size_t i  = static_cast<size_t>(e - e0);
@@ -465,49 +419,29 @@ int hc_get_morison_increments(hc_ctx* c, int body, double* p, double* eta2, doub
 int hc_morison_begin(hc_ctx* c, double t, const double* pos, const double* rpy, const double* linvel, const double* angvel) {
     HC_API_BEGIN_HOT(c)
     require(c->finalized, HC_ERR_INVALID, "hc_finalize has not been called");
-    require(!c->mor_pending, HC_ERR_INVALID, "hc_morison_begin twice without hc_morison_end");
+    c->mor.require_idle("hc_morison_begin twice without hc_morison_end");
     require(pos && rpy && linvel && angvel, HC_ERR_INVALID, "null state");
     const size_t n3 = 3 * static_cast<size_t>(c->N);
     require(std::isfinite(t) && hc::all_finite(pos, n3) && hc::all_finite(rpy, n3) && hc::all_finite(linvel, n3) && hc::all_finite(angvel, n3),
             HC_ERR_INVALID, "non-finite time or state");
-    require(!(c->mor2_on && !c->wave_dir.empty()), HC_ERR_UNSUPPORTED,
+    require(!(c->mor2.on && !c->wave_dir.empty()), HC_ERR_UNSUPPORTED,
             "Morison elements on the second-order sea are not available while wave directions are set (hc_set_wave_directions): clear "
             "the directions or switch the second-order sea off");
-    require(!(c->mor2_on && hc::kin_has_components(c)) || hc::wk2_component_count(c) <= hc::kWk2MaxFreq, HC_ERR_UNSUPPORTED,
+    require(!(c->mor2.on && hc::kin_has_components(c)) || hc::wk2_component_count(c) <= hc::kWk2MaxFreq, HC_ERR_UNSUPPORTED,
             "Morison elements on the second-order sea: more than 4096 wave components");
     int items = 0;
-    if (!c->mor_elems.empty())
-        for (int b = c->b0; b < c->b1; ++b) items += static_cast<int>(c->mor_elems[b].size());
-    c->mor_inc_flight = false;
-    if (items == 0) {
-        c->mor_pending = 1;
-        return HC_OK;
-    }
-    try {
-        hc::morison_enqueue(c, t, pos, rpy, linvel, angvel);
-    } catch (...) {
-        (void)hipStreamSynchronize(c->stream_mor);  // nothing stays pending
-        throw;
-    }
-    c->mor_pending = 2;
+    if (!c->morison.elems.empty())
+        for (int b = c->b0; b < c->b1; ++b) items += static_cast<int>(c->morison.elems[b].size());
+    c->mor2.flight = false;
+    c->mor.begin(items != 0, [&] { hc::morison_enqueue(c, t, pos, rpy, linvel, angvel); });
     HC_API_END(c)
 }
 
 int hc_morison_end(hc_ctx* c, double* out) {
     HC_API_BEGIN_HOT(c)
-    require(c->mor_pending != 0, HC_ERR_INVALID, "hc_morison_end without hc_morison_begin");
-    const int what = c->mor_pending;
-    c->mor_pending = 0;
-    const bool with_inc = c->mor_inc_flight;
-    c->mor_inc_flight = false;
-    c->mor_inc_off.clear();  // (stays so when the wait fails)
-    if (what == 2) HC_HIP(hipStreamSynchronize(c->stream_mor));
-    if (with_inc) {  // the evaluation that has completed is the one hc_get_morison_increments answers with
-        c->mor_inc_cur ^= 1;
-        c->mor_inc_off = c->mor_off;
-    }
+    const int what = c->mor.end("hc_morison_end without hc_morison_begin", &c->mor2);
     require(out != nullptr, HC_ERR_INVALID, "null output");
-    if (what == 2) std::copy(c->h_mor_out.p, c->h_mor_out.p + c->Dloc, out);
+    if (what == 2) std::copy(c->morison.h_out.p, c->morison.h_out.p + c->Dloc, out);
     else std::fill(out, out + c->Dloc, 0.0);
     HC_API_END(c)
 }

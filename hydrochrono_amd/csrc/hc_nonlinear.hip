@@ -1,6 +1,6 @@
 // hc_nonlinear.hip -- nonlinear buoyancy and Froude-Krylov forces on body surface panels and on triangles clipped at the free surface
 // (include/hydrochrono_amd.h: hc_set_surface_panels, hc_set_surface_triangles, hc_nonlinear_begin / hc_nonlinear_end).  Not in the reference (src/hydro_types.h:33 is a TODO).  Off the
-// step path, as hc_morison.hip: its own stream, component table, buffers and pinned staging; it reads and writes nothing a step
+// step path, as hc_morison.hip: a lane of its own (hc_side.hpp), its own buffers and pinned staging; it reads and writes nothing a step
 // uses, so it is not ordered against the direct queue.  DESIGN.md 3.7d and 3.7d' have the definitions, the kernels and their invariants;
 // 3.7h the surface on the second-order sea (hc_set_nonlinear_second_order): eta2 and q2 = -d phi2 / dt of the pair sum at every surface
 // point, added before the wet test and the clipping, and the quadratic term -1/2 rho |grad phi1|^2.
@@ -512,18 +512,18 @@ __global__ void __launch_bounds__(kWk2Threads) nl2_incr_kernel(Nl2Args a) {
 void upload_panels(hc_ctx* c) {
     std::vector<double> panel, tri;
     std::vector<int> chunk, off(c->nloc + 1, 0);
-    c->nl_runs.clear();
+    c->surface.runs.clear();
     int items = 0, tris = 0;
     for (int b = c->b0; b < c->b1; ++b) {
-        const int n  = c->nl_panels.empty() ? 0 : static_cast<int>(c->nl_panels[b].size());
-        const int nt = (n || c->nl_tris.empty()) ? 0 : static_cast<int>(c->nl_tris[b].size() / kNlTriDoubles);  // (the setters keep one kind)
+        const int n  = c->surface.panels.empty() ? 0 : static_cast<int>(c->surface.panels[b].size());
+        const int nt = (n || c->surface.tris.empty()) ? 0 : static_cast<int>(c->surface.tris[b].size() / kNlTriDoubles);  // (the setters keep one kind)
         if (n) {
-            for (const hc_surface_panel& p : c->nl_panels[b]) {
+            for (const hc_surface_panel& p : c->surface.panels[b]) {
                 panel.insert(panel.end(), p.c, p.c + 3);
                 panel.insert(panel.end(), p.s, p.s + 3);
             }
         } else if (nt) {
-            tri.insert(tri.end(), c->nl_tris[b].begin(), c->nl_tris[b].end());
+            tri.insert(tri.end(), c->surface.tris[b].begin(), c->surface.tris[b].end());
         }
         const int kind = n ? 0 : 1, len = n ? n : nt, at = n ? items : tris;
         const int chunk0 = static_cast<int>(chunk.size() / 3);
@@ -534,24 +534,24 @@ void upload_panels(hc_ctx* c) {
         }
         const int chunk1 = static_cast<int>(chunk.size() / 3);
         if (chunk1 > chunk0) {
-            if (!c->nl_runs.empty() && c->nl_runs[c->nl_runs.size() - 3] == kind)
-                c->nl_runs.back() += chunk1 - chunk0;
+            if (!c->surface.runs.empty() && c->surface.runs[c->surface.runs.size() - 3] == kind)
+                c->surface.runs.back() += chunk1 - chunk0;
             else
-                c->nl_runs.insert(c->nl_runs.end(), {kind, chunk0, chunk1 - chunk0});
+                c->surface.runs.insert(c->surface.runs.end(), {kind, chunk0, chunk1 - chunk0});
         }
         items += n;
         tris += nt;
         off[b - c->b0 + 1] = chunk1;
     }
-    c->d_nl_panel.upload(panel, c->stream_nl);
-    c->d_nl_tri.upload(tri, c->stream_nl);
-    c->d_nl_chunk.upload(chunk, c->stream_nl);
-    c->d_nl_off.upload(off, c->stream_nl);
-    c->nl_items  = items + tris;
-    c->nl_chunks = static_cast<int>(chunk.size() / 3);
-    if (c->d_nl_part.n < static_cast<size_t>(kNlOut) * c->nl_chunks) c->d_nl_part.alloc(static_cast<size_t>(kNlOut) * c->nl_chunks);
-    c->nl_dirty     = false;
-    c->nl_pts_dirty = true;  // upload_points, once an evaluation on the second-order sea needs them
+    c->surface.panel.upload(panel, c->nl.stream);
+    c->surface.tri.upload(tri, c->nl.stream);
+    c->surface.chunk.upload(chunk, c->nl.stream);
+    c->surface.off.upload(off, c->nl.stream);
+    c->surface.items  = items + tris;
+    c->surface.chunks = static_cast<int>(chunk.size() / 3);
+    if (c->surface.part.n < static_cast<size_t>(kNlOut) * c->surface.chunks) c->surface.part.alloc(static_cast<size_t>(kNlOut) * c->surface.chunks);
+    c->nl.dirty          = false;
+    c->surface.pts_dirty = true;  // upload_points, once an evaluation on the second-order sea needs them
 }
 
 // The distinct body-frame points of one body's list in the order of their first use -- a panel's centroid, a triangle's vertices;
@@ -566,129 +566,108 @@ int unique_points(const hc_ctx* c, int b, int base, std::vector<double>* pts, st
         if (at.second && pts) pts->insert(pts->end(), v, v + 3);
         if (idx) idx->push_back(base + at.first->second);
     };
-    if (!c->nl_panels.empty() && !c->nl_panels[b].empty()) {
-        for (const hc_surface_panel& p : c->nl_panels[b]) add(p.c);
-    } else if (!c->nl_tris.empty()) {
-        for (size_t e = 0; e + 3 <= c->nl_tris[b].size(); e += 3) add(c->nl_tris[b].data() + e);
+    if (!c->surface.panels.empty() && !c->surface.panels[b].empty()) {
+        for (const hc_surface_panel& p : c->surface.panels[b]) add(p.c);
+    } else if (!c->surface.tris.empty()) {
+        for (size_t e = 0; e + 3 <= c->surface.tris[b].size(); e += 3) add(c->surface.tris[b].data() + e);
     }
     return static_cast<int>(seen.size());
 }
 
 // the surface points of the owned bodies, body-major, and the point of every panel and of every triangle vertex: the two index lists
-// follow d_nl_panel and d_nl_tri item by item
+// follow `panel` and `tri` item by item
 void upload_points(hc_ctx* c) {
     std::vector<double> pts;
     std::vector<int> body, pidx, tidx, off(c->nloc + 1, 0);
     for (int b = c->b0; b < c->b1; ++b) {
-        const bool panels = !c->nl_panels.empty() && !c->nl_panels[b].empty();
+        const bool panels = !c->surface.panels.empty() && !c->surface.panels[b].empty();
         const int n = unique_points(c, b, off[b - c->b0], &pts, panels ? &pidx : &tidx);
         body.insert(body.end(), n, b);
         off[b - c->b0 + 1] = off[b - c->b0] + n;
     }
-    c->d_nl_pt.upload(pts, c->stream_nl);
-    c->d_nl_pbody.upload(body, c->stream_nl);
-    c->d_nl_pidx.upload(pidx, c->stream_nl);
-    c->d_nl_tidx.upload(tidx, c->stream_nl);
-    c->nl_pt_off    = off;
-    c->nl_pts_dirty = false;
+    c->surface.pt.upload(pts, c->nl.stream);
+    c->surface.pbody.upload(body, c->nl.stream);
+    c->surface.pidx.upload(pidx, c->nl.stream);
+    c->surface.tidx.upload(tidx, c->nl.stream);
+    c->nl2.off    = off;
+    c->surface.pts_dirty = false;
 }
 
-// The component table of the wave model in force, a copy of this path's own (as hc_morison.hip: another path may rebuild its table
-// while a launch of this one is in flight).
-void nonlinear_table(hc_ctx* c) {
-    const double phase = c->nl_opts.regular_phase;
-    if (kin_table_current(c, c->nl_serial, c->nl_phase, phase)) return;
-    const std::vector<double> kin = kin_table_host(c, phase);
-    const int nf = static_cast<int>(kin.size() / kKinCols);
-    std::vector<double> tab(static_cast<size_t>(kNlCols) * nf);
-    const std::vector<double> dir = kin_dir_columns_host(c);
+// The path's copy of the component table holds the columns its kernels read (kNlCols of them), one of them divided by k
+void nonlinear_shape(std::vector<double>& tab, std::vector<double>&, int nf) {
+    const std::vector<double> kin = tab;
     const int from[kNlCols] = {kKinAmp, kKinOmega, kKinK, kKinPhase, kKinW2A, kKinInvSinh, kKinDeep};
+    tab.resize(static_cast<size_t>(kNlCols) * nf);
     for (int col = 0; col < kNlCols; ++col)
         for (int i = 0; i < nf; ++i) tab[static_cast<size_t>(col) * nf + i] = kin[static_cast<size_t>(from[col]) * nf + i];
     for (int i = 0; i < nf; ++i) tab[static_cast<size_t>(kNlW2AoK) * nf + i] /= kin[static_cast<size_t>(kKinK) * nf + i];
-    tab.insert(tab.end(), dir.begin(), dir.end());
-    c->d_nl_tab.upload(tab, c->stream_nl);
-    c->nl_dir    = !dir.empty();
-    c->nl_nf     = nf;
-    c->nl_serial = c->wave_serial;
-    c->nl_phase  = phase;
 }
 
-// (the state is in h_nl_state already: hc_nonlinear_begin)
+// (the state is in h_state already: hc_nonlinear_begin)
 void nonlinear_enqueue(hc_ctx* c, double t) {
+    SurfaceData& d = c->surface;
     const size_t n3 = 3 * static_cast<size_t>(c->N);
     const size_t n_out = static_cast<size_t>(kNlOut) * c->nloc;
-    if (c->nl_dirty) upload_panels(c);
-    nonlinear_table(c);
-    if (c->d_nl_state.n < 2 * n3) c->d_nl_state.alloc(2 * n3);
-    if (c->h_nl_out.n < n_out) c->h_nl_out.alloc(n_out);
-    if (c->d_nl_out.n < n_out) c->d_nl_out.alloc(n_out);
-    const bool synthesised = kin_synthesised(c);
-    const double rd = c->irr.ramp_duration;
+    hipStream_t st = c->nl.stream;
+    if (c->nl.dirty) upload_panels(c);
+    c->nl.kin.refresh(c, c->nl.opts.regular_phase, st, nonlinear_shape);
+    if (d.state.n < 2 * n3) d.state.alloc(2 * n3);
+    if (d.h_out.n < n_out) d.h_out.alloc(n_out);
+    if (d.out.n < n_out) d.out.alloc(n_out);
     NlArgs a{};
-    a.tab          = c->d_nl_tab.p;
-    a.nf           = c->nl_nf;
-    a.panel        = c->d_nl_panel.p;
-    a.chunk        = c->d_nl_chunk.p;
-    a.state        = c->d_nl_state.p;
+    a.tab          = c->nl.kin.tab.p;
+    a.nf           = c->nl.kin.nf;
+    a.panel        = d.panel.p;
+    a.chunk        = d.chunk.p;
+    a.state        = d.state.p;
     a.N            = c->N;
     a.t            = t;
     a.depth        = c->depth;
-    a.mwl          = c->nl_opts.mwl;
+    a.mwl          = c->nl.opts.mwl;
     a.rho          = c->rho;
     a.g            = -c->gsys[2];  // gravity is (0, 0, -g): checked by hc_nonlinear_begin
     a.ramp         = kin_ramp(c, t);
-    a.stretch      = (synthesised && c->nl_opts.wave_stretching) ? 1 : 0;  // RegularWave has none
+    a.stretch      = (kin_synthesised(c) && c->nl.opts.wave_stretching) ? 1 : 0;  // RegularWave has none
     a.finite_depth = std::isfinite(c->depth) ? 1 : 0;
-    a.part         = c->d_nl_part.p;
+    a.part         = d.part.p;
     const int rows = static_cast<int>(n_out);
-    hipStream_t st = c->stream_nl;
-    // the second-order sea: tables of this path's own, then the increments of every surface point.  No components (NoWave, no model,
-    // an imported eta record) or no pair inside either band: order 1, no further launch.
-    bool order2 = false;
-    if (c->nl2_on && kin_has_components(c)) {
-        wk2_tables(c, c->nl2, st, c->nl_opts.regular_phase, c->nl2_cut, false);
-        order2 = c->nl2.any[0] || c->nl2.any[1];
-    }
-    HC_HIP(hipMemcpyAsync(c->d_nl_state.p, c->h_nl_state.p, 2 * n3 * sizeof(double), hipMemcpyHostToDevice, st));
+    // the second-order sea: tables of this path's own, then the increments of every surface point
+    const bool order2 = c->nl2.prepare(c, c->nl);
+    HC_HIP(hipMemcpyAsync(d.state.p, d.h_state.p, 2 * n3 * sizeof(double), hipMemcpyHostToDevice, st));
     if (order2) {
-        if (c->nl_pts_dirty) upload_points(c);
-        const int points   = c->nl_pt_off.back();
+        if (d.pts_dirty) upload_points(c);
+        const int points   = c->nl2.off.back();
         const size_t n_inc = static_cast<size_t>(kNlIncDoubles) * points;
-        PinnedBuffer<double>& h_inc = c->h_nl_inc[c->nl_inc_cur ^ 1];
-        if (c->d_nl_inc.n < n_inc) c->d_nl_inc.alloc(n_inc);
-        if (h_inc.n < n_inc) h_inc.alloc(n_inc);
+        double* h_inc      = c->nl2.stage(n_inc);
         Nl2Args m{};
-        m.sea           = Wk2Sea{c->nl2.d_tab.p, c->nl2.nf, c->nl2.d_pair.p, c->nl2.d_band.p, c->depth, a.mwl, a.finite_depth,
-                                 {c->nl2.any[0] ? 1 : 0, c->nl2.any[1] ? 1 : 0}};
-        m.point         = c->d_nl_pt.p;
-        m.body          = c->d_nl_pbody.p;
+        m.sea           = c->nl2.sea(c, a.mwl);
+        m.point         = d.pt.p;
+        m.body          = d.pbody.p;
         m.state         = a.state;
         m.N             = a.N;
         m.t             = t;
-        m.ramped        = (c->nl2_ramp && synthesised && rd > 0.0) ? 1 : 0;  // the switch only (wk2_ramp2)
-        m.ramp_duration = rd;
-        m.inc           = c->d_nl_inc.p;
+        m.ramped        = c->nl2.ramped(c);
+        m.ramp_duration = c->irr.ramp_duration;
+        m.inc           = c->nl2.d_inc.p;
         hipLaunchKernelGGL(nl2_incr_kernel, dim3(points), dim3(kWk2Threads), 0, st, m);
         HC_HIP(hipGetLastError());
-        HC_HIP(hipMemcpyAsync(h_inc.p, c->d_nl_inc.p, n_inc * sizeof(double), hipMemcpyDeviceToHost, st));
-        a.inc = c->d_nl_inc.p;
+        HC_HIP(hipMemcpyAsync(h_inc, c->nl2.d_inc.p, n_inc * sizeof(double), hipMemcpyDeviceToHost, st));
+        a.inc = c->nl2.d_inc.p;
     }
-    c->nl_inc_flight = order2;
-    for (size_t r = 0; r < c->nl_runs.size(); r += 3) {  // a run's chunk map and partials start at its first chunk: blockIdx.x counts from there
-        const int kind = c->nl_runs[r], chunk0 = c->nl_runs[r + 1], chunks = c->nl_runs[r + 2];
+    for (size_t r = 0; r < d.runs.size(); r += 3) {  // a run's chunk map and partials start at its first chunk: blockIdx.x counts from there
+        const int kind = d.runs[r], chunk0 = d.runs[r + 1], chunks = d.runs[r + 2];
         NlArgs ar = a;
-        ar.panel  = kind ? c->d_nl_tri.p : c->d_nl_panel.p;
-        ar.chunk  = c->d_nl_chunk.p + 3 * static_cast<size_t>(chunk0);
-        ar.part   = c->d_nl_part.p + static_cast<size_t>(kNlOut) * chunk0;
-        ar.pidx   = kind ? c->d_nl_tidx.p : c->d_nl_pidx.p;  // (indexed by the item, as the list)
+        ar.panel  = kind ? d.tri.p : d.panel.p;
+        ar.chunk  = d.chunk.p + 3 * static_cast<size_t>(chunk0);
+        ar.part   = d.part.p + static_cast<size_t>(kNlOut) * chunk0;
+        ar.pidx   = kind ? d.tidx.p : d.pidx.p;  // (indexed by the item, as the list)
         if (order2 && kind)
             hipLaunchKernelGGL(nl2_tris_kernel, dim3(chunks), dim3(kNlThreads), 0, st, ar);
         else if (order2)
             hipLaunchKernelGGL(nl2_panels_kernel, dim3(chunks), dim3(kNlThreads), 0, st, ar);
-        else if (c->nl_dir && kind)
+        else if (c->nl.kin.dir && kind)
             hipLaunchKernelGGL(nl_tris_dir_kernel, dim3(chunks), dim3(kNlThreads), 0, st, ar);
-        else if (c->nl_dir)
+        else if (c->nl.kin.dir)
             hipLaunchKernelGGL(nl_panels_dir_kernel, dim3(chunks), dim3(kNlThreads), 0, st, ar);
         else if (kind)
             hipLaunchKernelGGL(nl_tris_kernel, dim3(chunks), dim3(kNlThreads), 0, st, ar);
@@ -696,10 +675,9 @@ void nonlinear_enqueue(hc_ctx* c, double t) {
             hipLaunchKernelGGL(nl_panels_kernel, dim3(chunks), dim3(kNlThreads), 0, st, ar);
         HC_HIP(hipGetLastError());
     }
-    hipLaunchKernelGGL(nl_sum_kernel, dim3((rows + kNlThreads - 1) / kNlThreads), dim3(kNlThreads), 0, st, c->d_nl_part.p, c->d_nl_off.p, rows,
-                       c->d_nl_out.p);
+    hipLaunchKernelGGL(nl_sum_kernel, dim3((rows + kNlThreads - 1) / kNlThreads), dim3(kNlThreads), 0, st, d.part.p, d.off.p, rows, d.out.p);
     HC_HIP(hipGetLastError());
-    HC_HIP(hipMemcpyAsync(c->h_nl_out.p, c->d_nl_out.p, n_out * sizeof(double), hipMemcpyDeviceToHost, st));
+    HC_HIP(hipMemcpyAsync(d.h_out.p, d.out.p, n_out * sizeof(double), hipMemcpyDeviceToHost, st));
 }
 
 // The linear hydrostatic term of the owned bodies for pos, rpy (ComputeForceHydrostatics, src/hydro_forces.cpp:263-322), from the
@@ -728,6 +706,8 @@ void hs_linear_host(const hc_ctx* c, const double* pos, const double* rpy, doubl
     }
 }
 
+const char* const kNlInFlight = "a nonlinear evaluation is in flight (hc_nonlinear_end has not been called)";
+
 }  // namespace
 }  // namespace hc
 
@@ -738,22 +718,22 @@ int hc_set_surface_panels(hc_ctx* c, int body, const hc_surface_panel* panels, i
     require(body >= 0 && body < c->N, HC_ERR_INVALID, "body index out of range");
     require(n >= 0 && n <= hc::kSurfaceMaxPanels, HC_ERR_INVALID, "surface panel count negative or above the limit per body");
     require(n == 0 || panels, HC_ERR_INVALID, "null surface panel list");
-    require(!c->nl_pending, HC_ERR_INVALID, "a nonlinear evaluation is in flight (hc_nonlinear_end has not been called)");
+    c->nl.require_idle(hc::kNlInFlight);
     for (int e = 0; e < n; ++e)
         require(hc::all_finite(panels[e].c, 3) && hc::all_finite(panels[e].s, 3), HC_ERR_INVALID, "non-finite value in a surface panel");
-    if (!c->stream_nl) HC_HIP(hipStreamCreateWithFlags(&c->stream_nl, hipStreamNonBlocking));
-    if (c->nl_panels.empty()) c->nl_panels.resize(c->N);
-    c->nl_panels[body].assign(panels, panels + n);
-    if (!c->nl_tris.empty()) c->nl_tris[body].clear();  // a body carries panels or triangles
-    c->nl_dirty = true;
-    c->nl_inc_off.clear();  // hc_get_nonlinear_increments: the lists of the last evaluation are no longer the lists
+    c->nl.open();
+    if (c->surface.panels.empty()) c->surface.panels.resize(c->N);
+    c->surface.panels[body].assign(panels, panels + n);
+    if (!c->surface.tris.empty()) c->surface.tris[body].clear();  // a body carries panels or triangles
+    c->nl.dirty = true;
+    c->nl2.done.clear();  // hc_get_nonlinear_increments: the lists of the last evaluation are no longer the lists
     HC_API_END(c)
 }
 
 int hc_get_surface_panel_count(hc_ctx* c, int body, int* n) {
     HC_API_BEGIN_HOT(c)
     require(body >= 0 && body < c->N && n, HC_ERR_INVALID, "body index out of range or null pointer");
-    *n = c->nl_panels.empty() ? 0 : static_cast<int>(c->nl_panels[body].size());
+    *n = c->surface.panels.empty() ? 0 : static_cast<int>(c->surface.panels[body].size());
     HC_API_END(c)
 }
 
@@ -762,68 +742,47 @@ int hc_set_surface_triangles(hc_ctx* c, int body, const double* tri, int n) {
     require(body >= 0 && body < c->N, HC_ERR_INVALID, "body index out of range");
     require(n >= 0 && n <= hc::kSurfaceMaxPanels, HC_ERR_INVALID, "surface triangle count negative or above the limit per body");
     require(n == 0 || tri, HC_ERR_INVALID, "null surface triangle list");
-    require(!c->nl_pending, HC_ERR_INVALID, "a nonlinear evaluation is in flight (hc_nonlinear_end has not been called)");
+    c->nl.require_idle(hc::kNlInFlight);
     const size_t len = static_cast<size_t>(hc::kNlTriDoubles) * static_cast<size_t>(n);
     require(hc::all_finite(tri, len), HC_ERR_INVALID, "non-finite value in a surface triangle");
-    if (!c->stream_nl) HC_HIP(hipStreamCreateWithFlags(&c->stream_nl, hipStreamNonBlocking));
-    if (c->nl_tris.empty()) c->nl_tris.resize(c->N);
-    c->nl_tris[body].assign(tri, tri + len);
-    if (!c->nl_panels.empty()) c->nl_panels[body].clear();  // a body carries panels or triangles
-    c->nl_dirty = true;
-    c->nl_inc_off.clear();
+    c->nl.open();
+    if (c->surface.tris.empty()) c->surface.tris.resize(c->N);
+    c->surface.tris[body].assign(tri, tri + len);
+    if (!c->surface.panels.empty()) c->surface.panels[body].clear();  // a body carries panels or triangles
+    c->nl.dirty = true;
+    c->nl2.done.clear();
     HC_API_END(c)
 }
 
 int hc_get_surface_triangle_count(hc_ctx* c, int body, int* n) {
     HC_API_BEGIN_HOT(c)
     require(body >= 0 && body < c->N && n, HC_ERR_INVALID, "body index out of range or null pointer");
-    *n = c->nl_tris.empty() ? 0 : static_cast<int>(c->nl_tris[body].size() / hc::kNlTriDoubles);
+    *n = c->surface.tris.empty() ? 0 : static_cast<int>(c->surface.tris[body].size() / hc::kNlTriDoubles);
     HC_API_END(c)
 }
 
 int hc_set_nonlinear_options(hc_ctx* c, const hc_wave_kinematics_opts* o) {
     HC_API_BEGIN_HOT(c)
-    hc_wave_kinematics_opts v;
-    hc_wave_kinematics_opts_default(&v);
-    if (o) v = *o;
-    require(std::isfinite(v.mwl) && std::isfinite(v.regular_phase), HC_ERR_INVALID, "non-finite mwl or regular_phase");
-    require(!c->nl_pending, HC_ERR_INVALID, "a nonlinear evaluation is in flight (hc_nonlinear_end has not been called)");
-    c->nl_opts = v;
+    c->nl.set_options(o, true, "non-finite mwl or regular_phase", hc::kNlInFlight);
     HC_API_END(c)
 }
 
 int hc_set_nonlinear_second_order(hc_ctx* c, int on, double diff_lo, double diff_hi, double sum_lo, double sum_hi, int apply_ramp) {
     HC_API_BEGIN_HOT(c)
-    hc_wave_kinematics2_opts o;
-    hc_wave_kinematics2_opts_default(&o);
-    o.diff_lo = diff_lo, o.diff_hi = diff_hi, o.sum_lo = sum_lo, o.sum_hi = sum_hi;
-    const char* bad = hc::wk2_check_opts(o);
-    require(bad == nullptr, HC_ERR_INVALID, bad ? bad : "");
-    require(!c->nl_pending, HC_ERR_INVALID, "a nonlinear evaluation is in flight (hc_nonlinear_end has not been called)");
-    c->nl2_on     = on != 0;
-    c->nl2_cut[0] = diff_lo, c->nl2_cut[1] = diff_hi, c->nl2_cut[2] = sum_lo, c->nl2_cut[3] = sum_hi;
-    c->nl2_ramp   = apply_ramp != 0;
-    if (!c->nl2_on) {  // the second copy of the tables, the points and their increments go (nothing of this path is in flight)
-        c->nl2.release();
-        c->d_nl_inc.release();
-        c->d_nl_pt.release();
-        c->d_nl_pbody.release();
-        c->d_nl_pidx.release();
-        c->d_nl_tidx.release();
-        c->nl_pts_dirty = true;
-        c->nl_inc_off.clear();
+    c->nl2.set(c->nl, hc::kNlInFlight, on, diff_lo, diff_hi, sum_lo, sum_hi, apply_ramp);
+    if (!c->nl2.on) {  // the points go with the tables and the increments
+        c->surface.pt.release();
+        c->surface.pbody.release();
+        c->surface.pidx.release();
+        c->surface.tidx.release();
+        c->surface.pts_dirty = true;
     }
     HC_API_END(c)
 }
 
 int hc_get_nonlinear_second_order(hc_ctx* c, int* on, double* diff_lo, double* diff_hi, double* sum_lo, double* sum_hi, int* apply_ramp) {
     HC_API_BEGIN_HOT(c)
-    if (on) *on = c->nl2_on ? 1 : 0;
-    if (diff_lo) *diff_lo = c->nl2_cut[0];
-    if (diff_hi) *diff_hi = c->nl2_cut[1];
-    if (sum_lo) *sum_lo = c->nl2_cut[2];
-    if (sum_hi) *sum_hi = c->nl2_cut[3];
-    if (apply_ramp) *apply_ramp = c->nl2_ramp;
+    c->nl2.get(on, diff_lo, diff_hi, sum_lo, sum_hi, apply_ramp);
     HC_API_END(c)
 }
 
@@ -836,12 +795,12 @@ int hc_get_nonlinear_point_count(hc_ctx* c, int body, int* n) {
 
 int hc_get_nonlinear_increments(hc_ctx* c, int body, int n, double* p, double* eta2, double* q2) {
     HC_API_BEGIN_HOT(c)
-    require(c->nl2_on, HC_ERR_INVALID, "the surface on the second-order sea is switched off (hc_set_nonlinear_second_order)");
+    require(c->nl2.on, HC_ERR_INVALID, "the surface on the second-order sea is switched off (hc_set_nonlinear_second_order)");
     require(body >= c->b0 && body < c->b1, HC_ERR_INVALID, "body not owned by this context");
-    require(!c->nl_inc_off.empty(), HC_ERR_INVALID, "no nonlinear evaluation with a second-order part has completed");
-    const int e0 = c->nl_inc_off[body - c->b0], e1 = c->nl_inc_off[body - c->b0 + 1];
+    require(!c->nl2.done.empty(), HC_ERR_INVALID, "no nonlinear evaluation with a second-order part has completed");
+    const int e0 = c->nl2.done[body - c->b0], e1 = c->nl2.done[body - c->b0 + 1];
     require(n == e1 - e0, HC_ERR_INVALID, "n is not the body's surface point count (hc_get_nonlinear_point_count)");
-    const double* q = c->h_nl_inc[c->nl_inc_cur].p;
+    const double* q = c->nl2.last();
     for (int e = e0; e < e1; ++e) {
         const double* v = q + static_cast<size_t>(hc::kNlIncDoubles) * e;
         const size_t i  = static_cast<size_t>(e - e0);
@@ -855,61 +814,41 @@ int hc_get_nonlinear_increments(hc_ctx* c, int body, int n, double* p, double* e
 int hc_nonlinear_begin(hc_ctx* c, double t, const double* pos, const double* rpy) {
     HC_API_BEGIN_HOT(c)
     require(c->finalized, HC_ERR_INVALID, "hc_finalize has not been called");
-    require(!c->nl_pending, HC_ERR_INVALID, "hc_nonlinear_begin twice without hc_nonlinear_end");
+    c->nl.require_idle("hc_nonlinear_begin twice without hc_nonlinear_end");
     require(pos && rpy, HC_ERR_INVALID, "null state");
     const size_t n3 = 3 * static_cast<size_t>(c->N);
     require(std::isfinite(t) && hc::all_finite(pos, n3) && hc::all_finite(rpy, n3), HC_ERR_INVALID, "non-finite time or state");
     require(c->gsys[0] == 0.0 && c->gsys[1] == 0.0 && c->gsys[2] < 0.0, HC_ERR_INVALID,
             "the nonlinear surface forces need gravity (0, 0, -g): z up");
-    require(!(c->nl2_on && !c->wave_dir.empty()), HC_ERR_UNSUPPORTED,
+    require(!(c->nl2.on && !c->wave_dir.empty()), HC_ERR_UNSUPPORTED,
             "the surface on the second-order sea is not available while wave directions are set (hc_set_wave_directions): clear the "
             "directions or switch the second-order sea off");
-    require(!(c->nl2_on && hc::kin_has_components(c)) || hc::wk2_component_count(c) <= hc::kWk2MaxFreq, HC_ERR_UNSUPPORTED,
+    require(!(c->nl2.on && hc::kin_has_components(c)) || hc::wk2_component_count(c) <= hc::kWk2MaxFreq, HC_ERR_UNSUPPORTED,
             "the surface on the second-order sea: more than 4096 wave components");
     // the host copy of the state: the kernel's source, and what hc_nonlinear_end computes hs_lin from (the caller's arrays are
     // borrowed for this call only)
-    if (c->h_nl_state.n < 2 * n3) c->h_nl_state.alloc(2 * n3);
-    std::copy(pos, pos + n3, c->h_nl_state.p);
-    std::copy(rpy, rpy + n3, c->h_nl_state.p + n3);
+    if (c->surface.h_state.n < 2 * n3) c->surface.h_state.alloc(2 * n3);
+    std::copy(pos, pos + n3, c->surface.h_state.p);
+    std::copy(rpy, rpy + n3, c->surface.h_state.p + n3);
     int items = 0;
-    if (!c->nl_panels.empty())
-        for (int b = c->b0; b < c->b1; ++b) items += static_cast<int>(c->nl_panels[b].size());
-    if (!c->nl_tris.empty())
-        for (int b = c->b0; b < c->b1; ++b) items += static_cast<int>(c->nl_tris[b].size() / hc::kNlTriDoubles);
-    c->nl_inc_flight = false;
-    if (items == 0) {
-        c->nl_pending = 1;
-        return HC_OK;
-    }
-    try {
-        hc::nonlinear_enqueue(c, t);
-    } catch (...) {
-        (void)hipStreamSynchronize(c->stream_nl);  // nothing stays pending
-        throw;
-    }
-    c->nl_pending = 2;
+    if (!c->surface.panels.empty())
+        for (int b = c->b0; b < c->b1; ++b) items += static_cast<int>(c->surface.panels[b].size());
+    if (!c->surface.tris.empty())
+        for (int b = c->b0; b < c->b1; ++b) items += static_cast<int>(c->surface.tris[b].size() / hc::kNlTriDoubles);
+    c->nl2.flight = false;
+    c->nl.begin(items != 0, [&] { hc::nonlinear_enqueue(c, t); });
     HC_API_END(c)
 }
 
 int hc_nonlinear_end(hc_ctx* c, double* buoy, double* fk, double* hs_lin) {
     HC_API_BEGIN_HOT(c)
-    require(c->nl_pending != 0, HC_ERR_INVALID, "hc_nonlinear_end without hc_nonlinear_begin");
-    const int what = c->nl_pending;
-    c->nl_pending  = 0;
-    const bool with_inc = c->nl_inc_flight;
-    c->nl_inc_flight    = false;
-    c->nl_inc_off.clear();  // (stays so when the wait fails)
-    if (what == 2) HC_HIP(hipStreamSynchronize(c->stream_nl));
-    if (with_inc) {  // the evaluation that has completed is the one hc_get_nonlinear_increments answers with
-        c->nl_inc_cur ^= 1;
-        c->nl_inc_off = c->nl_pt_off;
-    }
+    const int what = c->nl.end("hc_nonlinear_end without hc_nonlinear_begin", &c->nl2);
     for (int bl = 0; bl < c->nloc; ++bl)
         for (int k = 0; k < 6; ++k) {
-            if (buoy) buoy[6 * bl + k] = what == 2 ? c->h_nl_out.p[hc::kNlOut * bl + k] : 0.0;
-            if (fk) fk[6 * bl + k] = what == 2 ? c->h_nl_out.p[hc::kNlOut * bl + 6 + k] : 0.0;
+            if (buoy) buoy[6 * bl + k] = what == 2 ? c->surface.h_out.p[hc::kNlOut * bl + k] : 0.0;
+            if (fk) fk[6 * bl + k] = what == 2 ? c->surface.h_out.p[hc::kNlOut * bl + 6 + k] : 0.0;
         }
-    if (hs_lin) hc::hs_linear_host(c, c->h_nl_state.p, c->h_nl_state.p + 3 * static_cast<size_t>(c->N), hs_lin);
+    if (hs_lin) hc::hs_linear_host(c, c->surface.h_state.p, c->surface.h_state.p + 3 * static_cast<size_t>(c->N), hs_lin);
     HC_API_END(c)
 }
 

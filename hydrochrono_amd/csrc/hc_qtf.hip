@@ -3,7 +3,7 @@
 // hc_sum_qtf_begin / hc_sum_qtf_end).  Not in the reference.  One implementation, two instances (hc_ctx::drift, hc_ctx::sum): the same
 // component table, bin map and projections U_m, V_m; the terms differ in the signs of the pair product (cos / sin of theta_i - theta_j
 // against theta_i + theta_j), in the drift term's modes 1 and 2, and in the words of their messages.  Off the step path: each term has
-// its own stream, component table, table copies and pinned staging; it reads and writes nothing a step or the other term uses, so it is
+// its own lane (hc_side.hpp), table copies and pinned staging; it reads and writes nothing a step or the other term uses, so it is
 // not ordered against the direct queue (as hc_morison.hip).  DESIGN.md 3.7e and 3.7i have the definitions, the projected evaluation
 // form, the kernels and their invariants.
 #include "hc_heading.hpp"
@@ -196,28 +196,23 @@ void qtf_append_nodes(std::vector<double>& pq, const std::vector<double>& T, int
 // (when a table, the wave model or the directions have changed).  The slots of the one-heading tables come first, in every list.
 void qtf_layout(hc_ctx* c, const QtfSpec& s) {
     QtfTerm& q         = c->*s.term;
-    const double phase = q.phase_opt;
-    const bool same_waves = kin_table_current(c, q.serial, q.phase, phase);
-    if (same_waves && !q.dirty) return;
-    hipStream_t st = q.stream;
-    q.serial       = ~0ULL;  // a failure below leaves nothing that counts as current
-    if (!same_waves) {
-        std::vector<double> tab = kin_table_host(c, phase);
-        q.nf = static_cast<int>(tab.size() / kKinCols);
-        q.amp.assign(tab.begin() + static_cast<size_t>(kKinAmp) * q.nf, tab.begin() + static_cast<size_t>(kKinAmp + 1) * q.nf);
-        q.omega.assign(tab.begin() + static_cast<size_t>(kKinOmega) * q.nf, tab.begin() + static_cast<size_t>(kKinOmega + 1) * q.nf);
+    KinTableCopy& kin  = q.lane.kin;
+    const double phase = q.lane.opts.regular_phase;
+    if (kin.current(c, phase) && !q.lane.dirty) return;
+    hipStream_t st = q.lane.stream;
+    kin.refresh(c, phase, st, [&](std::vector<double>& tab, std::vector<double>& dir, int nf) {
+        q.amp.assign(tab.begin() + static_cast<size_t>(kKinAmp) * nf, tab.begin() + static_cast<size_t>(kKinAmp + 1) * nf);
+        q.omega.assign(tab.begin() + static_cast<size_t>(kKinOmega) * nf, tab.begin() + static_cast<size_t>(kKinOmega + 1) * nf);
         // the direction columns behind the table's own (hc_qtf_dir.hip); none set: theta_i = 0, the phase of the one-heading kernels
-        std::vector<double> dir = kin_dir_columns_host(c);
         q.theta = c->wave_dir;
         if (dir.empty()) {
-            dir.assign(static_cast<size_t>(kDirCols) * q.nf, 0.0);
-            std::fill(dir.begin(), dir.begin() + q.nf, 1.0);
-            q.theta.assign(q.nf, 0.0);
+            dir.assign(static_cast<size_t>(kDirCols) * nf, 0.0);
+            std::fill(dir.begin(), dir.begin() + nf, 1.0);
+            q.theta.assign(nf, 0.0);
         }
-        tab.insert(tab.end(), dir.begin(), dir.end());
-        q.tab.upload(tab, st);
-    }
-    const int nf = q.nf;
+    });
+    kin.serial   = ~0ULL;  // the bin map below belongs to the table: a failure leaves nothing that counts as current
+    const int nf = kin.nf;
     std::vector<long long> desc;
     std::vector<int> rowptr, idx, slot_body;
     std::vector<double> wgt, em, pq;
@@ -273,7 +268,7 @@ void qtf_layout(hc_ctx* c, const QtfSpec& s) {
             rowptr.push_back(static_cast<int>(idx.size()));
             em.insert(em.end(), E.begin(), E.end());
             pq_n += n6 * (T.has_q ? 2 : 1);
-            if (q.dirty) {  // otherwise the device copy is in place
+            if (q.lane.dirty) {  // otherwise the device copy is in place
                 if (pass == 0) {
                     pq.insert(pq.end(), T.P.begin(), T.P.end());
                     if (T.has_q) pq.insert(pq.end(), T.Q.begin(), T.Q.end());
@@ -297,13 +292,12 @@ void qtf_layout(hc_ctx* c, const QtfSpec& s) {
     q.idx.upload(idx, st);
     q.w.upload(wgt, st);
     if (s.build_em) q.em.upload(em, st);
-    if (q.dirty) q.pq.upload(pq, st);
+    if (q.lane.dirty) q.pq.upload(pq, st);
     q.slot_body  = slot_body;
     q.slots_dir  = slots_dir;
     q.chunks_dir = chunks_dir;
-    q.dirty      = false;
-    q.serial     = c->wave_serial;
-    q.phase      = phase;
+    q.lane.dirty = false;
+    kin.serial   = c->wave_serial;
 }
 
 void qtf_enqueue(hc_ctx* c, const QtfSpec& s, double t, const double* pos) {
@@ -320,8 +314,8 @@ void qtf_enqueue(hc_ctx* c, const QtfSpec& s, double t, const double* pos) {
     std::copy(pos, pos + n3, q.h_pos.p);
     const double ramp = kin_ramp(c, t);
     QtfArgs a{};
-    a.tab     = q.tab.p;
-    a.nf      = q.nf;
+    a.tab     = q.lane.kin.tab.p;
+    a.nf      = q.lane.kin.nf;
     a.mode    = q.mode;
     a.desc    = q.desc.p;
     a.rowptr  = q.rowptr.p;
@@ -333,7 +327,7 @@ void qtf_enqueue(hc_ctx* c, const QtfSpec& s, double t, const double* pos) {
     a.t       = t;
     a.ramp2   = ramp * ramp;  // second order in the amplitude
     a.out     = q.out.p;
-    hipStream_t st = q.stream;
+    hipStream_t st = q.lane.stream;
     HC_HIP(hipMemcpyAsync(q.pos.p, q.h_pos.p, n3 * sizeof(double), hipMemcpyHostToDevice, st));
     if (nout_one) {
         hipLaunchKernelGGL(s.kernel, dim3(static_cast<unsigned>(nout_one)), dim3(kQtfThreads), 0, st, a);
@@ -367,7 +361,7 @@ int qtf_set_table(hc_ctx* c, const QtfSpec& s, int body, int nh, const double* b
         require(nh * nq <= kQtfMaxNodes, HC_ERR_INVALID, "heading count times frequency count of a QTF table must not exceed 1024 nodes");
     }
     require(nq == 0 || (omega && P && (!headings || beta)), HC_ERR_INVALID, "null frequency grid, heading grid or QTF table");
-    require(!q.pending, HC_ERR_INVALID, s.msg_in_flight);
+    q.lane.require_idle(s.msg_in_flight);
     const size_t nn = static_cast<size_t>(std::max(nh, 1)) * nq, n6 = 6 * nn * nn;
     if (nq) {
         require(all_finite(omega, nq) && all_finite(P, n6) && (!Q || all_finite(Q, n6)), HC_ERR_INVALID, s.msg_table);
@@ -375,7 +369,7 @@ int qtf_set_table(hc_ctx* c, const QtfSpec& s, int body, int nh, const double* b
         require(nh == 0 || all_finite(beta, nh), HC_ERR_INVALID, "non-finite value in a QTF heading grid");
         for (int j = 1; j < nh; ++j) require(beta[j] > beta[j - 1], HC_ERR_INVALID, "the QTF heading grid is not strictly increasing");
     }
-    if (!q.stream) HC_HIP(hipStreamCreateWithFlags(&q.stream, hipStreamNonBlocking));
+    q.lane.open();
     if (q.tabs.empty()) q.tabs.resize(c->N);
     QtfTable& T = q.tabs[body];
     T.nq        = nq;
@@ -385,7 +379,7 @@ int qtf_set_table(hc_ctx* c, const QtfSpec& s, int body, int nh, const double* b
     T.beta.assign(beta, beta + nh);
     T.P.assign(P, P + n6);
     T.Q.assign(Q, Q + (T.has_q ? n6 : 0));
-    q.dirty = true;
+    q.lane.dirty = true;
     HC_API_END(c)
 }
 
@@ -401,7 +395,7 @@ int qtf_set_mode(hc_ctx* c, const QtfSpec& s, int mode) {
     HC_API_BEGIN_HOT(c)
     QtfTerm& q = c->*s.term;
     require(mode >= 0 && mode <= s.mode_max, HC_ERR_INVALID, s.msg_mode);
-    require(!q.pending, HC_ERR_INVALID, s.msg_in_flight);
+    q.lane.require_idle(s.msg_in_flight);
     q.mode = mode;
     HC_API_END(c)
 }
@@ -415,13 +409,7 @@ int qtf_get_mode(hc_ctx* c, const QtfSpec& s, int* mode) {
 
 int qtf_set_options(hc_ctx* c, const QtfSpec& s, const hc_wave_kinematics_opts* o) {
     HC_API_BEGIN_HOT(c)
-    QtfTerm& q = c->*s.term;
-    hc_wave_kinematics_opts v;
-    hc_wave_kinematics_opts_default(&v);
-    if (o) v = *o;
-    require(std::isfinite(v.regular_phase), HC_ERR_INVALID, "non-finite regular_phase");
-    require(!q.pending, HC_ERR_INVALID, s.msg_in_flight);
-    q.phase_opt = v.regular_phase;
+    (c->*s.term).lane.set_options(o, false, "non-finite regular_phase", s.msg_in_flight);
     HC_API_END(c)
 }
 
@@ -429,7 +417,7 @@ int qtf_begin(hc_ctx* c, const QtfSpec& s, double t, const double* pos) {
     HC_API_BEGIN_HOT(c)
     QtfTerm& q = c->*s.term;
     require(c->finalized, HC_ERR_INVALID, "hc_finalize has not been called");
-    require(!q.pending, HC_ERR_INVALID, s.msg_twice);
+    q.lane.require_idle(s.msg_twice);
     require(pos != nullptr, HC_ERR_INVALID, "null state");
     require(std::isfinite(t) && all_finite(pos, 3 * static_cast<size_t>(c->N)), HC_ERR_INVALID, "non-finite time or position");
     bool one_heading = false;  // of any body of the system: every shard context answers alike
@@ -438,27 +426,14 @@ int qtf_begin(hc_ctx* c, const QtfSpec& s, double t, const double* pos) {
     bool any = false;
     if (!q.tabs.empty())
         for (int b = c->b0; b < c->b1; ++b) any = any || q.tabs[b].nq != 0;
-    if (!any || q.mode == 0 || !kin_has_components(c)) {
-        q.pending = 1;
-        return HC_OK;
-    }
-    try {
-        qtf_enqueue(c, s, t, pos);
-    } catch (...) {
-        (void)hipStreamSynchronize(q.stream);  // nothing stays pending
-        throw;
-    }
-    q.pending = 2;
+    q.lane.begin(any && q.mode != 0 && kin_has_components(c), [&] { qtf_enqueue(c, s, t, pos); });
     HC_API_END(c)
 }
 
 int qtf_end(hc_ctx* c, const QtfSpec& s, double* out) {
     HC_API_BEGIN_HOT(c)
     QtfTerm& q = c->*s.term;
-    require(q.pending != 0, HC_ERR_INVALID, s.msg_no_begin);
-    const int what = q.pending;
-    q.pending      = 0;
-    if (what == 2) HC_HIP(hipStreamSynchronize(q.stream));
+    const int what = q.lane.end(s.msg_no_begin);
     require(out != nullptr, HC_ERR_INVALID, "null output");
     std::fill(out, out + c->Dloc, 0.0);  // bodies without a table
     if (what == 2)

@@ -168,10 +168,7 @@ void hc_destroy(hc_ctx* ctx) {
     }
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     if (ctx->stream_am) (void)hipStreamDestroy(ctx->stream_am);
-    if (ctx->stream_mor) (void)hipStreamDestroy(ctx->stream_mor);
-    if (ctx->stream_nl) (void)hipStreamDestroy(ctx->stream_nl);
-    if (ctx->drift.stream) (void)hipStreamDestroy(ctx->drift.stream);
-    if (ctx->sum.stream) (void)hipStreamDestroy(ctx->sum.stream);
+    for (hc::SideLane* lane : {&ctx->mor, &ctx->nl, &ctx->drift.lane, &ctx->sum.lane}) lane->close();
     if (ctx->stream_wk2) (void)hipStreamDestroy(ctx->stream_wk2);
     if (ctx->ev_fin) (void)hipEventDestroy(ctx->ev_fin);
     if (ctx->ev_bg) (void)hipEventDestroy(ctx->ev_bg);

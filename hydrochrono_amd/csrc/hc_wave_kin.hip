@@ -72,6 +72,22 @@ std::vector<double> kin_dir_columns_host(const hc_ctx* c) {
     return col;
 }
 
+bool KinTableCopy::current(const hc_ctx* c, double regular_phase) const { return kin_table_current(c, serial, phase, regular_phase); }
+
+void KinTableCopy::refresh(hc_ctx* c, double regular_phase, hipStream_t st, const Shape& shape) {
+    if (current(c, regular_phase)) return;
+    serial = ~0ULL;  // a failure below leaves nothing that counts as current
+    std::vector<double> host = kin_table_host(c, regular_phase);
+    nf = static_cast<int>(host.size() / kKinCols);
+    std::vector<double> cols = kin_dir_columns_host(c);
+    if (shape) shape(host, cols, nf);
+    host.insert(host.end(), cols.begin(), cols.end());
+    tab.upload(host, st);
+    dir    = !cols.empty();
+    serial = c->wave_serial;
+    phase  = regular_phase;
+}
+
 namespace {
 
 constexpr int kKinThreads = 256;  // work items per workgroup, one per (point, time)
@@ -197,20 +213,6 @@ __global__ void __launch_bounds__(kKinThreads) wave_kinematics_kernel(KinArgs a)
     }
 }
 
-// The component table of the context's wave model on the device.  Rebuilt when a hc_set_wave_* call has come in since
-// (wave_serial) or the regular wave's phase differs from the cached one.
-void kin_table(hc_ctx* c, double regular_phase) {
-    if (kin_table_current(c, c->kin_serial, c->kin_phase, regular_phase)) return;
-    std::vector<double> tab = kin_table_host(c, regular_phase);
-    c->kin_nf = static_cast<int>(tab.size() / kKinCols);
-    const std::vector<double> dir = kin_dir_columns_host(c);
-    tab.insert(tab.end(), dir.begin(), dir.end());
-    c->d_kin_tab.upload(tab, c->stream);
-    c->kin_dir    = !dir.empty();
-    c->kin_serial = c->wave_serial;
-    c->kin_phase  = regular_phase;
-}
-
 void grow(hc::DeviceBuffer<double>& b, size_t n) {
     if (b.n < n) b.alloc(n);
 }
@@ -254,7 +256,7 @@ int hc_wave_kinematics(hc_ctx* c, const hc_wave_kinematics_opts* opts, int n_poi
         if (acc) std::fill(acc, acc + 3 * n, 0.0);
         return HC_OK;
     }
-    hc::kin_table(c, o.regular_phase);
+    c->kin.refresh(c, o.regular_phase, c->stream);
     // one buffer: points, times, then the requested outputs
     const size_t n_in = 3 * static_cast<size_t>(n_points) + n_times;
     const size_t n_out = (eta ? n : 0) + (vel ? 3 * n : 0) + (acc ? 3 * n : 0);
@@ -263,8 +265,8 @@ int hc_wave_kinematics(hc_ctx* c, const hc_wave_kinematics_opts* opts, int n_poi
     double* d_t   = d_xyz + 3 * static_cast<size_t>(n_points);
     double* d_out = d_t + n_times;
     hc::KinArgs a{};
-    a.tab          = c->d_kin_tab.p;
-    a.nf           = c->kin_nf;
+    a.tab          = c->kin.tab.p;
+    a.nf           = c->kin.nf;
     a.P            = n_points;
     a.T            = n_times;
     a.xyz          = d_xyz;
@@ -285,7 +287,7 @@ int hc_wave_kinematics(hc_ctx* c, const hc_wave_kinematics_opts* opts, int n_poi
     HC_HIP(hipMemcpyAsync(d_xyz, xyz, 3 * static_cast<size_t>(n_points) * sizeof(double), hipMemcpyHostToDevice, c->stream));
     HC_HIP(hipMemcpyAsync(d_t, t, static_cast<size_t>(n_times) * sizeof(double), hipMemcpyHostToDevice, c->stream));
     const unsigned blocks = static_cast<unsigned>((n + hc::kKinThreads - 1) / hc::kKinThreads);
-    if (c->kin_dir)
+    if (c->kin.dir)
         hipLaunchKernelGGL(hc::wave_kinematics_kernel<true>, dim3(blocks), dim3(hc::kKinThreads), 0, c->stream, a);
     else
         hipLaunchKernelGGL(hc::wave_kinematics_kernel<false>, dim3(blocks), dim3(hc::kKinThreads), 0, c->stream, a);

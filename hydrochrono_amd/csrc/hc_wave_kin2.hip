@@ -155,6 +155,19 @@ void wk2_tables(hc_ctx* c, Wk2TableSet& s, hipStream_t st, double regular_phase,
     s.serial = c->wave_serial;
 }
 
+bool Order2Part::prepare(hc_ctx* c, const SideLane& lane) {
+    if (!on || !kin_has_components(c)) return false;
+    wk2_tables(c, tabs, lane.stream, lane.opts.regular_phase, cut, false);
+    return tabs.any[0] || tabs.any[1];
+}
+
+Wk2Sea Order2Part::sea(const hc_ctx* c, double mwl) const {
+    return Wk2Sea{tabs.d_tab.p, tabs.nf, tabs.d_pair.p, tabs.d_band.p, c->depth, mwl, std::isfinite(c->depth) ? 1 : 0,
+                  {tabs.any[0] ? 1 : 0, tabs.any[1] ? 1 : 0}};
+}
+
+int Order2Part::ramped(const hc_ctx* c) const { return (ramp && kin_synthesised(c) && c->irr.ramp_duration > 0.0) ? 1 : 0; }
+
 namespace {
 
 // the tables hc_wave_kinematics2 and hc_wave_kinematics2_pair_tables read

@@ -1013,29 +1013,37 @@ class HydroGroup:
             out = out + self._drift_last
         return out + self._sum_last if sumf else out
 
-    # -- drift tables: every shard holds the tables of all bodies and computes those of its own --
-    def _drift_begin(self, t, pos):
+    # -- the terms beside the step: begin on every shard, then end on every shard; `nout` output arrays of D_local per shard --
+    def _side_begin(self, begin, end, nout, t, *arrays):
         begun = []
         try:
             for h in self.shards:
-                h._chk(self.lib.hc_drift_begin(h.ctx, float(t), _dp(pos)))
+                h._chk(begin(h.ctx, float(t), *(_dp(x) for x in arrays)))
                 begun.append(h)
         except HydroError:
-            for h in begun:
-                self.lib.hc_drift_end(h.ctx, _dp(np.empty(h.D_local)))
+            for h in begun:  # nothing stays pending
+                end(h.ctx, *(_dp(np.empty(h.D_local)) for _ in range(nout)))
             raise
 
-    def _drift_end(self, check=True):
-        out = np.empty(self.D)
+    def _side_end(self, end, nout, check=True):
+        out = tuple(np.empty(self.D) for _ in range(nout))
         rcs = []
         for h in self.shards:
-            part = np.empty(h.D_local)
-            rcs.append((h, self.lib.hc_drift_end(h.ctx, _dp(part))))
-            out[6 * h.b0:6 * h.b1] = part
+            part = tuple(np.empty(h.D_local) for _ in range(nout))
+            rcs.append((h, end(h.ctx, *(_dp(x) for x in part))))
+            for k in range(nout):
+                out[k][6 * h.b0:6 * h.b1] = part[k]
         for h, rc in rcs:
             if check:
                 h._chk(rc)
         return out
+
+    # -- drift tables: every shard holds the tables of all bodies and computes those of its own --
+    def _drift_begin(self, t, pos):
+        self._side_begin(self.lib.hc_drift_begin, self.lib.hc_drift_end, 1, t, pos)
+
+    def _drift_end(self, check=True):
+        return self._side_end(self.lib.hc_drift_end, 1, check)[0]
 
     def compute_drift(self, t, pos):
         self._drift_begin(t, _arr(pos, 3 * self.N))
@@ -1053,27 +1061,10 @@ class HydroGroup:
 
     # -- sum-frequency tables: every shard holds the tables of all bodies and computes those of its own --
     def _sum_begin(self, t, pos):
-        begun = []
-        try:
-            for h in self.shards:
-                h._chk(self.lib.hc_sum_qtf_begin(h.ctx, float(t), _dp(pos)))
-                begun.append(h)
-        except HydroError:
-            for h in begun:
-                self.lib.hc_sum_qtf_end(h.ctx, _dp(np.empty(h.D_local)))
-            raise
+        self._side_begin(self.lib.hc_sum_qtf_begin, self.lib.hc_sum_qtf_end, 1, t, pos)
 
     def _sum_end(self, check=True):
-        out = np.empty(self.D)
-        rcs = []
-        for h in self.shards:
-            part = np.empty(h.D_local)
-            rcs.append((h, self.lib.hc_sum_qtf_end(h.ctx, _dp(part))))
-            out[6 * h.b0:6 * h.b1] = part
-        for h, rc in rcs:
-            if check:
-                h._chk(rc)
-        return out
+        return self._side_end(self.lib.hc_sum_qtf_end, 1, check)[0]
 
     def compute_sum_qtf(self, t, pos):
         self._sum_begin(t, _arr(pos, 3 * self.N))
@@ -1103,28 +1094,10 @@ class HydroGroup:
         return self.shards[0].surface_triangle_count(b)
 
     def _nonlinear_begin(self, t, a):
-        begun = []
-        try:
-            for h in self.shards:
-                h._chk(self.lib.hc_nonlinear_begin(h.ctx, float(t), _dp(a[0]), _dp(a[1])))
-                begun.append(h)
-        except HydroError:
-            for h in begun:
-                self.lib.hc_nonlinear_end(h.ctx, None, None, None)
-            raise
+        self._side_begin(self.lib.hc_nonlinear_begin, self.lib.hc_nonlinear_end, 3, t, *a[:2])
 
     def _nonlinear_end(self, check=True):
-        out = tuple(np.empty(self.D) for _ in range(3))
-        rcs = []
-        for h in self.shards:
-            part = tuple(np.empty(h.D_local) for _ in range(3))
-            rcs.append((h, self.lib.hc_nonlinear_end(h.ctx, _dp(part[0]), _dp(part[1]), _dp(part[2]))))
-            for k in range(3):
-                out[k][6 * h.b0:6 * h.b1] = part[k]
-        for h, rc in rcs:
-            if check:
-                h._chk(rc)
-        return out
+        return self._side_end(self.lib.hc_nonlinear_end, 3, check)
 
     def compute_nonlinear(self, t, pos, rpy):
         n3 = 3 * self.N
@@ -1140,28 +1113,10 @@ class HydroGroup:
 
     # -- Morison elements: every shard holds the lists of all bodies and computes those of its own --
     def _morison_begin(self, t, a):
-        begun = []
-        try:
-            for h in self.shards:
-                h._chk(self.lib.hc_morison_begin(h.ctx, float(t), _dp(a[0]), _dp(a[1]), _dp(a[2]), _dp(a[3])))
-                begun.append(h)
-        except HydroError:
-            for h in begun:
-                self.lib.hc_morison_end(h.ctx, _dp(np.empty(h.D_local)))
-            raise
-        return begun
+        self._side_begin(self.lib.hc_morison_begin, self.lib.hc_morison_end, 1, t, *a)
 
     def _morison_end(self, check=True):
-        out = np.empty(self.D)
-        rcs = []
-        for h in self.shards:
-            part = np.empty(h.D_local)
-            rcs.append((h, self.lib.hc_morison_end(h.ctx, _dp(part))))
-            out[6 * h.b0:6 * h.b1] = part
-        for h, rc in rcs:
-            if check:
-                h._chk(rc)
-        return out
+        return self._side_end(self.lib.hc_morison_end, 1, check)[0]
 
     def compute_morison(self, t, pos, rpy, linvel, angvel):
         n3 = 3 * self.N
