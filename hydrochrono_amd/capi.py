@@ -217,6 +217,9 @@ SIGNATURES = {
     "hc_wave_kinematics2": (C.c_int, [C.c_void_p, C.POINTER(WaveKinematics2Opts), C.c_int, c_double_p, C.c_int, c_double_p,
                                       c_double_p, c_double_p, c_double_p]),
     "hc_wave_kinematics2_pair_tables": (C.c_int, [C.c_void_p, C.POINTER(WaveKinematics2Opts), c_double_p, c_double_p, c_double_p, c_double_p]),
+    "hc_wave_kinematics2_dir": (C.c_int, [C.c_void_p, C.POINTER(WaveKinematics2Opts), C.c_int, c_double_p, C.c_int, c_double_p,
+                                          c_double_p, c_double_p, c_double_p]),
+    "hc_wave_kinematics2_dir_pair_tables": (C.c_int, [C.c_void_p, C.POINTER(WaveKinematics2Opts), c_double_p, c_double_p, c_double_p, c_double_p]),
     "hc_synth_fill": (C.c_int, [C.c_void_p, C.c_ulonglong, C.c_int, C.c_double, C.c_int, C.c_double]),
 }
 

@@ -469,4 +469,11 @@ struct hc_ctx {
     size_t events_used = 0;
     bool sample_this_step = false;
     hc_profile_stats prof{};
+
+    // The second-order sea with directions (hc_wave_kinematics2_dir, hc_wave_kin2_dir.hip): what hc_wave_kinematics2 keeps, once
+    // more and the call's own -- its component table carries the two direction columns behind it.  Last in the struct: no member
+    // a step reads has moved.
+    hipStream_t stream_wk2d = nullptr;  // created by the first call
+    hc::Wk2TableSet wk2d;
+    hc::DeviceBuffer<double> d_wk2d_io;
 };

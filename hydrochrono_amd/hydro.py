@@ -514,25 +514,29 @@ class HydroForces:
         return o
 
     def wave_kinematics2(self, points, times, mwl=0.0, regular_phase=0.0, diff_band=(0.0, float("inf")), sum_band=(0.0, float("inf")),
-                         apply_ramp=True):
+                         apply_ramp=True, directional=False):
         """The second-order increments to wave_kinematics() at every point (P x 3) and time (T): eta2 (T, P), vel2 (T, P, 3),
         acc2 (T, P, 3); the caller adds them to the first-order values.  diff_band / sum_band: (lo, hi) in rad/s of the
-        difference and sum frequencies that take part.  See hc_wave_kinematics2 in include/hydrochrono_amd.h."""
+        difference and sum frequencies that take part.  See hc_wave_kinematics2 in include/hydrochrono_amd.h.
+        directional=True: the short-crested sea of set_wave_directions() (hc_wave_kinematics2_dir); the default is the long-crested
+        call, which refuses while directions are set."""
         xyz = np.ascontiguousarray(points, dtype=np.float64).reshape(-1, 3)
         t = _arr(times)
         P, T = xyz.shape[0], t.size
         eta, vel, acc = np.empty((T, P)), np.empty((T, P, 3)), np.empty((T, P, 3))
         o = self._wave2_opts(mwl, regular_phase, diff_band, sum_band, apply_ramp)
-        self._chk(self.lib.hc_wave_kinematics2(self.ctx, C.byref(o), P, _dp(xyz.reshape(-1)), T, _dp(t), _dp(eta.reshape(-1)),
-                                               _dp(vel.reshape(-1)), _dp(acc.reshape(-1))))
+        call = self.lib.hc_wave_kinematics2_dir if directional else self.lib.hc_wave_kinematics2
+        self._chk(call(self.ctx, C.byref(o), P, _dp(xyz.reshape(-1)), T, _dp(t), _dp(eta.reshape(-1)), _dp(vel.reshape(-1)), _dp(acc.reshape(-1))))
         return eta, vel, acc
 
-    def wave_pair_tables(self, regular_phase=0.0, diff_band=(0.0, float("inf")), sum_band=(0.0, float("inf"))):
-        """The device's pair tables of wave_kinematics2(): dict of Kp, Km, Bp, Bm, (nf, nf) each, zero outside the bands."""
+    def wave_pair_tables(self, regular_phase=0.0, diff_band=(0.0, float("inf")), sum_band=(0.0, float("inf")), directional=False):
+        """The device's pair tables of wave_kinematics2(): dict of Kp, Km, Bp, Bm, (nf, nf) each, zero outside the bands;
+        directional=True: those of the short-crested sea (hc_wave_kinematics2_dir_pair_tables)."""
         nf = self.wave_component_count()
         out = {n: np.zeros((nf, nf)) for n in ("Kp", "Km", "Bp", "Bm")}
         o = self._wave2_opts(0.0, regular_phase, diff_band, sum_band, True)
-        self._chk(self.lib.hc_wave_kinematics2_pair_tables(self.ctx, C.byref(o), *[_dp(out[n].reshape(-1)) for n in ("Kp", "Km", "Bp", "Bm")]))
+        call = self.lib.hc_wave_kinematics2_dir_pair_tables if directional else self.lib.hc_wave_kinematics2_pair_tables
+        self._chk(call(self.ctx, C.byref(o), *[_dp(out[n].reshape(-1)) for n in ("Kp", "Km", "Bp", "Bm")]))
         return out
 
     def wave_component_count(self):

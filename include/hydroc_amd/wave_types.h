@@ -157,12 +157,53 @@ class WaveBase {  // :52-79
         kinematics2(static_cast<int>(points.size()), points.empty() ? nullptr : points[0].data(), static_cast<int>(times.size()),
                     times.data(), eta2 ? eta2->data() : nullptr, vel2 ? vel2->data() : nullptr, acc2 ? acc2->data() : nullptr);
     }
+    // The same increments in the short-crested sea of SetDirections (hc_wave_kinematics2_dir; not in the reference): every pair of
+    // components interacts at the angle between its two directions, and the velocities gain a y component.  With no directions
+    // set it is the long-crested sea along +x, equal to the getters above to rounding.  Options: second_order_, mwl_, the phase.
+    double GetDirectionalSecondOrderElevation(const std::array<double, 3>& position, double time) {
+        double eta = 0.0;
+        kinematics2(1, position.data(), 1, &time, &eta, nullptr, nullptr, true);
+        return eta;
+    }
+    std::array<double, 3> GetDirectionalSecondOrderVelocity(const std::array<double, 3>& position, double time) {
+        std::array<double, 3> v{};
+        kinematics2(1, position.data(), 1, &time, nullptr, v.data(), nullptr, true);
+        return v;
+    }
+    std::array<double, 3> GetDirectionalSecondOrderAcceleration(const std::array<double, 3>& position, double time) {
+        std::array<double, 3> a{};
+        kinematics2(1, position.data(), 1, &time, nullptr, nullptr, a.data(), true);
+        return a;
+    }
+    template <class V, class = decltype(std::declval<const V&>().x() + std::declval<const V&>().z())>
+    double GetDirectionalSecondOrderElevation(const V& position, double time) {
+        return GetDirectionalSecondOrderElevation(as_array(position), time);
+    }
+    template <class V, class = decltype(std::declval<const V&>().x() + std::declval<const V&>().z())>
+    std::array<double, 3> GetDirectionalSecondOrderVelocity(const V& position, double time) {
+        return GetDirectionalSecondOrderVelocity(as_array(position), time);
+    }
+    template <class V, class = decltype(std::declval<const V&>().x() + std::declval<const V&>().z())>
+    std::array<double, 3> GetDirectionalSecondOrderAcceleration(const V& position, double time) {
+        return GetDirectionalSecondOrderAcceleration(as_array(position), time);
+    }
+    // Batched, as GetSecondOrderKinematics; each value has the bits of the single-point call.
+    void GetDirectionalSecondOrderKinematics(const std::vector<std::array<double, 3>>& points, const std::vector<double>& times,
+                                             std::vector<double>* eta2, std::vector<double>* vel2 = nullptr,
+                                             std::vector<double>* acc2 = nullptr) {
+        const size_t n = points.size() * times.size();
+        if (eta2) eta2->assign(n, 0.0);
+        if (vel2) vel2->assign(3 * n, 0.0);
+        if (acc2) acc2->assign(3 * n, 0.0);
+        kinematics2(static_cast<int>(points.size()), points.empty() ? nullptr : points[0].data(), static_cast<int>(times.size()),
+                    times.data(), eta2 ? eta2->data() : nullptr, vel2 ? vel2->data() : nullptr, acc2 ? acc2->data() : nullptr, true);
+    }
     // Wave heading and short-crested seas (hc_set_wave_directions; not in the reference, which ignores waves.direction): one
     // direction [rad, 0 along +x, positive towards +y] per component of the model -- 1 for a RegularWave, the number of spectrum
     // components for IrregularWaves (whose IRF model takes a uniform heading only).  The member is applied at the end of every Attach
     // (the library drops the directions with every new wave model); SetDirections also applies it to the context of the getters --
     // a sharded system sets them through TestHydro::SetWaveDirections, which reaches every shard.  GetElevation / GetVelocity / GetAcceleration, the Morison elements and the nonlinear surface forces then
-    // sample the directional sea; the second-order getters throw while directions are set.  Empty: the long-crested sea along +x.
+    // sample the directional sea; the GetSecondOrder* getters throw while directions are set (GetDirectionalSecondOrder* answer).  Empty: the long-crested sea along +x.
     std::vector<double> wave_directions_;
     void SetDirections(const std::vector<double>& theta_rad) {
         if (ctx_)  // (an error leaves the member as it was)
@@ -221,7 +262,8 @@ class WaveBase {  // :52-79
         const hc_wave_kinematics_opts o = KinematicsOptions();
         check(ctx_, hc_wave_kinematics(ctx_, &o, n_points, xyz, n_times, t, eta, vel, acc));
     }
-    void kinematics2(int n_points, const double* xyz, int n_times, const double* t, double* eta, double* vel, double* acc) {
+    void kinematics2(int n_points, const double* xyz, int n_times, const double* t, double* eta, double* vel, double* acc,
+                     bool directional = false) {
         if (!ctx_) throw std::runtime_error("wave model is not attached to a TestHydro");
         const hc_wave_kinematics_opts first = KinematicsOptions();
         hc_wave_kinematics2_opts o;
@@ -233,7 +275,8 @@ class WaveBase {  // :52-79
         o.sum_lo        = second_order_.sum_lo;
         o.sum_hi        = second_order_.sum_hi;
         o.apply_ramp    = second_order_.apply_ramp ? 1 : 0;
-        check(ctx_, hc_wave_kinematics2(ctx_, &o, n_points, xyz, n_times, t, eta, vel, acc));
+        check(ctx_, directional ? hc_wave_kinematics2_dir(ctx_, &o, n_points, xyz, n_times, t, eta, vel, acc)
+                                : hc_wave_kinematics2(ctx_, &o, n_points, xyz, n_times, t, eta, vel, acc));
     }
 };
 

@@ -972,6 +972,39 @@ int hc_wave_kinematics2(hc_ctx* ctx, const hc_wave_kinematics2_opts* o, int n_po
 int hc_wave_kinematics2_pair_tables(hc_ctx* ctx, const hc_wave_kinematics2_opts* o, double* Kp, double* Km, double* Bp, double* Bm);
 
 /* ------------------------------------------------------------------------------------------------
+ * Second-order irregular waves in a short-crested sea (not in the reference): the increments above for components that travel in
+ * directions of their own (hc_set_wave_directions).  A call beside hc_wave_kinematics2, which keeps refusing while directions are
+ * set.  DESIGN.md 3.7n has the checks and the kernels.
+ *
+ * Components (A_i, w_i, k_i, phi_i) as above; beta_i the direction of component i and (c_i, s_i) = (cos beta_i, sin beta_i) as the
+ * directional first-order kinematics hold them; with no directions set c_i = 1, s_i = 0.  R, r, b as above.
+ *     theta_i = k_i (x c_i + y s_i) - w_i t + phi_i                     (the expression of the directional hc_wave_kinematics)
+ *     gamma_ij = cos(beta_i - beta_j),   k_i . k_j = k_i k_j gamma_ij
+ *     kappa+-_x = k_i c_i +- k_j c_j,  kappa+-_y = k_i s_i +- k_j s_j,  |kappa+-| = sqrt(k_i^2 + k_j^2 +- 2 k_i k_j gamma_ij)
+ *     T(kappa) = |kappa| tanh(|kappa| h),   den+- = (r_i +- r_j)^2 - T(kappa+-)
+ *     D+_ij  = [ (r_i + r_j) (r_i (k_j^2 - R_j^2) + r_j (k_i^2 - R_i^2)) + 2 (r_i + r_j)^2 (k_i . k_j - R_i R_j) ] / den+
+ *     D-_ij  = [ (r_i - r_j) (r_j (k_i^2 - R_i^2) - r_i (k_j^2 - R_j^2)) + 2 (r_i - r_j)^2 (k_i . k_j + R_i R_j) ] / den-
+ *     K+-_ij = (D+-_ij - (k_i . k_j -+ R_i R_j)) / (r_i r_j) + (R_i + R_j)
+ *     B+-_ij = 1/4 b_i b_j D+-_ij / (w_i +- w_j),          D-_ij = B-_ij = 0 where w_i == w_j
+ *     eta2 = 1/4 sum A_i A_j [K-_ij cos(theta_i - theta_j) + K+_ij cos(theta_i + theta_j)]
+ *     u2x  = sum B kappa_x C cos Theta        u2y = sum B kappa_y C cos Theta        u2z = sum B |kappa| S sin Theta
+ *     a2x  = sum B kappa_x Omega C sin Theta  a2y = sum B kappa_y Omega C sin Theta  a2z = -sum B |kappa| Omega S cos Theta
+ * C and S as above at |kappa+-|; the sums over every i, every j and both signs.  In an infinite depth the sum-frequency potential,
+ * zero for a long-crested sea, is not zero for two components that cross.  z2, the bed, no stretching, the cut-off bands (on the
+ * frequencies alone), ramp * ramp, the 4096-component limit, the zero cases and the regular wave (the single pair i = j, along its
+ * heading) are those of hc_wave_kinematics2, and so is the statement on an item's bits.
+ *
+ * Works with or without directions set: without them it is the long-crested sea along +x evaluated by the directional kernels,
+ * equal to hc_wave_kinematics2 to rounding, not bit for bit.  Non-uniform directions exist on the spectral model and a regular wave
+ * only; a uniform heading on the IRF model is accepted.  The contract is that of hc_wave_kinematics2 with y finite as well; the
+ * tables (a set of this call's own, 4 nf^2 doubles) are cached on the wave model with its directions, the regular phase and the
+ * four cut-offs.  The Morison and nonlinear second-order switches keep refusing while directions are set.
+ * ---------------------------------------------------------------------------------------------- */
+int hc_wave_kinematics2_dir(hc_ctx* ctx, const hc_wave_kinematics2_opts* o, int n_points, const double* xyz,
+                            int n_times, const double* t, double* eta2, double* vel2, double* acc2);
+int hc_wave_kinematics2_dir_pair_tables(hc_ctx* ctx, const hc_wave_kinematics2_opts* o, double* Kp, double* Km, double* Bp, double* Bm);
+
+/* ------------------------------------------------------------------------------------------------
  * Synthetic many-body inputs generated directly in HBM (benchmark configurations C3/C4 of SURVEY 8d;
  * not part of the reference).  Fills K, K_hs, A_inf, excitation IRF for all local bodies from a
  * counter-based generator so that a 77 GB kernel never exists on the host.  hc_finalize still applies.
