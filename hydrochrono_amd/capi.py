@@ -180,6 +180,8 @@ SIGNATURES = {
     "hc_compute_morison": (C.c_int, [C.c_void_p, C.c_double, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
     "hc_set_morison_second_order": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int]),
     "hc_get_morison_second_order": (C.c_int, [C.c_void_p, c_int_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int_p]),
+    "hc_set_morison_second_order_directional": (C.c_int, [C.c_void_p, C.c_int]),
+    "hc_get_morison_second_order_directional": (C.c_int, [C.c_void_p, c_int_p]),
     "hc_get_morison_increments": (C.c_int, [C.c_void_p, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p]),
     "hc_set_surface_panels": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(SurfacePanel), C.c_int]),
     "hc_get_surface_panel_count": (C.c_int, [C.c_void_p, C.c_int, c_int_p]),

@@ -103,7 +103,8 @@ struct Wk2TableSet {
     double phase = 0.0, cut[4] = {0.0, 0.0, 0.0, 0.0};
     int nf = 0;
     bool any[2] = {false, false};       // some pair inside the difference / the sum band
-    DeviceBuffer<double> d_tab, d_pair;  // [kKinCols][nf], [4][nf][nf] (K+, K-, B+, B-)
+    bool dir = false;                   // built by wk2_dir_tables: d_tab carries the direction columns, the pair tables the angles
+    DeviceBuffer<double> d_tab, d_pair;  // [kKinCols][nf] (dir: [kKinCols + kDirCols][nf]), [4][nf][nf] (K+, K-, B+, B-)
     DeviceBuffer<int> d_band;            // [2][nf][2]: per sign (0 difference, 1 sum) and row, first and last column
     void release() {
         d_tab.release();
@@ -112,6 +113,7 @@ struct Wk2TableSet {
         serial = ~0ULL;
         nf = 0;
         any[0] = any[1] = false;
+        dir = false;
     }
 };
 

@@ -3,10 +3,12 @@
 // protocol), its own buffers and pinned staging; it reads and writes nothing a step uses, so it is not ordered against the direct queue
 // (as hc_wave_kinematics).
 // DESIGN.md 3.7c has the definition, the kernels and their invariants; 3.7g the elements on the second-order sea
-// (hc_set_morison_second_order): the increments of hc_wave_kinematics2 at every element, added before the wet test and the force.
+// (hc_set_morison_second_order): the increments of hc_wave_kinematics2 at every element, added before the wet test and the force;
+// 3.7o the same in a short-crested sea (hc_set_morison_second_order_directional): the increments of hc_wave_kinematics2_dir.
 #include "hc_internal.hpp"
 #include "hc_wave_kin.hpp"
 #include "hc_wave_kin2.hpp"
+#include "hc_wave_kin2_dir.hpp"
 #include "hc_wave_kin2_sum.hpp"
 
 using namespace hc::detail;
@@ -17,6 +19,7 @@ namespace {
 constexpr int kMorThreads = 256;  // work items per workgroup, one per element
 constexpr int kMorElemDoubles = 9;  // r, cd_area, cm_vol
 constexpr int kMorIncDoubles = 8;   // p, eta2, u2x, u2z, a2x, a2z of an element on the second-order sea
+constexpr int kMorDirIncDoubles = 10;  // p, eta2, u2[3], a2[3] of an element on the directional second-order sea
 
 struct MorArgs {
     const double* tab;  // [kKinCols][nf] (hc_wave_kin.hpp), with directions [kKinCols + kDirCols][nf]; nf = 0: still water
@@ -31,7 +34,8 @@ struct MorArgs {
     int stretch;       // Wheeler stretching
     int finite_depth;  // 0: water depth +inf
     double* item;      // [n_items][6] (F, M) of every element
-    const double* inc; // [n_items][kMorIncDoubles] of morison2_incr_kernel (the order-2 instantiation only)
+    const double* inc; // [n_items][kMorIncDoubles] of morison2_incr_kernel, with directions [n_items][kMorDirIncDoubles] of
+                       // morison2_dir_incr_kernel (the order-2 instantiations only)
 };
 
 // R = Rx(rpy0) Ry(rpy1) Rz(rpy2), d = R r, p = pos + d (x and z: the wave travels along x): one expression for the kernel that
@@ -64,11 +68,11 @@ __device__ inline MorFrame morison_frame(const double* el, const double* pos, co
 // kinematics pass (the same sincos); with stretching it is summed first.
 // ORDER2: the element's second-order increments (morison2_incr_kernel, earlier on the stream) are read after the first-order sums
 // and added before the wet test and the force; the first-order part, stretching by eta1 included, is the code of order 1.
-// DIR (order 1 only, morison_dir_items_kernel): the directional sea of wave_kinematics_kernel<true> -- the phase at k (x cos + y sin), the horizontal flow
+// DIR (morison_dir_items_kernel, morison2_dir_items_kernel): the directional sea of wave_kinematics_kernel<true> -- the phase at k (x cos + y sin), the horizontal flow
 // along (cos, sin), so that u_f and a_f have a y component; the long-crested instantiations keep their arithmetic.
+// ORDER2 and DIR: the ten doubles of morison2_dir_incr_kernel, u2y and a2y among them, enter the same places.
 template <bool ORDER2, bool DIR>
 __device__ __forceinline__ void morison_items_body(const MorArgs& a) {
-    static_assert(!(ORDER2 && DIR), "the second-order sea has no directions");
     constexpr int kDc = kKinCols, kDs = kKinCols + 1;  // rows of the direction columns (DIR only)
     __shared__ double s[DIR ? kKinCols + kDirCols : kKinCols][kKinTile];
     const int o       = blockIdx.x * kMorThreads + threadIdx.x;
@@ -157,8 +161,12 @@ __device__ __forceinline__ void morison_items_body(const MorArgs& a) {
     }
     if (!active) return;
     if (!a.stretch) eta = eta1;
-    double u2x = 0.0, u2z = 0.0, a2x = 0.0, a2z = 0.0;
-    if constexpr (ORDER2) {
+    double u2x = 0.0, u2y = 0.0, u2z = 0.0, a2x = 0.0, a2y = 0.0, a2z = 0.0;
+    if constexpr (ORDER2 && DIR) {
+        const double* q = a.inc + static_cast<size_t>(kMorDirIncDoubles) * o;
+        eta += q[3];
+        u2x = q[4], u2y = q[5], u2z = q[6], a2x = q[7], a2y = q[8], a2z = q[9];
+    } else if constexpr (ORDER2) {
         const double* q = a.inc + static_cast<size_t>(kMorIncDoubles) * o;
         eta += q[3];
         u2x = q[4], u2z = q[5], a2x = q[6], a2z = q[7];
@@ -177,7 +185,8 @@ __device__ __forceinline__ void morison_items_body(const MorArgs& a) {
     const double q0 = ufx - (lin[0] + (w1 * d2 - w2 * d1));
     double q1, a0, a1, a2;
     if constexpr (DIR) {
-        const double ufy = a.ramp * uy, afy = a.ramp * ay;
+        double ufy = a.ramp * uy, afy = a.ramp * ay;
+        if constexpr (ORDER2) ufy += u2y, afy += a2y;
         q1 = ufy - (lin[1] + (w2 * d0 - w0 * d2));
         a0 = r00 * afx + r10 * afy + r20 * afz;
         a1 = r01 * afx + r11 * afy + r21 * afz;
@@ -211,6 +220,7 @@ __global__ void __launch_bounds__(kMorThreads) morison_items_kernel(MorArgs a) {
     morison_items_body<ORDER2, false>(a);
 }
 __global__ void __launch_bounds__(kMorThreads) morison_dir_items_kernel(MorArgs a) { morison_items_body<false, true>(a); }
+__global__ void __launch_bounds__(kMorThreads) morison2_dir_items_kernel(MorArgs a) { morison_items_body<true, true>(a); }
 
 struct Mor2Args {
     Wk2Sea sea;           // the Morison path's own tables (hc_ctx::mor2), mwl of the Morison options
@@ -246,6 +256,35 @@ __global__ void __launch_bounds__(kWk2Threads) morison2_incr_kernel(Mor2Args a) 
         out[5] = sum[2] * ramp2;
         out[6] = sum[3] * ramp2;
         out[7] = sum[4] * ramp2;
+    }
+}
+
+// A value every lane of the wave holds, moved to scalar registers (its bits unchanged): the point of morison2_dir_incr_kernel
+// then costs the pair sum no vector register, as the point wk2_dir_sum_kernel loads with scalar loads costs it none
+__device__ __forceinline__ double wave_uniform(double v) {
+    return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
+}
+
+// The same in a short-crested sea: the point with its y, the pair sum of hc_wave_kinematics2_dir (wk2_dir_item_sum) and the
+// epilogue of wk2_dir_sum_kernel, so that the ten doubles stored are what that call returns for the stored point, bit for bit.
+// Of the frame only the point stays live across the pair sum.
+__global__ void __launch_bounds__(kWk2Threads) morison2_dir_incr_kernel(Mor2Args a) {
+    const int e       = blockIdx.x;  // the grid is n_items
+    const int b       = a.body[e];
+    const double* pos = a.state + 3 * b;
+    const MorFrame f  = morison_frame(a.elem + static_cast<size_t>(kMorElemDoubles) * e, pos, pos + 3 * a.N);
+    const double x = wave_uniform(f.x), y = wave_uniform(f.y), z = wave_uniform(f.z);
+    double sum[kWk2DirSums];
+    wk2_dir_item_sum<true, true>(a.sea, x, y, z, a.t, sum);
+    if (threadIdx.x == 0) {
+        const double ramp2 = wk2_ramp2(a.ramped != 0, a.ramp_duration, a.t);
+        double* out = a.inc + static_cast<size_t>(kMorDirIncDoubles) * e;
+        out[0] = x;
+        out[1] = y;
+        out[2] = z;
+        out[3] = 0.25 * sum[0] * ramp2;
+#pragma unroll
+        for (int k = 1; k < kWk2DirSums; ++k) out[3 + k] = sum[k] * ramp2;
     }
 }
 
@@ -312,10 +351,13 @@ void morison_enqueue(hc_ctx* c, double t, const double* pos, const double* rpy, 
     a.stretch      = (kin_synthesised(c) && c->mor.opts.wave_stretching) ? 1 : 0;  // RegularWave has none
     a.finite_depth = std::isfinite(c->depth) ? 1 : 0;
     a.item         = d.item.p;
-    // the second-order sea: tables of this path's own, then the increments of every element
-    const bool order2  = c->mor2.prepare(c, c->mor);
-    const size_t n_inc = static_cast<size_t>(kMorIncDoubles) * a.n_items;
-    double* h_inc      = order2 ? c->mor2.stage(n_inc) : nullptr;
+    // the second-order sea: tables of this path's own (with directions: those of the directional pair sum), then the increments of
+    // every element
+    const bool dir     = c->mor.kin.dir;
+    const bool order2  = dir ? c->mor2.prepare_dir(c, c->mor) : c->mor2.prepare(c, c->mor);
+    const int width    = dir ? kMorDirIncDoubles : kMorIncDoubles;
+    const size_t n_inc = static_cast<size_t>(width) * a.n_items;
+    double* h_inc      = order2 ? c->mor2.stage(n_inc, width) : nullptr;
     if (order2) a.inc = c->mor2.d_inc.p;
     HC_HIP(hipMemcpyAsync(d.state.p, d.h_state.p, 4 * n3 * sizeof(double), hipMemcpyHostToDevice, st));
     const dim3 item_grid((a.n_items + kMorThreads - 1) / kMorThreads);
@@ -330,11 +372,13 @@ void morison_enqueue(hc_ctx* c, double t, const double* pos, const double* rpy, 
         m.ramped        = c->mor2.ramped(c);
         m.ramp_duration = c->irr.ramp_duration;
         m.inc           = c->mor2.d_inc.p;
-        hipLaunchKernelGGL(morison2_incr_kernel, dim3(a.n_items), dim3(kWk2Threads), 0, st, m);
+        if (dir) hipLaunchKernelGGL(morison2_dir_incr_kernel, dim3(a.n_items), dim3(kWk2Threads), 0, st, m);
+        else hipLaunchKernelGGL(morison2_incr_kernel, dim3(a.n_items), dim3(kWk2Threads), 0, st, m);
         HC_HIP(hipGetLastError());
         HC_HIP(hipMemcpyAsync(h_inc, c->mor2.d_inc.p, n_inc * sizeof(double), hipMemcpyDeviceToHost, st));
-        hipLaunchKernelGGL(morison_items_kernel<true>, item_grid, dim3(kMorThreads), 0, st, a);
-    } else if (c->mor.kin.dir) {
+        if (dir) hipLaunchKernelGGL(morison2_dir_items_kernel, item_grid, dim3(kMorThreads), 0, st, a);
+        else hipLaunchKernelGGL(morison_items_kernel<true>, item_grid, dim3(kMorThreads), 0, st, a);
+    } else if (dir) {
         hipLaunchKernelGGL(morison_dir_items_kernel, item_grid, dim3(kMorThreads), 0, st, a);
     } else {
         hipLaunchKernelGGL(morison_items_kernel<false>, item_grid, dim3(kMorThreads), 0, st, a);
@@ -392,6 +436,19 @@ int hc_set_morison_second_order(hc_ctx* c, int on, double diff_lo, double diff_h
     HC_API_END(c)
 }
 
+int hc_set_morison_second_order_directional(hc_ctx* c, int on) {
+    HC_API_BEGIN_HOT(c)
+    c->mor.require_idle(hc::kMorInFlight);
+    c->mor2.dir_on = on != 0;
+    HC_API_END(c)
+}
+
+int hc_get_morison_second_order_directional(hc_ctx* c, int* on) {
+    HC_API_BEGIN_HOT(c)
+    if (on) *on = c->mor2.dir_on ? 1 : 0;
+    HC_API_END(c)
+}
+
 int hc_get_morison_second_order(hc_ctx* c, int* on, double* diff_lo, double* diff_hi, double* sum_lo, double* sum_hi, int* apply_ramp) {
     HC_API_BEGIN_HOT(c)
     c->mor2.get(on, diff_lo, diff_hi, sum_lo, sum_hi, apply_ramp);
@@ -404,14 +461,20 @@ int hc_get_morison_increments(hc_ctx* c, int body, double* p, double* eta2, doub
     require(body >= c->b0 && body < c->b1, HC_ERR_INVALID, "body not owned by this context");
     require(!c->mor2.done.empty(), HC_ERR_INVALID, "no Morison evaluation with a second-order part has completed");
     const double* q = c->mor2.last();
+    const int width = c->mor2.last_width();  // of the evaluation that completed: long-crested or directional
     const int e0 = c->mor2.done[body - c->b0], e1 = c->mor2.done[body - c->b0 + 1];
     for (int e = e0; e < e1; ++e) {
-        const double* v = q + static_cast<size_t>(hc::kMorIncDoubles) * e;
+        const double* v = q + static_cast<size_t>(width) * e;
         const size_t i  = static_cast<size_t>(e - e0);
         if (p) std::copy(v, v + 3, p + 3 * i);
         if (eta2) eta2[i] = v[3];
-        if (vel2) vel2[3 * i] = v[4], vel2[3 * i + 1] = 0.0, vel2[3 * i + 2] = v[5];
-        if (acc2) acc2[3 * i] = v[6], acc2[3 * i + 1] = 0.0, acc2[3 * i + 2] = v[7];
+        if (width == hc::kMorDirIncDoubles) {
+            if (vel2) std::copy(v + 4, v + 7, vel2 + 3 * i);
+            if (acc2) std::copy(v + 7, v + 10, acc2 + 3 * i);
+        } else {
+            if (vel2) vel2[3 * i] = v[4], vel2[3 * i + 1] = 0.0, vel2[3 * i + 2] = v[5];
+            if (acc2) acc2[3 * i] = v[6], acc2[3 * i + 1] = 0.0, acc2[3 * i + 2] = v[7];
+        }
     }
     HC_API_END(c)
 }
@@ -424,9 +487,10 @@ int hc_morison_begin(hc_ctx* c, double t, const double* pos, const double* rpy, 
     const size_t n3 = 3 * static_cast<size_t>(c->N);
     require(std::isfinite(t) && hc::all_finite(pos, n3) && hc::all_finite(rpy, n3) && hc::all_finite(linvel, n3) && hc::all_finite(angvel, n3),
             HC_ERR_INVALID, "non-finite time or state");
-    require(!(c->mor2.on && !c->wave_dir.empty()), HC_ERR_UNSUPPORTED,
-            "Morison elements on the second-order sea are not available while wave directions are set (hc_set_wave_directions): clear "
-            "the directions or switch the second-order sea off");
+    require(!(c->mor2.on && !c->wave_dir.empty() && !c->mor2.dir_on), HC_ERR_UNSUPPORTED,
+            "Morison elements on the second-order sea are not available while wave directions are set (hc_set_wave_directions): switch "
+            "the directional second-order sea on (hc_set_morison_second_order_directional), clear the directions or switch the "
+            "second-order sea off");
     require(!(c->mor2.on && hc::kin_has_components(c)) || hc::wk2_component_count(c) <= hc::kWk2MaxFreq, HC_ERR_UNSUPPORTED,
             "Morison elements on the second-order sea: more than 4096 wave components");
     int items = 0;

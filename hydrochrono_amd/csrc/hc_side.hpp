@@ -81,11 +81,13 @@ struct SideLane {
 // increments at the path's points with their two host copies: of the evaluation in flight and of the last completed one.
 struct Order2Part {
     bool on = false;
+    bool dir_on = false;  // hc_set_morison_second_order_directional: under directions the path runs the directional pair sum
     double cut[4] = {0.0, HUGE_VAL, 0.0, HUGE_VAL};
     int ramp = 1;
-    Wk2TableSet tabs;
+    Wk2TableSet tabs;       // long-crested or directional (Wk2TableSet::dir), as the evaluation that built them: never both at once
     DeviceBuffer<double> d_inc;
     PinnedBuffer<double> h_inc[2];
+    int h_width[2] = {0, 0};  // doubles per point in each host copy (the directional Morison path stores more)
     int cur = 0;            // which of the two holds the last completed one
     bool flight = false;    // the evaluation in flight writes the other one
     std::vector<int> off;   // [nloc + 1] first point of an owned body in the device copy of the lists
@@ -119,17 +121,21 @@ struct Order2Part {
     // The tables for the lane's regular phase, built on its stream; whether order 2 applies to this evaluation.  No components
     // (NoWave, no model, an imported eta record) or no pair inside either band: order 1, no further launch.
     bool prepare(hc_ctx* c, const SideLane& lane);  // hc_wave_kin2.hip
+    // ... in the directional sea: the tables of wk2_dir_tables in `tabs`
+    bool prepare_dir(hc_ctx* c, const SideLane& lane);  // hc_wave_kin2_dir.hip
     Wk2Sea sea(const hc_ctx* c, double mwl) const;  // hc_wave_kin2.hip
     int ramped(const hc_ctx* c) const;              // hc_wave_kin2.hip: the switch only (wk2_ramp2)
-    // the host copy the evaluation in flight writes, for n doubles (the device increments grow with it)
-    double* stage(size_t n) {
+    // the host copy the evaluation in flight writes, for n doubles, `width` per point (the device increments grow with it)
+    double* stage(size_t n, int width = 0) {
         PinnedBuffer<double>& h = h_inc[cur ^ 1];
         if (d_inc.n < n) d_inc.alloc(n);
         if (h.n < n) h.alloc(n);
+        h_width[cur ^ 1] = width;
         flight = true;
         return h.p;
     }
     const double* last() const { return h_inc[cur].p; }
+    int last_width() const { return h_width[cur]; }
     bool retire() {  // before the wait of the path's end
         const bool with_inc = flight;
         flight = false;

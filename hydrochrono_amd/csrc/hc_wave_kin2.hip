@@ -122,8 +122,9 @@ __global__ void __launch_bounds__(kWk2Threads) wk2_sum_kernel(Wk2SumArgs a) {
 int wk2_component_count(const hc_ctx* c) { return c->wave_kind == kWaveRegular ? 1 : static_cast<int>(c->spec_f.size()); }
 
 void wk2_tables(hc_ctx* c, Wk2TableSet& s, hipStream_t st, double regular_phase, const double cut[4], bool keep_empty) {
-    if (kin_table_current(c, s.serial, s.phase, regular_phase) && std::memcmp(s.cut, cut, sizeof(s.cut)) == 0) return;
+    if (!s.dir && kin_table_current(c, s.serial, s.phase, regular_phase) && std::memcmp(s.cut, cut, sizeof(s.cut)) == 0) return;
     s.serial = ~0ULL;  // nothing is cached until all of it is in place
+    s.dir    = false;  // (a set wk2_dir_tables filled before has another layout)
     const std::vector<double> tab = kin_table_host(c, regular_phase);
     const int nf = static_cast<int>(tab.size() / kKinCols);
     s.d_tab.upload(tab, st);

@@ -123,14 +123,15 @@ __global__ void __launch_bounds__(kWk2Threads) wk2_dir_sum_kernel(Wk2DirSumArgs 
     }
 }
 
-// The component table with the direction columns behind it ((1, 0) with no directions set), the pair tables and the band limits of
-// the context's wave model in c->wk2d, complete when the call returns: the rules of wk2_tables (current or absent: the mark goes
-// first and the stamp last; a direction change counts in wave_serial).
-void wk2_dir_tables(hc_ctx* c, hipStream_t st, const hc_wave_kinematics2_opts& o) {
-    Wk2TableSet& s = c->wk2d;
+}  // namespace
+
+// (declared in hc_wave_kin2_dir.hpp)  The rules of wk2_tables: current or absent -- the mark goes first and the stamp last; a
+// direction change counts in wave_serial; a set wk2_tables filled is not current here, whatever its stamp says.
+void wk2_dir_tables(hc_ctx* c, Wk2TableSet& s, hipStream_t st, const hc_wave_kinematics2_opts& o, bool keep_empty) {
     const double cut[4] = {o.diff_lo, o.diff_hi, o.sum_lo, o.sum_hi};
-    if (kin_table_current(c, s.serial, s.phase, o.regular_phase) && std::memcmp(s.cut, cut, sizeof(s.cut)) == 0) return;
+    if (s.dir && kin_table_current(c, s.serial, s.phase, o.regular_phase) && std::memcmp(s.cut, cut, sizeof(s.cut)) == 0) return;
     s.serial = ~0ULL;  // nothing is cached until all of it is in place
+    s.dir    = true;
     std::vector<double> tab = kin_table_host(c, o.regular_phase);
     const int nf = static_cast<int>(tab.size() / kKinCols);
     std::vector<double> dir = kin_dir_columns_host(c);
@@ -147,23 +148,39 @@ void wk2_dir_tables(hc_ctx* c, hipStream_t st, const hc_wave_kinematics2_opts& o
     s.d_tab.upload(tab, st);
     s.d_band.upload(band, st);
     const size_t n2 = static_cast<size_t>(nf) * nf;
-    if (s.d_pair.n != kWk2Tables * n2) s.d_pair.alloc(kWk2Tables * n2);
-    Wk2DirPairArgs a{};
-    a.tab          = s.d_tab.p;
-    a.nf           = nf;
-    a.finite_depth = std::isfinite(c->depth) ? 1 : 0;
-    a.g            = std::fabs(c->g);
-    a.depth        = c->depth;
-    std::copy(cut, cut + 4, a.cut);
-    a.pair = s.d_pair.p;
-    hipLaunchKernelGGL(wk2_dir_pair_kernel, dim3(static_cast<unsigned>((n2 + kWk2Threads - 1) / kWk2Threads)), dim3(kWk2Threads), 0, st, a);
-    HC_HIP(hipGetLastError());
-    HC_HIP(hipStreamSynchronize(st));
+    if (!(s.any[0] || s.any[1]) && !keep_empty) {
+        s.d_pair.release();
+    } else {
+        if (s.d_pair.n != kWk2Tables * n2) s.d_pair.alloc(kWk2Tables * n2);
+        Wk2DirPairArgs a{};
+        a.tab          = s.d_tab.p;
+        a.nf           = nf;
+        a.finite_depth = std::isfinite(c->depth) ? 1 : 0;
+        a.g            = std::fabs(c->g);
+        a.depth        = c->depth;
+        std::copy(cut, cut + 4, a.cut);
+        a.pair = s.d_pair.p;
+        hipLaunchKernelGGL(wk2_dir_pair_kernel, dim3(static_cast<unsigned>((n2 + kWk2Threads - 1) / kWk2Threads)), dim3(kWk2Threads), 0, st, a);
+        HC_HIP(hipGetLastError());
+        HC_HIP(hipStreamSynchronize(st));
+    }
     s.nf    = nf;
     s.phase = o.regular_phase;
     std::copy(cut, cut + 4, s.cut);
     s.serial = c->wave_serial;
 }
+
+bool Order2Part::prepare_dir(hc_ctx* c, const SideLane& lane) {
+    if (!on || !kin_has_components(c)) return false;
+    hc_wave_kinematics2_opts o;
+    hc_wave_kinematics2_opts_default(&o);
+    o.regular_phase = lane.opts.regular_phase;
+    o.diff_lo = cut[0], o.diff_hi = cut[1], o.sum_lo = cut[2], o.sum_hi = cut[3];
+    wk2_dir_tables(c, tabs, lane.stream, o, false);
+    return tabs.any[0] || tabs.any[1];
+}
+
+namespace {
 
 hc_wave_kinematics2_opts wk2_dir_opts(const hc_wave_kinematics2_opts* opts) {
     hc_wave_kinematics2_opts o;
@@ -194,7 +211,7 @@ int hc_wave_kinematics2_dir(hc_ctx* c, const hc_wave_kinematics2_opts* opts, int
     if (n == 0 || !(eta || vel || acc)) return HC_OK;
     if (waves) {
         if (!c->stream_wk2d) HC_HIP(hipStreamCreateWithFlags(&c->stream_wk2d, hipStreamNonBlocking));
-        hc::wk2_dir_tables(c, c->stream_wk2d, o);
+        hc::wk2_dir_tables(c, c->wk2d, c->stream_wk2d, o, true);
     }
     // NoWave, no model, an imported eta record (no components), or no pair inside either band: zeros, no launch
     if (!waves || !(c->wk2d.any[0] || c->wk2d.any[1])) {
@@ -260,7 +277,7 @@ int hc_wave_kinematics2_dir_pair_tables(hc_ctx* c, const hc_wave_kinematics2_opt
     if (!hc::kin_has_components(c)) return HC_OK;
     require(hc::wk2_component_count(c) <= hc::kWk2MaxFreq, HC_ERR_UNSUPPORTED, "more than 4096 wave components");
     if (!c->stream_wk2d) HC_HIP(hipStreamCreateWithFlags(&c->stream_wk2d, hipStreamNonBlocking));
-    hc::wk2_dir_tables(c, c->stream_wk2d, o);
+    hc::wk2_dir_tables(c, c->wk2d, c->stream_wk2d, o, true);
     const size_t n2 = static_cast<size_t>(c->wk2d.nf) * c->wk2d.nf;
     double* out[hc::kWk2Tables] = {Kp, Km, Bp, Bm};
     for (int k = 0; k < hc::kWk2Tables; ++k)

@@ -165,4 +165,11 @@ __device__ inline void wk2_dir_item_sum(const Wk2Sea& a, double x, double y, dou
     for (int k = 0; k < kWk2DirSums; ++k) out[k] = tid == 0 ? red[k][0] : 0.0;
 }
 
+// ---- hc_wave_kin2_dir.hip: the host side the users share (hc_wave_kinematics2_dir; hc_morison.hip through Order2Part::prepare_dir) ----
+// The component table with the direction columns behind it ((1, 0) with no directions set), the pair tables (wk2_dir_pair_kernel)
+// and the band limits of the context's wave model in `s`, built on `st` and complete when the call returns.  Rebuilt as wk2_tables
+// rebuilds its own, and when `s` holds a long-crested set (Wk2TableSet::dir).  With no pair inside either band the pair tables hold
+// zeros, or -- keep_empty false: nobody reads them -- are released and no kernel is launched.
+void wk2_dir_tables(hc_ctx* c, Wk2TableSet& s, hipStream_t st, const hc_wave_kinematics2_opts& o, bool keep_empty);
+
 }  // namespace hc

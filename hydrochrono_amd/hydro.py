@@ -586,9 +586,21 @@ class HydroForces:
         self._chk(self.lib.hc_get_morison_second_order(self.ctx, C.byref(on), *[C.byref(x) for x in v], C.byref(ramp)))
         return dict(on=bool(on.value), diff_band=(v[0].value, v[1].value), sum_band=(v[2].value, v[3].value), apply_ramp=bool(ramp.value))
 
+    def set_morison_second_order_directional(self, on=True):
+        """With set_morison_second_order() on and wave directions set, the elements see the increments of
+        wave_kinematics2(directional=True) -- u2 and a2 with their y components -- where the evaluation otherwise refuses.  A switch
+        of its own, kept when second order goes off and on; without directions it changes nothing.  See
+        hc_set_morison_second_order_directional in include/hydrochrono_amd.h."""
+        self._chk(self.lib.hc_set_morison_second_order_directional(self.ctx, int(bool(on))))
+
+    def morison_second_order_directional(self):
+        on = C.c_int()
+        self._chk(self.lib.hc_get_morison_second_order_directional(self.ctx, C.byref(on)))
+        return bool(on.value)
+
     def morison_increments(self, b):
         """What the elements of body b (0-based, owned) saw in the last evaluation on the second-order sea: dict of p (n, 3),
-        eta2 (n), vel2 (n, 3), acc2 (n, 3)."""
+        eta2 (n), vel2 (n, 3), acc2 (n, 3); the y components are zero after a long-crested evaluation."""
         n = self.morison_count(b)
         out = dict(p=np.empty((n, 3)), eta2=np.empty(n), vel2=np.empty((n, 3)), acc2=np.empty((n, 3)))
         self._chk(self.lib.hc_get_morison_increments(self.ctx, int(b), *[_dp(out[k].reshape(-1)) for k in ("p", "eta2", "vel2", "acc2")]))
@@ -1143,6 +1155,9 @@ class HydroGroup:
 
     def morison_second_order(self):
         return self.shards[0].morison_second_order()
+
+    def morison_second_order_directional(self):
+        return self.shards[0].morison_second_order_directional()
 
     def morison_increments(self, b):
         # the shard that owns the body answers

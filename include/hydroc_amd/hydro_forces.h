@@ -352,6 +352,12 @@ class TestHydro {
         for (hc_ctx* c : ctxs_) check(c, hc_set_morison_second_order(c, on ? 1 : 0, diff_lo, diff_hi, sum_lo, sum_hi, apply_ramp ? 1 : 0));
         have_time_ = false;
     }
+    // Under wave directions the elements see the increments of WaveBase::GetDirectionalSecondOrder* instead of a refusal
+    // (hc_set_morison_second_order_directional): a switch of its own beside SetMorisonSecondOrder.  Applied to every shard context.
+    void SetMorisonSecondOrderDirectional(bool on) {
+        for (hc_ctx* c : ctxs_) check(c, hc_set_morison_second_order_directional(c, on ? 1 : 0));
+        have_time_ = false;
+    }
     // What the elements of a body saw in the last evaluation on the second-order sea (hc_get_morison_increments): one entry per
     // element, answered by the shard that owns the body.
     MorisonIncrements GetMorisonIncrements(int body_index_1_based) {

@@ -542,11 +542,13 @@ int hc_wave_kinematics(hc_ctx* ctx, const hc_wave_kinematics_opts* o, int n_poin
  * hc_get_wave_directions: *n = the count (0: none set); theta may be NULL (size query).
  *
  * What refuses while directions are set (HC_ERR_UNSUPPORTED from the compute / begin call, nothing stays pending; as before once
- * they are cleared): hc_wave_kinematics2, the Morison elements and the nonlinear surface on the second-order sea
- * (hc_set_morison_second_order / hc_set_nonlinear_second_order with `on`), and hc_drift_begin with a drift mode != 0 /
- * hc_sum_qtf_begin with a sum mode != 0 while some body of the system holds a one-heading table of that term (hc_set_drift_qtf,
- * hc_set_sum_qtf): their pair sums and those tables are of one long-crested heading.  QTF tables on a heading grid
- * (hc_set_drift_qtf_headings, hc_set_sum_qtf_headings) are evaluated.
+ * they are cleared): hc_wave_kinematics2 (hc_wave_kinematics2_dir is the call for this sea); the Morison elements on the
+ * second-order sea (hc_set_morison_second_order with `on`) unless hc_set_morison_second_order_directional is on, which makes them
+ * see the increments of hc_wave_kinematics2_dir; the nonlinear surface on the second-order sea (hc_set_nonlinear_second_order with
+ * `on`), which has no directional form yet; and hc_drift_begin with a drift mode != 0 / hc_sum_qtf_begin with a sum mode != 0 while
+ * some body of the system holds a one-heading table of that term (hc_set_drift_qtf, hc_set_sum_qtf): their pair sums and those
+ * tables are of one long-crested heading.  QTF tables on a heading grid (hc_set_drift_qtf_headings, hc_set_sum_qtf_headings) are
+ * evaluated.
  *
  * First-order excitation under a heading: hc_set_excitation_rao_headings gives a body its excitation coefficients on a grid of
  * headings, dir_rad[n_dir] strictly increasing, mag / phase [6][n_dir][nw] (the layout of a BEMIO file; magnitudes per rho g as for
@@ -632,9 +634,26 @@ int hc_compute_morison(hc_ctx* ctx, double t, const double* pos, const double* r
  * (hc_set_nonlinear_second_order); the drift term stays first order. */
 int hc_set_morison_second_order(hc_ctx* ctx, int on, double diff_lo, double diff_hi, double sum_lo, double sum_hi, int apply_ramp);
 int hc_get_morison_second_order(hc_ctx* ctx, int* on, double* diff_lo, double* diff_hi, double* sum_lo, double* sum_hi, int* apply_ramp);
+/* The same in a short-crested sea.  While hc_set_morison_second_order is on and wave directions are set
+ * (hc_set_wave_directions; a uniform heading on the IRF model included), hc_morison_begin answers HC_ERR_UNSUPPORTED unless this
+ * switch is on (default 0).  With it on, element e sees eta = eta1 + eta2 in the wet test and u_f = ramp u1 + u2,
+ * a_f = ramp a1 + a2 with all three components, where eta1, u1, a1 are the directional first-order values (hc_set_wave_directions:
+ * Morison options, stretching by eta1) and eta2, u2, a2 are what hc_wave_kinematics2_dir returns for the same FP64 point p and time,
+ * bit for bit, with mwl and regular_phase of the Morison options and the four cut-offs and apply_ramp of
+ * hc_set_morison_second_order.  The force formula is the directional first-order one.  The pair tables are those of the directional
+ * pair sum, again this path's own (not shared with hc_wave_kinematics2_dir's; the one set of this path holds either kind, rebuilt
+ * when the directions come or go); on = 0 of hc_set_morison_second_order frees them.  The rules above carry over: no components or
+ * no pair inside either band -- no second-order launch and the directional first-order bits; more than 4096 components --
+ * HC_ERR_UNSUPPORTED from hc_morison_begin; a body's bits depend on that body's state and elements, the wave model with its
+ * directions, t and the options only.
+ * The switch is independent of hc_set_morison_second_order: it keeps its value when that one goes off and on, has no effect while
+ * that one is off, and none without directions (the long-crested path, its kernels and its bits).  HC_ERR_INVALID: a
+ * hc_morison_begin without its end. */
+int hc_set_morison_second_order_directional(hc_ctx* ctx, int on);
+int hc_get_morison_second_order_directional(hc_ctx* ctx, int* on);
 /* What the elements of `body` (0-based, owned by this context) saw in the last completed evaluation that had a second-order part:
- * their points p[n][3] and the increments eta2[n], vel2[n][3], acc2[n][3] (y components 0), n = the body's element count at that
- * evaluation.  Any pointer may be NULL.  HC_ERR_INVALID: second order is off, no such evaluation has completed yet (one without a
+ * their points p[n][3] and the increments eta2[n], vel2[n][3], acc2[n][3], n = the body's element count at that evaluation.  After a
+ * directional evaluation vel2[.][1] and acc2[.][1] carry u2y and a2y; after a long-crested one they are 0.  Any pointer may be NULL.  HC_ERR_INVALID: second order is off, no such evaluation has completed yet (one without a
  * second-order part -- no components, empty bands, no element on an owned body -- forgets the one before, and so does
  * hc_set_morison_elements), or the body is not owned by this context. */
 int hc_get_morison_increments(hc_ctx* ctx, int body, double* p, double* eta2, double* vel2, double* acc2);
