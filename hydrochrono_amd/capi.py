@@ -193,6 +193,8 @@ SIGNATURES = {
     "hc_compute_nonlinear": (C.c_int, [C.c_void_p, C.c_double, c_double_p, c_double_p, c_double_p, c_double_p, c_double_p]),
     "hc_set_nonlinear_second_order": (C.c_int, [C.c_void_p, C.c_int, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int]),
     "hc_get_nonlinear_second_order": (C.c_int, [C.c_void_p, c_int_p, c_double_p, c_double_p, c_double_p, c_double_p, c_int_p]),
+    "hc_set_nonlinear_second_order_directional": (C.c_int, [C.c_void_p, C.c_int]),
+    "hc_get_nonlinear_second_order_directional": (C.c_int, [C.c_void_p, c_int_p]),
     "hc_get_nonlinear_point_count": (C.c_int, [C.c_void_p, C.c_int, c_int_p]),
     "hc_get_nonlinear_increments": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p]),
     "hc_set_drift_qtf": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_double_p, c_double_p, c_double_p]),

@@ -3,10 +3,12 @@
 // step path, as hc_morison.hip: a lane of its own (hc_side.hpp), its own buffers and pinned staging; it reads and writes nothing a step
 // uses, so it is not ordered against the direct queue.  DESIGN.md 3.7d and 3.7d' have the definitions, the kernels and their invariants;
 // 3.7h the surface on the second-order sea (hc_set_nonlinear_second_order): eta2 and q2 = -d phi2 / dt of the pair sum at every surface
-// point, added before the wet test and the clipping, and the quadratic term -1/2 rho |grad phi1|^2.
+// point, added before the wet test and the clipping, and the quadratic term -1/2 rho |grad phi1|^2; 3.7p the same in a
+// short-crested sea (hc_set_nonlinear_second_order_directional): eta2 and q2 of the directional pair sum, u1 with its y component.
 #include "hc_internal.hpp"
 #include "hc_wave_kin.hpp"
 #include "hc_wave_kin2.hpp"
+#include "hc_wave_kin2_dir.hpp"
 #include "hc_wave_kin2_sum.hpp"
 
 #include <array>
@@ -39,7 +41,7 @@ struct NlArgs {
     int stretch;       // Wheeler stretching
     int finite_depth;  // 0: water depth +inf
     double* part;      // [chunks][12] per-chunk sums
-    // the order-2 kernels only: the increments of nl2_incr_kernel, [points][kNlIncDoubles], and the surface point of every panel
+    // the order-2 kernels only: the increments of nl2_incr_kernel or nl2_dir_incr_kernel, [points][kNlIncDoubles], and the surface point of every panel
     // ([panels]) or triangle vertex ([triangles][3]) in it
     const double* inc;
     const int* pidx;
@@ -77,11 +79,12 @@ __device__ __forceinline__ void nl_rotate(const NlFrame& f, const double* c, dou
 // ORDER2 (nl2_panels_kernel): the component loop also sums the first-order velocity u1 at the same z_e (a sincos where order 1 has
 // a cos), and the centroid's increments eta2, q2 (nl2_incr_kernel, earlier on the stream) are read after the loop: eta2 enters the
 // wet test, rho q2 - 1/2 rho ramp^2 |u1|^2 the dynamic pressure.  Everything else is the code of order 1.
-// DIR (order 1 only, nl_panels_dir_kernel): the directional sea of wave_kinematics_kernel<true> -- cos and sin of every component's
-// direction staged behind the other columns, the phase at k (x cos + y sin); the pressure is a scalar, so nothing else changes.
+// DIR (nl_panels_dir_kernel, nl2_dir_panels_kernel): the directional sea of wave_kinematics_kernel<true> -- cos and sin of every
+// component's direction staged behind the other columns, the phase at k (x cos + y sin); the pressure is a scalar, so nothing else
+// changes at order 1.  ORDER2 and DIR: the horizontal part of u1 lies along every component's direction, so |u1|^2 gains u1y^2; the
+// increments are those of nl2_dir_incr_kernel.
 template <bool ORDER2, bool DIR = false>
 __device__ __forceinline__ void nl_panels_body(const NlArgs& a) {
-    static_assert(!(ORDER2 && DIR), "the second-order sea has no directions");
     constexpr int kDc = kNlCols, kDs = kNlCols + 1;  // rows of the direction columns (DIR only)
     __shared__ double s[DIR ? kNlCols + kDirCols : kNlCols][kKinTile];
     __shared__ double red[kNlOut][kNlThreads];
@@ -132,7 +135,7 @@ __device__ __forceinline__ void nl_panels_body(const NlArgs& a) {
     const double ze = zs - a.mwl;  // under stretching mwl is subtracted a second time, as in the reference
 
     // ---- dynamic pressure sum (and eta without stretching) ----
-    double pd = 0.0, eta1 = 0.0, ux = 0.0, uz = 0.0;
+    double pd = 0.0, eta1 = 0.0, ux = 0.0, uy = 0.0, uz = 0.0;
     for (int i0 = 0; i0 < a.nf; i0 += kKinTile) {
         const int m = min(kKinTile, a.nf - i0);
         __syncthreads();
@@ -144,7 +147,9 @@ __device__ __forceinline__ void nl_panels_body(const NlArgs& a) {
         for (int i = 0; i < m; ++i) {
             const double k = s[kNlK][i];
             double sn = 0.0, cs;
-            if constexpr (ORDER2)
+            if constexpr (ORDER2 && DIR)
+                sincos(kin_kx<true>(k, x, y, s[kDc][i], s[kDs][i]) - s[kNlOmega][i] * t + s[kNlPhase][i], &sn, &cs);
+            else if constexpr (ORDER2)
                 sincos(k * x - s[kNlOmega][i] * t + s[kNlPhase][i], &sn, &cs);
             else
                 cs = cos(kin_kx<DIR>(k, x, y, DIR ? s[kDc][i] : 0.0, DIR ? s[kDs][i] : 0.0) - s[kNlOmega][i] * t + s[kNlPhase][i]);
@@ -159,7 +164,12 @@ __device__ __forceinline__ void nl_panels_body(const NlArgs& a) {
             pd += s[kNlW2AoK][i] * px * cs;
             if constexpr (ORDER2) {  // u1 of the kinematics (omega A is the table's column there), unramped
                 const double wa = s[kNlOmega][i] * s[kNlAmp][i];
-                ux += wa * px * cs;
+                if constexpr (DIR) {  // the horizontal flow along (cos, sin) of the component's direction
+                    ux += wa * px * cs * s[kDc][i];
+                    uy += wa * px * cs * s[kDs][i];
+                } else {
+                    ux += wa * px * cs;
+                }
                 uz += wa * pz * sn;
             }
         }
@@ -176,7 +186,10 @@ __device__ __forceinline__ void nl_panels_body(const NlArgs& a) {
     const bool wet  = active && (z - a.mwl <= eta);
     const double ps = -(a.rho * a.g) * (z - a.mwl);
     double pw       = a.rho * pd * a.ramp;
-    if constexpr (ORDER2) pw = pw + a.rho * q2 - 0.5 * a.rho * (a.ramp * a.ramp) * (ux * ux + uz * uz);
+    if constexpr (ORDER2 && DIR)
+        pw = pw + a.rho * q2 - 0.5 * a.rho * (a.ramp * a.ramp) * (ux * ux + uy * uy + uz * uz);
+    else if constexpr (ORDER2)
+        pw = pw + a.rho * q2 - 0.5 * a.rho * (a.ramp * a.ramp) * (ux * ux + uz * uz);
     double v[kNlOut];
     v[0]  = -ps * n0;
     v[1]  = -ps * n1;
@@ -211,6 +224,7 @@ __device__ __forceinline__ void nl_panels_body(const NlArgs& a) {
 __global__ void __launch_bounds__(kNlThreads) nl_panels_kernel(NlArgs a) { nl_panels_body<false>(a); }
 __global__ void __launch_bounds__(kNlThreads) nl2_panels_kernel(NlArgs a) { nl_panels_body<true>(a); }
 __global__ void __launch_bounds__(kNlThreads) nl_panels_dir_kernel(NlArgs a) { nl_panels_body<false, true>(a); }
+__global__ void __launch_bounds__(kNlThreads) nl2_dir_panels_kernel(NlArgs a) { nl_panels_body<true, true>(a); }
 
 // One work item per (owned body, component): the serial sum over the body's chunk partials in chunk order.
 __global__ void __launch_bounds__(kNlThreads) nl_sum_kernel(const double* part, const int* off, int rows, double* out) {
@@ -275,11 +289,10 @@ __device__ __forceinline__ void nl_sub_triangle(const NlVertex& q0, const NlVert
 // contribute exact zeros, as dry triangles do.  Then the fixed tree; lane 0 stores the chunk's 12-vector.
 // ORDER2 (nl2_tris_kernel): as in the panel kernel -- u1 of every vertex in the component loop, the vertices' increments after it,
 // eta2 into h and rho q2 - 1/2 rho ramp^2 |u1|^2 into p_d before the case table, which is the one of order 1.
-// DIR (order 1 only, nl_tris_dir_kernel): as in the panel kernel -- every vertex's phase at k (x cos + y sin), eta at the vertices
-// where the triangle is clipped included.
+// DIR (nl_tris_dir_kernel, nl2_dir_tris_kernel): as in the panel kernel -- every vertex's phase at k (x cos + y sin), eta at the
+// vertices where the triangle is clipped included; with ORDER2 u1y of every vertex and the increments of nl2_dir_incr_kernel.
 template <bool ORDER2, bool DIR = false>
 __device__ __forceinline__ void nl_tris_body(const NlArgs& a) {
-    static_assert(!(ORDER2 && DIR), "the second-order sea has no directions");
     constexpr int kDc = kNlCols, kDs = kNlCols + 1;  // rows of the direction columns (DIR only)
     __shared__ double s[DIR ? kNlCols + kDirCols : kNlCols][kKinTile];
     __shared__ double red[kNlOut][kNlThreads];
@@ -341,6 +354,7 @@ __device__ __forceinline__ void nl_tris_body(const NlArgs& a) {
     // ---- dynamic pressure sums (and eta without stretching): three independent chains per component ----
     double pd0 = 0.0, pd1 = 0.0, pd2 = 0.0, e0 = 0.0, e1 = 0.0, e2 = 0.0;
     double ux0 = 0.0, ux1 = 0.0, ux2 = 0.0, uz0 = 0.0, uz1 = 0.0, uz2 = 0.0;
+    double uy0 = 0.0, uy1 = 0.0, uy2 = 0.0;  // (ORDER2 and DIR only)
     for (int i0 = 0; i0 < a.nf; i0 += kKinTile) {
         const int m = min(kKinTile, a.nf - i0);
         __syncthreads();
@@ -353,7 +367,11 @@ __device__ __forceinline__ void nl_tris_body(const NlArgs& a) {
             const double k = s[kNlK][i];
             const double dc = DIR ? s[kDc][i] : 0.0, ds = DIR ? s[kDs][i] : 0.0;
             double sn0 = 0.0, sn1 = 0.0, sn2 = 0.0, cs0, cs1, cs2;
-            if constexpr (ORDER2) {
+            if constexpr (ORDER2 && DIR) {
+                sincos(kin_kx<true>(k, x0, y0, dc, ds) - s[kNlOmega][i] * t + s[kNlPhase][i], &sn0, &cs0);
+                sincos(kin_kx<true>(k, x1, y1, dc, ds) - s[kNlOmega][i] * t + s[kNlPhase][i], &sn1, &cs1);
+                sincos(kin_kx<true>(k, x2, y2, dc, ds) - s[kNlOmega][i] * t + s[kNlPhase][i], &sn2, &cs2);
+            } else if constexpr (ORDER2) {
                 sincos(k * x0 - s[kNlOmega][i] * t + s[kNlPhase][i], &sn0, &cs0);
                 sincos(k * x1 - s[kNlOmega][i] * t + s[kNlPhase][i], &sn1, &cs1);
                 sincos(k * x2 - s[kNlOmega][i] * t + s[kNlPhase][i], &sn2, &cs2);
@@ -385,9 +403,18 @@ __device__ __forceinline__ void nl_tris_body(const NlArgs& a) {
             pd2 += s[kNlW2AoK][i] * px2 * cs2;
             if constexpr (ORDER2) {  // u1 of the kinematics at every vertex, unramped
                 const double wa = s[kNlOmega][i] * s[kNlAmp][i];
-                ux0 += wa * px0 * cs0;
-                ux1 += wa * px1 * cs1;
-                ux2 += wa * px2 * cs2;
+                if constexpr (DIR) {  // the horizontal flow along (cos, sin) of the component's direction
+                    ux0 += wa * px0 * cs0 * dc;
+                    ux1 += wa * px1 * cs1 * dc;
+                    ux2 += wa * px2 * cs2 * dc;
+                    uy0 += wa * px0 * cs0 * ds;
+                    uy1 += wa * px1 * cs1 * ds;
+                    uy2 += wa * px2 * cs2 * ds;
+                } else {
+                    ux0 += wa * px0 * cs0;
+                    ux1 += wa * px1 * cs1;
+                    ux2 += wa * px2 * cs2;
+                }
                 uz0 += wa * pz0 * sn0;
                 uz1 += wa * pz1 * sn1;
                 uz2 += wa * pz2 * sn2;
@@ -417,7 +444,12 @@ __device__ __forceinline__ void nl_tris_body(const NlArgs& a) {
     q0.pd = a.rho * pd0 * a.ramp;
     q1.pd = a.rho * pd1 * a.ramp;
     q2.pd = a.rho * pd2 * a.ramp;
-    if constexpr (ORDER2) {
+    if constexpr (ORDER2 && DIR) {
+        const double hr2 = 0.5 * a.rho * (a.ramp * a.ramp);
+        q0.pd = q0.pd + a.rho * qa - hr2 * (ux0 * ux0 + uy0 * uy0 + uz0 * uz0);
+        q1.pd = q1.pd + a.rho * qb - hr2 * (ux1 * ux1 + uy1 * uy1 + uz1 * uz1);
+        q2.pd = q2.pd + a.rho * qc - hr2 * (ux2 * ux2 + uy2 * uy2 + uz2 * uz2);
+    } else if constexpr (ORDER2) {
         const double hr2 = 0.5 * a.rho * (a.ramp * a.ramp);
         q0.pd = q0.pd + a.rho * qa - hr2 * (ux0 * ux0 + uz0 * uz0);
         q1.pd = q1.pd + a.rho * qb - hr2 * (ux1 * ux1 + uz1 * uz1);
@@ -470,6 +502,7 @@ __device__ __forceinline__ void nl_tris_body(const NlArgs& a) {
 __global__ void __launch_bounds__(kNlThreads) nl_tris_kernel(NlArgs a) { nl_tris_body<false>(a); }
 __global__ void __launch_bounds__(kNlThreads) nl2_tris_kernel(NlArgs a) { nl_tris_body<true>(a); }
 __global__ void __launch_bounds__(kNlThreads) nl_tris_dir_kernel(NlArgs a) { nl_tris_body<false, true>(a); }
+__global__ void __launch_bounds__(kNlThreads) nl2_dir_tris_kernel(NlArgs a) { nl_tris_body<true, true>(a); }
 
 struct Nl2Args {
     Wk2Sea sea;           // the nonlinear path's own tables (hc_ctx::nl2), mwl of the nonlinear options
@@ -503,6 +536,28 @@ __global__ void __launch_bounds__(kWk2Threads) nl2_incr_kernel(Nl2Args a) {
         out[2] = z;
         out[3] = 0.25 * sum[0] * ramp2;
         out[4] = sum[5] * ramp2;
+    }
+}
+
+// The same in a short-crested sea: the point with its y, the pair sum of hc_wave_kinematics2_dir (wk2_dir_item_sum) with the q2
+// accumulator and the epilogue of wk2_dir_sum_kernel -- eta2 is what that call returns for the stored point, bit for bit.
+__global__ void __launch_bounds__(kWk2Threads) nl2_dir_incr_kernel(Nl2Args a) {
+    const int e       = blockIdx.x;  // the grid is the number of points
+    const double* pos = a.state + 3 * a.body[e];
+    const NlFrame f   = nl_frame(pos + 3 * a.N);
+    double d0, d1, d2;
+    nl_rotate(f, a.point + 3 * static_cast<size_t>(e), d0, d1, d2);
+    const double x = pos[0] + d0, y = pos[1] + d1, z = pos[2] + d2;
+    double sum[kWk2DirSums + 1];
+    wk2_dir_item_sum<true, false, true>(a.sea, x, y, z, a.t, sum);
+    if (threadIdx.x == 0) {
+        const double ramp2 = wk2_ramp2(a.ramped != 0, a.ramp_duration, a.t);
+        double* out = a.inc + static_cast<size_t>(kNlIncDoubles) * e;
+        out[0] = x;
+        out[1] = y;
+        out[2] = z;
+        out[3] = 0.25 * sum[0] * ramp2;
+        out[4] = sum[kWk2DirSums] * ramp2;
     }
 }
 
@@ -631,8 +686,10 @@ void nonlinear_enqueue(hc_ctx* c, double t) {
     a.finite_depth = std::isfinite(c->depth) ? 1 : 0;
     a.part         = d.part.p;
     const int rows = static_cast<int>(n_out);
-    // the second-order sea: tables of this path's own, then the increments of every surface point
-    const bool order2 = c->nl2.prepare(c, c->nl);
+    // the second-order sea: tables of this path's own (with directions: those of the directional pair sum), then the increments of
+    // every surface point
+    const bool dir    = c->nl.kin.dir;
+    const bool order2 = dir ? c->nl2.prepare_dir(c, c->nl) : c->nl2.prepare(c, c->nl);
     HC_HIP(hipMemcpyAsync(d.state.p, d.h_state.p, 2 * n3 * sizeof(double), hipMemcpyHostToDevice, st));
     if (order2) {
         if (d.pts_dirty) upload_points(c);
@@ -649,7 +706,8 @@ void nonlinear_enqueue(hc_ctx* c, double t) {
         m.ramped        = c->nl2.ramped(c);
         m.ramp_duration = c->irr.ramp_duration;
         m.inc           = c->nl2.d_inc.p;
-        hipLaunchKernelGGL(nl2_incr_kernel, dim3(points), dim3(kWk2Threads), 0, st, m);
+        if (dir) hipLaunchKernelGGL(nl2_dir_incr_kernel, dim3(points), dim3(kWk2Threads), 0, st, m);
+        else hipLaunchKernelGGL(nl2_incr_kernel, dim3(points), dim3(kWk2Threads), 0, st, m);
         HC_HIP(hipGetLastError());
         HC_HIP(hipMemcpyAsync(h_inc, c->nl2.d_inc.p, n_inc * sizeof(double), hipMemcpyDeviceToHost, st));
         a.inc = c->nl2.d_inc.p;
@@ -661,7 +719,11 @@ void nonlinear_enqueue(hc_ctx* c, double t) {
         ar.chunk  = d.chunk.p + 3 * static_cast<size_t>(chunk0);
         ar.part   = d.part.p + static_cast<size_t>(kNlOut) * chunk0;
         ar.pidx   = kind ? d.tidx.p : d.pidx.p;  // (indexed by the item, as the list)
-        if (order2 && kind)
+        if (order2 && dir && kind)
+            hipLaunchKernelGGL(nl2_dir_tris_kernel, dim3(chunks), dim3(kNlThreads), 0, st, ar);
+        else if (order2 && dir)
+            hipLaunchKernelGGL(nl2_dir_panels_kernel, dim3(chunks), dim3(kNlThreads), 0, st, ar);
+        else if (order2 && kind)
             hipLaunchKernelGGL(nl2_tris_kernel, dim3(chunks), dim3(kNlThreads), 0, st, ar);
         else if (order2)
             hipLaunchKernelGGL(nl2_panels_kernel, dim3(chunks), dim3(kNlThreads), 0, st, ar);
@@ -780,6 +842,19 @@ int hc_set_nonlinear_second_order(hc_ctx* c, int on, double diff_lo, double diff
     HC_API_END(c)
 }
 
+int hc_set_nonlinear_second_order_directional(hc_ctx* c, int on) {
+    HC_API_BEGIN_HOT(c)
+    c->nl.require_idle(hc::kNlInFlight);
+    c->nl2.dir_on = on != 0;
+    HC_API_END(c)
+}
+
+int hc_get_nonlinear_second_order_directional(hc_ctx* c, int* on) {
+    HC_API_BEGIN_HOT(c)
+    if (on) *on = c->nl2.dir_on ? 1 : 0;
+    HC_API_END(c)
+}
+
 int hc_get_nonlinear_second_order(hc_ctx* c, int* on, double* diff_lo, double* diff_hi, double* sum_lo, double* sum_hi, int* apply_ramp) {
     HC_API_BEGIN_HOT(c)
     c->nl2.get(on, diff_lo, diff_hi, sum_lo, sum_hi, apply_ramp);
@@ -820,9 +895,10 @@ int hc_nonlinear_begin(hc_ctx* c, double t, const double* pos, const double* rpy
     require(std::isfinite(t) && hc::all_finite(pos, n3) && hc::all_finite(rpy, n3), HC_ERR_INVALID, "non-finite time or state");
     require(c->gsys[0] == 0.0 && c->gsys[1] == 0.0 && c->gsys[2] < 0.0, HC_ERR_INVALID,
             "the nonlinear surface forces need gravity (0, 0, -g): z up");
-    require(!(c->nl2.on && !c->wave_dir.empty()), HC_ERR_UNSUPPORTED,
-            "the surface on the second-order sea is not available while wave directions are set (hc_set_wave_directions): clear the "
-            "directions or switch the second-order sea off");
+    require(!(c->nl2.on && !c->wave_dir.empty() && !c->nl2.dir_on), HC_ERR_UNSUPPORTED,
+            "the surface on the second-order sea is not available while wave directions are set (hc_set_wave_directions): switch the "
+            "directional second-order sea on (hc_set_nonlinear_second_order_directional), clear the directions or switch the "
+            "second-order sea off");
     require(!(c->nl2.on && hc::kin_has_components(c)) || hc::wk2_component_count(c) <= hc::kWk2MaxFreq, HC_ERR_UNSUPPORTED,
             "the surface on the second-order sea: more than 4096 wave components");
     // the host copy of the state: the kernel's source, and what hc_nonlinear_end computes hs_lin from (the caller's arrays are

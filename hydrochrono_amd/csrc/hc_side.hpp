@@ -81,7 +81,9 @@ struct SideLane {
 // increments at the path's points with their two host copies: of the evaluation in flight and of the last completed one.
 struct Order2Part {
     bool on = false;
-    bool dir_on = false;  // hc_set_morison_second_order_directional: under directions the path runs the directional pair sum
+    // hc_set_morison_second_order_directional, hc_set_nonlinear_second_order_directional: under directions the path runs the
+    // directional pair sum
+    bool dir_on = false;
     double cut[4] = {0.0, HUGE_VAL, 0.0, HUGE_VAL};
     int ramp = 1;
     Wk2TableSet tabs;       // long-crested or directional (Wk2TableSet::dir), as the evaluation that built them: never both at once

@@ -37,21 +37,27 @@ constexpr int kWk2DirSums = 7;  // 4 eta2, u2x, u2y, u2z, a2x, a2y, a2z
 // per pair and sign sigma, tau, |kappa|, kappa_x, kappa_y, e^{|kappa| z2} and the finite-depth factors are computed -- |kappa+| is
 // not k_i + k_j here, so no product of staged factors stands in for its profile.  e^{|kappa| z2} is an exp of a finite,
 // non-positive argument: 0, never NaN, once it underflows.  The two signs share one loop body (sg = -1, +1).
-// out (work item 0 only; zeros elsewhere): 4 eta2, u2x, u2y, u2z, a2x, a2y, a2z before the ramp.
-template <bool ETA, bool KIN>
-__device__ inline void wk2_dir_item_sum(const Wk2Sea& a, double x, double y, double z, double t, double (&out)[kWk2DirSums]) {
+// out (work item 0 only; zeros elsewhere): 4 eta2, u2x, u2y, u2z, a2x, a2y, a2z before the ramp, and with Q2 an eighth value
+// q2 = -d phi2 / dt = sum B Omega C cos Theta [m^2/s^2] (wk2_item_sum's Q2 in this sea): one more accumulator over
+// the same pairs with B C as u2x forms it, one more row of the tree.  Q2 without KIN stages k, w and the directions and computes
+// |kappa|, e^{|kappa| z2} and the finite-depth C, but no velocity or acceleration; eta2 has the same bits in every instantiation.
+template <bool ETA, bool KIN, bool Q2 = false>
+__device__ inline void wk2_dir_item_sum(const Wk2Sea& a, double x, double y, double z, double t,
+                                        double (&out)[Q2 ? kWk2DirSums + 1 : kWk2DirSums]) {
 #pragma clang fp contract(off)
-    constexpr int kT = kKinTile, kTK = KIN ? kKinTile : 1, kDc = kKinCols, kDs = kKinCols + 1;
+    constexpr bool PROF = KIN || Q2;  // the pair's wave number and depth profile are wanted
+    constexpr int kT = kKinTile, kTK = PROF ? kKinTile : 1, kDc = kKinCols, kDs = kKinCols + 1;
+    constexpr int kR = Q2 ? kWk2DirSums + 1 : kWk2DirSums;
     __shared__ double sc[2][kT], ss[2][kT], sA[2][kT];  // [0]: the tile of rows, [1]: the tile of columns
     __shared__ double sk[2][kTK], sw[2][kTK], sdc[2][kTK], sds[2][kTK];
-    __shared__ double red[kWk2DirSums][kWk2Threads];
+    __shared__ double red[kR][kWk2Threads];
     const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
     const int nf = a.nf;
     const long long n2 = static_cast<long long>(nf) * nf;
     double z2 = fmin(z - a.mwl, 0.0);
     if (a.finite_depth && z2 < -a.depth) z2 = -a.depth;
     const double zh = a.finite_depth ? z2 + a.depth : 0.0;
-    double eta = 0.0, ux = 0.0, uy = 0.0, uz = 0.0, ax = 0.0, ay = 0.0, az = 0.0;
+    double eta = 0.0, ux = 0.0, uy = 0.0, uz = 0.0, ax = 0.0, ay = 0.0, az = 0.0, q2 = 0.0;
 
     for (int j0 = 0; j0 < nf; j0 += kT) {
         const int mj = min(kT, nf - j0), j1 = j0 + mj - 1;
@@ -80,7 +86,7 @@ __device__ inline void wk2_dir_item_sum(const Wk2Sea& a, double x, double y, dou
                     sc[h][tid] = cs;
                     ss[h][tid] = sn;
                     sA[h][tid] = a.tab[kKinAmp * nf + i];
-                    if constexpr (KIN) {
+                    if constexpr (PROF) {
                         sk[h][tid]  = k;
                         sw[h][tid]  = w;
                         sdc[h][tid] = dc;
@@ -93,11 +99,13 @@ __device__ inline void wk2_dir_item_sum(const Wk2Sea& a, double x, double y, dou
                 const int i = i0 + r;
                 const double ci = sc[0][r], si = ss[0][r], Ai = sA[0][r];
                 double ki = 0.0, wi = 0.0, dci = 0.0, dsi = 0.0, kci = 0.0, ksi = 0.0;
-                if constexpr (KIN) {
+                if constexpr (PROF) {
                     ki  = sk[0][r];
                     wi  = sw[0][r];
                     dci = sdc[0][r];
                     dsi = sds[0][r];
+                }
+                if constexpr (KIN) {
                     kci = ki * dci;
                     ksi = ki * dsi;
                 }
@@ -117,14 +125,15 @@ __device__ inline void wk2_dir_item_sum(const Wk2Sea& a, double x, double y, dou
                         const double cT = fma(ci, cj, -(si * sjs)), sT = fma(si, cj, ci * sjs);
                         const double wgt = j == i ? 1.0 : 2.0;
                         if constexpr (ETA) eta = fma(wgt * (Ai * sA[1][c]) * Kt[j], cT, eta);
-                        if constexpr (KIN) {
+                        if constexpr (PROF) {
                             const double B   = wgt * Bt[j];
                             const double kjs = sg * sk[1][c], Om = wi + sg * sw[1][c];
                             const double dcj = sdc[1][c], dsj = sds[1][c];
                             double sig, tau;
                             wk2_dir_angle(dci, dsi, dcj, dsj, sig, tau);
                             const double ak = sqrt(wk2_dir_kappa2(ki, kjs, sig, tau));
-                            const double kx = kci + kjs * dcj, ky = ksi + kjs * dsj;
+                            double kx = 0.0, ky = 0.0;  // (KIN only)
+                            if constexpr (KIN) kx = kci + kjs * dcj, ky = ksi + kjs * dsj;
                             const double e  = exp(ak * z2);
                             double C = e, S = e;
                             if (a.finite_depth) {  // (uniform over the launch)
@@ -132,14 +141,18 @@ __device__ inline void wk2_dir_item_sum(const Wk2Sea& a, double x, double y, dou
                                 C = e * (1.0 + q) * d;
                                 S = e * (1.0 - q) * d;
                             }
-                            const double bC = B * C, bS = B * ak * S;
-                            const double bx = bC * kx, by = bC * ky;
-                            ux = fma(bx, cT, ux);
-                            uy = fma(by, cT, uy);
-                            uz = fma(bS, sT, uz);
-                            ax = fma(bx * Om, sT, ax);
-                            ay = fma(by * Om, sT, ay);
-                            az = fma(-(bS * Om), cT, az);
+                            const double bC = B * C;
+                            if constexpr (KIN) {
+                                const double bS = B * ak * S;
+                                const double bx = bC * kx, by = bC * ky;
+                                ux = fma(bx, cT, ux);
+                                uy = fma(by, cT, uy);
+                                uz = fma(bS, sT, uz);
+                                ax = fma(bx * Om, sT, ax);
+                                ay = fma(by * Om, sT, ay);
+                                az = fma(-(bS * Om), cT, az);
+                            }
+                            if constexpr (Q2) q2 = fma(bC * Om, cT, q2);
                         }
                     }
                 }
@@ -153,19 +166,20 @@ __device__ inline void wk2_dir_item_sum(const Wk2Sea& a, double x, double y, dou
     red[4][tid] = ax;
     red[5][tid] = ay;
     red[6][tid] = az;
+    if constexpr (Q2) red[7][tid] = q2;
     // ---- fixed-shape tree over the 256 lanes: lane l adds lane l + h for h = 128, 64, ..., 1 (wk2_item_sum) ----
     for (int h = kWk2Threads / 2; h > 0; h >>= 1) {
         __syncthreads();
         if (tid < h) {
 #pragma unroll
-            for (int k = 0; k < kWk2DirSums; ++k) red[k][tid] += red[k][tid + h];
+            for (int k = 0; k < kR; ++k) red[k][tid] += red[k][tid + h];
         }
     }
 #pragma unroll
-    for (int k = 0; k < kWk2DirSums; ++k) out[k] = tid == 0 ? red[k][0] : 0.0;
+    for (int k = 0; k < kR; ++k) out[k] = tid == 0 ? red[k][0] : 0.0;
 }
 
-// ---- hc_wave_kin2_dir.hip: the host side the users share (hc_wave_kinematics2_dir; hc_morison.hip through Order2Part::prepare_dir) ----
+// ---- hc_wave_kin2_dir.hip: the host side the users share (hc_wave_kinematics2_dir; hc_morison.hip and hc_nonlinear.hip through Order2Part::prepare_dir) ----
 // The component table with the direction columns behind it ((1, 0) with no directions set), the pair tables (wk2_dir_pair_kernel)
 // and the band limits of the context's wave model in `s`, built on `st` and complete when the call returns.  Rebuilt as wk2_tables
 // rebuilds its own, and when `s` holds a long-crested set (Wk2TableSet::dir).  With no pair inside either band the pair tables hold

@@ -689,6 +689,18 @@ class HydroForces:
         self._chk(self.lib.hc_get_nonlinear_second_order(self.ctx, C.byref(on), *[C.byref(x) for x in v], C.byref(ramp)))
         return dict(on=bool(on.value), diff_band=(v[0].value, v[1].value), sum_band=(v[2].value, v[3].value), apply_ramp=bool(ramp.value))
 
+    def set_nonlinear_second_order_directional(self, on=True):
+        """With set_nonlinear_second_order() on and wave directions set, the surface points see eta2 and q2 of
+        wave_kinematics2(directional=True)'s pair sum and |u1|^2 with its y component, where the evaluation otherwise refuses.  A
+        switch of its own, kept when second order goes off and on; without directions it changes nothing.  See
+        hc_set_nonlinear_second_order_directional in include/hydrochrono_amd.h."""
+        self._chk(self.lib.hc_set_nonlinear_second_order_directional(self.ctx, int(bool(on))))
+
+    def nonlinear_second_order_directional(self):
+        on = C.c_int()
+        self._chk(self.lib.hc_get_nonlinear_second_order_directional(self.ctx, C.byref(on)))
+        return bool(on.value)
+
     def nonlinear_point_count(self, b):
         """The distinct surface points of body b (0-based): panel centroids or triangle vertices, a shared vertex once."""
         n = C.c_int()
@@ -1142,6 +1154,9 @@ class HydroGroup:
 
     def nonlinear_second_order(self):
         return self.shards[0].nonlinear_second_order()
+
+    def nonlinear_second_order_directional(self):
+        return self.shards[0].nonlinear_second_order_directional()
 
     def nonlinear_point_count(self, b):
         return self.shards[0].nonlinear_point_count(b)

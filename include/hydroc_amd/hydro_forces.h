@@ -458,6 +458,13 @@ class TestHydro {
         for (hc_ctx* c : ctxs_) check(c, hc_set_nonlinear_second_order(c, on ? 1 : 0, diff_lo, diff_hi, sum_lo, sum_hi, apply_ramp ? 1 : 0));
         have_time_ = false;
     }
+    // Under wave directions the surface points see eta2 and q2 of the directional pair sum (WaveBase::GetDirectionalSecondOrder*) and
+    // |u1|^2 with its y component instead of a refusal (hc_set_nonlinear_second_order_directional): a switch of its own beside
+    // SetNonlinearSecondOrder.  Applied to every shard context.
+    void SetNonlinearSecondOrderDirectional(bool on) {
+        for (hc_ctx* c : ctxs_) check(c, hc_set_nonlinear_second_order_directional(c, on ? 1 : 0));
+        have_time_ = false;
+    }
     // What the surface points of a body saw in the last evaluation on the second-order sea (hc_get_nonlinear_increments): one entry
     // per distinct point, answered by the shard that owns the body.
     NonlinearIncrements GetNonlinearIncrements(int body_index_1_based) {

@@ -545,7 +545,7 @@ int hc_wave_kinematics(hc_ctx* ctx, const hc_wave_kinematics_opts* o, int n_poin
  * they are cleared): hc_wave_kinematics2 (hc_wave_kinematics2_dir is the call for this sea); the Morison elements on the
  * second-order sea (hc_set_morison_second_order with `on`) unless hc_set_morison_second_order_directional is on, which makes them
  * see the increments of hc_wave_kinematics2_dir; the nonlinear surface on the second-order sea (hc_set_nonlinear_second_order with
- * `on`), which has no directional form yet; and hc_drift_begin with a drift mode != 0 / hc_sum_qtf_begin with a sum mode != 0 while
+ * `on`) unless hc_set_nonlinear_second_order_directional is on, which gives it eta2 and q2 of that sea; and hc_drift_begin with a drift mode != 0 / hc_sum_qtf_begin with a sum mode != 0 while
  * some body of the system holds a one-heading table of that term (hc_set_drift_qtf, hc_set_sum_qtf): their pair sums and those
  * tables are of one long-crested heading.  QTF tables on a heading grid (hc_set_drift_qtf_headings, hc_set_sum_qtf_headings) are
  * evaluated.
@@ -631,7 +631,8 @@ int hc_compute_morison(hc_ctx* ctx, double t, const double* pos, const double* r
  * by on = 0.  HC_ERR_INVALID: a negative or NaN cut-off, lo > hi, or a hc_morison_begin without its end.  More than 4096 wave
  * components: hc_morison_begin returns HC_ERR_UNSUPPORTED and nothing stays pending.
  * Not included (out of scope): stretching of the second-order part.  The surface panels and triangles have a switch of their own
- * (hc_set_nonlinear_second_order); the drift term stays first order. */
+ * (hc_set_nonlinear_second_order, and hc_set_nonlinear_second_order_directional in a short-crested sea); the drift term stays first
+ * order. */
 int hc_set_morison_second_order(hc_ctx* ctx, int on, double diff_lo, double diff_hi, double sum_lo, double sum_hi, int apply_ramp);
 int hc_get_morison_second_order(hc_ctx* ctx, int* on, double* diff_lo, double* diff_hi, double* sum_lo, double* sum_hi, int* apply_ramp);
 /* The same in a short-crested sea.  While hc_set_morison_second_order is on and wave directions are set
@@ -782,6 +783,26 @@ int hc_compute_nonlinear(hc_ctx* ctx, double t, const double* pos, const double*
  * bound on the extrapolated first-order pressure at dry vertices. */
 int hc_set_nonlinear_second_order(hc_ctx* ctx, int on, double diff_lo, double diff_hi, double sum_lo, double sum_hi, int apply_ramp);
 int hc_get_nonlinear_second_order(hc_ctx* ctx, int* on, double* diff_lo, double* diff_hi, double* sum_lo, double* sum_hi, int* apply_ramp);
+/* The same in a short-crested sea.  While hc_set_nonlinear_second_order is on and wave directions are set
+ * (hc_set_wave_directions; a uniform heading on the IRF model and a regular wave with one heading included), hc_nonlinear_begin
+ * answers HC_ERR_UNSUPPORTED unless this switch is on (default 0).  With it on, every surface point P sees
+ *     eta  = eta1 + eta2 in the wet test and the clipping height: eta1 of the directional first-order kernels, eta2 what
+ *         hc_wave_kinematics2_dir returns for the same FP64 point P and time, bit for bit, with mwl and regular_phase of the
+ *         nonlinear options and the four cut-offs and apply_ramp of hc_set_nonlinear_second_order
+ *     q2   = -d phi2 / dt = sum_{+-} sum_ij B+-_ij Omega+-_ij C(|kappa+-_ij|, z2) cos Theta+-_ij, times ramp * ramp: the pair tables,
+ *         bands, weights, z2, |kappa| = |k_i e_i +- k_j e_j| and profile C of that call's u2x
+ *     u1   = (u1x, u1y, u1z), the unramped first-order directional velocity at the z_e of p_d1; its horizontal part lies along
+ *         every component's direction
+ *     p_d  = ramp p_d1 + rho q2 - 1/2 rho ramp^2 (u1x^2 + u1y^2 + u1z^2)
+ * and everything else as above.  The pair tables are those of the directional pair sum, again this path's own (the one set of this
+ * path holds either kind, rebuilt when the directions come or go); on = 0 of hc_set_nonlinear_second_order frees them.  The rules
+ * above carry over: no components or no pair inside either band -- no second-order launch and the directional first-order bits; more
+ * than 4096 components -- HC_ERR_UNSUPPORTED from hc_nonlinear_begin; hc_get_nonlinear_increments answers as before.
+ * The switch is independent of hc_set_nonlinear_second_order: it keeps its value when that one goes off and on, has no effect while
+ * that one is off, and none without directions (the long-crested path, its kernels and its bits).  HC_ERR_INVALID: a
+ * hc_nonlinear_begin without its end.  `on` of the getter may be NULL. */
+int hc_set_nonlinear_second_order_directional(hc_ctx* ctx, int on);
+int hc_get_nonlinear_second_order_directional(hc_ctx* ctx, int* on);
 /* The number of distinct surface points of `body` (0-based, any body of the system): of its panel centroids or its triangle
  * vertices, in the order of their first use. */
 int hc_get_nonlinear_point_count(hc_ctx* ctx, int body, int* n);
