@@ -110,6 +110,9 @@ SIGNATURES = {
     "hc_set_wave_irregular": (C.c_int, [C.c_void_p, C.POINTER(IrregularWaveParams)]),
     "hc_set_wave_irregular_eta": (C.c_int, [C.c_void_p, C.POINTER(IrregularWaveParams), c_double_p, c_double_p, C.c_int]),
     "hc_read_eta_file": (C.c_int, [C.c_char_p, c_double_p, c_double_p, C.c_int, c_int_p]),
+    "hc_set_eta_record_components": (C.c_int, [C.c_void_p, C.c_double, C.c_double, C.c_int]),
+    "hc_clear_eta_record_components": (C.c_int, [C.c_void_p]),
+    "hc_get_eta_record_components": (C.c_int, [C.c_void_p, c_int_p, c_int_p] + [c_double_p] * 7),
     "hc_set_eta_synthesis": (C.c_int, [C.c_void_p, C.c_int]),
     "hc_set_wave_irregular_spectral": (C.c_int, [C.c_void_p, C.POINTER(IrregularWaveParams)]),
     "hc_set_convolution_mode": (C.c_int, [C.c_void_p, C.c_int]),

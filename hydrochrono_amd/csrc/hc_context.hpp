@@ -332,6 +332,18 @@ struct hc_ctx {
     bool eta_record = false;
     std::vector<double> rec_t, rec_eta;
     double eta_h = 0.0;
+    // the record's wave components (hc_set_eta_record_components, hc_eta_components.hip): bin and amplitude per kept component -- the
+    // spec_* vectors above hold f, A^2 / (2 df), df, phase and k -- and what the getter reports beside them.  Empty: none set, the
+    // record has no component table.  Dropped by every hc_set_wave_* call.
+    std::vector<int> rec_m;
+    std::vector<double> rec_amp;
+    double rec_mean = 0.0, rec_share = 0.0, rec_rms = 0.0;
+    bool record_components() const { return wave_kind == hc::kWaveIrregular && eta_record && !rec_amp.empty(); }
+    void drop_record_components() {
+        rec_m.clear();
+        rec_amp.clear();
+        rec_mean = rec_share = rec_rms = 0.0;
+    }
     hc::DeviceBuffer<double> d_kex, d_ex_tau, d_ex_width, d_eta_t, d_eta;
     hc::DeviceBuffer<double> d_spec_mag, d_spec_phase, d_spec_amp, d_spec_omega, d_spec_phi;  // spectral (component-sum) mode
     unsigned long long wave_serial = 0;  // counts the hc_set_wave_* calls (voids the kinematics table below)

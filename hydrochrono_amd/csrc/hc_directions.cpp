@@ -139,8 +139,10 @@ int hc_set_wave_directions(hc_ctx* c, int n, const double* theta) {
     if (n > 0 && theta) th.assign(theta, theta + n);
     if (!th.empty()) {
         const bool components = c->wave_kind == hc::kWaveRegular || c->wave_kind == hc::kWaveSpectral ||
-                                (c->wave_kind == hc::kWaveIrregular && !c->eta_record);
-        require(components, HC_ERR_INVALID, "the wave model in force has no components to give directions to (NoWave, no model or an imported eta record)");
+                                (c->wave_kind == hc::kWaveIrregular && !c->eta_record) || c->record_components();
+        require(components, HC_ERR_INVALID,
+                "the wave model in force has no components to give directions to (NoWave, no model or an imported eta record without "
+                "components: hc_set_eta_record_components)");
         const int nf = c->wave_kind == hc::kWaveRegular ? 1 : static_cast<int>(c->spec_f.size());
         require(n == nf, HC_ERR_INVALID, "the direction count is not the component count of the wave model (1 for a regular wave, else nf)");
         for (double v : th) require(std::isfinite(v), HC_ERR_INVALID, "non-finite wave direction");

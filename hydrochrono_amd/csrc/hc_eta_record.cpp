@@ -78,6 +78,7 @@ int hc_set_wave_irregular_eta(hc_ctx* c, const hc_irregular_wave_params* pp, con
     c->rec_eta.assign(eta, eta + n);
     c->eta_h      = x.h;
     c->eta_record = true;
+    c->drop_record_components();  // a new record has none until hc_set_eta_record_components is called for it
     commit_excitation(c, ex);
     c->wave_nb_arg = p.num_bodies;
     HC_HIP(hipStreamSynchronize(c->stream));

@@ -41,7 +41,7 @@ int hc_get_sizes(hc_ctx* c, int* N, int* n_local, int* S, int* L, int* nf, int* 
     if (n_local) *n_local = c->nloc;
     if (S) *S = c->S;
     if (L) *L = c->L;
-    if (nf) *nf = c->nf;
+    if (nf) *nf = c->record_components() ? static_cast<int>(c->rec_amp.size()) : c->nf;  // a record's components are no step state (nf stays 0 there)
     if (nt) *nt = c->eta_record ? static_cast<int>(c->rec_t.size()) : c->nt;  // an imported record: as given, without its zero extension
     if (H) *H = static_cast<int>(c->times.size());
     if (Hcap) *Hcap = c->Hcap;

@@ -755,6 +755,7 @@ int hc_set_wave_none(hc_ctx* c, int num_bodies_arg) {
     c->wave_kind   = hc::kWaveNone;
     c->wave_nb_arg = num_bodies_arg;
     c->eta_record  = false;
+    c->drop_record_components();
     choose_exc_config(c);
     HC_API_END(c)
 }
@@ -796,6 +797,7 @@ int hc_set_wave_regular(hc_ctx* c, int num_bodies_arg, double amplitude, double 
     c->wave_kind   = hc::kWaveRegular;
     c->wave_nb_arg = num_bodies_arg;
     c->eta_record  = false;
+    c->drop_record_components();
     choose_exc_config(c);
     HC_API_END(c)
 }
@@ -891,6 +893,7 @@ int hc_set_wave_irregular(hc_ctx* c, const hc_irregular_wave_params* pp) {
     c->eta_t.swap(eta_t);
     c->eta.swap(eta);
     c->eta_record = false;
+    c->drop_record_components();
     commit_excitation(c, ex);
     c->wave_nb_arg = p.num_bodies;
     HC_HIP(hipStreamSynchronize(c->stream));
@@ -947,6 +950,7 @@ int hc_set_wave_irregular_spectral(hc_ctx* c, const hc_irregular_wave_params* pp
     c->wave_kind   = hc::kWaveSpectral;
     c->wave_nb_arg = p.num_bodies;
     c->eta_record  = false;
+    c->drop_record_components();
     choose_exc_config(c);
     HC_API_END(c)
 }

@@ -11,7 +11,7 @@ using namespace hc::detail;
 namespace hc {
 
 std::vector<double> kin_table_host(const hc_ctx* c, double regular_phase) {
-    if (c->wave_kind == kWaveNone || (c->wave_kind == kWaveIrregular && c->eta_record)) return {};
+    if (c->wave_kind == kWaveNone || (c->wave_kind == kWaveIrregular && c->eta_record && !c->record_components())) return {};
     std::vector<double> amp, omega, k, phase;
     if (c->wave_kind == kWaveRegular) {
         amp   = {c->reg_amp};
@@ -20,10 +20,11 @@ std::vector<double> kin_table_host(const hc_ctx* c, double regular_phase) {
         phase = {regular_phase};
     } else {
         const size_t nf = c->spec_f.size();
+        const bool rec  = c->record_components();  // the amplitudes of the analysis as they are, not through S and back
         amp.resize(nf);
         omega.resize(nf);
         for (size_t i = 0; i < nf; ++i) {
-            amp[i]   = std::sqrt(2 * c->spec_S[i] * c->spec_df[i]);
+            amp[i]   = rec ? c->rec_amp[i] : std::sqrt(2 * c->spec_S[i] * c->spec_df[i]);
             omega[i] = 2 * M_PI * c->spec_f[i];
         }
         k     = c->spec_k;
@@ -48,7 +49,8 @@ std::vector<double> kin_table_host(const hc_ctx* c, double regular_phase) {
 }
 
 bool kin_has_components(const hc_ctx* c) {
-    return c->wave_kind == kWaveRegular || c->wave_kind == kWaveSpectral || (c->wave_kind == kWaveIrregular && !c->eta_record);
+    return c->wave_kind == kWaveRegular || c->wave_kind == kWaveSpectral || (c->wave_kind == kWaveIrregular && !c->eta_record) ||
+           c->record_components();
 }
 
 bool kin_synthesised(const hc_ctx* c) { return (c->wave_kind == kWaveIrregular && !c->eta_record) || c->wave_kind == kWaveSpectral; }
@@ -249,8 +251,9 @@ int hc_wave_kinematics(hc_ctx* c, const hc_wave_kinematics_opts* opts, int n_poi
     const long long n = static_cast<long long>(n_points) * n_times;
     require(n <= hc::kKinMaxItems, HC_ERR_INVALID, "too many (point, time) pairs for one call");
     if (n == 0 || !(eta || vel || acc)) return HC_OK;
-    // NoWave (wave_types.h:103-109), and an imported eta record (no spectrum: GetEtaIrregular & co. over no component): zeros, no launch
-    if (c->wave_kind == hc::kWaveNone || (c->wave_kind == hc::kWaveIrregular && c->eta_record)) {
+    // NoWave (wave_types.h:103-109), and an imported eta record without components (no spectrum: GetEtaIrregular & co. over no
+    // component): zeros, no launch
+    if (!hc::kin_has_components(c)) {
         if (eta) std::fill(eta, eta + n, 0.0);
         if (vel) std::fill(vel, vel + 3 * n, 0.0);
         if (acc) std::fill(acc, acc + 3 * n, 0.0);

@@ -23,12 +23,15 @@ enum KinCol {
 };
 
 // The table of the context's wave model (regular: one component with the caller's phase; irregular and spectral: the spectrum of
-// the context, A_i = sqrt(2 S_i df_i) and w_i = 2 pi f_i as build_spectrum / the reference compute them).  Empty for NoWave and
-// for an imported eta record (no spectrum).
+// the context, A_i = sqrt(2 S_i df_i) and w_i = 2 pi f_i as build_spectrum / the reference compute them; an imported eta record
+// with components (hc_set_eta_record_components): the amplitudes of its analysis as they are).  Empty for NoWave and for an imported
+// eta record without components (no spectrum).
 std::vector<double> kin_table_host(const hc_ctx* c, double regular_phase);
-// Some component in that table: a regular wave, or a synthesised irregular model (not NoWave, no model, an imported eta record)
+// Some component in that table: a regular wave, a synthesised irregular model, or an imported eta record whose components are set
+// (not NoWave, no model, a record without them)
 bool kin_has_components(const hc_ctx* c);
-// A synthesised irregular model (irregular without an imported eta record, or spectral): the ramp and Wheeler stretching apply to it
+// A synthesised irregular model (irregular without an imported eta record, or spectral): the ramp and Wheeler stretching apply to it.
+// A record is used as given, with or without components: no ramp (kin_ramp is 1)
 bool kin_synthesised(const hc_ctx* c);
 // The ramp factor of the first-order quantities at time t (that of the spectral excitation, hc_kernels.hip): a synthesised model with
 // ramp_duration > 0 rises as max(t, 0) / ramp_duration up to ramp_duration; 1 otherwise

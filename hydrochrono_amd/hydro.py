@@ -169,6 +169,25 @@ class HydroForces:
         p.simulation_dt = simulation_dt
         self._chk(self.lib.hc_set_wave_irregular_eta(self.ctx, C.byref(p), _dp(t), _dp(eta), t.size))
 
+    def set_eta_record_components(self, f_min, f_max, max_components=0):
+        """Give the imported record wave components: its discrete Fourier coefficients on its own grid inside [f_min, f_max] Hz,
+        the max_components largest (0: all).  The wave kinematics and every side term then see that sea -- the periodic continuation
+        of the record; the excitation convolution is not touched.  See hc_set_eta_record_components in include/hydrochrono_amd.h."""
+        self._chk(self.lib.hc_set_eta_record_components(self.ctx, float(f_min), float(f_max), int(max_components)))
+
+    def clear_eta_record_components(self):
+        self._chk(self.lib.hc_clear_eta_record_components(self.ctx))
+
+    def eta_record_components(self):
+        """dict: m (bins), f [Hz], A, phase, k per kept component; mean, variance_share, rms_residual of the analysed samples."""
+        n = C.c_int()
+        s = [C.c_double() for _ in range(3)]
+        self._chk(self.lib.hc_get_eta_record_components(self.ctx, C.byref(n), None, None, None, None, None, *[C.byref(x) for x in s]))
+        m = np.zeros(n.value, dtype=np.int32)
+        v = [np.zeros(n.value) for _ in range(4)]
+        self._chk(self.lib.hc_get_eta_record_components(self.ctx, None, m.ctypes.data_as(capi.c_int_p), *[_dp(x) for x in v], None, None, None))
+        return dict(m=m, f=v[0], A=v[1], phase=v[2], k=v[3], mean=s[0].value, variance_share=s[1].value, rms_residual=s[2].value)
+
     def set_eta_synthesis(self, mode):
         """0 = direct FP64 sum (default), 1 = rocFFT chirp-z."""
         self._chk(self.lib.hc_set_eta_synthesis(self.ctx, int(mode)))
@@ -1189,6 +1208,18 @@ class HydroGroup:
         # every shard takes the whole record
         for h in self.shards:
             h.add_waves_irregular_eta(t, eta, simulation_dt, num_bodies)
+
+    def set_eta_record_components(self, f_min, f_max, max_components=0):
+        # every shard analyses the whole record and gets the same bits
+        for h in self.shards:
+            h.set_eta_record_components(f_min, f_max, max_components)
+
+    def clear_eta_record_components(self):
+        for h in self.shards:
+            h.clear_eta_record_components()
+
+    def eta_record_components(self):
+        return self.shards[0].eta_record_components()
 
     def components(self):
         parts = [h.components() for h in sorted(self.shards, key=lambda h: h.b0)]

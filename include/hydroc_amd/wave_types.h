@@ -14,7 +14,7 @@
 // members afterwards has no effect.  eta_file_path_ reads the record with hc_read_eta_file and attaches it with
 // hc_set_wave_irregular_eta, whose defined behaviour replaces the reference's undefined one (src/wave_types.cpp:480-500 vs :784-785;
 // DESIGN.md section 3): the record is zero-extended, there is no spectrum (GetSpectrum throws the reference's message), and the
-// kinematics are zeros.  The mesh helper the irregular demos call (SetUpWaveMesh / GetMeshFile / GetWaveMeshVelocity) is there so that they
+// kinematics are zeros -- unless components are set (IrregularWaves::SetRecordComponents).  The mesh helper the irregular demos call (SetUpWaveMesh / GetMeshFile / GetWaveMeshVelocity) is there so that they
 // compile.  GetSecondOrderElevation / GetSecondOrderVelocity / GetSecondOrderAcceleration and the batched GetSecondOrderKinematics
 // (hc_wave_kinematics2) give the second-order increments of an irregular sea; they have no counterpart in the reference.
 #pragma once
@@ -115,7 +115,7 @@ class WaveBase {  // :52-79
     }
     // Second-order increments of the long-crested sea of Sharma and Dean (hc_wave_kinematics2; not in the reference): what a caller
     // adds to GetElevation / GetVelocity / GetAcceleration.  mwl_ and a regular wave's phase are those of the first-order calls,
-    // the cut-offs and the ramp switch are second_order_; NoWave (and an imported eta record) give zeros.
+    // the cut-offs and the ramp switch are second_order_; NoWave (and an imported eta record, unless components are set) give zeros.
     struct SecondOrderOptions {
         double diff_lo = 0.0, diff_hi = HUGE_VAL, sum_lo = 0.0, sum_hi = HUGE_VAL;  // rad/s
         bool apply_ramp = true;
@@ -373,14 +373,41 @@ class IrregularWaves : public WaveBase {  // :294-380
     }
     // Exporter inputs (src/wave_types.cpp:461-478, read by the runner at run_hydrochrono_from_yaml.cpp:668-679).  GetSpectrum returns
     // the spectral densities S(f) its comment promises; the reference returns a member it never fills ("do not reproduce").
+    // After SetRecordComponents an imported record answers with the one-sided periodogram A^2 / (2 df) of its kept components.
     std::vector<double> GetSpectrum() {
-        if (!params_.eta_file_path_.empty())  // spectrumCreated_ == false (src/wave_types.cpp:461-467)
+        if (!params_.eta_file_path_.empty() && !record_has_components())  // spectrumCreated_ == false (src/wave_types.cpp:461-467)
             throw std::runtime_error("Spectrum has not been created. Initialize with wave height and period to create spectrum.");
         return spectrum(1);
     }
     std::vector<double> GetFreeSurfaceElevation() { return table(false); }
     std::vector<double> GetFreeSurfaceTime() const { return table(true); }
     std::vector<double> GetFrequenciesHz() const { return spectrum(0); }
+    // Wave components of an imported record (not in the reference; hc_set_eta_record_components in hydrochrono_amd.h): the record's
+    // discrete Fourier coefficients inside [f_min_hz, f_max_hz], the max_components largest (0: all).  GetElevation / GetVelocity /
+    // GetAcceleration and the side terms of the TestHydro this model is attached to then see that sea, the periodic continuation of
+    // the record; the excitation convolution keeps its bits.  A sharded system calls it on the model of every shard.
+    struct RecordComponents {
+        std::vector<int> m;                     // bins of the record's Fourier grid
+        std::vector<double> f, A, phase, k;     // Hz, m, rad, rad/m
+        double mean = 0.0, variance_share = 0.0, rms_residual = 0.0;
+    };
+    void SetRecordComponents(double f_min_hz, double f_max_hz, int max_components = 0) {
+        need_ctx();
+        check(ctx_, hc_set_eta_record_components(ctx_, f_min_hz, f_max_hz, max_components));
+    }
+    void ClearRecordComponents() {
+        need_ctx();
+        check(ctx_, hc_clear_eta_record_components(ctx_));
+    }
+    RecordComponents GetRecordComponents() const {
+        need_ctx();
+        RecordComponents r;
+        int n = 0;
+        check(ctx_, hc_get_eta_record_components(ctx_, &n, nullptr, nullptr, nullptr, nullptr, nullptr, &r.mean, &r.variance_share, &r.rms_residual));
+        r.m.resize(n), r.f.resize(n), r.A.resize(n), r.phase.resize(n), r.k.resize(n);
+        check(ctx_, hc_get_eta_record_components(ctx_, nullptr, r.m.data(), r.f.data(), r.A.data(), r.phase.data(), r.k.data(), nullptr, nullptr, nullptr));
+        return r;
+    }
     // Visualisation helper the reference's irregular-wave demos call (demos/sphere/demo_sphere_irreg_waves.cpp:144-153,
     // src/wave_types.cpp:846-864): the free-surface elevation over the simulated time as a Wavefront OBJ ribbon (x = -t, y = -10 / +10,
     // z = eta(t)) that the demo drags past the body with GetWaveMeshVelocity().  Off the force path; written from the eta(t) table the
@@ -431,6 +458,10 @@ class IrregularWaves : public WaveBase {  // :294-380
     }
     void need_ctx() const {
         if (!ctx_) throw std::runtime_error("IrregularWaves is not attached to a TestHydro");
+    }
+    bool record_has_components() const {
+        int n = 0;
+        return ctx_ && hc_get_eta_record_components(ctx_, &n, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr) == HC_OK && n > 0;
     }
     IrregularWaveParams params_;
     std::string mesh_file_name_;

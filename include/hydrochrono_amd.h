@@ -154,10 +154,48 @@ int hc_set_wave_irregular(hc_ctx* ctx, const hc_irregular_wave_params* params);
  *   excitation   the IRF is resampled on the simulation_dt grid as by hc_set_wave_irregular; simulation_duration, the spectrum
  *                parameters and hc_set_eta_synthesis are ignored.
  *   queries      hc_get_eta_table returns the record as given (nt = n, without the zero extension); nf = 0, hc_get_spectrum returns
- *                nothing; hc_wave_kinematics returns zeros (the reference's kinematics over an empty spectrum);
- *                hc_export_irregular_inputs_h5 gives HC_ERR_INVALID.
+ *                nothing; hc_wave_kinematics returns zeros (the reference's kinematics over an empty spectrum), unless components
+ *                are set (hc_set_eta_record_components below); hc_export_irregular_inputs_h5 gives HC_ERR_INVALID.
  * Row-sharded contexts take the whole record each. */
 int hc_set_wave_irregular_eta(hc_ctx* ctx, const hc_irregular_wave_params* params, const double* t, const double* eta, int n);
+
+/* Wave components of an imported eta record (not in the reference, whose record branch has no spectrum).  Opt-in: until this call
+ * a record drives the excitation convolution and nothing else -- still water for hc_wave_kinematics, the Morison elements, the
+ * nonlinear surface pressure, the QTF terms and the second-order sums -- with the bits it always had.  The call makes the record's
+ * discrete Fourier coefficients on its own grid the component table (A, w, k, phi) that all of those read, so each of them runs
+ * under a record through the kernels it has.  Valid only while the wave model is an imported record (else HC_ERR_INVALID).
+ *   grid         n samples, h = (t[n-1] - t[0]) / (n-1), T_w = n h.  If |t[j] - (t[0] + j h)| <= 1e-9 h for every j the samples are
+ *                used as given; otherwise the n values are those of the record's piecewise-linear interpolant (the one the
+ *                excitation path reads) at t[0] + j h.  n >= 4.
+ *   bins         f_m = m / T_w, 1 <= m <= floor(n / 2); the candidates are the bins with f_min_hz <= f_m <= f_max_hz (none:
+ *                HC_ERR_INVALID).  The mean (m = 0) is never a component; the getter reports it.
+ *   coefficient  c_m = (2 / n) sum_j eta_j exp(+i 2 pi ((m j) mod n) / n) on the GPU in FP64 (the Nyquist bin of an even n halved),
+ *                the product m j reduced in 64-bit integers; one workgroup per bin with a fixed summation order, so a bin's bits
+ *                depend on the record and on m only -- not on the band, on how many bins are computed, or on the shard.  The host
+ *                turns c_m to the absolute time origin, c_m exp(i w_m t[0]), the product formed and reduced in long double;
+ *                A_m = |c_m|, phi_m = arg c_m in the convention of hc_wave_kinematics: eta(0, t) = sum A cos(phi - w t).
+ *   selection    max_components <= 0 keeps every candidate, else the max_components of largest A (ties: the lower m); the kept
+ *                components are stored in ascending frequency.
+ *   context      f = f_m, df = 1 / T_w, phase = phi_m, k from the dispersion relation at the context's depth and g as for a
+ *                synthesised model; the component table takes A_m itself.  The call counts as a wave-model change for every cached
+ *                component table and drops the wave directions, as every hc_set_wave_* call does; a later hc_set_wave_* call drops
+ *                the components.  No ramp and no Wheeler stretching on the force terms (the record is used as given); the limits of
+ *                the terms (component counts of the QTF and second-order sums) apply as to a synthesised sea.  hc_set_wave_directions
+ *                accepts one uniform heading, as for hc_set_wave_irregular.  The excitation path is not touched: the record still
+ *                drives the convolution, zero extension included, with the same bits.  Synchronous on the context's stream.
+ *   LIMIT        the component sea is the PERIODIC continuation of the record with period T_w, while the excitation path has zeros
+ *                outside [t[0], t[n-1]]: keep the side terms inside the record.  No window is applied.
+ *   queries      hc_get_sizes reports nf = the kept count; hc_get_spectrum returns f, the one-sided periodogram A^2 / (2 df), df,
+ *                phase and k; hc_export_irregular_inputs_h5 keeps refusing.
+ * hc_clear_eta_record_components returns the record to its state before the call, bits included (HC_ERR_INVALID without a record;
+ * nothing set: no effect).
+ * hc_get_eta_record_components: *n = the kept count (0: none set); per kept component its bin m, f [Hz], A, phi and k; mean = the
+ * mean of the analysed samples; variance_share = sum A^2 / 2 over their variance; rms_residual = the RMS of samples - mean -
+ * reconstruction at the sample times (evaluated on the GPU with the exact integer phases).  Any pointer may be NULL (size query). */
+int hc_set_eta_record_components(hc_ctx* ctx, double f_min_hz, double f_max_hz, int max_components);
+int hc_clear_eta_record_components(hc_ctx* ctx);
+int hc_get_eta_record_components(hc_ctx* ctx, int* n, int* m, double* f, double* amplitude, double* phase, double* k, double* mean,
+                                 double* variance_share, double* rms_residual);
 /* IrregularWaves::ReadEtaFromFile (src/wave_types.cpp:480-500) without a context: every line is `time : eta` (read as
  * `ss >> time >> delimiter >> eta`; the delimiter must be ':', what follows the value is ignored).  *n = number of samples;
  * t = eta = NULL: size query.  Errors (message in hc_last_error(NULL)): HC_ERR_RUNTIME "Unable to open file at: <path>." and
@@ -501,6 +539,8 @@ int hc_get_simulation_parameters(hc_ctx* ctx, double* rho, double* g, double* wa
  *   z_s = depth (z' - eta) / (depth + eta) (Wheeler), from which the profile subtracts mwl once more, as the reference does; for
  *   an infinite depth (where the reference gives NaN) at the limit z_s = z' - eta.
  *   NoWave (include/hydroc/wave_types.h:103-109), or no wave model: zeros, no launch.
+ *   An imported eta record: zeros, no launch, unless components are set (hc_set_eta_record_components): then the sum over them,
+ *   with stretching as the options say.
  * Not ramped (the eta(t) table is; kinematics are not).  Without directions (hc_set_wave_directions below) the sea runs along +x
  * and only x enters the phase, as in the reference, which ignores waves.direction; with directions every component has its own
  * and y enters as well.
@@ -531,7 +571,7 @@ int hc_wave_kinematics(hc_ctx* ctx, const hc_wave_kinematics_opts* o, int n_poin
  *
  * hc_set_wave_directions: n = the component count (1 for a regular wave, nf for hc_set_wave_irregular and
  * hc_set_wave_irregular_spectral); n == 0 or theta == NULL clears the directions.  HC_ERR_INVALID: a wrong n, a non-finite angle,
- * NoWave, no model or an imported eta record (no components), a direction outside a body's heading grid, or non-uniform directions
+ * NoWave, no model or an imported eta record (no components, unless components are set), a direction outside a body's heading grid, or non-uniform directions
  * on the spectral model while a local body has no heading tables.  HC_ERR_UNSUPPORTED: non-uniform directions on the IRF model of
  * hc_set_wave_irregular -- its excitation is one convolution of eta(0, t), which a spread sea does not have: use
  * hc_set_wave_irregular_spectral.  A uniform heading is accepted there; the caller's excitation IRF is then understood to be the one
@@ -581,7 +621,8 @@ int hc_wave_spreading_directions(int nf, double heading_rad, double s, int n_bin
  *     eta, u_f, a_f = hc_wave_kinematics at p and t with the Morison options; for the two synthesised irregular models u_f and a_f
  *         are multiplied by the ramp of hc_set_wave_irregular_spectral (ramp_duration > 0 and t < ramp_duration: 0 for t <= 0, else
  *         t / ramp_duration; its derivative is not added); a regular wave is not ramped; NoWave, no model or an imported eta
- *         record: still water (eta = u_f = a_f = 0)
+ *         record: still water (eta = u_f = a_f = 0), unless components are set (hc_set_eta_record_components): then the sea of
+ *         those components, not ramped and not stretched
  *     wet when p.z - mwl <= eta; a dry element contributes nothing
  *     u = R^T (u_f - v_e),  a = R^T a_f,  F_body,i = 1/2 rho cd_area_i |u_i| u_i + rho cm_vol_i a_i,  F = R F_body,  M = d x F
  * A body's 6-vector is the sum of (F, M) over its elements in element index order: world frame, at the body reference, the sign of
@@ -622,7 +663,7 @@ int hc_compute_morison(hc_ctx* ctx, double t, const double* pos, const double* r
  *         applies as written there: fields held at z2 = min(z - mwl, 0) and at -h below the bed, no stretching, the true depth,
  *         ramp * ramp on all three increments (eta2 included) with apply_ramp
  *     eta = eta1 + eta2,  u_f = u1 + u2,  a_f = a1 + a2;  wet when p.z - mwl <= eta;  the force formula is unchanged
- * NoWave, no wave model, an imported eta record, or cut-offs that leave no pair inside either band: no second-order launch, the
+ * NoWave, no wave model, an imported eta record (unless components are set), or cut-offs that leave no pair inside either band: no second-order launch, the
  * result is that of order 1 bit for bit.  With on = 0 (the default) every Morison call makes the launches and returns the bits it
  * did before this switch existed.  The increments of an element are those hc_wave_kinematics2 returns for its point, bit for bit;
  * a body's bits still depend on that body's state and elements, the wave model, t and the options only.
@@ -681,7 +722,8 @@ int hc_get_morison_increments(hc_ctx* ctx, int body, double* p, double* eta2, do
  *         mwl subtraction, otherwise p.z - mwl; the infinite-depth limit included.  p_s always uses the true p.z.
  *     p_d is multiplied by the ramp the Morison term applies to u_f, under the same conditions (the two synthesised irregular models;
  *         a regular wave is not ramped).  The eta of the wet test is not ramped.
- *     NoWave, no wave model, or an imported eta record: eta = p_d = 0; the kernel still runs and gives pure nonlinear buoyancy.
+ *     NoWave, no wave model, or an imported eta record (unless components are set): eta = p_d = 0; the kernel still runs and gives
+ *     pure nonlinear buoyancy.
  *     buoy_e = (-p_s n, d x (-p_s n)),  fk_e = (-p_d n, d x (-p_d n)): world frame, at the body reference, the sign of an applied force.
  * Per owned body three 6-vectors: buoy and fk, the sums over its panels (a deterministic sum: its bits depend on that body's state,
  * its own panel list, the wave model, t and the options only -- not on the number of bodies, on other bodies' lists, or on the shard
@@ -716,7 +758,7 @@ int hc_get_surface_panel_count(hc_ctx* ctx, int body, int* n);
  *     R as above,  d_j = R v_j,  P_j = pos + d_j
  *     eta_j, p_s,j, p_d,j: exactly what the panel definition above gives for a panel whose point p is P_j -- the same expressions,
  *         component order, profile test, stretching with the second mwl subtraction, infinite-depth limit and ramp; still water for
- *         NoWave, no model or an eta record.  eta_j equals hc_wave_kinematics at (P_j, t), bit for bit, under the same options.
+ *         NoWave, no model or an eta record (unless components are set).  eta_j equals hc_wave_kinematics at (P_j, t), bit for bit, under the same options.
  *     h_j = P_j.z - mwl - eta_j; the vertex is wet iff h_j <= 0.
  * Wet part.  h, p_s and p_d are taken as linear over the triangle; the wet part is {h <= 0}:
  *     0 wet vertices   nothing
@@ -770,7 +812,7 @@ int hc_compute_nonlinear(hc_ctx* ctx, double t, const double* pos, const double*
  * terms are what cancels the first-order pressure's second-order residue at the free surface: p_s + p_d at z = mwl + eta1 + eta2 is
  * of third order in the amplitudes.  They enter before the wet test and the clipping, so the result cannot be composed from the
  * other calls.
- * NoWave, no wave model, an imported eta record, or cut-offs that leave no pair inside either band: the launches and the bits of
+ * NoWave, no wave model, an imported eta record (unless components are set), or cut-offs that leave no pair inside either band: the launches and the bits of
  * order 1.  With on = 0 (the default) every call makes the launches and returns the bits it did before this switch existed.  A
  * body's bits still depend on that body's state and list, the wave model, t and the options only.
  * The pair tables are this path's own (a third copy of 4 nf^2 doubles beside those of hc_wave_kinematics2 and the Morison
@@ -839,7 +881,7 @@ int hc_get_nonlinear_increments(hc_ctx* ctx, int body, int n, double* p /* [n][3
  * mistake: the zeros off the diagonal are taken as data.
  * The result is multiplied by ramp * ramp (second order in the amplitude), ramp being the factor the Morison term applies to u_f
  * under the same conditions: the two synthesised irregular models are ramped, a regular wave is not.
- * NoWave, no wave model, an imported eta record (no components), mode 0: zeros, no launch.  A body without a table: zeros.
+ * NoWave, no wave model, an imported eta record (no components, unless components are set), mode 0: zeros, no launch.  A body without a table: zeros.
  * World frame, at the body reference, the sign of an applied force.  A regular wave gives the constant A^2 T(w, w).
  * Sum-frequency QTFs are a term of their own (hc_set_sum_qtf below).  The tables hold one heading: while wave directions are set
  * (hc_set_wave_directions) and some body holds such a table hc_drift_begin with a mode != 0 returns HC_ERR_UNSUPPORTED.
@@ -916,7 +958,7 @@ int hc_compute_drift(hc_ctx* ctx, double t, const double* pos, double* out_Dloca
  *     P_s(w_i, w_j) = sum_mn W[i][m] W[j][n] P_s[m][n] (bilinear), Q likewise,
  * i.e. Re sum_ij A_i A_j T_s(w_i, w_j) exp(i (theta_i + theta_j)).  ramp as for the drift term: the two synthesised irregular models
  * are ramped, a regular wave is not; a regular wave gives A^2 [P_s(w, w) cos 2 theta - Q_s(w, w) sin 2 theta].
- * NoWave, no wave model, an imported eta record (no components), mode 0: zeros, no launch.  A body without a table: zeros.
+ * NoWave, no wave model, an imported eta record (no components, unless components are set), mode 0: zeros, no launch.  A body without a table: zeros.
  * World frame, at the body reference, the sign of an applied force.
  * There is no cut-off band on w_i + w_j: a caller who wants one zeroes table entries.  The tables hold one heading: while wave
  * directions are set (hc_set_wave_directions) and some body holds such a table hc_sum_qtf_begin with a mode != 0 returns
@@ -985,7 +1027,7 @@ int hc_compute_sum_qtf(hc_ctx* ctx, double t, const double* pos, double* out_Dlo
  * Ramp: with apply_ramp (the default) the increments are multiplied by ramp * ramp, ramp being the factor the Morison term applies
  * to u_f under the same conditions (the two synthesised irregular models, ramp_duration > 0 and t < ramp_duration; a regular wave
  * is not ramped).  hc_wave_kinematics itself is not ramped, hence the switch.
- * NoWave, no wave model, or an imported eta record (no components): zeros, no launch.  A regular wave: the single pair i = j,
+ * NoWave, no wave model, or an imported eta record (no components, unless components are set): zeros, no launch.  A regular wave: the single pair i = j,
  * which is Stokes' second-order term plus the constant set-down.  More than 4096 components: HC_ERR_UNSUPPORTED (the four pair
  * tables take 4 nf^2 doubles of device memory: 8 MB at 512 components, 134 MB at 2048, 537 MB at 4096).
  *
