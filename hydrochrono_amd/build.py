@@ -25,7 +25,7 @@ BEMIO_LIB = os.path.join(LIBDIR, "libhc_bemio.so")
 
 SOURCES = ["hc_kernels.hip", "hc_runtime.cpp", "hc_step.cpp", "hc_pass.cpp", "hc_setup.cpp", "hc_query.cpp", "hc_direct.cpp", "hc_host_math.cpp", "hc_yaml.cpp",
            "hc_eta_fft.cpp", "hc_wave_kin.hip", "hc_eta_record.cpp", "hc_morison.hip", "hc_nonlinear.hip", "hc_qtf.hip", "hc_qtf_dir.hip", "hc_wave_kin2.hip",
-           "hc_wave_kin2_dir.hip", "hc_directions.cpp", "hc_eta_components.hip"]
+           "hc_directions.cpp", "hc_eta_components.hip"]
 # kernel-argument preload: the leading scalar / pointer arguments of a kernel arrive in scalar registers with the wave (up to 16 words:
 # added_mass_mv_tagged_kernel starts without a single argument load); kernels whose first argument is a struct -- the step path's -- are
 # unaffected.  The code object only: the library's embedded copies go through HIP launches.

@@ -103,7 +103,7 @@ struct Wk2TableSet {
     double phase = 0.0, cut[4] = {0.0, 0.0, 0.0, 0.0};
     int nf = 0;
     bool any[2] = {false, false};       // some pair inside the difference / the sum band
-    bool dir = false;                   // built by wk2_dir_tables: d_tab carries the direction columns, the pair tables the angles
+    bool dir = false;                   // built with `dir`: d_tab carries the direction columns, the pair tables the angles
     DeviceBuffer<double> d_tab, d_pair;  // [kKinCols][nf] (dir: [kKinCols + kDirCols][nf]), [4][nf][nf] (K+, K-, B+, B-)
     DeviceBuffer<int> d_band;            // [2][nf][2]: per sign (0 difference, 1 sum) and row, first and last column
     void release() {
@@ -115,6 +115,14 @@ struct Wk2TableSet {
         any[0] = any[1] = false;
         dir = false;
     }
+};
+
+// What a second-order kinematics call keeps (hc_wave_kin2.hip): a stream of its own, created by the first call, the tables of the
+// wave model, regular phase and cut-offs they were built for, and a grow-only buffer for points, times and outputs
+struct Wk2Call {
+    hipStream_t stream = nullptr;
+    Wk2TableSet tabs;
+    DeviceBuffer<double> io;
 };
 
 }  // namespace hc
@@ -368,11 +376,10 @@ struct hc_ctx {
     // Wave drift forces (hc_set_drift_qtf) and sum-frequency wave forces (hc_set_sum_qtf): hc_qtf.hip
     hc::QtfTerm drift, sum;
 
-    // Second-order wave kinematics (hc_wave_kinematics2, hc_wave_kin2.hip): the tables of the wave model, regular phase and cut-offs
-    // they were built for; its own stream and a grow-only buffer for points, times and outputs, nothing a step uses
-    hipStream_t stream_wk2 = nullptr;  // created by the first call
-    hc::Wk2TableSet wk2;
-    hc::DeviceBuffer<double> d_wk2_io;
+    // Second-order wave kinematics (hc_wave_kin2.hip), nothing a step uses: [0] hc_wave_kinematics2, [1] hc_wave_kinematics2_dir,
+    // whose component table carries the two direction columns behind it.  Two instances: the calls keep independent caches and
+    // streams, so one never rebuilds or waits for the other's.
+    hc::Wk2Call wk2[2];
 
     // GEMV configuration + scratch
     int chunk_gp = 0, nchunks_rad = 0, chunk_gp_ex = 0, nchunks_ex = 0, ngp_ex = 0;
@@ -483,11 +490,4 @@ struct hc_ctx {
     size_t events_used = 0;
     bool sample_this_step = false;
     hc_profile_stats prof{};
-
-    // The second-order sea with directions (hc_wave_kinematics2_dir, hc_wave_kin2_dir.hip): what hc_wave_kinematics2 keeps, once
-    // more and the call's own -- its component table carries the two direction columns behind it.  Last in the struct: no member
-    // a step reads has moved.
-    hipStream_t stream_wk2d = nullptr;  // created by the first call
-    hc::Wk2TableSet wk2d;
-    hc::DeviceBuffer<double> d_wk2d_io;
 };

@@ -35,7 +35,7 @@ struct MorArgs {
     int finite_depth;  // 0: water depth +inf
     double* item;      // [n_items][6] (F, M) of every element
     const double* inc; // [n_items][kMorIncDoubles] of morison2_incr_kernel, with directions [n_items][kMorDirIncDoubles] of
-                       // morison2_dir_incr_kernel (the order-2 instantiations only)
+                       // morison2_incr_kernel<true> (the order-2 instantiations only)
 };
 
 // R = Rx(rpy0) Ry(rpy1) Rz(rpy2), d = R r, p = pos + d (x and z: the wave travels along x): one expression for the kernel that
@@ -70,7 +70,7 @@ __device__ inline MorFrame morison_frame(const double* el, const double* pos, co
 // and added before the wet test and the force; the first-order part, stretching by eta1 included, is the code of order 1.
 // DIR (morison_dir_items_kernel, morison2_dir_items_kernel): the directional sea of wave_kinematics_kernel<true> -- the phase at k (x cos + y sin), the horizontal flow
 // along (cos, sin), so that u_f and a_f have a y component; the long-crested instantiations keep their arithmetic.
-// ORDER2 and DIR: the ten doubles of morison2_dir_incr_kernel, u2y and a2y among them, enter the same places.
+// ORDER2 and DIR: the ten doubles of morison2_incr_kernel<true>, u2y and a2y among them, enter the same places.
 template <bool ORDER2, bool DIR>
 __device__ __forceinline__ void morison_items_body(const MorArgs& a) {
     constexpr int kDc = kKinCols, kDs = kKinCols + 1;  // rows of the direction columns (DIR only)
@@ -221,6 +221,9 @@ __global__ void __launch_bounds__(kMorThreads) morison_items_kernel(MorArgs a) {
 }
 __global__ void __launch_bounds__(kMorThreads) morison_dir_items_kernel(MorArgs a) { morison_items_body<false, true>(a); }
 __global__ void __launch_bounds__(kMorThreads) morison2_dir_items_kernel(MorArgs a) { morison_items_body<true, true>(a); }
+// [order 2][directions set]
+void (*const kMorItems[2][2])(MorArgs) = {{morison_items_kernel<false>, morison_dir_items_kernel},
+                                          {morison_items_kernel<true>, morison2_dir_items_kernel}};
 
 struct Mor2Args {
     Wk2Sea sea;           // the Morison path's own tables (hc_ctx::mor2), mwl of the Morison options
@@ -234,57 +237,44 @@ struct Mor2Args {
     double* inc;          // [n_items][kMorIncDoubles]
 };
 
+// A value every lane of the wave holds, moved to scalar registers (its bits unchanged): the point of morison2_incr_kernel<true>
+// then costs the pair sum no vector register, as the point wk2_sum_kernel loads with scalar loads costs it none
+__device__ __forceinline__ double wave_uniform(double v) {
+    return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
+}
+
 // One workgroup per element of the owned bodies: the point of morison_items_kernel (morison_frame), then the pair sum of
-// hc_wave_kinematics2 at that point and time (wk2_item_sum, with its epilogue): what it stores is what that call returns for the
-// stored point, bit for bit.
+// hc_wave_kinematics2 at that point and time with the epilogue of wk2_sum_kernel: the eight doubles it stores are what that call
+// returns for the stored point, bit for bit.
+// DIR: the short-crested sea -- the point with its y in scalar registers (of the frame only the point stays live across the pair
+// sum), the pair sum of hc_wave_kinematics2_dir, and ten doubles, u2y and a2y among them.
+template <bool DIR>
 __global__ void __launch_bounds__(kWk2Threads) morison2_incr_kernel(Mor2Args a) {
     const int e       = blockIdx.x;  // the grid is n_items
     const int b       = a.body[e];
     const double* pos = a.state + 3 * b;
     const MorFrame f  = morison_frame(a.elem + static_cast<size_t>(kMorElemDoubles) * e, pos, pos + 3 * a.N);
-    const double x = f.x, y = pos[1] + f.d1, z = f.z;
-    double sum[5];
-    wk2_item_sum<true, true>(a.sea, x, z, a.t, sum);
+    double x, y, z;
+    if constexpr (DIR) x = wave_uniform(f.x), y = wave_uniform(f.y), z = wave_uniform(f.z);
+    else x = f.x, y = pos[1] + f.d1, z = f.z;
+    double sum[wk2_sums(DIR)];
+    wk2_sea_sum<DIR, true, true>(a.sea, x, y, z, a.t, sum);
     if (threadIdx.x == 0) {
         const double ramp2 = wk2_ramp2(a.ramped != 0, a.ramp_duration, a.t);
-        double* out = a.inc + static_cast<size_t>(kMorIncDoubles) * e;
+        double* out = a.inc + static_cast<size_t>(DIR ? kMorDirIncDoubles : kMorIncDoubles) * e;
         out[0] = x;
         out[1] = y;
         out[2] = z;
         out[3] = 0.25 * sum[0] * ramp2;
-        out[4] = sum[1] * ramp2;
-        out[5] = sum[2] * ramp2;
-        out[6] = sum[3] * ramp2;
-        out[7] = sum[4] * ramp2;
-    }
-}
-
-// A value every lane of the wave holds, moved to scalar registers (its bits unchanged): the point of morison2_dir_incr_kernel
-// then costs the pair sum no vector register, as the point wk2_dir_sum_kernel loads with scalar loads costs it none
-__device__ __forceinline__ double wave_uniform(double v) {
-    return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
-}
-
-// The same in a short-crested sea: the point with its y, the pair sum of hc_wave_kinematics2_dir (wk2_dir_item_sum) and the
-// epilogue of wk2_dir_sum_kernel, so that the ten doubles stored are what that call returns for the stored point, bit for bit.
-// Of the frame only the point stays live across the pair sum.
-__global__ void __launch_bounds__(kWk2Threads) morison2_dir_incr_kernel(Mor2Args a) {
-    const int e       = blockIdx.x;  // the grid is n_items
-    const int b       = a.body[e];
-    const double* pos = a.state + 3 * b;
-    const MorFrame f  = morison_frame(a.elem + static_cast<size_t>(kMorElemDoubles) * e, pos, pos + 3 * a.N);
-    const double x = wave_uniform(f.x), y = wave_uniform(f.y), z = wave_uniform(f.z);
-    double sum[kWk2DirSums];
-    wk2_dir_item_sum<true, true>(a.sea, x, y, z, a.t, sum);
-    if (threadIdx.x == 0) {
-        const double ramp2 = wk2_ramp2(a.ramped != 0, a.ramp_duration, a.t);
-        double* out = a.inc + static_cast<size_t>(kMorDirIncDoubles) * e;
-        out[0] = x;
-        out[1] = y;
-        out[2] = z;
-        out[3] = 0.25 * sum[0] * ramp2;
+        if constexpr (DIR) {
 #pragma unroll
-        for (int k = 1; k < kWk2DirSums; ++k) out[3 + k] = sum[k] * ramp2;
+            for (int k = 1; k < kWk2DirSums; ++k) out[3 + k] = sum[k] * ramp2;
+        } else {
+            out[4] = sum[1] * ramp2;
+            out[5] = sum[2] * ramp2;
+            out[6] = sum[3] * ramp2;
+            out[7] = sum[4] * ramp2;
+        }
     }
 }
 
@@ -354,7 +344,7 @@ void morison_enqueue(hc_ctx* c, double t, const double* pos, const double* rpy, 
     // the second-order sea: tables of this path's own (with directions: those of the directional pair sum), then the increments of
     // every element
     const bool dir     = c->mor.kin.dir;
-    const bool order2  = dir ? c->mor2.prepare_dir(c, c->mor) : c->mor2.prepare(c, c->mor);
+    const bool order2  = c->mor2.prepare(c, c->mor, dir);
     const int width    = dir ? kMorDirIncDoubles : kMorIncDoubles;
     const size_t n_inc = static_cast<size_t>(width) * a.n_items;
     double* h_inc      = order2 ? c->mor2.stage(n_inc, width) : nullptr;
@@ -372,17 +362,11 @@ void morison_enqueue(hc_ctx* c, double t, const double* pos, const double* rpy, 
         m.ramped        = c->mor2.ramped(c);
         m.ramp_duration = c->irr.ramp_duration;
         m.inc           = c->mor2.d_inc.p;
-        if (dir) hipLaunchKernelGGL(morison2_dir_incr_kernel, dim3(a.n_items), dim3(kWk2Threads), 0, st, m);
-        else hipLaunchKernelGGL(morison2_incr_kernel, dim3(a.n_items), dim3(kWk2Threads), 0, st, m);
+        hipLaunchKernelGGL(dir ? morison2_incr_kernel<true> : morison2_incr_kernel<false>, dim3(a.n_items), dim3(kWk2Threads), 0, st, m);
         HC_HIP(hipGetLastError());
         HC_HIP(hipMemcpyAsync(h_inc, c->mor2.d_inc.p, n_inc * sizeof(double), hipMemcpyDeviceToHost, st));
-        if (dir) hipLaunchKernelGGL(morison2_dir_items_kernel, item_grid, dim3(kMorThreads), 0, st, a);
-        else hipLaunchKernelGGL(morison_items_kernel<true>, item_grid, dim3(kMorThreads), 0, st, a);
-    } else if (dir) {
-        hipLaunchKernelGGL(morison_dir_items_kernel, item_grid, dim3(kMorThreads), 0, st, a);
-    } else {
-        hipLaunchKernelGGL(morison_items_kernel<false>, item_grid, dim3(kMorThreads), 0, st, a);
     }
+    hipLaunchKernelGGL(kMorItems[order2][dir], item_grid, dim3(kMorThreads), 0, st, a);
     HC_HIP(hipGetLastError());
     hipLaunchKernelGGL(morison_sum_kernel, dim3((c->Dloc + kMorThreads - 1) / kMorThreads), dim3(kMorThreads), 0, st, d.item.p, d.off.p,
                        c->Dloc, d.out.p);

@@ -41,7 +41,7 @@ struct NlArgs {
     int stretch;       // Wheeler stretching
     int finite_depth;  // 0: water depth +inf
     double* part;      // [chunks][12] per-chunk sums
-    // the order-2 kernels only: the increments of nl2_incr_kernel or nl2_dir_incr_kernel, [points][kNlIncDoubles], and the surface point of every panel
+    // the order-2 kernels only: the increments of nl2_incr_kernel<DIR>, [points][kNlIncDoubles], and the surface point of every panel
     // ([panels]) or triangle vertex ([triangles][3]) in it
     const double* inc;
     const int* pidx;
@@ -82,7 +82,7 @@ __device__ __forceinline__ void nl_rotate(const NlFrame& f, const double* c, dou
 // DIR (nl_panels_dir_kernel, nl2_dir_panels_kernel): the directional sea of wave_kinematics_kernel<true> -- cos and sin of every
 // component's direction staged behind the other columns, the phase at k (x cos + y sin); the pressure is a scalar, so nothing else
 // changes at order 1.  ORDER2 and DIR: the horizontal part of u1 lies along every component's direction, so |u1|^2 gains u1y^2; the
-// increments are those of nl2_dir_incr_kernel.
+// increments are those of nl2_incr_kernel<true>.
 template <bool ORDER2, bool DIR = false>
 __device__ __forceinline__ void nl_panels_body(const NlArgs& a) {
     constexpr int kDc = kNlCols, kDs = kNlCols + 1;  // rows of the direction columns (DIR only)
@@ -290,7 +290,7 @@ __device__ __forceinline__ void nl_sub_triangle(const NlVertex& q0, const NlVert
 // ORDER2 (nl2_tris_kernel): as in the panel kernel -- u1 of every vertex in the component loop, the vertices' increments after it,
 // eta2 into h and rho q2 - 1/2 rho ramp^2 |u1|^2 into p_d before the case table, which is the one of order 1.
 // DIR (nl_tris_dir_kernel, nl2_dir_tris_kernel): as in the panel kernel -- every vertex's phase at k (x cos + y sin), eta at the
-// vertices where the triangle is clipped included; with ORDER2 u1y of every vertex and the increments of nl2_dir_incr_kernel.
+// vertices where the triangle is clipped included; with ORDER2 u1y of every vertex and the increments of nl2_incr_kernel<true>.
 template <bool ORDER2, bool DIR = false>
 __device__ __forceinline__ void nl_tris_body(const NlArgs& a) {
     constexpr int kDc = kNlCols, kDs = kNlCols + 1;  // rows of the direction columns (DIR only)
@@ -503,6 +503,9 @@ __global__ void __launch_bounds__(kNlThreads) nl_tris_kernel(NlArgs a) { nl_tris
 __global__ void __launch_bounds__(kNlThreads) nl2_tris_kernel(NlArgs a) { nl_tris_body<true>(a); }
 __global__ void __launch_bounds__(kNlThreads) nl_tris_dir_kernel(NlArgs a) { nl_tris_body<false, true>(a); }
 __global__ void __launch_bounds__(kNlThreads) nl2_dir_tris_kernel(NlArgs a) { nl_tris_body<true, true>(a); }
+// [order 2][directions set][triangles]
+void (*const kNlItems[2][2][2])(NlArgs) = {{{nl_panels_kernel, nl_tris_kernel}, {nl_panels_dir_kernel, nl_tris_dir_kernel}},
+                                           {{nl2_panels_kernel, nl2_tris_kernel}, {nl2_dir_panels_kernel, nl2_dir_tris_kernel}}};
 
 struct Nl2Args {
     Wk2Sea sea;           // the nonlinear path's own tables (hc_ctx::nl2), mwl of the nonlinear options
@@ -517,8 +520,10 @@ struct Nl2Args {
 };
 
 // One workgroup per distinct surface point of the owned bodies: the point of the item kernels (nl_frame, nl_rotate), then the pair
-// sum of hc_wave_kinematics2 at that point and time with its epilogue (1/4 on eta2, ramp^2) -- eta2 is what that call returns for the
-// stored point, bit for bit -- and q2 = -d phi2 / dt from the same pairs.  No velocity or acceleration is computed.
+// sum of hc_wave_kinematics2 -- DIR: of hc_wave_kinematics2_dir, which reads the point's y -- at that point and time with the
+// epilogue of wk2_sum_kernel (1/4 on eta2, ramp^2): eta2 is what that call returns for the stored point, bit for bit, and
+// q2 = -d phi2 / dt comes from the same pairs, behind the sea's other sums.  No velocity or acceleration is computed.
+template <bool DIR>
 __global__ void __launch_bounds__(kWk2Threads) nl2_incr_kernel(Nl2Args a) {
     const int e       = blockIdx.x;  // the grid is the number of points
     const double* pos = a.state + 3 * a.body[e];
@@ -526,8 +531,8 @@ __global__ void __launch_bounds__(kWk2Threads) nl2_incr_kernel(Nl2Args a) {
     double d0, d1, d2;
     nl_rotate(f, a.point + 3 * static_cast<size_t>(e), d0, d1, d2);
     const double x = pos[0] + d0, y = pos[1] + d1, z = pos[2] + d2;
-    double sum[6];
-    wk2_item_sum<true, false, true>(a.sea, x, z, a.t, sum);
+    double sum[wk2_sums(DIR) + 1];
+    wk2_sea_sum<DIR, true, false, true>(a.sea, x, y, z, a.t, sum);
     if (threadIdx.x == 0) {
         const double ramp2 = wk2_ramp2(a.ramped != 0, a.ramp_duration, a.t);
         double* out = a.inc + static_cast<size_t>(kNlIncDoubles) * e;
@@ -535,29 +540,7 @@ __global__ void __launch_bounds__(kWk2Threads) nl2_incr_kernel(Nl2Args a) {
         out[1] = y;
         out[2] = z;
         out[3] = 0.25 * sum[0] * ramp2;
-        out[4] = sum[5] * ramp2;
-    }
-}
-
-// The same in a short-crested sea: the point with its y, the pair sum of hc_wave_kinematics2_dir (wk2_dir_item_sum) with the q2
-// accumulator and the epilogue of wk2_dir_sum_kernel -- eta2 is what that call returns for the stored point, bit for bit.
-__global__ void __launch_bounds__(kWk2Threads) nl2_dir_incr_kernel(Nl2Args a) {
-    const int e       = blockIdx.x;  // the grid is the number of points
-    const double* pos = a.state + 3 * a.body[e];
-    const NlFrame f   = nl_frame(pos + 3 * a.N);
-    double d0, d1, d2;
-    nl_rotate(f, a.point + 3 * static_cast<size_t>(e), d0, d1, d2);
-    const double x = pos[0] + d0, y = pos[1] + d1, z = pos[2] + d2;
-    double sum[kWk2DirSums + 1];
-    wk2_dir_item_sum<true, false, true>(a.sea, x, y, z, a.t, sum);
-    if (threadIdx.x == 0) {
-        const double ramp2 = wk2_ramp2(a.ramped != 0, a.ramp_duration, a.t);
-        double* out = a.inc + static_cast<size_t>(kNlIncDoubles) * e;
-        out[0] = x;
-        out[1] = y;
-        out[2] = z;
-        out[3] = 0.25 * sum[0] * ramp2;
-        out[4] = sum[kWk2DirSums] * ramp2;
+        out[4] = sum[wk2_sums(DIR)] * ramp2;
     }
 }
 
@@ -689,7 +672,7 @@ void nonlinear_enqueue(hc_ctx* c, double t) {
     // the second-order sea: tables of this path's own (with directions: those of the directional pair sum), then the increments of
     // every surface point
     const bool dir    = c->nl.kin.dir;
-    const bool order2 = dir ? c->nl2.prepare_dir(c, c->nl) : c->nl2.prepare(c, c->nl);
+    const bool order2 = c->nl2.prepare(c, c->nl, dir);
     HC_HIP(hipMemcpyAsync(d.state.p, d.h_state.p, 2 * n3 * sizeof(double), hipMemcpyHostToDevice, st));
     if (order2) {
         if (d.pts_dirty) upload_points(c);
@@ -706,8 +689,7 @@ void nonlinear_enqueue(hc_ctx* c, double t) {
         m.ramped        = c->nl2.ramped(c);
         m.ramp_duration = c->irr.ramp_duration;
         m.inc           = c->nl2.d_inc.p;
-        if (dir) hipLaunchKernelGGL(nl2_dir_incr_kernel, dim3(points), dim3(kWk2Threads), 0, st, m);
-        else hipLaunchKernelGGL(nl2_incr_kernel, dim3(points), dim3(kWk2Threads), 0, st, m);
+        hipLaunchKernelGGL(dir ? nl2_incr_kernel<true> : nl2_incr_kernel<false>, dim3(points), dim3(kWk2Threads), 0, st, m);
         HC_HIP(hipGetLastError());
         HC_HIP(hipMemcpyAsync(h_inc, c->nl2.d_inc.p, n_inc * sizeof(double), hipMemcpyDeviceToHost, st));
         a.inc = c->nl2.d_inc.p;
@@ -719,22 +701,7 @@ void nonlinear_enqueue(hc_ctx* c, double t) {
         ar.chunk  = d.chunk.p + 3 * static_cast<size_t>(chunk0);
         ar.part   = d.part.p + static_cast<size_t>(kNlOut) * chunk0;
         ar.pidx   = kind ? d.tidx.p : d.pidx.p;  // (indexed by the item, as the list)
-        if (order2 && dir && kind)
-            hipLaunchKernelGGL(nl2_dir_tris_kernel, dim3(chunks), dim3(kNlThreads), 0, st, ar);
-        else if (order2 && dir)
-            hipLaunchKernelGGL(nl2_dir_panels_kernel, dim3(chunks), dim3(kNlThreads), 0, st, ar);
-        else if (order2 && kind)
-            hipLaunchKernelGGL(nl2_tris_kernel, dim3(chunks), dim3(kNlThreads), 0, st, ar);
-        else if (order2)
-            hipLaunchKernelGGL(nl2_panels_kernel, dim3(chunks), dim3(kNlThreads), 0, st, ar);
-        else if (c->nl.kin.dir && kind)
-            hipLaunchKernelGGL(nl_tris_dir_kernel, dim3(chunks), dim3(kNlThreads), 0, st, ar);
-        else if (c->nl.kin.dir)
-            hipLaunchKernelGGL(nl_panels_dir_kernel, dim3(chunks), dim3(kNlThreads), 0, st, ar);
-        else if (kind)
-            hipLaunchKernelGGL(nl_tris_kernel, dim3(chunks), dim3(kNlThreads), 0, st, ar);
-        else
-            hipLaunchKernelGGL(nl_panels_kernel, dim3(chunks), dim3(kNlThreads), 0, st, ar);
+        hipLaunchKernelGGL(kNlItems[order2][dir][kind != 0], dim3(chunks), dim3(kNlThreads), 0, st, ar);
         HC_HIP(hipGetLastError());
     }
     hipLaunchKernelGGL(nl_sum_kernel, dim3((rows + kNlThreads - 1) / kNlThreads), dim3(kNlThreads), 0, st, d.part.p, d.off.p, rows, d.out.p);

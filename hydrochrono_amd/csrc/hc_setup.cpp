@@ -169,8 +169,8 @@ void hc_destroy(hc_ctx* ctx) {
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     if (ctx->stream_am) (void)hipStreamDestroy(ctx->stream_am);
     for (hc::SideLane* lane : {&ctx->mor, &ctx->nl, &ctx->drift.lane, &ctx->sum.lane}) lane->close();
-    if (ctx->stream_wk2) (void)hipStreamDestroy(ctx->stream_wk2);
-    if (ctx->stream_wk2d) (void)hipStreamDestroy(ctx->stream_wk2d);
+    for (hc::Wk2Call& w : ctx->wk2)
+        if (w.stream) (void)hipStreamDestroy(w.stream);
     if (ctx->ev_fin) (void)hipEventDestroy(ctx->ev_fin);
     if (ctx->ev_bg) (void)hipEventDestroy(ctx->ev_bg);
     delete ctx;

@@ -77,7 +77,7 @@ struct SideLane {
 };
 
 // The second-order sea of a path (hc_set_morison_second_order, hc_set_nonlinear_second_order): tables of its own, built on the
-// lane's stream (a hc_wave_kinematics2 call with other cut-offs may rebuild `wk2` while a launch of the path is in flight), and the
+// lane's stream (a hc_wave_kinematics2 call with other cut-offs may rebuild its `wk2[]` set while a launch of the path is in flight), and the
 // increments at the path's points with their two host copies: of the evaluation in flight and of the last completed one.
 struct Order2Part {
     bool on = false;
@@ -120,11 +120,10 @@ struct Order2Part {
         d_inc.release();
         done.clear();
     }
-    // The tables for the lane's regular phase, built on its stream; whether order 2 applies to this evaluation.  No components
-    // (NoWave, no model, an imported eta record) or no pair inside either band: order 1, no further launch.
-    bool prepare(hc_ctx* c, const SideLane& lane);  // hc_wave_kin2.hip
-    // ... in the directional sea: the tables of wk2_dir_tables in `tabs`
-    bool prepare_dir(hc_ctx* c, const SideLane& lane);  // hc_wave_kin2_dir.hip
+    // The tables for the lane's regular phase (wk2_tables; `dir`: in the layout of the short-crested sea), built on its stream;
+    // whether order 2 applies to this evaluation.  No components (NoWave, no model, an imported eta record) or no pair inside either
+    // band: order 1, no further launch.
+    bool prepare(hc_ctx* c, const SideLane& lane, bool dir);  // hc_wave_kin2.hip
     Wk2Sea sea(const hc_ctx* c, double mwl) const;  // hc_wave_kin2.hip
     int ramped(const hc_ctx* c) const;              // hc_wave_kin2.hip: the switch only (wk2_ramp2)
     // the host copy the evaluation in flight writes, for n doubles, `width` per point (the device increments grow with it)

@@ -1,5 +1,5 @@
 // hc_wave_kin2_dir.hpp -- the pair sum of the second-order wave kinematics in a short-crested sea as a device function, and the
-// angle and wave-number forms its pair kernel shares (hc_wave_kin2_dir.hip: wk2_dir_pair_kernel, wk2_dir_sum_kernel).  HIP only.
+// angle and wave-number forms the pair kernel shares (hc_wave_kin2.hip: wk2_pair_kernel<true>, wk2_sum_kernel<true, ...>).  HIP only.
 // DESIGN.md 3.7n has the definition and the invariants; the long-crested sum is hc_wave_kin2_sum.hpp, which this leaves alone.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -179,11 +179,16 @@ __device__ inline void wk2_dir_item_sum(const Wk2Sea& a, double x, double y, dou
     for (int k = 0; k < kR; ++k) out[k] = tid == 0 ? red[k][0] : 0.0;
 }
 
-// ---- hc_wave_kin2_dir.hip: the host side the users share (hc_wave_kinematics2_dir; hc_morison.hip and hc_nonlinear.hip through Order2Part::prepare_dir) ----
-// The component table with the direction columns behind it ((1, 0) with no directions set), the pair tables (wk2_dir_pair_kernel)
-// and the band limits of the context's wave model in `s`, built on `st` and complete when the call returns.  Rebuilt as wk2_tables
-// rebuilds its own, and when `s` holds a long-crested set (Wk2TableSet::dir).  With no pair inside either band the pair tables hold
-// zeros, or -- keep_empty false: nobody reads them -- are released and no kernel is launched.
-void wk2_dir_tables(hc_ctx* c, Wk2TableSet& s, hipStream_t st, const hc_wave_kinematics2_opts& o, bool keep_empty);
+// The pair sum of either sea behind one name, for the kernels that exist once per sea (wk2_sum_kernel, morison2_incr_kernel,
+// nl2_incr_kernel): wk2_item_sum, which has no y, or wk2_dir_item_sum.  The two stay two functions -- their arithmetic differs on
+// purpose -- and each keeps its own bits.  out: wk2_sums(DIR) values, and q2 behind them with Q2.
+constexpr int wk2_sums(bool dir) { return dir ? kWk2DirSums : 5; }
+
+template <bool DIR, bool ETA, bool KIN, bool Q2 = false>
+__device__ __forceinline__ void wk2_sea_sum(const Wk2Sea& a, double x, double y, double z, double t,
+                                            double (&out)[wk2_sums(DIR) + (Q2 ? 1 : 0)]) {
+    if constexpr (DIR) wk2_dir_item_sum<ETA, KIN, Q2>(a, x, y, z, t, out);
+    else wk2_item_sum<ETA, KIN, Q2>(a, x, z, t, out);
+}
 
 }  // namespace hc

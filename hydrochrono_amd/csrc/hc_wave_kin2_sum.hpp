@@ -1,6 +1,7 @@
 // hc_wave_kin2_sum.hpp -- the pair sum of the second-order wave kinematics as a device function, shared by the kernels that run it
-// (hc_wave_kin2.hip: wk2_sum_kernel; hc_morison.hip: morison2_incr_kernel; hc_nonlinear.hip: nl2_incr_kernel), and the host calls
-// that build the tables it reads.  HIP only.  DESIGN.md 3.7f has the definition and the invariants, 3.7g and 3.7h the other users.
+// (hc_wave_kin2.hip: wk2_sum_kernel; hc_morison.hip: morison2_incr_kernel; hc_nonlinear.hip: nl2_incr_kernel -- their <false>
+// instantiations; the short-crested sea's sum is hc_wave_kin2_dir.hpp), and the host calls that build the tables of either sea.
+// HIP only.  DESIGN.md 3.7f has the definition and the invariants, 3.7g and 3.7h the other users.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -181,12 +182,15 @@ __device__ inline void wk2_item_sum(const Wk2Sea& a, double x, double z, double 
     for (int k = 0; k < kR; ++k) out[k] = tid == 0 ? red[k][0] : 0.0;
 }
 
-// ---- hc_wave_kin2.hip: the host side both users share ----
+// ---- hc_wave_kin2.hip: the host side all users share (the four calls; hc_morison.hip and hc_nonlinear.hip through Order2Part) ----
 int wk2_component_count(const hc_ctx* c);
-// The component table, the pair tables and the band limits of the context's wave model in `s`, built on `st` (wk2_pair_kernel) and
-// complete when the call returns.  Rebuilt when a hc_set_wave_* call has come in since (wave_serial), the regular wave's phase or a
-// cut-off differs from the cached one.  With no pair inside either band the pair tables hold zeros, or -- keep_empty false: nobody
-// reads them -- are released.
-void wk2_tables(hc_ctx* c, Wk2TableSet& s, hipStream_t st, double regular_phase, const double cut[4], bool keep_empty);
+// The component table, the pair tables and the band limits of the context's wave model in `s`, built on `st` (wk2_pair_kernel<dir>)
+// and complete when the call returns.  `dir`: the layout of the short-crested sea -- the direction columns behind the component
+// table ((1, 0) with no directions set) and the angles in the pair tables.  Rebuilt when a hc_set_wave_* call has come in since
+// (wave_serial; a direction change counts), the regular wave's phase or a cut-off differs from the cached one, or `s` holds the
+// other layout (Wk2TableSet::dir).  The mark goes first and the stamp last: a failure on the way leaves nothing that counts as
+// current.  With no pair inside either band the pair tables hold zeros, or -- keep_empty false: nobody reads them -- are released
+// and no kernel is launched.
+void wk2_tables(hc_ctx* c, Wk2TableSet& s, hipStream_t st, double regular_phase, const double cut[4], bool keep_empty, bool dir);
 
 }  // namespace hc

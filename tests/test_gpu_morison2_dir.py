@@ -1,5 +1,5 @@
 """Morison elements on the second-order sea in a short-crested sea on the GPU (hc_set_morison_second_order_directional;
-csrc/hc_morison.hip: morison2_dir_incr_kernel and morison2_dir_items_kernel) against the tests' NumPy restatement
+csrc/hc_morison.hip: morison2_incr_kernel<true> and morison2_dir_items_kernel) against the tests' NumPy restatement
 (tests/morison2_dir_ref.py), fed the context's own spectrum and directions, on the input sets of tests/morison2_dir_inputs.py.
 
 Tolerance: the bound morison2_dir_ref returns per body and component -- that of tests/test_gpu_morison2.py with the directional

@@ -1,5 +1,5 @@
 """The nonlinear surface forces on the second-order sea in a short-crested sea on the GPU (hc_set_nonlinear_second_order_directional;
-csrc/hc_nonlinear.hip: nl2_dir_incr_kernel, nl2_dir_panels_kernel, nl2_dir_tris_kernel) against the tests' NumPy restatement
+csrc/hc_nonlinear.hip: nl2_incr_kernel<true>, nl2_dir_panels_kernel, nl2_dir_tris_kernel) against the tests' NumPy restatement
 (tests/nonlinear2_dir_ref.py), fed the context's own spectrum and directions, on the input sets of tests/nonlinear2_dir_inputs.py.
 
 Tolerance: the bound nonlinear2_dir_ref returns per body and component -- that of tests/test_gpu_nonlinear2.py with the directional

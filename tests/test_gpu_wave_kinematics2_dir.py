@@ -400,3 +400,81 @@ def test_the_long_crested_call_still_refuses_under_directions(HF):
         with pytest.raises(HydroError) as e:
             call()
         assert e.value.status == capi.HC_ERR_UNSUPPORTED and "direction" in str(e.value)
+
+
+# ------------------------------------------------------------------------------------------------
+# 10: the two calls and the Morison path share one table builder: every cached set follows its own key
+# ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("nf", [3, 257])  # 257: one component past a 256-wide tile -- both tile loops and the skipped tile pair run
+def test_interleaved_calls_give_the_bits_of_a_fresh_handle(HF, nf):
+    """One handle walks through hc_wave_kinematics2, hc_wave_kinematics2_dir and the two pair-table calls in turn, under different
+    cut-offs and regular phases, without directions and then with them; a Morison path beside them evaluates while directions are
+    set and cleared, so that its tables change layout every time.  Whatever the handle's sets held before, every result has the
+    bits of a fresh handle that makes that one call."""
+    import morison2_inputs as mi
+    case = sphere_case()
+    waves = wi.sphere_waves(nf, 0.07, 0.11) if nf == 3 else wi.sphere_waves(nf)
+    beta = di.spread(nf)
+    elements = mi.random_elements(3, 5, spread=4.0)
+    pts = np.array([[-40.0, 0.0, -2.0], [25.0, 7.5, 0.5], [60.0, -11.0, -30.0]])
+    times = np.array([7.3, 41.7])  # inside the ramp of 20 s and after it
+
+    def make(directions):
+        h = HF.from_case(case)
+        spread_sea(h, case, waves)
+        if directions:
+            h.set_wave_directions(beta)
+        h.set_morison_elements(0, *elements)
+        h.set_morison_options(mwl=0.1)
+        h.set_morison_second_order_directional(True)
+        return h
+
+    h = make(False)
+    w = comp_of(h)[1]
+    assert w.size == nf and np.all(np.diff(w) > 0)
+    full = dict(diff_band=w2.FULL, sum_band=w2.FULL)
+    cut = dict(diff_band=(0.0, 0.6 * (w[-1] - w[0])), sum_band=(2.0 * w[0], w[0] + w[-1]))  # both cut through the matrix
+    diag = dict(diff_band=(0.0, 0.0), sum_band=wi.NO_PAIR)  # the diagonal alone: no row of the first tile reaches the second
+    fields = lambda directional, phase, bands: (lambda x: x.wave_kinematics2(pts, times, mwl=0.2, regular_phase=phase,
+                                                                            directional=directional, **bands))
+    tables = lambda directional, phase, bands: (lambda x: tuple(x.wave_pair_tables(regular_phase=phase, directional=directional,
+                                                                                  **bands).values()))
+
+    def morison(bands):
+        def call(x):
+            x.set_morison_second_order(True, **bands)
+            out = [x.compute_morison(t, *mi.moving_state(1, -2.0, t)) for t in times]
+            inc = x.morison_increments(0)
+            return out + [inc["p"], inc["eta2"], inc["vel2"], inc["acc2"]]
+        return call
+
+    fresh = {}
+    seen = []
+
+    def check(directions, what, call):
+        if (directions, what) not in fresh:
+            f = make(directions)
+            fresh[directions, what] = call(f)
+            f.close()
+        got, ref = call(h), fresh[directions, what]
+        assert len(got) == len(ref) and same_bits(got, ref), (nf, directions, what, len(seen))
+        seen.append(got)
+
+    walk = [("lc full", fields(False, 0.0, full)), ("dir cut", fields(True, 0.4, cut)), ("lc tables cut", tables(False, 0.0, cut)),
+            ("morison cut", morison(cut)), ("dir tables diag", tables(True, 0.4, diag)), ("lc full", fields(False, 0.0, full)),
+            ("dir diag", fields(True, 0.4, diag)), ("lc diag", fields(False, 0.7, diag)), ("dir cut", fields(True, 0.4, cut)),
+            ("lc tables cut", tables(False, 0.0, cut)), ("dir tables full", tables(True, 0.0, full)), ("dir full", fields(True, 0.0, full))]
+    for what, call in walk:
+        check(False, what, call)
+    assert all(a.any() for a in seen[0]) and all(a.any() for a in seen[1]) and seen[3][3].any()
+    for rounds in range(2):  # the Morison tables alternate between the two layouts; the directional call's follow the directions
+        h.set_wave_directions(beta)
+        for what, call in walk:
+            if what.startswith(("dir", "morison")):
+                check(True, what, call)
+        assert seen[-1][1][..., 1].any()  # u2y is there
+        h.set_wave_directions(None)
+        for what, call in (walk[3], walk[0], walk[1], walk[2]):
+            check(False, what, call)
+        assert not seen[-4][4][:, 1].any()  # the long-crested increments of the elements again: no u2y
+    h.close()

@@ -137,7 +137,7 @@ def test_new_kernels_build_without_scratch_or_spills(tmp_path):
     notes = {m.group(2): (int(m.group(3)), int(m.group(4)), int(m.group(5)), int(m.group(1))) for m in re.finditer(
         r"\.group_segment_fixed_size:\s+(\d+).*?\.name:\s+(\S+).*?\.private_segment_fixed_size:\s+(\d+).*?\.vgpr_count:\s+(\d+)"
         r".*?\.vgpr_spill_count:\s+(\d+)", txt, re.S)}
-    incr = [n for n in notes if "morison2_dir_incr_kernel" in n]
+    incr = [n for n in notes if "morison2_incr_kernelILb1E" in n]  # the directional instantiation
     items = [n for n in notes if "morison2_dir_items_kernel" in n]
     assert len(incr) == 1 and len(items) == 1, sorted(notes)
     for name in incr + items:

@@ -103,7 +103,7 @@ def test_new_kernels_build_without_scratch_or_spills(tmp_path):
     txt = subprocess.run([readelf, "--notes", co], capture_output=True, text=True, check=True).stdout
     notes = {m.group(1): (int(m.group(2)), int(m.group(3)), int(m.group(4))) for m in re.finditer(
         r"\.name:\s+(\S+).*?\.private_segment_fixed_size:\s+(\d+).*?\.vgpr_count:\s+(\d+).*?\.vgpr_spill_count:\s+(\d+)", txt, re.S)}
-    incr = [n for n in notes if "morison2_incr_kernel" in n]
+    incr = [n for n in notes if "morison2_incr_kernelILb0E" in n]  # the long-crested instantiation
     items = [n for n in notes if "morison_items_kernel" in n]
     assert len(incr) == 1 and len(items) == 2, sorted(notes)  # the increments, and the item kernel of order 1 and of order 2
     for name in incr + items:

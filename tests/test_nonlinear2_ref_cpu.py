@@ -162,7 +162,7 @@ def test_new_kernels_build_without_scratch_or_spills(tmp_path):
     notes = {m.group(2): (int(m.group(1)), int(m.group(3)), int(m.group(4)), int(m.group(5))) for m in re.finditer(
         r"\.group_segment_fixed_size:\s+(\d+).*?\.name:\s+(\S+).*?\.private_segment_fixed_size:\s+(\d+).*?\.vgpr_count:\s+(\d+).*?\.vgpr_spill_count:\s+(\d+)",
         txt, re.S)}
-    for kernel in ("nl2_incr_kernel", "nl2_panels_kernel", "nl2_tris_kernel", "nl_panels_kernel", "nl_tris_kernel"):
+    for kernel in ("nl2_incr_kernelILb0E", "nl2_panels_kernel","nl2_tris_kernel", "nl_panels_kernel", "nl_tris_kernel"):
         found = [v for n, v in notes.items() if kernel in n]
         assert len(found) == 1, (kernel, sorted(notes))
         lds, scratch, vgpr, spills = found[0]

@@ -181,20 +181,22 @@ def test_kernels_build_without_scratch_or_spills(tmp_path):
     readelf = "/opt/rocm/lib/llvm/bin/llvm-readelf"
     assert os.path.exists(readelf), "llvm-readelf not found"
     from hydrochrono_amd import build as hb
-    co = str(tmp_path / "hc_wave_kin2_dir.co")
+    # the directional kernels are the <true, ...> instantiations of csrc/hc_wave_kin2.hip (ILb1E in the symbol)
+    co = str(tmp_path / "hc_wave_kin2.co")
     subprocess.run([hb._hipcc(), "--offload-arch=gfx950", "-O3", "-std=c++17", "--genco", "--no-gpu-bundle-output", "-Wno-unused-result",
-                    "-I", os.path.join(ROOT, "include"), os.path.join(hb.CSRC, "hc_wave_kin2_dir.hip"), "-o", co], check=True)
+                    "-I", os.path.join(ROOT, "include"), os.path.join(hb.CSRC, "hc_wave_kin2.hip"), "-o", co], check=True)
     txt = subprocess.run([readelf, "--notes", co], capture_output=True, text=True, check=True).stdout
     notes = {m.group(2): (int(m.group(3)), int(m.group(4)), int(m.group(5)), int(m.group(1))) for m in re.finditer(
         r"\.group_segment_fixed_size:\s+(\d+).*?\.name:\s+(\S+).*?\.private_segment_fixed_size:\s+(\d+).*?\.vgpr_count:\s+(\d+)"
         r".*?\.vgpr_spill_count:\s+(\d+)", txt, re.S)}
-    assert sum("wk2_dir_pair_kernel" in n for n in notes) == 1 and sum("wk2_dir_sum_kernel" in n for n in notes) == 3, sorted(notes)
+    notes = {n: v for n, v in notes.items() if "wk2_pair_kernelILb1E" in n or "wk2_sum_kernelILb1E" in n}
+    assert sum("wk2_pair_kernel" in n for n in notes) == 1 and sum("wk2_sum_kernel" in n for n in notes) == 3, sorted(notes)
     for name, (scratch, vgpr, spills, lds) in sorted(notes.items()):
         print(f"{name}: {vgpr} VGPRs, {lds} B LDS, {scratch} B scratch, {spills} spills")
         assert scratch == 0 and spills == 0, (name, scratch, spills)
         assert lds <= 160 * 1024 // 3, (name, lds)  # three workgroups per CU
         assert vgpr <= 512 // 3, (name, vgpr)       # and the registers of a SIMD hold as many of its waves
-    assert "hc_wave_kin2_dir.hip" in hb.SOURCES and "hc_wave_kin2_dir.hpp" in hb.HEADERS
+    assert "hc_wave_kin2.hip" in hb.SOURCES and "hc_wave_kin2_dir.hpp" in hb.HEADERS
 
 
 def test_abi_declares_the_entry_points():
