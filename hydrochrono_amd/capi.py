@@ -54,6 +54,12 @@ class SurfacePanel(C.Structure):
     _fields_ = [("c", C.c_double * 3), ("s", C.c_double * 3)]
 
 
+class RadiationMode(C.Structure):
+    """hc_radiation_mode: row 0..5 of the body, column 0..D-1, complex pole and residue."""
+    _fields_ = [("row", C.c_int), ("col", C.c_int), ("lambda_re", C.c_double), ("lambda_im", C.c_double),
+                ("rho_re", C.c_double), ("rho_im", C.c_double)]
+
+
 class ProfileStats(C.Structure):
     _fields_ = [("hydrostatics_seconds", C.c_double), ("radiation_seconds", C.c_double), ("waves_seconds", C.c_double),
                 ("hydrostatics_calls", C.c_int), ("radiation_calls", C.c_int), ("waves_calls", C.c_int),
@@ -227,6 +233,14 @@ SIGNATURES = {
     "hc_wave_kinematics2_dir": (C.c_int, [C.c_void_p, C.POINTER(WaveKinematics2Opts), C.c_int, c_double_p, C.c_int, c_double_p,
                                           c_double_p, c_double_p, c_double_p]),
     "hc_wave_kinematics2_dir_pair_tables": (C.c_int, [C.c_void_p, C.POINTER(WaveKinematics2Opts), c_double_p, c_double_p, c_double_p, c_double_p]),
+    "hc_set_radiation_modes": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(RadiationMode), C.c_int]),
+    "hc_get_radiation_mode_count": (C.c_int, [C.c_void_p, C.c_int, c_int_p]),
+    "hc_set_radiation_modes_depth": (C.c_int, [C.c_void_p, C.c_int]),
+    "hc_radiation_modes_begin": (C.c_int, [C.c_void_p, C.c_double, c_double_p, c_double_p]),
+    "hc_radiation_modes_end": (C.c_int, [C.c_void_p, c_double_p]),
+    "hc_compute_radiation_modes": (C.c_int, [C.c_void_p, C.c_double, c_double_p, c_double_p, c_double_p]),
+    "hc_reset_radiation_modes": (C.c_int, [C.c_void_p]),
+    "hc_get_radiation_modes_irf": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_double_p, c_double_p]),
     "hc_synth_fill": (C.c_int, [C.c_void_p, C.c_ulonglong, C.c_int, C.c_double, C.c_int, C.c_double]),
 }
 

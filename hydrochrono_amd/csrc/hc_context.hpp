@@ -127,6 +127,7 @@ struct Wk2Call {
 
 }  // namespace hc
 
+#include "hc_modal_ring.hpp"
 #include "hc_side.hpp"  // KinTableCopy, SideLane, Order2Part: made of the types above
 
 namespace hc {
@@ -189,6 +190,19 @@ struct SurfaceData {
     DeviceBuffer<double> pt;          // [points][3]
     DeviceBuffer<int> pbody;          // [points] body of a point
     DeviceBuffer<int> pidx, tidx;     // [panels], [triangles][3]: index into the points, following `panel` / `tri`
+};
+
+// Radiation modes (hc_set_radiation_modes, hc_radiation_modes.hip): the lists of all bodies of the system on the host, those of the
+// owned bodies row-major on the device in structure-of-arrays form with the modal state z and the velocities v of every snapshot
+// slot (hc_modal_ring.hpp), and the pinned staging
+struct RadiationModesData {
+    std::vector<std::vector<hc_radiation_mode>> modes;  // [N]
+    ModalRing ring;
+    int items = 0;                  // modes of the owned bodies
+    DeviceBuffer<int> col, off;     // [items] column of a mode, [Dloc + 1] first mode of an owned row
+    DeviceBuffer<double> lam, res;  // [items][2] pole, residue times rho
+    DeviceBuffer<double> z, v, out; // [depth][items][2], [depth][D], [Dloc]
+    PinnedBuffer<double> h_v, h_out;
 };
 
 struct BodyHost {
@@ -375,6 +389,11 @@ struct hc_ctx {
 
     // Wave drift forces (hc_set_drift_qtf) and sum-frequency wave forces (hc_set_sum_qtf): hc_qtf.hip
     hc::QtfTerm drift, sum;
+
+    // State-space radiation by modal recursion (hc_set_radiation_modes, hc_radiation_modes.hip): a lane of its own
+    // (of it the stream and the begin / end protocol are used: the term reads no wave table), the lists and the snapshot ring
+    hc::SideLane radm;
+    hc::RadiationModesData radmodes;
 
     // Second-order wave kinematics (hc_wave_kin2.hip), nothing a step uses: [0] hc_wave_kinematics2, [1] hc_wave_kinematics2_dir,
     // whose component table carries the two direction columns behind it.  Two instances: the calls keep independent caches and

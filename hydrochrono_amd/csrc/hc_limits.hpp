@@ -45,6 +45,7 @@ constexpr int kDriftMaxFreq = 256;  // frequencies of a body's drift QTF grid (h
 constexpr int kQtfMaxHeadings = 16;  // headings of a QTF table on a heading grid (hc_set_drift_qtf_headings, hc_set_sum_qtf_headings)
 constexpr int kQtfMaxNodes = 1024;   // (heading, frequency) nodes J = nh nq of such a table: U, V [J] stay in LDS, four nodes per lane
 constexpr int kSurfaceMaxPanels = 1 << 20;  // surface panels one body may carry (hc_set_surface_panels): 4096 chunks of 256
+constexpr int kRadiationModesMaxPerPair = 16;  // modes one (row, column) pair may carry (hc_set_radiation_modes)
 
 #if defined(__HIPCC__)
 #define HC_HOST_DEVICE __host__ __device__

@@ -168,7 +168,7 @@ void hc_destroy(hc_ctx* ctx) {
     }
     if (ctx->stream) (void)hipStreamDestroy(ctx->stream);
     if (ctx->stream_am) (void)hipStreamDestroy(ctx->stream_am);
-    for (hc::SideLane* lane : {&ctx->mor, &ctx->nl, &ctx->drift.lane, &ctx->sum.lane}) lane->close();
+    for (hc::SideLane* lane : {&ctx->mor, &ctx->nl, &ctx->drift.lane, &ctx->sum.lane, &ctx->radm}) lane->close();
     for (hc::Wk2Call& w : ctx->wk2)
         if (w.stream) (void)hipStreamDestroy(w.stream);
     if (ctx->ev_fin) (void)hipEventDestroy(ctx->ev_fin);

@@ -1501,7 +1501,9 @@ const char* hc_dispatch_mode_reason(const hc_ctx* c) {
 int hc_reset_history(hc_ctx* c) {
     HC_API_BEGIN(c)
     require(c->finalized, HC_ERR_INVALID, "hc_finalize has not been called");
+    c->radm.require_idle("a radiation-modes evaluation is in flight (hc_radiation_modes_end has not been called)");
     HC_HIP(hipDeviceSynchronize());  // steps may still be running on a caller's stream (hc_step_device)
+    c->radmodes.ring.reset();        // the modal radiation term starts anew as well (hc_reset_radiation_modes)
     c->times.clear();
     c->retired.clear();
     c->head = -1;

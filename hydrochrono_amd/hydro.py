@@ -212,7 +212,8 @@ class HydroForces:
         out = np.empty(self.D_local)
         morison, nonlinear, drift = self.__dict__.get("_morison_any"), self._nonlinear_on(), self._drift_on()
         sumf = self._sum_on()
-        if morison or nonlinear or drift or sumf:
+        radm = self.__dict__.get("_radm_any")
+        if morison or nonlinear or drift or sumf or radm:
             # the side terms run on streams of their own beside the step; the composition is made here (the C ABI total stays the
             # reference's): begin all, step, end all
             if nonlinear:
@@ -241,6 +242,18 @@ class HydroForces:
                     if drift:
                         self.lib.hc_drift_end(self.ctx, _dp(np.empty(self.D_local)))
                     self._chk(rc_begin)
+            if radm:
+                rc_begin = self.lib.hc_radiation_modes_begin(self.ctx, t, _dp(a[2]), _dp(a[3]))
+                if rc_begin:
+                    if nonlinear:
+                        self.lib.hc_nonlinear_end(self.ctx, None, None, None)
+                    if morison:
+                        self.lib.hc_morison_end(self.ctx, _dp(np.empty(self.D_local)))
+                    if drift:
+                        self.lib.hc_drift_end(self.ctx, _dp(np.empty(self.D_local)))
+                    if sumf:
+                        self.lib.hc_sum_qtf_end(self.ctx, _dp(np.empty(self.D_local)))
+                    self._chk(rc_begin)
             rc = capi.step_raw(self.lib)(self.ctx, t, a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, a[3].ctypes.data, out.ctypes.data)
             rc_end = 0
             if nonlinear:
@@ -255,6 +268,9 @@ class HydroForces:
             if sumf:
                 sm = np.empty(self.D_local)
                 rc_end = self.lib.hc_sum_qtf_end(self.ctx, _dp(sm)) or rc_end
+            if radm:
+                rm = np.empty(self.D_local)
+                rc_end = self.lib.hc_radiation_modes_end(self.ctx, _dp(rm)) or rc_end
             self._chk(rc or rc_end)
             if nonlinear:
                 self._nonlinear_last = nl
@@ -268,6 +284,9 @@ class HydroForces:
             if sumf:
                 self._sum_last = sm
                 out = out + sm
+            if radm:
+                self._radm_last = rm
+                out = out - rm
             return out
         # raw addresses through a c_void_p prototype: this call sits in per-step loops
         rc = capi.step_raw(self.lib)(self.ctx, t, a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, a[3].ctypes.data, out.ctypes.data)
@@ -924,6 +943,83 @@ class HydroForces:
         m = self.__dict__.get("_sum_last")
         return np.zeros(self.D_local) if m is None or not self._sum_on() else m.copy()
 
+    # -- state-space radiation by modal recursion (an extension beyond the reference) --
+    def set_radiation_modes(self, b, modes):
+        """Replaces the radiation modes of body b (0-based): an iterable of (row 0..5, col 0..D-1, lambda, rho) with complex pole
+        (Re < 0) and residue in the units of the K given to set_body; an empty list clears them.  Once a body carries modes, step()
+        returns total - modal radiation term: the term is independent of the convolution, so a modes-only caller gives the body a
+        zero IRF (set_zero_rirf).  See hc_set_radiation_modes in include/hydrochrono_amd.h."""
+        modes = list(modes)
+        raw = (capi.RadiationMode * max(1, len(modes)))()
+        for k, (row, col, lam, rho) in enumerate(modes):
+            lam, rho = complex(lam), complex(rho)
+            raw[k] = capi.RadiationMode(int(row), int(col), lam.real, lam.imag, rho.real, rho.imag)
+        self._chk(self.lib.hc_set_radiation_modes(self.ctx, int(b), raw, len(modes)))
+        counts = self.__dict__.setdefault("_radm_counts", {})
+        counts[int(b)] = len(modes)
+        self._radm_any = any(counts.values())
+
+    def set_radiation_state_space(self, b, A, B, C):
+        """The modes of body b from state-space models: A, B, C nested [6][D] lists (or object arrays) holding per pair an (n, n)
+        matrix, an n-vector and an n-vector of any order n (None or an empty A: no model on that pair), K(tau) = C exp(A tau) B.
+        Converted on the host (radiation_modes.state_space_to_modes); a defective or unstable A is refused."""
+        from .radiation_modes import state_space_to_modes
+        modes = []
+        for r in range(6):
+            for c in range(self.D):
+                if A[r][c] is None or np.size(A[r][c]) == 0:
+                    continue
+                modes += [(r, c, lam, rho) for lam, rho in state_space_to_modes(A[r][c], B[r][c], C[r][c])]
+        self.set_radiation_modes(b, modes)
+
+    def radiation_mode_count(self, b):
+        n = C.c_int()
+        self._chk(self.lib.hc_get_radiation_mode_count(self.ctx, int(b), C.byref(n)))
+        return n.value
+
+    def set_radiation_modes_depth(self, depth):
+        """Snapshots of the modal state kept for steps back in time: 2 .. 64, default 4."""
+        self._chk(self.lib.hc_set_radiation_modes_depth(self.ctx, int(depth)))
+
+    def reset_radiation_modes(self):
+        self._chk(self.lib.hc_reset_radiation_modes(self.ctx))
+
+    def radiation_modes_irf(self, b, tau):
+        """K [6][D][n] = sum Re[rho exp(lambda tau)] of body b's modes, without the rho factor: what a fit is checked against."""
+        tau = _arr(tau)
+        K = np.empty((6, self.D, tau.size))
+        self._chk(self.lib.hc_get_radiation_modes_irf(self.ctx, int(b), tau.size, _dp(tau), _dp(K.reshape(-1))))
+        return K
+
+    def set_zero_rirf(self, b, dt=0.05):
+        """A zero radiation IRF of two samples for body b (before finalize): for a caller whose radiation comes from the modes alone.
+        Every body of a system needs the same dt."""
+        t = np.array([0.0, float(dt)])
+        K = np.zeros(6 * self.D * 2)
+        self._chk(self.lib.hc_set_rirf(self.ctx, int(b), _dp(t), 2, _dp(K)))
+
+    def compute_radiation_modes(self, t, linvel, angvel):
+        """Advances the modal state to time t with the velocities given and returns the modal radiation term of the owned bodies
+        (sign and meaning of compute_radiation); zeros at the first call and without modes."""
+        lv, av = _arr(linvel, 3 * self.N), _arr(angvel, 3 * self.N)
+        out = np.empty(self.D_local)
+        self._chk(self.lib.hc_compute_radiation_modes(self.ctx, float(t), _dp(lv), _dp(av), _dp(out)))
+        return out
+
+    def radiation_modes_begin(self, t, linvel, angvel):
+        lv, av = _arr(linvel, 3 * self.N), _arr(angvel, 3 * self.N)
+        self._chk(self.lib.hc_radiation_modes_begin(self.ctx, float(t), _dp(lv), _dp(av)))
+
+    def radiation_modes_end(self):
+        out = np.empty(self.D_local)
+        self._chk(self.lib.hc_radiation_modes_end(self.ctx, _dp(out)))
+        return out
+
+    def radiation_modes(self):
+        """The modal radiation term of the last step() (zeros when no body carries modes)."""
+        m = self.__dict__.get("_radm_last")
+        return np.zeros(self.D_local) if m is None or not self.__dict__.get("_radm_any") else m.copy()
+
 
 def wave_spreading_directions(nf, heading, s=0.0, n_bins=15, seed=1, lib=None):
     """hc_wave_spreading_directions: nf equal-energy directions of the cos-2s spreading about `heading` (no context needed)."""
@@ -1011,6 +1107,7 @@ class HydroGroup:
         nonlinear = self.shards[0]._nonlinear_on()  # every shard holds the lists of all bodies and the mode
         drift = self.shards[0]._drift_on()
         sumf = self.shards[0]._sum_on()
+        radm = self.shards[0].__dict__.get("_radm_any")  # every shard holds the lists of all bodies
         if nonlinear:
             self._nonlinear_begin(t, a)
         if morison:
@@ -1040,6 +1137,19 @@ class HydroGroup:
                 if drift:
                     self._drift_end(check=False)
                 raise
+        if radm:
+            try:
+                self._radm_begin(t, a[2], a[3])
+            except HydroError:
+                if nonlinear:
+                    self._nonlinear_end(check=False)
+                if morison:
+                    self._morison_end(check=False)
+                if drift:
+                    self._drift_end(check=False)
+                if sumf:
+                    self._sum_end(check=False)
+                raise
         rc = self._step(self._ctxs, len(self.shards), t, a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, a[3].ctypes.data, out.ctypes.data)
         if nonlinear:
             self._nonlinear_last = self._nonlinear_end(check=not rc)
@@ -1049,6 +1159,8 @@ class HydroGroup:
             self._drift_last = self._drift_end(check=not rc)
         if sumf:
             self._sum_last = self._sum_end(check=not rc)
+        if radm:
+            self._radm_last = self._radm_end(check=not rc)
         if rc:
             raise HydroError(rc, self.lib.hc_last_error(self.shards[0].ctx).decode())
         if nonlinear:
@@ -1058,7 +1170,9 @@ class HydroGroup:
             out = out + self._morison_last
         if drift:
             out = out + self._drift_last
-        return out + self._sum_last if sumf else out
+        if sumf:
+            out = out + self._sum_last
+        return out - self._radm_last if radm else out
 
     # -- the terms beside the step: begin on every shard, then end on every shard; `nout` output arrays of D_local per shard --
     def _side_begin(self, begin, end, nout, t, *arrays):
@@ -1132,6 +1246,27 @@ class HydroGroup:
 
     def sum_qtf_headings(self, b):
         return self.shards[0].sum_qtf_headings(b)
+
+    # -- radiation modes: every shard holds the lists of all bodies and advances the rows of its own --
+    def _radm_begin(self, t, linvel, angvel):
+        self._side_begin(self.lib.hc_radiation_modes_begin, self.lib.hc_radiation_modes_end, 1, t, linvel, angvel)
+
+    def _radm_end(self, check=True):
+        return self._side_end(self.lib.hc_radiation_modes_end, 1, check)[0]
+
+    def compute_radiation_modes(self, t, linvel, angvel):
+        self._radm_begin(t, _arr(linvel, 3 * self.N), _arr(angvel, 3 * self.N))
+        return self._radm_end()
+
+    def radiation_modes(self):
+        m = self.__dict__.get("_radm_last")
+        return np.zeros(self.D) if m is None or not self.shards[0].__dict__.get("_radm_any") else m.copy()
+
+    def radiation_modes_irf(self, b, tau):
+        return self.shards[0].radiation_modes_irf(b, tau)
+
+    def radiation_mode_count(self, b):
+        return self.shards[0].radiation_mode_count(b)
 
     # -- surface panels and triangles: every shard holds the lists of all bodies and computes those of its own --
     def surface_panel_count(self, b):

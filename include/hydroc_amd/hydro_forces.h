@@ -29,6 +29,7 @@
 
 #include <algorithm>
 #include <array>
+#include <complex>
 #include <cstdlib>
 #include <limits>
 #include <memory>
@@ -156,6 +157,13 @@ struct MorisonIncrements {
 struct NonlinearIncrements {
     std::vector<std::array<double, 3>> p;
     std::vector<double> eta2, q2;
+};
+
+// A radiation mode of a body (not in the reference; hc_radiation_mode): row 0..5 of the body, column 0..6N-1, complex pole
+// (Re < 0) and residue, K_rc(tau) = sum Re[rho exp(lambda tau)] in the units of the file's K.
+struct RadiationMode {
+    int row = 0, col = 0;
+    std::complex<double> lambda{-1.0, 0.0}, rho{0.0, 0.0};
 };
 
 // A surface panel of a body (not in the reference; hc_surface_panel): centroid [m] and area vector [m^2] (area times the outward
@@ -612,6 +620,46 @@ class TestHydro {
         return out;
     }
 
+    // State-space radiation by modal recursion (not in the reference; include/hydrochrono_amd.h: hc_set_radiation_modes).  Once a body
+    // carries modes, CoordinateFuncForBody returns total - modal radiation term: hc_radiation_modes_begin on every shard, the step,
+    // hc_radiation_modes_end on every shard, one elementwise subtraction.  The term is independent of the convolution: what the file's
+    // K gives is still in the total.  The body index is 1-based; an empty vector clears the list.
+    void SetRadiationModes(int body_index_1_based, const std::vector<RadiationMode>& modes) {
+        if (body_index_1_based < 1 || body_index_1_based > num_bodies_) throw std::out_of_range("SetRadiationModes: body index out of range");
+        std::vector<hc_radiation_mode> raw(modes.size());
+        for (size_t e = 0; e < modes.size(); ++e)
+            raw[e] = hc_radiation_mode{modes[e].row, modes[e].col, modes[e].lambda.real(), modes[e].lambda.imag(), modes[e].rho.real(),
+                                       modes[e].rho.imag()};
+        for (hc_ctx* c : ctxs_) check(c, hc_set_radiation_modes(c, body_index_1_based - 1, raw.data(), static_cast<int>(raw.size())));
+        radm_count_.resize(static_cast<size_t>(num_bodies_), 0);
+        radm_count_[static_cast<size_t>(body_index_1_based - 1)] = raw.size();
+        have_radm_ = std::any_of(radm_count_.begin(), radm_count_.end(), [](size_t n) { return n != 0; });
+        have_time_ = false;  // the cached total belongs to the lists before
+    }
+    // snapshots kept for steps back in time (hc_set_radiation_modes_depth), and a fresh start of the modal state
+    void SetRadiationModesDepth(int depth) {
+        for (hc_ctx* c : ctxs_) check(c, hc_set_radiation_modes_depth(c, depth));
+    }
+    void ResetRadiationModes() {
+        for (hc_ctx* c : ctxs_) check(c, hc_reset_radiation_modes(c));
+        have_time_ = false;
+    }
+    // advances the modal state to the bodies' present time with their present velocities: the modal radiation term, 6 N values
+    std::vector<double> ComputeForceRadiationModes() {
+        gather_state();
+        std::vector<double> out(6 * static_cast<size_t>(num_bodies_));
+        radm_begin(bodies_[0]->GetChTime());
+        radm_end(out.data());
+        return out;
+    }
+
+    // the modal radiation term of the last CoordinateFuncForBody evaluation (zeros before the first one)
+    std::vector<double> GetForceRadiationModes() const {
+        std::vector<double> out(6 * static_cast<size_t>(num_bodies_), 0.0);
+        if (have_radm_ && radm_force_.size() == out.size()) out = radm_force_;
+        return out;
+    }
+
     // src/hydro_forces.cpp:693-711: the radiation IRF value the convolution uses (rho-scaled; the processed kernel in
     // TaperedDirect mode).  Reads one value back from the GPU -- a debugging accessor, as in the reference.
     double GetRIRFval(int row, int col, int st) {
@@ -676,6 +724,22 @@ class TestHydro {
                     throw;
                 }
             }
+            if (have_radm_) {
+                try {
+                    radm_begin(t);
+                } catch (...) {  // nothing stays pending
+                    std::vector<double> drop(total_force_.size());
+                    if (nonlinear)
+                        for (hc_ctx* c : ctxs_) (void)hc_nonlinear_end(c, nullptr, nullptr, nullptr);
+                    if (have_morison_)
+                        for (hc_ctx* c : ctxs_) (void)hc_morison_end(c, drop.data() + row0(c));
+                    if (drift)
+                        for (hc_ctx* c : ctxs_) (void)hc_drift_end(c, drop.data() + row0(c));
+                    if (sumf)
+                        for (hc_ctx* c : ctxs_) (void)hc_sum_qtf_end(c, drop.data() + row0(c));
+                    throw;
+                }
+            }
             const int rc = ctxs_.size() == 1 ? hc_step(ctx_, t, pos_.data(), rpy_.data(), lin_.data(), ang_.data(), total_force_.data())
                                              : hc_step_multi(ctxs_.data(), static_cast<int>(ctxs_.size()), t, pos_.data(), rpy_.data(), lin_.data(),
                                                              ang_.data(), total_force_.data());
@@ -721,6 +785,15 @@ class TestHydro {
                 } else {
                     sum_end(sum_force_.data());
                     for (size_t i = 0; i < total_force_.size(); ++i) total_force_[i] += sum_force_[i];
+                }
+            }
+            if (have_radm_) {
+                radm_force_.resize(total_force_.size());
+                if (rc != HC_OK) {
+                    for (hc_ctx* c : ctxs_) (void)hc_radiation_modes_end(c, radm_force_.data() + row0(c));  // nothing stays pending
+                } else {
+                    radm_end(radm_force_.data());
+                    for (size_t i = 0; i < total_force_.size(); ++i) total_force_[i] -= radm_force_[i];
                 }
             }
             check(ctx_, rc);
@@ -925,6 +998,28 @@ class TestHydro {
         }
         if (failed) check(failed, rc);
     }
+    void radm_begin(double t) {
+        for (size_t g = 0; g < ctxs_.size(); ++g) {
+            const int rc = hc_radiation_modes_begin(ctxs_[g], t, lin_.data(), ang_.data());
+            if (rc != HC_OK) {
+                std::vector<double> drop(6 * static_cast<size_t>(num_bodies_));
+                for (size_t h = 0; h < g; ++h) (void)hc_radiation_modes_end(ctxs_[h], drop.data());
+                check(ctxs_[g], rc);
+            }
+        }
+    }
+    void radm_end(double* out) {  // every shard is ended, then the first failure is reported
+        int rc = HC_OK;
+        hc_ctx* failed = nullptr;
+        for (hc_ctx* c : ctxs_) {
+            const int r = hc_radiation_modes_end(c, out + row0(c));
+            if (r != HC_OK && rc == HC_OK) {
+                rc     = r;
+                failed = c;
+            }
+        }
+        if (failed) check(failed, rc);
+    }
     static int row0(hc_ctx* c) {  // first output row of a shard context
         int b0 = 0;
         check(c, hc_get_shard(c, &b0, nullptr));
@@ -949,6 +1044,9 @@ class TestHydro {
     std::vector<double> sum_force_;        // the sum-frequency term of the last evaluation
     std::vector<size_t> sum_size_;         // grid size of every body's sum-frequency table
     int sum_mode_ = 0;                     // 0 off, 1 on
+    std::vector<double> radm_force_;       // the modal radiation term of the last evaluation
+    std::vector<size_t> radm_count_;       // radiation modes per body
+    bool have_radm_ = false;
     std::array<double, 3> gravity_{0.0, 0.0, -9.81};
     bool have_time_   = false;
     double prev_time_ = -1.0;

@@ -1087,6 +1087,58 @@ int hc_wave_kinematics2_dir(hc_ctx* ctx, const hc_wave_kinematics2_opts* o, int 
 int hc_wave_kinematics2_dir_pair_tables(hc_ctx* ctx, const hc_wave_kinematics2_opts* o, double* Kp, double* Km, double* Bp, double* Bm);
 
 /* ------------------------------------------------------------------------------------------------
+ * State-space radiation by modal recursion (not in the reference, which carries radiation_calculation: state_space in hydro.yaml
+ * and reads no state-space data): the radiation force from a modal model of the impulse response instead of the convolution over
+ * the velocity history.  No history and no time grid: the state moves from one accepted time to the next by a closed formula that
+ * holds for any step length.  DESIGN.md 3.7r has the mathematics, the kernel and the checks.
+ *
+ * A mode belongs to a pair (row of an owned body, column c in 0 .. D-1) and has a complex pole lambda, Re lambda < 0, and a complex
+ * residue rho:   K_rc(tau) = sum_m Re[rho_m exp(lambda_m tau)].  A real pole has lambda_im = 0; a conjugate pair is ONE mode with the
+ * real part taken, its residue twice the pair's.  Residues are in the units of the K given to hc_set_rirf (BEMIO-normalised): the
+ * library multiplies them by rho as it does K, so modes fitted to that K give the force the convolution gives.
+ *
+ * With the velocity linear between two consecutive accepted times t_n < t_n+1, h = t_n+1 - t_n, x = lambda h:
+ *     z_n+1 = e^x z_n + h [(phi1(x) - phi2(x)) v_n + phi2(x) v_n+1],   phi1 = (e^x - 1) / x,   phi2 = (e^x - 1 - x) / x^2
+ *     rad_r(t_n+1) = sum_c sum_m Re[rho_m z_m]
+ * with the sign and meaning of hc_compute_radiation (the total is hs - rad + waves).  The first call, at t_0, sets z = 0, stores
+ * v(t_0) and returns zeros.  The term is independent of the convolution: hc_step and hc_compute_radiation are not touched, and a
+ * caller subtracts what it has set -- a modes-only caller passes a short zero IRF to hc_set_rirf (hc_finalize still wants one).
+ *
+ * Time: the lane keeps z and v of the last `depth` accepted times (hc_set_radiation_modes_depth, 2 .. 64, default 4; depth * 16 B
+ * per mode).  A call at t above the newest time advances from the newest snapshot.  A call at t equal to it is the convolution's
+ * duplicate-time error (HC_ERR_RUNTIME).  A call at t below it is a rejected step: the snapshots at times >= t are dropped and the
+ * step advances from the newest one that survives; if none does: HC_ERR_INVALID, the state stays as it was.
+ *
+ * It runs on a stream of its own beside the steps, as the Morison term does: hc_radiation_modes_begin copies the velocities up and
+ * enqueues, hc_radiation_modes_end waits and copies out; exactly one end per begin.  A row's bits depend on that row's modes, the
+ * velocity samples and the times only -- not on N, on other rows' lists or on the shard.  Not part of hc_step_device / hc_step_multi.
+ * ---------------------------------------------------------------------------------------------- */
+typedef struct hc_radiation_mode {
+    int row; /* 0 .. 5 of the body */
+    int col; /* 0 .. D-1 */
+    double lambda_re, lambda_im, rho_re, rho_im;
+} hc_radiation_mode;
+/* Replaces the list of `body` (0-based, any body of the system; one outside this context's shard is accepted and ignored); n = 0
+ * clears it.  Within a pair the modes keep the order given.  A changed list empties the snapshot ring: the next call is a first
+ * call.  HC_ERR_INVALID: body out of range, n < 0, a null list with n > 0, a non-finite value, Re lambda >= 0, a row or column out
+ * of range, more than 16 modes on one pair, or a hc_radiation_modes_begin without its end. */
+int hc_set_radiation_modes(hc_ctx* ctx, int body, const hc_radiation_mode* modes, int n);
+int hc_get_radiation_mode_count(hc_ctx* ctx, int body, int* n);
+/* 2 .. 64 (default 4); empties the ring.  HC_ERR_INVALID outside that range or while a begin is pending. */
+int hc_set_radiation_modes_depth(hc_ctx* ctx, int depth);
+/* linvel, angvel [3N] as hc_compute_radiation; rad_Dlocal [D_local].  Needs hc_finalize.  HC_ERR_INVALID on a non-finite time or
+ * velocity, on a second begin, on an end without a begin; nothing stays pending after a failed begin.  No owned body carries a
+ * mode: zeros, and the ring is not touched. */
+int hc_radiation_modes_begin(hc_ctx* ctx, double t, const double* linvel, const double* angvel);
+int hc_radiation_modes_end(hc_ctx* ctx, double* rad_Dlocal);
+int hc_compute_radiation_modes(hc_ctx* ctx, double t, const double* linvel, const double* angvel, double* rad_Dlocal);
+/* Empties the ring (hc_reset_history calls it as well): the next call is a first call.  HC_ERR_INVALID while a begin is pending. */
+int hc_reset_radiation_modes(hc_ctx* ctx);
+/* sum Re[rho exp(lambda tau)] of the body's modes WITHOUT the rho factor, on the host: K [6][D][n_tau], what a fit is checked
+ * against.  Any body of the system. */
+int hc_get_radiation_modes_irf(hc_ctx* ctx, int body, int n_tau, const double* tau, double* K_6xDxn);
+
+/* ------------------------------------------------------------------------------------------------
  * Synthetic many-body inputs generated directly in HBM (benchmark configurations C3/C4 of SURVEY 8d;
  * not part of the reference).  Fills K, K_hs, A_inf, excitation IRF for all local bodies from a
  * counter-based generator so that a 77 GB kernel never exists on the host.  hc_finalize still applies.
