@@ -963,14 +963,8 @@ class HydroForces:
         """The modes of body b from state-space models: A, B, C nested [6][D] lists (or object arrays) holding per pair an (n, n)
         matrix, an n-vector and an n-vector of any order n (None or an empty A: no model on that pair), K(tau) = C exp(A tau) B.
         Converted on the host (radiation_modes.state_space_to_modes); a defective or unstable A is refused."""
-        from .radiation_modes import state_space_to_modes
-        modes = []
-        for r in range(6):
-            for c in range(self.D):
-                if A[r][c] is None or np.size(A[r][c]) == 0:
-                    continue
-                modes += [(r, c, lam, rho) for lam, rho in state_space_to_modes(A[r][c], B[r][c], C[r][c])]
-        self.set_radiation_modes(b, modes)
+        from .radiation_modes import state_space_pairs_to_modes
+        self.set_radiation_modes(b, state_space_pairs_to_modes(A, B, C, self.D))
 
     def radiation_mode_count(self, b):
         n = C.c_int()

@@ -53,11 +53,24 @@ def state_space_to_modes(A, B, C, cond_max=1e10):
     return _fold_conjugates(lam, res, lam.imag, tol)
 
 
+def state_space_pairs_to_modes(A, B, C, D):
+    """The (row, col, lambda, rho) list of one body from nested [6][D] A, B, C (lists or object arrays): state_space_to_modes of
+    every pair that holds a model, in row-major pair order; None or an empty A is a pair without one."""
+    modes = []
+    for r in range(6):
+        for c in range(int(D)):
+            if A[r][c] is None or np.size(A[r][c]) == 0:
+                continue
+            modes += [(r, c, lam, rho) for lam, rho in state_space_to_modes(A[r][c], B[r][c], C[r][c])]
+    return modes
+
+
 def fit_radiation_modes(K_row_col, t, max_order=10, r2_min=0.99):
     """Modes of one (row, column) pair from its impulse response sampled on the uniform grid t (t[0] = 0): a Hankel-SVD realisation
     (Kung's method, as BEMIO's state-space fit) of the samples taken as the Markov parameters K_k = C A^k B, its discrete poles mu
     mapped to lambda = log(mu) / dt.  The order rises from 1 until R^2 >= r2_min or max_order is reached; orders that give a pole
-    on or outside the unit circle are passed over.  Returns (modes, R^2 achieved); ValueError if no order gives a stable model."""
+    on or outside the unit circle are passed over.  Returns (modes, R^2 achieved); ValueError if no order gives a stable model.
+    A pair with no response (every sample zero) has no modes: ([], 1.0)."""
     K = np.asarray(K_row_col, dtype=np.float64).reshape(-1)
     t = np.asarray(t, dtype=np.float64).reshape(-1)
     if K.size != t.size or K.size < 4:
@@ -65,6 +78,8 @@ def fit_radiation_modes(K_row_col, t, max_order=10, r2_min=0.99):
     dt = (t[-1] - t[0]) / (t.size - 1)
     if not dt > 0.0 or np.max(np.abs(np.diff(t) - dt)) > 1e-9 * dt:
         raise ValueError("t must be uniform and increasing")
+    if not K.any():
+        return [], 1.0
     rows = K.size // 2
     cols = K.size - rows
     H = K[np.arange(rows)[:, None] + np.arange(cols)[None, :]]

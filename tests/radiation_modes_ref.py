@@ -1,7 +1,9 @@
 """numpy.longdouble restatement of the modal radiation term (hydrochrono_amd/csrc/hc_radiation_modes.hip): the
 recurrence z_n+1 = e^x z_n + h [(phi1 - phi2) v_n + phi2 v_n+1] per mode, the row sums, and the snapshot ring with its rule for a
 step back in time.  Written from the definitions, not from the kernel: phi1 and phi2 have their own series threshold and length
-here.  tests/test_radiation_modes_ref_cpu.py keeps it honest against closed forms."""
+here.  tests/test_radiation_modes_ref_cpu.py keeps it honest against closed forms.  Below it, what the fit and state-space tests
+share (tests/test_radiation_modes_fit_cpu.py, tests/test_gpu_radiation_modes_fit.py): expm_taylor, z_sine_phase, fit_body, the
+nested state-space structure and the samples with a negative real discrete pole."""
 import numpy as np
 
 LD = np.longdouble
@@ -108,6 +110,74 @@ def device_rows(modes_by_body, b0, b1, rho_water):
             sel.sort(key=lambda m: m[1])
             rows.append([(m[1], m[2], rho_water * complex(m[3])) for m in sel])
     return rows
+
+
+def expm_taylor(A, tau):
+    """exp(A tau) from its Taylor series in longdouble (scaling and squaring: |A tau| / 2^s < 1/2)."""
+    A = np.asarray(A, dtype=LD) * LD(tau)
+    s = max(0, int(np.ceil(np.log2(max(float(np.max(np.sum(np.abs(A), axis=1))), 1e-30)))) + 1)
+    A = A / LD(2 ** s)
+    E, term = np.eye(A.shape[0], dtype=LD), np.eye(A.shape[0], dtype=LD)
+    for k in range(1, 40):
+        term = term @ A / LD(k)
+        E = E + term
+    for _ in range(s):
+        E = E @ E
+    return E
+
+
+def z_sine_phase(lam, omega, phase, t):
+    """z(t) from z(0) = 0 under v = sin(omega t + phase): the two quadratures superposed.  t may be an array."""
+    lam, t, w = CLD(lam), np.asarray(t, dtype=LD), LD(omega)
+    el = np.exp(lam * t)
+    plus = (np.exp(CLD(1j) * w * t) - el) / (CLD(1j) * w - lam)
+    minus = (np.exp(CLD(-1j) * w * t) - el) / (CLD(-1j) * w - lam)
+    return np.cos(LD(phase)) * (plus - minus) / CLD(2j) + np.sin(LD(phase)) * (plus + minus) / CLD(2)
+
+
+def fit_body(K, t, D, **fit_opts):
+    """fit_radiation_modes over the pairs of one body's K [6][D][S] that carry a response, max |K_rc| > 1e-6 max |K|: (modes,
+    per_pair) with modes the (row, col, lambda, rho) list for set_radiation_modes and per_pair[(r, c)] = (n_modes, R^2, L1),
+    L1 = dt sum_k |K_fit(tau_k) - K(tau_k)|."""
+    from hydrochrono_amd.radiation_modes import fit_radiation_modes, modes_irf
+    K = np.asarray(K, dtype=np.float64).reshape(6, int(D), -1)
+    t = np.asarray(t, dtype=np.float64).reshape(-1)
+    dt = (t[-1] - t[0]) / (t.size - 1)
+    top = float(np.abs(K).max())
+    modes, per_pair = [], {}
+    for r in range(6):
+        for c in range(int(D)):
+            if not np.abs(K[r, c]).max() > 1e-6 * top:
+                continue
+            fitted, r2 = fit_radiation_modes(K[r, c], t, **fit_opts)
+            modes += [(r, c, lam, rho) for lam, rho in fitted]
+            per_pair[(r, c)] = (len(fitted), r2, float(dt * np.sum(np.abs(modes_irf(fitted, t - t[0]) - K[r, c]))))
+    return modes, per_pair
+
+
+def nested_state_space(D, seed=11):
+    """[6][D] A, B, C: pairs of orders 1, 2, 3, 4 and 7 (the matrices of the conversion's own test), the rest None or empty, in
+    lists and in object arrays alike.  Returns (A, B, C, {(r, c): (A, B, C)})."""
+    rng = np.random.default_rng(seed)
+    where = {(0, 0): 1, (0, D - 1): 2, (2, 7): 3, (3, 3): 4, (5, 6): 7, (5, D - 1): 2, (1, 0): 3}
+    A = [[None] * D for _ in range(6)]
+    B = [[None] * D for _ in range(6)]
+    C = [[None] * D for _ in range(6)]
+    pairs = {}
+    for (r, c), n in where.items():
+        A[r][c] = rng.normal(size=(n, n)) - (1.5 + np.sqrt(n)) * np.eye(n)
+        B[r][c], C[r][c] = rng.normal(size=n), rng.normal(size=n)
+        pairs[(r, c)] = (A[r][c], B[r][c], C[r][c])
+    for r, c in ((0, 1), (4, 4), (5, 0)):  # "no model" spelled as an empty array; B and C are not looked at
+        A[r][c] = np.zeros((0, 0))
+    A[4][2], B[4][2], C[4][2] = [], [], []
+    return A, B, C, pairs
+
+
+def negative_pole_samples():
+    """K_k = 3 (-0.8)^k + 2 0.9^k on 60 samples of dt = 0.05: (K, t).  Its fit holds a negative real discrete pole."""
+    k = np.arange(60)
+    return 3.0 * (-0.8) ** k + 2.0 * 0.9 ** k, 0.05 * k
 
 
 def pack_velocity(linvel, angvel):

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import radiation_modes_ref as rm
+from radiation_modes_ref import expm_taylor
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 LD = np.longdouble
@@ -116,20 +117,6 @@ def test_fit_recovers_three_known_modes():
     # between the samples as well: the modes are a continuous-time model
     tf = 0.0125 * np.arange(1600)
     assert np.max(np.abs(modes_irf(modes, tf) - modes_irf(known, tf))) < 1e-8
-
-
-def expm_taylor(A, tau):
-    """exp(A tau) from its Taylor series in longdouble (scaling and squaring: |A tau| / 2^s < 1/2)."""
-    A = np.asarray(A, dtype=LD) * LD(tau)
-    s = max(0, int(np.ceil(np.log2(max(float(np.max(np.sum(np.abs(A), axis=1))), 1e-30)))) + 1)
-    A = A / LD(2 ** s)
-    E, term = np.eye(A.shape[0], dtype=LD), np.eye(A.shape[0], dtype=LD)
-    for k in range(1, 40):
-        term = term @ A / LD(k)
-        E = E + term
-    for _ in range(s):
-        E = E @ E
-    return E
 
 
 def test_state_space_to_modes_agrees_with_the_matrix_exponential():
