@@ -24,7 +24,7 @@ TUNING_LIB = os.path.join(LIBDIR, "libhydrochrono_amd_tuning.so")
 BEMIO_LIB = os.path.join(LIBDIR, "libhc_bemio.so")
 
 SOURCES = ["hc_kernels.hip", "hc_runtime.cpp", "hc_step.cpp", "hc_pass.cpp", "hc_setup.cpp", "hc_query.cpp", "hc_direct.cpp", "hc_host_math.cpp", "hc_yaml.cpp",
-           "hc_eta_fft.cpp", "hc_wave_kin.hip", "hc_eta_record.cpp", "hc_morison.hip", "hc_nonlinear.hip", "hc_qtf.hip", "hc_qtf_dir.hip", "hc_wave_kin2.hip",
+           "hc_eta_fft.cpp", "hc_wave_kin.hip", "hc_eta_record.cpp", "hc_morison.hip", "hc_morison_members.hip", "hc_nonlinear.hip", "hc_qtf.hip", "hc_qtf_dir.hip", "hc_wave_kin2.hip",
            "hc_directions.cpp", "hc_eta_components.hip", "hc_radiation_modes.hip"]
 # kernel-argument preload: the leading scalar / pointer arguments of a kernel arrive in scalar registers with the wave (up to 16 words:
 # added_mass_mv_tagged_kernel starts without a single argument load); kernels whose first argument is a struct -- the step path's -- are
@@ -32,7 +32,7 @@ SOURCES = ["hc_kernels.hip", "hc_runtime.cpp", "hc_step.cpp", "hc_pass.cpp", "hc
 PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
 KERNEL_CO = os.path.join(LIBDIR, "hc_kernels.co")  # the same kernels as a stand-alone code object, for the direct AQL dispatch (hc_direct.hpp)
 TUNING_CO = os.path.join(LIBDIR, "hc_kernels_tuning.co")
-HEADERS = ["hc_kernels.hpp", "hc_tail.hpp", "hc_tail_kernels.hpp", "hc_context.hpp", "hc_internal.hpp", "hc_host_math.hpp", "hc_limits.hpp", "hc_plan.hpp", "hc_history.hpp", "hc_direct.hpp", "hc_fanout.hpp", "hc_h5data.hpp", "hc_eta_record.hpp", "hc_eta_components.hpp", "hc_wave_kin.hpp", "hc_wave_kin2.hpp", "hc_wave_kin2_sum.hpp", "hc_wave_kin2_dir.hpp", "hc_qtf.hpp", "hc_heading.hpp", "hc_side.hpp", "hc_modal_ring.hpp", os.path.join(ROOT, "include", "hydrochrono_amd.h"),
+HEADERS = ["hc_kernels.hpp", "hc_tail.hpp", "hc_tail_kernels.hpp", "hc_context.hpp", "hc_internal.hpp", "hc_host_math.hpp", "hc_limits.hpp", "hc_plan.hpp", "hc_history.hpp", "hc_direct.hpp", "hc_fanout.hpp", "hc_h5data.hpp", "hc_eta_record.hpp", "hc_eta_components.hpp", "hc_wave_kin.hpp", "hc_wave_kin2.hpp", "hc_wave_kin2_sum.hpp", "hc_wave_kin2_dir.hpp", "hc_qtf.hpp", "hc_heading.hpp", "hc_side.hpp", "hc_morison_members.hpp", "hc_modal_ring.hpp", os.path.join(ROOT, "include", "hydrochrono_amd.h"),
            os.path.join(ROOT, "include", "hydrochrono_amd_host.h"), os.path.join(ROOT, "include", "hydrochrono_amd_yaml.h")]
 
 

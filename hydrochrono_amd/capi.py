@@ -49,6 +49,12 @@ class MorisonElement(C.Structure):
     _fields_ = [("r", C.c_double * 3), ("cd_area", C.c_double * 3), ("cm_vol", C.c_double * 3)]
 
 
+class MorisonMember(C.Structure):
+    """hc_morison_member: end points in the body frame, the diameter at each, Cd, Cm, segments (88 bytes)."""
+    _fields_ = [("r0", C.c_double * 3), ("r1", C.c_double * 3), ("d0", C.c_double), ("d1", C.c_double), ("cd", C.c_double),
+                ("cm", C.c_double), ("n_seg", C.c_int)]
+
+
 class SurfacePanel(C.Structure):
     """hc_surface_panel: centroid and area vector (outward normal times area) in the body frame."""
     _fields_ = [("c", C.c_double * 3), ("s", C.c_double * 3)]
@@ -192,6 +198,9 @@ SIGNATURES = {
     "hc_set_morison_second_order_directional": (C.c_int, [C.c_void_p, C.c_int]),
     "hc_get_morison_second_order_directional": (C.c_int, [C.c_void_p, c_int_p]),
     "hc_get_morison_increments": (C.c_int, [C.c_void_p, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p]),
+    "hc_set_morison_members": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(MorisonMember), C.c_int]),
+    "hc_get_morison_member_count": (C.c_int, [C.c_void_p, C.c_int, c_int_p]),
+    "hc_get_morison_member_forces": (C.c_int, [C.c_void_p, C.c_int, c_double_p]),
     "hc_set_surface_panels": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(SurfacePanel), C.c_int]),
     "hc_get_surface_panel_count": (C.c_int, [C.c_void_p, C.c_int, c_int_p]),
     "hc_set_surface_triangles": (C.c_int, [C.c_void_p, C.c_int, c_double_p, C.c_int]),

@@ -172,6 +172,21 @@ struct MorisonData {
     PinnedBuffer<double> h_state, h_out;
 };
 
+// Morison strip members (hc_set_morison_members, hc_morison_members.hip), on the lane of the elements: the lists of all bodies of
+// the system on the host, those of the owned bodies flattened body-major on the device -- a member's 11 doubles and 4 ints, the
+// member of every node and of every Gauss point -- and the pinned staging of the two sum levels
+struct MorisonMemberData {
+    std::vector<std::vector<hc_morison_member>> lists;  // [N]
+    bool dirty = false;                     // a list has changed since the device copy was made
+    int members = 0, nodes = 0, points = 0;  // of the owned bodies: members, nodes (n_seg + 1 each), Gauss points (2 n_seg each)
+    std::vector<int> off;                   // [nloc + 1] first member of an owned body
+    DeviceBuffer<double> tab, h, item, mout, out;  // [members][11], [nodes], [points][6], [members][6], [nloc][6]
+    DeviceBuffer<int> desc, node_member, point_member, d_off;  // [members][4] body, n_seg, first node, first point; [nodes]; [points]; off
+    PinnedBuffer<double> h_mout, h_out;
+    bool flight = false;  // the evaluation in flight has a member part
+    bool done   = false;  // h_mout holds a completed evaluation of the lists as they are (hc_get_morison_member_forces)
+};
+
 // Surface panels and triangles (hc_set_surface_panels, hc_set_surface_triangles, hc_nonlinear.hip): the lists of all bodies of the
 // system on the host, those of the owned bodies flattened body-major on the device with their chunk map, and the pinned staging.  A
 // body carries panels or triangles ([N] lists of 9 doubles per triangle, clipped at the free surface by nl_tris_kernel); both kinds
@@ -385,6 +400,7 @@ struct hc_ctx {
     hc::SideLane mor, nl;
     hc::Order2Part mor2, nl2;
     hc::MorisonData morison;
+    hc::MorisonMemberData members;  // strip members, on the lane `mor` behind the elements (DESIGN.md 3.7c')
     hc::SurfaceData surface;
 
     // Wave drift forces (hc_set_drift_qtf) and sum-frequency wave forces (hc_set_sum_qtf): hc_qtf.hip

@@ -41,6 +41,8 @@ constexpr int kSlotStateMaxBodies = 170;  // 12 N + 1 doubles fit, and 6 N <= 4 
                                           // (every system whose step is ONE launch: wide systems begin at 6 N = 1024)
 
 constexpr int kMorisonMaxElements = 4096;  // Morison elements one body may carry (hc_set_morison_elements)
+constexpr int kMorisonMaxMembers = 1024;   // Morison strip members one body may carry (hc_set_morison_members)
+constexpr int kMorisonMaxSegments = 64;    // segments of one member: 65 nodes, 128 Gauss points
 constexpr int kDriftMaxFreq = 256;  // frequencies of a body's drift QTF grid (hc_set_drift_qtf): one lane of the workgroup per bin
 constexpr int kQtfMaxHeadings = 16;  // headings of a QTF table on a heading grid (hc_set_drift_qtf_headings, hc_set_sum_qtf_headings)
 constexpr int kQtfMaxNodes = 1024;   // (heading, frequency) nodes J = nh nq of such a table: U, V [J] stay in LDS, four nodes per lane

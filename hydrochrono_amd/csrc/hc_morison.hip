@@ -6,6 +6,7 @@
 // (hc_set_morison_second_order): the increments of hc_wave_kinematics2 at every element, added before the wet test and the force;
 // 3.7o the same in a short-crested sea (hc_set_morison_second_order_directional): the increments of hc_wave_kinematics2_dir.
 #include "hc_internal.hpp"
+#include "hc_morison_members.hpp"
 #include "hc_wave_kin.hpp"
 #include "hc_wave_kin2.hpp"
 #include "hc_wave_kin2_dir.hpp"
@@ -350,6 +351,11 @@ void morison_enqueue(hc_ctx* c, double t, const double* pos, const double* rpy, 
     double* h_inc      = order2 ? c->mor2.stage(n_inc, width) : nullptr;
     if (order2) a.inc = c->mor2.d_inc.p;
     HC_HIP(hipMemcpyAsync(d.state.p, d.h_state.p, 4 * n3 * sizeof(double), hipMemcpyHostToDevice, st));
+    // strip members only (hc_morison_members.hip): no element launch, the element part of the result is zero
+    if (a.n_items == 0) {
+        members_enqueue(c, t, d.state.p);
+        return;
+    }
     const dim3 item_grid((a.n_items + kMorThreads - 1) / kMorThreads);
     if (order2) {
         Mor2Args m{};
@@ -372,6 +378,7 @@ void morison_enqueue(hc_ctx* c, double t, const double* pos, const double* rpy, 
                        c->Dloc, d.out.p);
     HC_HIP(hipGetLastError());
     HC_HIP(hipMemcpyAsync(d.h_out.p, d.out.p, static_cast<size_t>(c->Dloc) * sizeof(double), hipMemcpyDeviceToHost, st));
+    if (members_owned(c) != 0) members_enqueue(c, t, d.state.p);  // behind the element launches
 }
 
 const char* const kMorInFlight = "a Morison evaluation is in flight (hc_morison_end has not been called)";
@@ -477,20 +484,34 @@ int hc_morison_begin(hc_ctx* c, double t, const double* pos, const double* rpy, 
             "second-order sea off");
     require(!(c->mor2.on && hc::kin_has_components(c)) || hc::wk2_component_count(c) <= hc::kWk2MaxFreq, HC_ERR_UNSUPPORTED,
             "Morison elements on the second-order sea: more than 4096 wave components");
+    const int members = hc::members_owned(c);
+    require(!(c->mor2.on && members != 0), HC_ERR_UNSUPPORTED,
+            "Morison strip members see the first-order sea only: switch the second-order sea off (hc_set_morison_second_order) or clear "
+            "the members of the owned bodies (hc_set_morison_members)");
     int items = 0;
     if (!c->morison.elems.empty())
         for (int b = c->b0; b < c->b1; ++b) items += static_cast<int>(c->morison.elems[b].size());
-    c->mor2.flight = false;
-    c->mor.begin(items != 0, [&] { hc::morison_enqueue(c, t, pos, rpy, linvel, angvel); });
+    c->mor2.flight    = false;
+    c->members.flight = false;
+    c->mor.begin(items != 0 || members != 0, [&] { hc::morison_enqueue(c, t, pos, rpy, linvel, angvel); });
     HC_API_END(c)
 }
 
 int hc_morison_end(hc_ctx* c, double* out) {
     HC_API_BEGIN_HOT(c)
+    const bool with_members = c->members.flight;
+    c->members.flight       = false;
     const int what = c->mor.end("hc_morison_end without hc_morison_begin", &c->mor2);
+    if (what == 2 && with_members) c->members.done = true;  // hc_get_morison_member_forces answers with this evaluation
     require(out != nullptr, HC_ERR_INVALID, "null output");
-    if (what == 2) std::copy(c->morison.h_out.p, c->morison.h_out.p + c->Dloc, out);
+    if (what == 2 && c->morison.items != 0) std::copy(c->morison.h_out.p, c->morison.h_out.p + c->Dloc, out);
     else std::fill(out, out + c->Dloc, 0.0);
+    if (what == 2 && with_members) {  // elements + members, one addition per component of a body that carries members
+        const hc::MorisonMemberData& m = c->members;
+        for (int lb = 0; lb < c->nloc; ++lb)
+            if (m.off[lb + 1] != m.off[lb])
+                for (int k = 6 * lb; k < 6 * lb + 6; ++k) out[k] = out[k] + m.h_out.p[k];
+    }
     HC_API_END(c)
 }
 

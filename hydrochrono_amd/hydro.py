@@ -598,7 +598,43 @@ class HydroForces:
         self._chk(self.lib.hc_set_morison_elements(self.ctx, int(b), elems, n))
         counts = self.__dict__.setdefault("_morison_counts", {})
         counts[int(b)] = n
-        self._morison_any = any(counts.values())
+        self._morison_any = any(counts.values()) or any(self.__dict__.get("_morison_member_counts", {}).values())
+
+    def set_morison_members(self, b, r0, r1, diameter, cd, cm, n_seg):
+        """Replaces the strip-member list of body b (0-based): r0, r1 are (n, 3) end points in the body frame; diameter is a scalar,
+        (n,) or (n, 2) (at r0 and at r1, linear in between); cd, cm, n_seg are scalars or (n,).  Empty arrays clear the list.  A
+        body with members counts as one that carries elements: step() returns total + Morison term (elements + members)."""
+        r0, r1 = (np.ascontiguousarray(x, dtype=np.float64).reshape(-1, 3) for x in (r0, r1))
+        if r0.shape != r1.shape:
+            raise ValueError("r0 and r1 must have the same shape (n, 3)")
+        n = r0.shape[0]
+        dia = np.asarray(diameter, dtype=np.float64)
+        dia = np.broadcast_to(dia[:, None] if dia.ndim == 1 else dia, (n, 2))
+        cd, cm = (np.broadcast_to(np.asarray(x, dtype=np.float64), (n,)) for x in (cd, cm))
+        seg = np.broadcast_to(np.asarray(n_seg), (n,))
+        if np.any(seg != np.floor(seg)):
+            raise ValueError("n_seg must be whole numbers")
+        members = (capi.MorisonMember * max(n, 1))()
+        for e in range(n):
+            m = members[e]
+            m.r0[:], m.r1[:] = r0[e], r1[e]
+            m.d0, m.d1, m.cd, m.cm, m.n_seg = dia[e, 0], dia[e, 1], cd[e], cm[e], int(seg[e])
+        self._chk(self.lib.hc_set_morison_members(self.ctx, int(b), members, n))
+        counts = self.__dict__.setdefault("_morison_member_counts", {})
+        counts[int(b)] = n
+        self._morison_any = any(counts.values()) or any(self.__dict__.get("_morison_counts", {}).values())
+
+    def morison_member_count(self, b):
+        n = C.c_int()
+        self._chk(self.lib.hc_get_morison_member_count(self.ctx, int(b), C.byref(n)))
+        return n.value
+
+    def morison_member_forces(self, b):
+        """The 6-vectors (n, 6) of the members of body b (0-based, owned) in the last completed evaluation; their serial sum in
+        member order is the body's member part, bit for bit."""
+        out = np.empty((self.morison_member_count(b), 6))
+        self._chk(self.lib.hc_get_morison_member_forces(self.ctx, int(b), _dp(out.reshape(-1)) if out.size else _dp(np.empty(1))))
+        return out
 
     def morison_count(self, b):
         n = C.c_int()
@@ -1321,6 +1357,16 @@ class HydroGroup:
 
     def morison_second_order_directional(self):
         return self.shards[0].morison_second_order_directional()
+
+    def morison_member_count(self, b):
+        return self.shards[0].morison_member_count(b)
+
+    def morison_member_forces(self, b):
+        # the shard that owns the body answers
+        for h in self.shards:
+            if h.b0 <= int(b) < h.b1:
+                return h.morison_member_forces(b)
+        raise IndexError(f"body {b} out of range")
 
     def morison_increments(self, b):
         # the shard that owns the body answers

@@ -145,6 +145,14 @@ struct MorisonElement {
     std::array<double, 3> r{0, 0, 0}, cd_area{0, 0, 0}, cm_vol{0, 0, 0};
 };
 
+// A Morison strip member of a body (not in the reference; hc_morison_member): a slender cylinder from r0 to r1 in the body frame,
+// diameter d0 at r0 and d1 at r1, transverse Cd and Cm, integrated along its wet length in n_seg segments (1..64).
+struct MorisonMember {
+    std::array<double, 3> r0{0, 0, 0}, r1{0, 0, 0};
+    double d0 = 0.0, d1 = 0.0, cd = 0.0, cm = 0.0;
+    int n_seg = 1;
+};
+
 // What the Morison elements of a body saw of the second-order sea (TestHydro::GetMorisonIncrements): per element the world point
 // and the increments of WaveBase::GetSecondOrderElevation / Velocity / Acceleration there.
 struct MorisonIncrements {
@@ -305,8 +313,49 @@ class TestHydro {
         for (hc_ctx* c : ctxs_) check(c, hc_set_morison_elements(c, body_index_1_based - 1, raw.data(), static_cast<int>(raw.size())));
         morison_count_.resize(static_cast<size_t>(num_bodies_), 0);
         morison_count_[static_cast<size_t>(body_index_1_based - 1)] = raw.size();
-        have_morison_ = std::any_of(morison_count_.begin(), morison_count_.end(), [](size_t n) { return n != 0; });
+        update_have_morison();
         have_time_    = false;  // the cached total belongs to the lists before
+    }
+    // Morison strip members (hc_set_morison_members): cylinders between two end points, cut at the free surface.  A body with
+    // members counts as one that carries elements: the Morison term CoordinateFuncForBody adds is elements + members.  An empty
+    // vector clears the list.
+    void SetMorisonMembers(int body_index_1_based, const std::vector<MorisonMember>& members) {
+        if (body_index_1_based < 1 || body_index_1_based > num_bodies_) throw std::out_of_range("SetMorisonMembers: body index out of range");
+        std::vector<hc_morison_member> raw(members.size());
+        for (size_t e = 0; e < members.size(); ++e) {
+            for (int k = 0; k < 3; ++k) {
+                raw[e].r0[k] = members[e].r0[k];
+                raw[e].r1[k] = members[e].r1[k];
+            }
+            raw[e].d0    = members[e].d0;
+            raw[e].d1    = members[e].d1;
+            raw[e].cd    = members[e].cd;
+            raw[e].cm    = members[e].cm;
+            raw[e].n_seg = members[e].n_seg;
+        }
+        for (hc_ctx* c : ctxs_) check(c, hc_set_morison_members(c, body_index_1_based - 1, raw.data(), static_cast<int>(raw.size())));
+        morison_member_count_.resize(static_cast<size_t>(num_bodies_), 0);
+        morison_member_count_[static_cast<size_t>(body_index_1_based - 1)] = raw.size();
+        update_have_morison();
+        have_time_ = false;
+    }
+    // The 6-vectors of a body's members in the last evaluation (hc_get_morison_member_forces), from the context that owns the body
+    std::vector<std::array<double, 6>> GetMorisonMemberForces(int body_index_1_based) {
+        if (body_index_1_based < 1 || body_index_1_based > num_bodies_) throw std::out_of_range("GetMorisonMemberForces: body index out of range");
+        const int b = body_index_1_based - 1;
+        for (hc_ctx* c : ctxs_) {
+            int b0 = 0, b1 = 0, n = 0;
+            check(c, hc_get_shard(c, &b0, &b1));
+            if (b < b0 || b >= b1) continue;
+            check(c, hc_get_morison_member_count(c, b, &n));
+            std::vector<std::array<double, 6>> out(static_cast<size_t>(n));
+            std::vector<double> flat(6 * static_cast<size_t>(n) + 1);
+            check(c, hc_get_morison_member_forces(c, b, flat.data()));
+            for (size_t e = 0; e < out.size(); ++e)
+                for (size_t k = 0; k < 6; ++k) out[e][k] = flat[6 * e + k];
+            return out;
+        }
+        throw std::out_of_range("GetMorisonMemberForces: no context owns the body");
     }
     // mwl, regular phase and stretching of the kinematics the elements see (those of WaveBase::GetVelocity & co.)
     void SetMorisonOptions(double mwl = 0.0, double regular_phase = 0.0, bool wave_stretching = true) {
@@ -1034,7 +1083,12 @@ class TestHydro {
     std::vector<double> total_force_, pos_, rpy_, lin_, ang_;
     std::vector<double> morison_force_;  // the Morison term of the last evaluation
     std::vector<size_t> morison_count_;  // elements per body
-    bool have_morison_ = false;
+    std::vector<size_t> morison_member_count_;  // strip members per body
+    bool have_morison_ = false;  // some body carries elements or members
+    void update_have_morison() {
+        const auto any = [](const std::vector<size_t>& v) { return std::any_of(v.begin(), v.end(), [](size_t n) { return n != 0; }); };
+        have_morison_ = any(morison_count_) || any(morison_member_count_);
+    }
     std::vector<double> nonlinear_force_;  // buoy | fk | hs_lin of the last evaluation
     std::vector<size_t> panel_count_;      // surface panels or triangles per body (a body carries one kind)
     int nonlinear_mode_ = 0;               // 0 off, 1 buoyancy, 2 buoyancy + Froude-Krylov

@@ -648,7 +648,8 @@ int hc_get_morison_count(hc_ctx* ctx, int body, int* n);
 int hc_set_morison_options(hc_ctx* ctx, const hc_wave_kinematics_opts* o);
 /* begin enqueues (state as for hc_step: [3N] each), end waits and copies the 6 * n_local values of the owned bodies; exactly one
  * end per begin.  Needs hc_finalize.  HC_ERR_INVALID on a non-finite state or t, on a second begin, on an end without a begin;
- * nothing stays pending after a failure.  With no element on any owned body: zeros, no launch. */
+ * nothing stays pending after a failure.  With no element and no strip member (hc_set_morison_members, below) on any owned body:
+ * zeros, no launch. */
 int hc_morison_begin(hc_ctx* ctx, double t, const double* pos, const double* rpy, const double* linvel, const double* angvel);
 int hc_morison_end(hc_ctx* ctx, double* out_Dlocal);
 int hc_compute_morison(hc_ctx* ctx, double t, const double* pos, const double* rpy, const double* linvel, const double* angvel,
@@ -699,6 +700,49 @@ int hc_get_morison_second_order_directional(hc_ctx* ctx, int* on);
  * second-order part -- no components, empty bands, no element on an owned body -- forgets the one before, and so does
  * hc_set_morison_elements), or the body is not owned by this context. */
 int hc_get_morison_increments(hc_ctx* ctx, int body, double* p, double* eta2, double* vel2, double* acc2);
+
+/* Morison strip members (DESIGN.md 3.7c'): a slender cylinder given as OpenFAST and WEC-Sim give it -- two end points, a diameter
+ * at each, Cd and Cm -- integrated along its wet length.  The drag acts along the flow component normal to the member's axis, so an
+ * inclined member is right for every flow direction, and the member is cut at the instantaneous free surface, so the force is
+ * continuous in the draft.  With R, d = R r, p = pos + d, v_e = linvel + angvel x d exactly as the elements define them, the state
+ * of hc_step and the options of hc_set_morison_options:
+ *     nodes      j = 0..n_seg at r_j = r0 + (j / n_seg)(r1 - r0), P_j = pos + R r_j;  eta_j = the first-order elevation
+ *                hc_wave_kinematics returns at (P_j, t) with the Morison options (the directional sea while hc_set_wave_directions
+ *                holds, still water where the elements have still water);  h_j = P_j.z - mwl - eta_j;  the node is wet iff h_j <= 0
+ *     segment    (nodes j, j + 1, local sigma in [0, 1] from node j), h taken as linear along it: both nodes wet -- the wet part is
+ *                [0, 1]; both dry -- nothing; else one cut at sigma* = h_x / (h_x - h_y) measured from the wet end x (h_x <= 0 < h_y):
+ *                the wet part [sigma_a, sigma_b] is [0, sigma*] when node j is the wet one and [1 - sigma*, 1] when node j + 1 is
+ *     quadrature two Gauss-Legendre points per wet segment, sigma_g = sigma_a + (sigma_b - sigma_a)(1/2 -+ 1/(2 sqrt 3)), weight
+ *                w_g = 1/2 (sigma_b - sigma_a) |r1 - r0| / n_seg (exact for a cubic load per length, so for a constant one at any n_seg)
+ *     per point  s = (j + sigma_g) / n_seg, r_g = r0 + s (r1 - r0), D_g = d0 + s (d1 - d0);  d, p, v_e as above;  u_f, a_f = what an
+ *                element at p sees: hc_wave_kinematics at (p, t) with the Morison options, Wheeler stretching by the point's own
+ *                eta when it is on, times the Morison ramp; no second wet test at the point;  with the unit axis
+ *                a^ = R (r1 - r0) / |r1 - r0|:  q = u_f - v_e,  q_n = q - (q . a^) a^,  a_n = a_f - (a_f . a^) a^,
+ *                dF = w_g [1/2 rho cd D_g |q_n| q_n + rho cm (pi / 4) D_g^2 a_n],  dM = d x dF
+ * A member's 6-vector is the serial sum of its Gauss points (segment order, the lower point first); a body's member vector is the
+ * serial sum of its members in index order: hc_get_morison_member_forces returns the first level [n][6], and summing its rows
+ * serially in FP64 reproduces the second bit for bit.  hc_morison_end / hc_compute_morison return, per component, elements + members
+ * with one IEEE addition for a body that carries members, and exactly the bits they returned before for a body that carries none.
+ * A body's bits depend on that body's state, its own member list, the wave model with its directions, t and the options only.
+ * Members see the first-order sea: while hc_set_morison_second_order is on and an owned body carries members, hc_morison_begin
+ * answers HC_ERR_UNSUPPORTED and nothing stays pending.
+ * Not included: axial (end-cap) drag and added mass, which stay point elements; MacCamy-Fuchs diffraction; the body-acceleration
+ * term; members on the second-order sea. */
+typedef struct hc_morison_member {
+    double r0[3], r1[3]; /* end points in the body frame, relative to the point pos[b] locates [m]; r0 != r1 */
+    double d0, d1;       /* diameter at r0 and at r1 [m], linear in between; >= 0 */
+    double cd;           /* transverse drag coefficient, >= 0 */
+    double cm;           /* transverse inertia coefficient (1 + Ca outside the BEM mesh, Ca or 0 inside), >= 0 */
+    int n_seg;           /* segments along the member, 1..64 */
+} hc_morison_member;     /* 88 bytes */
+/* Replaces the member list of `body` (0-based, any body of the system); n = 0 clears it; at most 1024 per body.  HC_ERR_INVALID: body
+ * out of range, n < 0, a null list with n > 0, a non-finite value, a negative diameter or coefficient, r0 == r1, n_seg outside
+ * 1..64, more than 1024 members, or a hc_morison_begin without its end. */
+int hc_set_morison_members(hc_ctx* ctx, int body, const hc_morison_member* members, int n);
+int hc_get_morison_member_count(hc_ctx* ctx, int body, int* n);
+/* The 6-vectors of the members of `body` in the last completed evaluation, [n][6].  HC_ERR_INVALID: a body this context does not
+ * own, a null output, or no evaluation with members completed since a member list was last set. */
+int hc_get_morison_member_forces(hc_ctx* ctx, int body, double* out_nx6);
 
 /* ------------------------------------------------------------------------------------------------
  * Nonlinear buoyancy and Froude-Krylov forces on body surface panels (not in the reference: src/hydro_types.h:33 is a TODO): the
