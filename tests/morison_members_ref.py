@@ -33,6 +33,8 @@ The bound returned with it (per body and component) is derived, not tuned.  It h
      and the products a few ulp of the uncancelled magnitude each (the 64).  Per point: U = |(|u_f| + |linvel| + |angvel x d| by
      absolute products)|_2, A = |a_f|_2, f_mag = 1/2 rho cd D U^2 + rho cm (pi / 4) D^2 A, force magnitude w_g f_mag per component,
      moment magnitude |d|_2 sqrt(3) w_g f_mag.
+A member's own row carries the same three parts accumulated over that member's points alone, with items_m = 2 n_seg_m (the row is
+one serial sum of the member's points, at most items_m roundings, and the 64 are per point, not per sum): `member_bound`.
 """
 import numpy as np
 
@@ -72,13 +74,14 @@ def member_lists(r0, r1, diameter, cd, cm, n_seg):
 def members(comp, depth, rho, lists, t, pos, rpy, linvel, angvel, mwl=0.0, stretching=False, ramp=1.0):
     """lists: per body None or (r0 (n, 3), r1 (n, 3), diameter (n, 2), cd (n), cm (n), n_seg (n)).  comp: (A, w, k, phi), with a
     fifth entry theta for the directional sea, or None for still water.
-    Returns dict(F [N][6], bound [N][6], members = per body [n][6], margin = min |h_j| over all nodes, eta_bound = max delta h_j,
+    Returns dict(F [N][6], bound [N][6], members = per body [n][6], member_bound = per body [n][6], points = per body and member the
+    Gauss points' (dF, dM) [2 x wet or cut segments][6] in index order, margin = min |h_j| over all nodes, eta_bound = max delta h_j,
     clear = every node has |h_j| > delta h_j, cases = per body the set of segment cases met: 'wet', 'dry', 'cut0' (node j wet),
     'cut1' (node j + 1 wet))."""
     pos, rpy, linvel, angvel = (np.asarray(x, dtype=np.float64).reshape(-1, 3) for x in (pos, rpy, linvel, angvel))
     N = pos.shape[0]
     F, bound = np.zeros((N, 6)), np.zeros((N, 6))
-    per_member, cases = [], []
+    per_member, per_member_bound, per_point, cases = [], [], [], []
     margin, eta_bound, clear = np.inf, 0.0, True
     sumA = 0.0 if comp is None else float(np.sum(np.abs(comp[0])))
     kmax = 0.0 if comp is None else float(np.max(np.abs(comp[2])))
@@ -89,12 +92,14 @@ def members(comp, depth, rho, lists, t, pos, rpy, linvel, angvel, mwl=0.0, stret
         cases.append(seen)
         if n == 0:
             per_member.append(np.zeros((0, 6)))
+            per_member_bound.append(np.zeros((0, 6)))
+            per_point.append([])
             continue
         R = mr.rotation(rpy[b])
         pb = pos[b].astype(LD)
         w = angvel[b].astype(LD)
         wn = float(np.sqrt(np.sum(w * w)))
-        rows = np.zeros((n, 6), dtype=LD)
+        rows, row_bound, pts = np.zeros((n, 6), dtype=LD), np.zeros((n, 6), dtype=LD), []
         kin_err, cut_err, mag = np.zeros(6, dtype=LD), np.zeros(6, dtype=LD), np.zeros(6, dtype=LD)
         items = 0
         for m in range(n):
@@ -136,7 +141,9 @@ def members(comp, depth, rho, lists, t, pos, rpy, linvel, angvel, mwl=0.0, stret
                     dsig.append(dsg)
             items += 2 * ns
             if not sg:
+                pts.append(np.zeros((0, 6)))
                 continue
+            kin_m, cut_m, mag_m = np.zeros(6, dtype=LD), np.zeros(6, dtype=LD), np.zeros(6, dtype=LD)
             sg, wg, dsig = np.array(sg, dtype=LD), np.array(wg, dtype=LD), np.array(dsig)
             rg = r0[None, :] + sg[:, None] * e[None, :]
             D = d0 + sg * (d1 - d0)
@@ -157,20 +164,21 @@ def members(comp, depth, rho, lists, t, pos, rpy, linvel, angvel, mwl=0.0, stret
             dF = wg[:, None] * (c1[:, None] * speed[:, None] * qn + c2[:, None] * an)
             dM = np.cross(d, dF)
             rows[m, :3], rows[m, 3:] = dF.sum(axis=0), dM.sum(axis=0)
+            pts.append(np.concatenate([dF, dM], axis=1).astype(np.float64))
             dlen = np.sqrt(np.sum(d * d, axis=1))
             # 1: kinematics
             du = np.sqrt(np.sum((KIN_TOL * usc) ** 2, axis=1))
             da = np.sqrt(np.sum((KIN_TOL * asc) ** 2, axis=1))
             eF = wg * (c1 * 2 * speed * du + c2 * da)
-            kin_err[:3] += eF.sum()
-            kin_err[3:] += (dlen * SQRT3 * eF).sum()
+            kin_m[:3], kin_m[3:] = eF.sum(), (dlen * SQRT3 * eF).sum()
+            kin_err += kin_m
             # 3: magnitudes without cancellation
             Uf = np.sqrt(np.sum(np.abs(uf) ** 2, axis=1)).astype(LD)
             U = np.sqrt(np.sum((np.abs(uf).astype(LD) + ve_abs) ** 2, axis=1))
             A = np.sqrt(np.sum(af * af, axis=1)).astype(LD)
             fmag = c1 * U * U + c2 * A
-            mag[:3] += (wg * fmag).sum()
-            mag[3:] += (dlen * SQRT3 * wg * fmag).sum()
+            mag_m[:3], mag_m[3:] = (wg * fmag).sum(), (dlen * SQRT3 * wg * fmag).sum()
+            mag += mag_m
             # 2: the cut (every point of a cut segment carries its segment's delta sigma*; each segment is counted once, with
             # the larger of its two points' figures)
             Dmax, seg_len = max(d0, d1), L / LD(ns)
@@ -183,7 +191,12 @@ def members(comp, depth, rho, lists, t, pos, rpy, linvel, angvel, mwl=0.0, stret
             for i in range(0, len(sg), 2):
                 cut_err[:3] += max(per_pt[i], per_pt[i + 1])
                 cut_err[3:] += max(per_pt[i] * arm[i], per_pt[i + 1] * arm[i + 1])
+                cut_m[:3] += max(per_pt[i], per_pt[i + 1])
+                cut_m[3:] += max(per_pt[i] * arm[i], per_pt[i + 1] * arm[i + 1])
+            row_bound[m] = kin_m + cut_m + (2 * ns + 64) * EPS * mag_m
         per_member.append(rows.astype(np.float64))
+        per_member_bound.append(row_bound.astype(np.float64))
+        per_point.append(pts)
         F[b] = rows.sum(axis=0).astype(np.float64)
         bound[b] = (kin_err + cut_err + (items + 64) * EPS * mag).astype(np.float64)
-    return dict(F=F, bound=bound, members=per_member, margin=margin, eta_bound=eta_bound, clear=clear, cases=cases)
+    return dict(F=F, bound=bound, members=per_member, member_bound=per_member_bound, points=per_point, margin=margin, eta_bound=eta_bound, clear=clear, cases=cases)

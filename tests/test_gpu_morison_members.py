@@ -85,7 +85,8 @@ def serial_sum(rows):
 
 
 def compare(h, case, lists, comp, t, state, what, mwl=0.0, stretching=False, ramp=1.0, need=()):
-    """GPU against the restatement, inside the derived bound; asserts the node margin first.  Returns the GPU result and the reference."""
+    """GPU against the restatement, inside the derived bound, the body vectors and every member's row (`member_bound`: the same three
+    parts over that member's points alone); asserts the node margin first.  Returns the GPU result and the reference."""
     ref = mm.members(comp, case["water_depth"], case["rho"], lists, t, *state, mwl=mwl, stretching=stretching, ramp=ramp)
     assert ref["clear"] and ref["margin"] > ref["eta_bound"], \
         f"{what}: a node is {ref['margin']:.3e} m from the free surface, the eta bound is {ref['eta_bound']:.3e} m (choose other inputs)"
@@ -100,6 +101,10 @@ def compare(h, case, lists, comp, t, state, what, mwl=0.0, stretching=False, ram
         if ml is not None and h.b0 <= b < h.b1:
             rows = h.morison_member_forces(b)
             assert rows.shape == ref["members"][b].shape
+            merr = np.abs(rows - ref["members"][b])
+            mworst = float(np.max(merr / np.maximum(ref["member_bound"][b], 1e-300))) if rows.size else 0.0
+            print(f"{what}: body {b}: worst |member row - ref| / member bound = {mworst:.3e}")
+            assert np.all(merr <= ref["member_bound"][b]), f"{what}: body {b}'s member rows: worst {mworst:.3e} of the member bound"
             assert same_bits(serial_sum(rows), got[b - h.b0]), f"{what}: the serial sum of body {b}'s member rows is not the body vector"
     for c in need:
         assert any(c in s for s in ref["cases"]), (what, c, ref["cases"])

@@ -1,7 +1,11 @@
 """The begin / end protocol the four terms beside the step share (csrc/hc_side.hpp: Morison elements, the nonlinear surface pressure,
 the drift and the sum-frequency QTF forces): the same sequence of statuses for each of them, on the smallest input each accepts --
-two bodies under a regular wave, one Morison element, one surface panel, a drift and a sum table with nq = 2.  The terms share one
-context: every lane is its own, so the order of the cases does not matter."""
+two bodies under a regular wave, one Morison element, one surface panel, a drift and a sum table with nq = 2; and once more for the
+Morison lane opened by one strip member alone.  The terms share one
+context.  The Morison, nonlinear, drift and sum lanes are each their own; the two Morison cases (and the Morison case of
+test_increments_follow_the_completed_evaluation) share the Morison lane and clean up after themselves -- "morison" sets its own
+element at its start, "morison members" clears that element first and its member when it leaves -- so the order of the cases does
+not matter."""
 import ctypes as C
 
 import numpy as np
@@ -39,6 +43,14 @@ def element():
     return e
 
 
+def member():
+    from hydrochrono_amd import capi
+    m = (capi.MorisonMember * 1)()
+    m[0].r0[:], m[0].r1[:] = (0, 0, -3.0), (0, 0, 2.0)
+    m[0].d0, m[0].d1, m[0].cd, m[0].cm, m[0].n_seg = 1.0, 1.0, 1.0, 0.0, 2
+    return m
+
+
 def panel():
     from hydrochrono_amd import capi
     p = (capi.SurfacePanel * 1)()
@@ -52,7 +64,18 @@ class Term:
 
     def __init__(self, lib, c, name):
         self.name, self.null_end = name, name != "nonlinear"
-        if name == "morison":
+        self.leave = lambda: None
+        if name == "morison members":  # the Morison lane opened by hc_set_morison_members alone: it never has an element
+            assert lib.hc_set_morison_elements(c, 0, None, 0) == 0
+            self.outs = [OUT.copy()]
+            self.begin = lambda: lib.hc_morison_begin(c, 0.0, dp(POS), dp(Z), dp(LIN), dp(Z))
+            self.end = lambda outs: lib.hc_morison_end(c, *outs)
+            self.fill = lambda: lib.hc_set_morison_members(c, 0, member(), 1)
+            self.clear = lambda: lib.hc_set_morison_members(c, 0, None, 0)
+            self.setters = [self.fill, lambda: lib.hc_set_morison_options(c, None),
+                            lambda: lib.hc_set_morison_second_order(c, 0, 0.0, np.inf, 0.0, np.inf, 1)]
+            self.leave = self.clear  # (the other Morison cases of this module's one context switch the second-order sea on)
+        elif name == "morison":
             self.outs = [OUT.copy()]
             self.begin = lambda: lib.hc_morison_begin(c, 0.0, dp(POS), dp(Z), dp(LIN), dp(Z))
             self.end = lambda outs: lib.hc_morison_end(c, *outs)
@@ -90,11 +113,18 @@ class Term:
         return self.end([dp(o) for o in self.outs])
 
 
-@pytest.mark.parametrize("name", ["morison", "nonlinear", "drift", "sum"])
+@pytest.mark.parametrize("name", ["morison", "nonlinear", "drift", "sum", "morison members"])
 def test_begin_end_protocol(ctx, name):
+    term = Term(ctx.lib, ctx.ctx, name)
+    try:
+        begin_end_protocol(term, name)
+    finally:
+        term.leave()
+
+
+def begin_end_protocol(term, name):
     from hydrochrono_amd import capi
     INV, OK = capi.HC_ERR_INVALID, capi.HC_OK
-    term = Term(ctx.lib, ctx.ctx, name)
     assert term.fill() == OK
     # begin twice; no setter and no options call while one is pending; exactly one end per begin
     assert term.begin() == OK

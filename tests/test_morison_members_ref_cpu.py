@@ -109,6 +109,45 @@ def test_force_is_continuous_in_the_draft_where_an_element_list_jumps():
         assert step_e > lip * delta
 
 
+def test_body_bound_keeps_its_bits_beside_the_per_member_bound():
+    """`bound` of two inputs of this file, bit for bit as before `member_bound` was split off the same derivation"""
+    ref = mm.members(None, 50.0, RHO, one([0.3, -0.2, -7.25], [0.3, -0.2, 4.0], 1.3, 0.9, 2.0, 3), 0.0, Z3, Z3, [[0.7, 0, 0]], Z3)
+    want = [float.fromhex("0x1.2ced300000000p-35")] * 3 + [float.fromhex("0x1.f17aaa5633fbap-33")] * 3
+    assert ref["bound"][0].tolist() == want
+    A, om, phi, t = 1.0, 1.1, 0.4, 2.0  # the column of convergence_errors() at n_seg = 8
+    comp = wk.regular_components(A, om, om * om / 9.81, phi)
+    ref = mm.members(comp, np.inf, RHO, one([0, 0, -21.0], [0, 0, 6.0], 2.0, 0.0, 2.0, 8), t, Z3, Z3, Z3, Z3)
+    want = [float.fromhex("0x1.09b7046f9497bp-20")] * 3 + [float.fromhex("0x1.5acfaf787ff4cp-17")] * 3
+    assert ref["bound"][0].tolist() == want
+    # one member: its own bound is the body's with items_m = items
+    assert np.array_equal(ref["member_bound"][0][0], ref["bound"][0])
+
+
+def test_a_gauss_point_credited_to_the_neighbouring_member_breaks_the_member_bound_only():
+    """What `member_bound` is for: the last Gauss point of a member summed into the next member's row (a first-segment offset or a
+    point-to-member entry wrong by one) moves both rows by a whole point's force, and the body total by summation order alone."""
+    A, om = 0.6, 1.4
+    comp = wk.regular_components(A, om, om * om / 9.81, 0.3)
+    r0 = [[0.0, 0.0, -6.0], [1.0, 1.0, -7.0], [-4.0, -3.0, -5.0]]
+    r1 = [[0.0, 0.0, 7.0], [1.5, 1.0, -2.0], [4.0, 3.0, 5.5]]
+    lists = [mm.member_lists(r0, r1, [1.2, 0.7, 0.9], 1.0, 2.0, [4, 2, 3])]
+    ref = mm.members(comp, np.inf, RHO, lists, 1.7, [[0.0, 0.0, -2.0]], Z3, [[0.4, 0.1, 0.0]], [[0.0, 0.02, 0.01]])
+    assert ref["clear"]
+    pts = ref["points"][0]
+    right = np.array([p.sum(axis=0) for p in pts])
+    assert np.all(np.abs(right - ref["members"][0]) <= ref["member_bound"][0]) and np.all(ref["member_bound"][0] > 0.0)
+    for m in (0, 1):
+        wrong = [p.copy() for p in pts]
+        moved, wrong[m] = wrong[m][-1:], wrong[m][:-1]
+        wrong[m + 1] = np.concatenate([moved, wrong[m + 1]])
+        rows = np.array([p.sum(axis=0) for p in wrong])
+        assert np.abs(moved[0, :3]).max() > 1.0
+        for k in (m, m + 1):
+            assert np.any(np.abs(rows[k] - ref["members"][0][k]) > ref["member_bound"][0][k]), (m, k)
+        assert np.all(np.abs(rows.sum(axis=0) - ref["F"][0]) <= ref["bound"][0]), m
+        assert np.array_equal(rows[2 - 2 * m], right[2 - 2 * m])  # the third member is not touched
+
+
 def convergence_errors():
     """|F_x - closed form| of the inertia force on a fixed vertical cylinder in a deep-water regular wave, integrated to the
     instantaneous surface: F_x = rho cm (pi / 4) D^2 w^2 A sin(theta) (e^{k eta} - e^{-k draft}) / k, theta = -w t + phi at x = 0"""
