@@ -1,6 +1,7 @@
 """HydroForces -- Python mirror of the reference's `TestHydro` surface (include/hydroc/hydro_forces.h:164-285),
 implemented purely by calls into the C ABI (include/hydrochrono_amd.h).  No arithmetic happens here."""
 import ctypes as C
+from typing import Callable, NamedTuple
 
 import numpy as np
 
@@ -215,79 +216,11 @@ class HydroForces:
         radm = self.__dict__.get("_radm_any")
         if morison or nonlinear or drift or sumf or radm:
             # the side terms run on streams of their own beside the step; the composition is made here (the C ABI total stays the
-            # reference's): begin all, step, end all
-            if nonlinear:
-                self._chk(self.lib.hc_nonlinear_begin(self.ctx, t, _dp(a[0]), _dp(a[1])))
-            if morison:
-                rc_begin = self.lib.hc_morison_begin(self.ctx, t, _dp(a[0]), _dp(a[1]), _dp(a[2]), _dp(a[3]))
-                if rc_begin:
-                    if nonlinear:
-                        self.lib.hc_nonlinear_end(self.ctx, None, None, None)  # nothing stays pending
-                    self._chk(rc_begin)
-            if drift:
-                rc_begin = self.lib.hc_drift_begin(self.ctx, t, _dp(a[0]))
-                if rc_begin:
-                    if nonlinear:
-                        self.lib.hc_nonlinear_end(self.ctx, None, None, None)
-                    if morison:
-                        self.lib.hc_morison_end(self.ctx, _dp(np.empty(self.D_local)))
-                    self._chk(rc_begin)
-            if sumf:
-                rc_begin = self.lib.hc_sum_qtf_begin(self.ctx, t, _dp(a[0]))
-                if rc_begin:
-                    if nonlinear:
-                        self.lib.hc_nonlinear_end(self.ctx, None, None, None)
-                    if morison:
-                        self.lib.hc_morison_end(self.ctx, _dp(np.empty(self.D_local)))
-                    if drift:
-                        self.lib.hc_drift_end(self.ctx, _dp(np.empty(self.D_local)))
-                    self._chk(rc_begin)
-            if radm:
-                rc_begin = self.lib.hc_radiation_modes_begin(self.ctx, t, _dp(a[2]), _dp(a[3]))
-                if rc_begin:
-                    if nonlinear:
-                        self.lib.hc_nonlinear_end(self.ctx, None, None, None)
-                    if morison:
-                        self.lib.hc_morison_end(self.ctx, _dp(np.empty(self.D_local)))
-                    if drift:
-                        self.lib.hc_drift_end(self.ctx, _dp(np.empty(self.D_local)))
-                    if sumf:
-                        self.lib.hc_sum_qtf_end(self.ctx, _dp(np.empty(self.D_local)))
-                    self._chk(rc_begin)
-            rc = capi.step_raw(self.lib)(self.ctx, t, a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, a[3].ctypes.data, out.ctypes.data)
-            rc_end = 0
-            if nonlinear:
-                nl = tuple(np.empty(self.D_local) for _ in range(3))
-                rc_end = self.lib.hc_nonlinear_end(self.ctx, _dp(nl[0]), _dp(nl[1]), _dp(nl[2]))
-            if morison:
-                mor = np.empty(self.D_local)
-                rc_end = self.lib.hc_morison_end(self.ctx, _dp(mor)) or rc_end
-            if drift:
-                dr = np.empty(self.D_local)
-                rc_end = self.lib.hc_drift_end(self.ctx, _dp(dr)) or rc_end
-            if sumf:
-                sm = np.empty(self.D_local)
-                rc_end = self.lib.hc_sum_qtf_end(self.ctx, _dp(sm)) or rc_end
-            if radm:
-                rm = np.empty(self.D_local)
-                rc_end = self.lib.hc_radiation_modes_end(self.ctx, _dp(rm)) or rc_end
-            self._chk(rc or rc_end)
-            if nonlinear:
-                self._nonlinear_last = nl
-                out = _compose_nonlinear(out, nl, self._nonlinear_mode, self._panel_counts, self.b0, self.b1)
-            if morison:
-                self._morison_last = mor
-                out = out + mor
-            if drift:
-                self._drift_last = dr
-                out = out + dr
-            if sumf:
-                self._sum_last = sm
-                out = out + sm
-            if radm:
-                self._radm_last = rm
-                out = out - rm
-            return out
+            # reference's): the one-shard case of the driver that HydroGroup.step uses
+            def step():
+                return capi.step_raw(self.lib)(self.ctx, t, a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, a[3].ctypes.data, out.ctypes.data)
+            return _step_with_side_terms(self, self, [(self.ctx, 0, self.D_local)], (nonlinear, morison, drift, sumf, radm), step, t, a, out,
+                                         self.b0, self.b1)
         # raw addresses through a c_void_p prototype: this call sits in per-step loops
         rc = capi.step_raw(self.lib)(self.ctx, t, a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, a[3].ctypes.data, out.ctypes.data)
         if rc:
@@ -1082,6 +1015,99 @@ def _compose_nonlinear(total, nl, mode, counts, b0, b1):
     return out
 
 
+class _SideTerm(NamedTuple):
+    """A term that runs on a lane of its own beside the step: its C begin / end pair, which of (pos, rpy, linvel, angvel) the begin
+    takes, how many D_local arrays the end fills, whether it is on (asked of a HydroForces), where the last value is kept, and how
+    it joins the total: compose(out, x, cfg, b0, b1), cfg the HydroForces that holds the nonlinear mode and the panel counts."""
+    name: str
+    begin: str
+    end: str
+    slots: tuple
+    nout: int
+    on: Callable
+    last: str
+    compose: Callable
+
+
+# the order of the rows is the order of the begins, of the ends and of the composition
+_SIDE_TERMS = (
+    _SideTerm("nonlinear", "hc_nonlinear_begin", "hc_nonlinear_end", (0, 1), 3, lambda h: h._nonlinear_on(), "_nonlinear_last",
+              lambda out, x, cfg, b0, b1: _compose_nonlinear(out, x, cfg._nonlinear_mode, cfg._panel_counts, b0, b1)),
+    _SideTerm("morison", "hc_morison_begin", "hc_morison_end", (0, 1, 2, 3), 1, lambda h: h.__dict__.get("_morison_any"), "_morison_last",
+              lambda out, x, *_: out + x),
+    _SideTerm("drift", "hc_drift_begin", "hc_drift_end", (0,), 1, lambda h: h._drift_on(), "_drift_last", lambda out, x, *_: out + x),
+    _SideTerm("sum", "hc_sum_qtf_begin", "hc_sum_qtf_end", (0,), 1, lambda h: h._sum_on(), "_sum_last", lambda out, x, *_: out + x),
+    _SideTerm("radm", "hc_radiation_modes_begin", "hc_radiation_modes_end", (2, 3), 1, lambda h: h.__dict__.get("_radm_any"), "_radm_last",
+              lambda out, x, *_: out - x),
+)
+_NONLINEAR, _MORISON, _DRIFT, _SUM, _RADM = _SIDE_TERMS
+
+
+def _side_error(lib, ctx, rc):
+    return HydroError(rc, lib.hc_last_error(ctx).decode())
+
+
+def _side_drop(lib, ctxs, term):
+    """Ends `term` on the contexts (ctx, first row, rows) into scratch arrays: nothing stays pending."""
+    end = getattr(lib, term.end)
+    for ctx, _, n in ctxs:
+        end(ctx, *(_dp(np.empty(n)) for _ in range(term.nout)))
+
+
+def _side_begin(lib, ctxs, term, t, a):
+    """Begins `term` on every context with the arrays a[slot]; a refusal ends it on the contexts before and is raised."""
+    begin = getattr(lib, term.begin)
+    args = [_dp(a[s]) for s in term.slots]
+    for g, (ctx, _, _) in enumerate(ctxs):
+        rc = begin(ctx, float(t), *args)
+        if rc:
+            err = _side_error(lib, ctx, rc)
+            _side_drop(lib, ctxs[:g], term)
+            raise err
+
+
+def _side_end(lib, ctxs, term, D):
+    """Ends `term` on every context, each into its rows of arrays of D: (the array, or the tuple of them where the term has several;
+    the error of the first context that refused, or None)."""
+    end = getattr(lib, term.end)
+    val = tuple(np.empty(D) for _ in range(term.nout))
+    err = None
+    for ctx, row, n in ctxs:
+        rc = end(ctx, *(_dp(x[row:row + n]) for x in val))
+        if rc and err is None:
+            err = _side_error(lib, ctx, rc)
+    return (val if term.nout > 1 else val[0]), err
+
+
+def _step_with_side_terms(owner, cfg, ctxs, on, step, t, a, out, b0, b1):
+    """The step with the terms of _SIDE_TERMS whose flag in `on` is set, on the contexts (ctx, first row, rows) of one system:
+    begin each term on every context in table order -- a refused begin ends what was begun, and is raised; step() -> status, which
+    fills `out`; end every term on every context, whatever the step answered; raise the step's error, else the first end's (table
+    order, then context order); then, and only then, keep the values in owner.<term.last> and compose them in table order."""
+    lib = owner.lib
+    terms = [term for term, flag in zip(_SIDE_TERMS, on) if flag]
+    for k, term in enumerate(terms):
+        try:
+            _side_begin(lib, ctxs, term, t, a)
+        except HydroError:
+            for earlier in terms[:k]:
+                _side_drop(lib, ctxs, earlier)
+            raise
+    rc = step()
+    err = _side_error(lib, ctxs[0][0], rc) if rc else None
+    vals = []
+    for term in terms:
+        val, end_err = _side_end(lib, ctxs, term, out.size)
+        vals.append(val)
+        err = err or end_err
+    if err:
+        raise err
+    for term, val in zip(terms, vals):
+        setattr(owner, term.last, val)
+        out = term.compose(out, val, cfg, b0, b1)
+    return out
+
+
 def read_eta_file(path):
     """IrregularWaves::ReadEtaFromFile: the `time : eta` lines of an eta file as (t, eta); HydroError with the reference's message
     on a file that cannot be opened or a line that cannot be parsed."""
@@ -1111,7 +1137,8 @@ class HydroGroup:
         if covered[0][0] != 0 or covered[-1][1] != self.N or any(a[1] != b[0] for a, b in zip(covered, covered[1:])):
             raise ValueError("the shards do not partition bodies [0, N)")
         self._ctxs = (C.c_void_p * len(self.shards))(*[h.ctx for h in self.shards])
-        self._step = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)(
+        self._side_ctxs = [(h.ctx, 6 * h.b0, h.D_local) for h in self.shards]  # (context, first row, rows) as the side-term driver takes them
+        self._step =C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_int, C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)(
             ("hc_step_multi", self.lib))
 
     @classmethod
@@ -1133,116 +1160,44 @@ class HydroGroup:
         n3 = 3 * self.N
         a = [_arr(x, n3) for x in (pos, rpy, linvel, angvel)]
         out = np.empty(self.D)
-        morison = any(h.__dict__.get("_morison_any") for h in self.shards)
-        nonlinear = self.shards[0]._nonlinear_on()  # every shard holds the lists of all bodies and the mode
-        drift = self.shards[0]._drift_on()
-        sumf = self.shards[0]._sum_on()
-        radm = self.shards[0].__dict__.get("_radm_any")  # every shard holds the lists of all bodies
-        if nonlinear:
-            self._nonlinear_begin(t, a)
-        if morison:
-            try:
-                self._morison_begin(t, a)
-            except HydroError:
-                if nonlinear:
-                    self._nonlinear_end(check=False)
-                raise
-        if drift:
-            try:
-                self._drift_begin(t, a[0])
-            except HydroError:
-                if nonlinear:
-                    self._nonlinear_end(check=False)
-                if morison:
-                    self._morison_end(check=False)
-                raise
-        if sumf:
-            try:
-                self._sum_begin(t, a[0])
-            except HydroError:
-                if nonlinear:
-                    self._nonlinear_end(check=False)
-                if morison:
-                    self._morison_end(check=False)
-                if drift:
-                    self._drift_end(check=False)
-                raise
-        if radm:
-            try:
-                self._radm_begin(t, a[2], a[3])
-            except HydroError:
-                if nonlinear:
-                    self._nonlinear_end(check=False)
-                if morison:
-                    self._morison_end(check=False)
-                if drift:
-                    self._drift_end(check=False)
-                if sumf:
-                    self._sum_end(check=False)
-                raise
-        rc = self._step(self._ctxs, len(self.shards), t, a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, a[3].ctypes.data, out.ctypes.data)
-        if nonlinear:
-            self._nonlinear_last = self._nonlinear_end(check=not rc)
-        if morison:
-            self._morison_last = self._morison_end(check=not rc)
-        if drift:
-            self._drift_last = self._drift_end(check=not rc)
-        if sumf:
-            self._sum_last = self._sum_end(check=not rc)
-        if radm:
-            self._radm_last = self._radm_end(check=not rc)
-        if rc:
-            raise HydroError(rc, self.lib.hc_last_error(self.shards[0].ctx).decode())
-        if nonlinear:
-            h0 = self.shards[0]
-            out = _compose_nonlinear(out, self._nonlinear_last, h0._nonlinear_mode, h0._panel_counts, 0, self.N)
-        if morison:
-            out = out + self._morison_last
-        if drift:
-            out = out + self._drift_last
-        if sumf:
-            out = out + self._sum_last
-        return out - self._radm_last if radm else out
 
-    # -- the terms beside the step: begin on every shard, then end on every shard; `nout` output arrays of D_local per shard --
-    def _side_begin(self, begin, end, nout, t, *arrays):
-        begun = []
-        try:
-            for h in self.shards:
-                h._chk(begin(h.ctx, float(t), *(_dp(x) for x in arrays)))
-                begun.append(h)
-        except HydroError:
-            for h in begun:  # nothing stays pending
-                end(h.ctx, *(_dp(np.empty(h.D_local)) for _ in range(nout)))
-            raise
+        def step():
+            return self._step(self._ctxs, len(self.shards), t, a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, a[3].ctypes.data, out.ctypes.data)
+        return _step_with_side_terms(self, self.shards[0], self._side_ctxs, [self._side_on(term) for term in _SIDE_TERMS], step, t, a, out,
+                                     0, self.N)
 
-    def _side_end(self, end, nout, check=True):
-        out = tuple(np.empty(self.D) for _ in range(nout))
-        rcs = []
-        for h in self.shards:
-            part = tuple(np.empty(h.D_local) for _ in range(nout))
-            rcs.append((h, end(h.ctx, *(_dp(x) for x in part))))
-            for k in range(nout):
-                out[k][6 * h.b0:6 * h.b1] = part[k]
-        for h, rc in rcs:
-            if check:
-                h._chk(rc)
-        return out
+    # -- the terms beside the step (_SIDE_TERMS).  Every shard holds the lists, tables and modes of all bodies and computes the rows of
+    # its own: a term is begun on every shard, then ended on every shard, each into its rows --
+    def _side_on(self, term):
+        # the first shard answers for all; the element lists are asked of each
+        return any(term.on(h) for h in self.shards) if term is _MORISON else term.on(self.shards[0])
 
-    # -- drift tables: every shard holds the tables of all bodies and computes those of its own --
-    def _drift_begin(self, t, pos):
-        self._side_begin(self.lib.hc_drift_begin, self.lib.hc_drift_end, 1, t, pos)
+    def _begin_term(self, term, t, *arrays):
+        _side_begin(self.lib, self._side_ctxs, term, t, dict(zip(term.slots, (_arr(x, 3 * self.N) for x in arrays))))
 
-    def _drift_end(self, check=True):
-        return self._side_end(self.lib.hc_drift_end, 1, check)[0]
+    def _end_term(self, term):
+        val, err = _side_end(self.lib, self._side_ctxs, term, self.D)
+        if err:
+            raise err
+        return val
+
+    def _compute_term(self, term, t, *arrays):
+        self._begin_term(term, t, *arrays)
+        return self._end_term(term)
+
+    def _last_term(self, term):
+        """The term's value in the last step(); zeros before the first one and while the term is off."""
+        m = self.__dict__.get(term.last)
+        if m is None or not self._side_on(term):
+            m = tuple(np.zeros(self.D) for _ in range(term.nout))
+            return m if term.nout > 1 else m[0]
+        return tuple(x.copy() for x in m) if term.nout > 1 else m.copy()
 
     def compute_drift(self, t, pos):
-        self._drift_begin(t, _arr(pos, 3 * self.N))
-        return self._drift_end()
+        return self._compute_term(_DRIFT, t, pos)
 
     def drift(self):
-        m = self.__dict__.get("_drift_last")
-        return np.zeros(self.D) if m is None or not self.shards[0]._drift_on() else m.copy()
+        return self._last_term(_DRIFT)
 
     def drift_qtf_size(self, b):
         return self.shards[0].drift_qtf_size(b)
@@ -1250,26 +1205,17 @@ class HydroGroup:
     def drift_qtf_headings(self, b):
         return self.shards[0].drift_qtf_headings(b)
 
-    # -- sum-frequency tables: every shard holds the tables of all bodies and computes those of its own --
-    def _sum_begin(self, t, pos):
-        self._side_begin(self.lib.hc_sum_qtf_begin, self.lib.hc_sum_qtf_end, 1, t, pos)
-
-    def _sum_end(self, check=True):
-        return self._side_end(self.lib.hc_sum_qtf_end, 1, check)[0]
-
     def compute_sum_qtf(self, t, pos):
-        self._sum_begin(t, _arr(pos, 3 * self.N))
-        return self._sum_end()
+        return self._compute_term(_SUM, t, pos)
 
     def sum_qtf_begin(self, t, pos):
-        self._sum_begin(t, _arr(pos, 3 * self.N))
+        self._begin_term(_SUM, t, pos)
 
     def sum_qtf_end(self):
-        return self._sum_end()
+        return self._end_term(_SUM)
 
     def sum_qtf(self):
-        m = self.__dict__.get("_sum_last")
-        return np.zeros(self.D) if m is None or not self.shards[0]._sum_on() else m.copy()
+        return self._last_term(_SUM)
 
     def sum_qtf_size(self, b):
         return self.shards[0].sum_qtf_size(b)
@@ -1277,20 +1223,11 @@ class HydroGroup:
     def sum_qtf_headings(self, b):
         return self.shards[0].sum_qtf_headings(b)
 
-    # -- radiation modes: every shard holds the lists of all bodies and advances the rows of its own --
-    def _radm_begin(self, t, linvel, angvel):
-        self._side_begin(self.lib.hc_radiation_modes_begin, self.lib.hc_radiation_modes_end, 1, t, linvel, angvel)
-
-    def _radm_end(self, check=True):
-        return self._side_end(self.lib.hc_radiation_modes_end, 1, check)[0]
-
     def compute_radiation_modes(self, t, linvel, angvel):
-        self._radm_begin(t, _arr(linvel, 3 * self.N), _arr(angvel, 3 * self.N))
-        return self._radm_end()
+        return self._compute_term(_RADM, t, linvel, angvel)
 
     def radiation_modes(self):
-        m = self.__dict__.get("_radm_last")
-        return np.zeros(self.D) if m is None or not self.shards[0].__dict__.get("_radm_any") else m.copy()
+        return self._last_term(_RADM)
 
     def radiation_modes_irf(self, b, tau):
         return self.shards[0].radiation_modes_irf(b, tau)
@@ -1298,43 +1235,23 @@ class HydroGroup:
     def radiation_mode_count(self, b):
         return self.shards[0].radiation_mode_count(b)
 
-    # -- surface panels and triangles: every shard holds the lists of all bodies and computes those of its own --
     def surface_panel_count(self, b):
         return self.shards[0].surface_panel_count(b)
 
     def surface_triangle_count(self, b):
         return self.shards[0].surface_triangle_count(b)
 
-    def _nonlinear_begin(self, t, a):
-        self._side_begin(self.lib.hc_nonlinear_begin, self.lib.hc_nonlinear_end, 3, t, *a[:2])
-
-    def _nonlinear_end(self, check=True):
-        return self._side_end(self.lib.hc_nonlinear_end, 3, check)
-
     def compute_nonlinear(self, t, pos, rpy):
-        n3 = 3 * self.N
-        a = [_arr(x, n3) for x in (pos, rpy)]
-        self._nonlinear_begin(t, a)
-        return self._nonlinear_end()
+        return self._compute_term(_NONLINEAR, t, pos, rpy)
 
     def nonlinear(self):
-        m = self.__dict__.get("_nonlinear_last")
-        if m is None or not self.shards[0]._nonlinear_on():
-            return tuple(np.zeros(self.D) for _ in range(3))
-        return tuple(x.copy() for x in m)
-
-    # -- Morison elements: every shard holds the lists of all bodies and computes those of its own --
-    def _morison_begin(self, t, a):
-        self._side_begin(self.lib.hc_morison_begin, self.lib.hc_morison_end, 1, t, *a)
-
-    def _morison_end(self, check=True):
-        return self._side_end(self.lib.hc_morison_end, 1, check)[0]
+        return self._last_term(_NONLINEAR)
 
     def compute_morison(self, t, pos, rpy, linvel, angvel):
-        n3 = 3 * self.N
-        a = [_arr(x, n3) for x in (pos, rpy, linvel, angvel)]
-        self._morison_begin(t, a)
-        return self._morison_end()
+        return self._compute_term(_MORISON, t, pos, rpy, linvel, angvel)
+
+    def morison(self):
+        return self._last_term(_MORISON)
 
     def nonlinear_second_order(self):
         return self.shards[0].nonlinear_second_order()
@@ -1374,10 +1291,6 @@ class HydroGroup:
             if h.b0 <= int(b) < h.b1:
                 return h.morison_increments(b)
         raise IndexError(f"body {b} out of range")
-
-    def morison(self):
-        m = self.__dict__.get("_morison_last")
-        return np.zeros(self.D) if m is None or not any(h.__dict__.get("_morison_any") for h in self.shards) else m.copy()
 
     def add_waves_irregular_eta(self, t, eta, simulation_dt, num_bodies=None):
         # every shard takes the whole record

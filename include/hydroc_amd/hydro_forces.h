@@ -439,11 +439,7 @@ class TestHydro {
         throw std::out_of_range("GetMorisonIncrements: no context owns the body");
     }
     std::vector<double> ComputeForceMorison() {
-        gather_state();
-        std::vector<double> out(6 * static_cast<size_t>(num_bodies_));
-        morison_begin(bodies_[0]->GetChTime());
-        morison_end(out.data());
-        return out;
+        return compute_alone(kMorison);
     }
 
     // Nonlinear buoyancy and Froude-Krylov forces on surface panels (not in the reference; include/hydrochrono_amd.h:
@@ -544,12 +540,7 @@ class TestHydro {
     }
     // buoy | fk | hs_lin of all bodies for the bodies' present state, 6 N values each
     std::vector<double> ComputeForceNonlinear() {
-        gather_state();
-        const size_t D = 6 * static_cast<size_t>(num_bodies_);
-        std::vector<double> out(3 * D);
-        nonlinear_begin(bodies_[0]->GetChTime());
-        nonlinear_end(out.data(), out.data() + D, out.data() + 2 * D);
-        return out;
+        return compute_alone(kNonlinear);
     }
 
     // Second-order wave drift forces from difference-frequency QTF tables (not in the reference; include/hydrochrono_amd.h:
@@ -609,11 +600,7 @@ class TestHydro {
     }
     // the drift term of all bodies for the bodies' present positions, 6 N values
     std::vector<double> ComputeForceDrift() {
-        gather_state();
-        std::vector<double> out(6 * static_cast<size_t>(num_bodies_));
-        drift_begin(bodies_[0]->GetChTime());
-        drift_end(out.data());
-        return out;
+        return compute_alone(kDrift);
     }
 
     // Second-order wave forces from sum-frequency QTF tables (not in the reference; include/hydrochrono_amd.h: hc_set_sum_qtf).
@@ -662,11 +649,7 @@ class TestHydro {
     }
     // the sum-frequency term of all bodies for the bodies' present positions, 6 N values
     std::vector<double> ComputeForceSumQTF() {
-        gather_state();
-        std::vector<double> out(6 * static_cast<size_t>(num_bodies_));
-        sum_begin(bodies_[0]->GetChTime());
-        sum_end(out.data());
-        return out;
+        return compute_alone(kSum);
     }
 
     // State-space radiation by modal recursion (not in the reference; include/hydrochrono_amd.h: hc_set_radiation_modes).  Once a body
@@ -695,11 +678,7 @@ class TestHydro {
     }
     // advances the modal state to the bodies' present time with their present velocities: the modal radiation term, 6 N values
     std::vector<double> ComputeForceRadiationModes() {
-        gather_state();
-        std::vector<double> out(6 * static_cast<size_t>(num_bodies_));
-        radm_begin(bodies_[0]->GetChTime());
-        radm_end(out.data());
-        return out;
+        return compute_alone(kRadm);
     }
 
     // the modal radiation term of the last CoordinateFuncForBody evaluation (zeros before the first one)
@@ -730,122 +709,33 @@ class TestHydro {
         if (!(have_time_ && t == prev_time_)) {
             have_time_ = false;  // an evaluation that throws leaves no total behind: the next call at this time evaluates again
             gather_state();
-            const bool nonlinear = nonlinear_on();
-            if (nonlinear) nonlinear_begin(t);
-            if (have_morison_) {
+            // the side terms beside the step, in the order of side_terms(): begin all, step, end all, compose
+            const auto terms = side_terms();
+            for (size_t k = 0; k < terms.size(); ++k) {
+                if (!terms[k].on) continue;
                 try {
-                    morison_begin(t);
-                } catch (...) {
-                    if (nonlinear)
-                        for (hc_ctx* c : ctxs_) (void)hc_nonlinear_end(c, nullptr, nullptr, nullptr);  // nothing stays pending
-                    throw;
-                }
-            }
-            const bool drift = drift_on();
-            if (drift) {
-                try {
-                    drift_begin(t);
+                    begin_all(terms[k], t);
                 } catch (...) {  // nothing stays pending
-                    if (nonlinear)
-                        for (hc_ctx* c : ctxs_) (void)hc_nonlinear_end(c, nullptr, nullptr, nullptr);
-                    if (have_morison_) {
-                        morison_force_.resize(total_force_.size());
-                        for (hc_ctx* c : ctxs_) (void)hc_morison_end(c, morison_force_.data() + row0(c));
-                    }
-                    throw;
-                }
-            }
-            const bool sumf = sum_on();
-            if (sumf) {
-                try {
-                    sum_begin(t);
-                } catch (...) {  // nothing stays pending
-                    if (nonlinear)
-                        for (hc_ctx* c : ctxs_) (void)hc_nonlinear_end(c, nullptr, nullptr, nullptr);
-                    if (have_morison_) {
-                        morison_force_.resize(total_force_.size());
-                        for (hc_ctx* c : ctxs_) (void)hc_morison_end(c, morison_force_.data() + row0(c));
-                    }
-                    if (drift) {
-                        drift_force_.resize(total_force_.size());
-                        for (hc_ctx* c : ctxs_) (void)hc_drift_end(c, drift_force_.data() + row0(c));
-                    }
-                    throw;
-                }
-            }
-            if (have_radm_) {
-                try {
-                    radm_begin(t);
-                } catch (...) {  // nothing stays pending
-                    std::vector<double> drop(total_force_.size());
-                    if (nonlinear)
-                        for (hc_ctx* c : ctxs_) (void)hc_nonlinear_end(c, nullptr, nullptr, nullptr);
-                    if (have_morison_)
-                        for (hc_ctx* c : ctxs_) (void)hc_morison_end(c, drop.data() + row0(c));
-                    if (drift)
-                        for (hc_ctx* c : ctxs_) (void)hc_drift_end(c, drop.data() + row0(c));
-                    if (sumf)
-                        for (hc_ctx* c : ctxs_) (void)hc_sum_qtf_end(c, drop.data() + row0(c));
+                    for (size_t j = 0; j < k; ++j)
+                        if (terms[j].on) drop(terms[j], ctxs_.size());
                     throw;
                 }
             }
             const int rc = ctxs_.size() == 1 ? hc_step(ctx_, t, pos_.data(), rpy_.data(), lin_.data(), ang_.data(), total_force_.data())
                                              : hc_step_multi(ctxs_.data(), static_cast<int>(ctxs_.size()), t, pos_.data(), rpy_.data(), lin_.data(),
                                                              ang_.data(), total_force_.data());
-            if (nonlinear) {
-                const size_t D = total_force_.size();
-                nonlinear_force_.resize(3 * D);
-                double *buoy = nonlinear_force_.data(), *fk = buoy + D, *hs = fk + D;
-                if (rc != HC_OK) {
-                    for (hc_ctx* c : ctxs_) (void)hc_nonlinear_end(c, nullptr, nullptr, nullptr);  // nothing stays pending
-                } else {
-                    nonlinear_end(buoy, fk, hs);
-                    for (size_t body = 0; body < panel_count_.size(); ++body) {
-                        if (panel_count_[body] == 0) continue;
-                        for (size_t i = 6 * body; i < 6 * body + 6; ++i) {
-                            total_force_[i] = total_force_[i] - hs[i] + buoy[i];
-                            if (nonlinear_mode_ == 2) total_force_[i] = total_force_[i] + fk[i];
-                        }
-                    }
-                }
-            }
-            if (have_morison_) {
-                morison_force_.resize(total_force_.size());
-                if (rc != HC_OK) {
-                    for (hc_ctx* c : ctxs_) (void)hc_morison_end(c, morison_force_.data() + row0(c));  // nothing stays pending
-                } else {
-                    morison_end(morison_force_.data());
-                    for (size_t i = 0; i < total_force_.size(); ++i) total_force_[i] += morison_force_[i];
-                }
-            }
-            if (drift) {
-                drift_force_.resize(total_force_.size());
-                if (rc != HC_OK) {
-                    for (hc_ctx* c : ctxs_) (void)hc_drift_end(c, drift_force_.data() + row0(c));  // nothing stays pending
-                } else {
-                    drift_end(drift_force_.data());
-                    for (size_t i = 0; i < total_force_.size(); ++i) total_force_[i] += drift_force_[i];
-                }
-            }
-            if (sumf) {
-                sum_force_.resize(total_force_.size());
-                if (rc != HC_OK) {
-                    for (hc_ctx* c : ctxs_) (void)hc_sum_qtf_end(c, sum_force_.data() + row0(c));  // nothing stays pending
-                } else {
-                    sum_end(sum_force_.data());
-                    for (size_t i = 0; i < total_force_.size(); ++i) total_force_[i] += sum_force_[i];
-                }
-            }
-            if (have_radm_) {
-                radm_force_.resize(total_force_.size());
-                if (rc != HC_OK) {
-                    for (hc_ctx* c : ctxs_) (void)hc_radiation_modes_end(c, radm_force_.data() + row0(c));  // nothing stays pending
-                } else {
-                    radm_end(radm_force_.data());
-                    for (size_t i = 0; i < total_force_.size(); ++i) total_force_[i] -= radm_force_[i];
-                }
+            Failure failed;  // every term is ended whatever the step answered; the step's error goes first, then the first end's
+            for (const SideTerm& s : terms) {
+                if (!s.on) continue;
+                std::vector<double>& x = this->*s.result;
+                x.resize(s.nout * total_force_.size());
+                const Failure f = end_all(s, x.data());
+                if (!failed.ctx) failed = f;
             }
             check(ctx_, rc);
+            if (failed.ctx) check(failed.ctx, failed.rc);
+            for (const SideTerm& s : terms)
+                if (s.on) compose(s);
             prev_time_ = t;
             have_time_ = true;
         }
@@ -939,28 +829,6 @@ class TestHydro {
             }
         }
     }
-    void morison_begin(double t) {
-        for (size_t g = 0; g < ctxs_.size(); ++g) {
-            const int rc = hc_morison_begin(ctxs_[g], t, pos_.data(), rpy_.data(), lin_.data(), ang_.data());
-            if (rc != HC_OK) {
-                std::vector<double> drop(6 * static_cast<size_t>(num_bodies_));
-                for (size_t h = 0; h < g; ++h) (void)hc_morison_end(ctxs_[h], drop.data());
-                check(ctxs_[g], rc);
-            }
-        }
-    }
-    void morison_end(double* out) {  // every shard is ended, then the first failure is reported
-        int rc = HC_OK;
-        hc_ctx* failed = nullptr;
-        for (hc_ctx* c : ctxs_) {
-            const int r = hc_morison_end(c, out + row0(c));
-            if (r != HC_OK && rc == HC_OK) {
-                rc     = r;
-                failed = c;
-            }
-        }
-        if (failed) check(failed, rc);
-    }
     // the 0-based index of a body a surface list is set on
     int surface_body(int body_index_1_based, const char* who) const {
         if (body_index_1_based < 1 || body_index_1_based > num_bodies_) throw std::out_of_range(std::string(who) + ": body index out of range");
@@ -975,99 +843,95 @@ class TestHydro {
     bool nonlinear_on() const {
         return nonlinear_mode_ != 0 && std::any_of(panel_count_.begin(), panel_count_.end(), [](size_t n) { return n != 0; });
     }
-    void nonlinear_begin(double t) {
-        for (size_t g = 0; g < ctxs_.size(); ++g) {
-            const int rc = hc_nonlinear_begin(ctxs_[g], t, pos_.data(), rpy_.data());
-            if (rc != HC_OK) {
-                for (size_t h = 0; h < g; ++h) (void)hc_nonlinear_end(ctxs_[h], nullptr, nullptr, nullptr);
-                check(ctxs_[g], rc);
-            }
-        }
-    }
-    void nonlinear_end(double* buoy, double* fk, double* hs_lin) {  // every shard is ended, then the first failure is reported
-        int rc = HC_OK;
-        hc_ctx* failed = nullptr;
-        for (hc_ctx* c : ctxs_) {
-            const int r0 = row0(c);
-            const int r  = hc_nonlinear_end(c, buoy + r0, fk + r0, hs_lin + r0);
-            if (r != HC_OK && rc == HC_OK) {
-                rc     = r;
-                failed = c;
-            }
-        }
-        if (failed) check(failed, rc);
-    }
     bool drift_on() const {
         return drift_mode_ != 0 && std::any_of(drift_size_.begin(), drift_size_.end(), [](size_t n) { return n != 0; });
-    }
-    void drift_begin(double t) {
-        for (size_t g = 0; g < ctxs_.size(); ++g) {
-            const int rc = hc_drift_begin(ctxs_[g], t, pos_.data());
-            if (rc != HC_OK) {
-                std::vector<double> drop(total_force_.size());
-                for (size_t h = 0; h < g; ++h) (void)hc_drift_end(ctxs_[h], drop.data());
-                check(ctxs_[g], rc);
-            }
-        }
-    }
-    void drift_end(double* out) {  // every shard is ended, then the first failure is reported
-        int rc = HC_OK;
-        hc_ctx* failed = nullptr;
-        for (hc_ctx* c : ctxs_) {
-            const int r = hc_drift_end(c, out + row0(c));
-            if (r != HC_OK && rc == HC_OK) {
-                rc     = r;
-                failed = c;
-            }
-        }
-        if (failed) check(failed, rc);
     }
     bool sum_on() const {
         return sum_mode_ != 0 && std::any_of(sum_size_.begin(), sum_size_.end(), [](size_t n) { return n != 0; });
     }
-    void sum_begin(double t) {
+    // A term that runs on a lane of its own beside the step.  side_terms() lists them in the order of their begins, their ends and
+    // their composition; a new term is one more row, its result vector and its "on" flag.
+    struct SideTerm {
+        bool on;      // takes part in CoordinateFuncForBody
+        size_t nout;  // vectors of 6 N values the end fills, one behind the other in *result
+        int (*begin)(const TestHydro&, hc_ctx*, double t);
+        int (*end)(hc_ctx*, double* out, size_t D);  // out: the shard's first row of the first vector; the others follow D apart
+        std::vector<double> TestHydro::*result;      // the term of the last evaluation
+        int sign;                                    // +1: added to the total, -1: subtracted, 0: the per-body nonlinear composition
+    };
+    enum { kNonlinear, kMorison, kDrift, kSum, kRadm, kSideTerms };
+    std::array<SideTerm, kSideTerms> side_terms() const {
+        return {{{nonlinear_on(), 3, [](const TestHydro& h, hc_ctx* c, double t) { return hc_nonlinear_begin(c, t, h.pos_.data(), h.rpy_.data()); },
+                  [](hc_ctx* c, double* o, size_t D) { return hc_nonlinear_end(c, o, o + D, o + 2 * D); }, &TestHydro::nonlinear_force_, 0},
+                 {have_morison_, 1,
+                  [](const TestHydro& h, hc_ctx* c, double t) {
+                      return hc_morison_begin(c, t, h.pos_.data(), h.rpy_.data(), h.lin_.data(), h.ang_.data());
+                  },
+                  [](hc_ctx* c, double* o, size_t) { return hc_morison_end(c, o); }, &TestHydro::morison_force_, +1},
+                 {drift_on(), 1, [](const TestHydro& h, hc_ctx* c, double t) { return hc_drift_begin(c, t, h.pos_.data()); },
+                  [](hc_ctx* c, double* o, size_t) { return hc_drift_end(c, o); }, &TestHydro::drift_force_, +1},
+                 {sum_on(), 1, [](const TestHydro& h, hc_ctx* c, double t) { return hc_sum_qtf_begin(c, t, h.pos_.data()); },
+                  [](hc_ctx* c, double* o, size_t) { return hc_sum_qtf_end(c, o); }, &TestHydro::sum_force_, +1},
+                 {have_radm_, 1,
+                  [](const TestHydro& h, hc_ctx* c, double t) { return hc_radiation_modes_begin(c, t, h.lin_.data(), h.ang_.data()); },
+                  [](hc_ctx* c, double* o, size_t) { return hc_radiation_modes_end(c, o); }, &TestHydro::radm_force_, -1}}};
+    }
+    struct Failure {
+        hc_ctx* ctx = nullptr;
+        int rc      = HC_OK;
+    };
+    // ends the term on the first n shards into a scratch buffer, whatever they answer: nothing stays pending
+    void drop(const SideTerm& s, size_t n) {
+        const size_t D = total_force_.size();
+        std::vector<double> scratch(s.nout * D);
+        for (size_t g = 0; g < n; ++g) (void)s.end(ctxs_[g], scratch.data() + row0(ctxs_[g]), D);
+    }
+    // begins the term on every shard; a refusal ends it on the shards before, and is thrown
+    void begin_all(const SideTerm& s, double t) {
         for (size_t g = 0; g < ctxs_.size(); ++g) {
-            const int rc = hc_sum_qtf_begin(ctxs_[g], t, pos_.data());
+            const int rc = s.begin(*this, ctxs_[g], t);
             if (rc != HC_OK) {
-                std::vector<double> drop(total_force_.size());
-                for (size_t h = 0; h < g; ++h) (void)hc_sum_qtf_end(ctxs_[h], drop.data());
+                drop(s, g);
                 check(ctxs_[g], rc);
             }
         }
     }
-    void sum_end(double* out) {  // every shard is ended, then the first failure is reported
-        int rc = HC_OK;
-        hc_ctx* failed = nullptr;
+    // ends the term on every shard, each into its rows of out [nout][6 N]; the first failure is returned, not thrown
+    Failure end_all(const SideTerm& s, double* out) {
+        Failure first;
         for (hc_ctx* c : ctxs_) {
-            const int r = hc_sum_qtf_end(c, out + row0(c));
-            if (r != HC_OK && rc == HC_OK) {
-                rc     = r;
-                failed = c;
-            }
+            const int rc = s.end(c, out + row0(c), total_force_.size());
+            if (rc != HC_OK && !first.ctx) first = Failure{c, rc};
         }
-        if (failed) check(failed, rc);
+        return first;
     }
-    void radm_begin(double t) {
-        for (size_t g = 0; g < ctxs_.size(); ++g) {
-            const int rc = hc_radiation_modes_begin(ctxs_[g], t, lin_.data(), ang_.data());
-            if (rc != HC_OK) {
-                std::vector<double> drop(6 * static_cast<size_t>(num_bodies_));
-                for (size_t h = 0; h < g; ++h) (void)hc_radiation_modes_end(ctxs_[h], drop.data());
-                check(ctxs_[g], rc);
-            }
-        }
+    // a term for the bodies' present state, outside CoordinateFuncForBody: nout vectors of 6 N values
+    std::vector<double> compute_alone(size_t k) {
+        gather_state();
+        const SideTerm s = side_terms()[k];
+        std::vector<double> out(s.nout * total_force_.size());
+        begin_all(s, bodies_[0]->GetChTime());
+        const Failure f = end_all(s, out.data());
+        if (f.ctx) check(f.ctx, f.rc);
+        return out;
     }
-    void radm_end(double* out) {  // every shard is ended, then the first failure is reported
-        int rc = HC_OK;
-        hc_ctx* failed = nullptr;
-        for (hc_ctx* c : ctxs_) {
-            const int r = hc_radiation_modes_end(c, out + row0(c));
-            if (r != HC_OK && rc == HC_OK) {
-                rc     = r;
-                failed = c;
+    void compose(const SideTerm& s) {
+        const std::vector<double>& x = this->*s.result;
+        const size_t D = total_force_.size();
+        if (s.sign > 0) {
+            for (size_t i = 0; i < D; ++i) total_force_[i] += x[i];
+        } else if (s.sign < 0) {
+            for (size_t i = 0; i < D; ++i) total_force_[i] -= x[i];
+        } else {  // total - hs_lin + buoy (+ fk in mode 2) on the rows of every body that carries a surface list
+            const double *buoy = x.data(), *fk = buoy + D, *hs = fk + D;
+            for (size_t body = 0; body < panel_count_.size(); ++body) {
+                if (panel_count_[body] == 0) continue;
+                for (size_t i = 6 * body; i < 6 * body + 6; ++i) {
+                    total_force_[i] = total_force_[i] - hs[i] + buoy[i];
+                    if (nonlinear_mode_ == 2) total_force_[i] = total_force_[i] + fk[i];
+                }
             }
         }
-        if (failed) check(failed, rc);
     }
     static int row0(hc_ctx* c) {  // first output row of a shard context
         int b0 = 0;

@@ -9,7 +9,9 @@
 // ComputeForceSumQTF (24).  The output does not depend on the device list.  The lists, tables and states are those of
 // tests/side_terms2_inputs.py (cpp_*: dyadic values, the same bits there).
 // Exit 3: a second read at the same time gave other bits; exit 4: with every list and table cleared the Morison, drift or
-// sum-frequency term, or the buoyancy or Froude-Krylov part of the nonlinear term, is not zero.
+// sum-frequency term, or the buoyancy or Froude-Krylov part of the nonlinear term, is not zero; exit 5: with radiation modes as the fifth
+// term and an evaluation of them begun by hand, CoordinateFuncForBody did not throw, or left an evaluation pending on some context, or
+// ended the one begun by hand.
 // Built with plain g++ by tests/test_side_terms2_cpu.py, run on the GPU by tests/test_gpu_side_terms2.py.
 #include <array>
 #include <cstdio>
@@ -157,6 +159,31 @@ int main(int argc, char** argv) {
             for (const auto* vec : {&mor, &nl, &dft, &smf})
                 for (double v : *vec) std::printf(" %a", v);
             std::printf("\n");
+        }
+        // the modal radiation term as the fifth, and an evaluation of it begun by hand on the last shard: the fifth begin there is
+        // refused, the evaluation throws, and every evaluation it had begun on any context has been ended
+        {
+            hydro.SetRadiationModes(2, {RadiationMode{2, 8, {-0.75, 1.5}, {12.0, -4.0}}});
+            set_state(mock, steps);
+            hc_ctx* last = hydro.contexts().back();
+            const std::vector<double> vel(12, 0.0);
+            std::vector<double> drop(72);
+            if (hc_radiation_modes_begin(last, mock[0]->time, vel.data(), vel.data()) != HC_OK) return 5;
+            bool thrown = false;
+            try {
+                (void)hydro.CoordinateFuncForBody(1, 0);
+            } catch (const std::exception&) {
+                thrown = true;
+            }
+            if (!thrown) return 5;
+            for (hc_ctx* c : hydro.contexts()) {
+                if (hc_nonlinear_end(c, drop.data(), drop.data() + 24, drop.data() + 48) != HC_ERR_INVALID) return 5;
+                if (hc_morison_end(c, drop.data()) != HC_ERR_INVALID) return 5;
+                if (hc_drift_end(c, drop.data()) != HC_ERR_INVALID) return 5;
+                if (hc_sum_qtf_end(c, drop.data()) != HC_ERR_INVALID) return 5;
+                if (hc_radiation_modes_end(c, drop.data()) != (c == last ? HC_OK : HC_ERR_INVALID)) return 5;
+            }
+            hydro.SetRadiationModes(2, {});  // ... and the evaluation below, at the same time, is a whole one
         }
         // everything cleared: no term is left
         for (int b = 1; b <= 4; ++b) {
