@@ -32,7 +32,7 @@ SOURCES = ["hc_kernels.hip", "hc_runtime.cpp", "hc_step.cpp", "hc_pass.cpp", "hc
 PRELOAD = ["-mllvm", "-amdgpu-kernarg-preload-count=16"]
 KERNEL_CO = os.path.join(LIBDIR, "hc_kernels.co")  # the same kernels as a stand-alone code object, for the direct AQL dispatch (hc_direct.hpp)
 TUNING_CO = os.path.join(LIBDIR, "hc_kernels_tuning.co")
-HEADERS = ["hc_kernels.hpp", "hc_tail.hpp", "hc_tail_kernels.hpp", "hc_context.hpp", "hc_internal.hpp", "hc_host_math.hpp", "hc_limits.hpp", "hc_plan.hpp", "hc_history.hpp", "hc_direct.hpp", "hc_fanout.hpp", "hc_h5data.hpp", "hc_eta_record.hpp", "hc_eta_components.hpp", "hc_wave_kin.hpp", "hc_wave_kin2.hpp", "hc_wave_kin2_sum.hpp", "hc_wave_kin2_dir.hpp", "hc_qtf.hpp", "hc_heading.hpp", "hc_side.hpp", "hc_morison_members.hpp", "hc_modal_ring.hpp", os.path.join(ROOT, "include", "hydrochrono_amd.h"),
+HEADERS = ["hc_kernels.hpp", "hc_tail.hpp", "hc_tail_kernels.hpp", "hc_context.hpp", "hc_internal.hpp", "hc_host_math.hpp", "hc_limits.hpp", "hc_plan.hpp", "hc_history.hpp", "hc_direct.hpp", "hc_fanout.hpp", "hc_h5data.hpp", "hc_eta_record.hpp", "hc_eta_components.hpp", "hc_wave_kin.hpp", "hc_wave_kin2.hpp", "hc_wave_kin2_sum.hpp", "hc_wave_kin2_dir.hpp", "hc_qtf.hpp", "hc_heading.hpp", "hc_side.hpp", "hc_morison_members.hpp", "hc_member_increments.hpp", "hc_modal_ring.hpp", os.path.join(ROOT, "include", "hydrochrono_amd.h"),
            os.path.join(ROOT, "include", "hydrochrono_amd_host.h"), os.path.join(ROOT, "include", "hydrochrono_amd_yaml.h")]
 
 

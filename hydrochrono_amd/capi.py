@@ -201,6 +201,11 @@ SIGNATURES = {
     "hc_set_morison_members": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(MorisonMember), C.c_int]),
     "hc_get_morison_member_count": (C.c_int, [C.c_void_p, C.c_int, c_int_p]),
     "hc_get_morison_member_forces": (C.c_int, [C.c_void_p, C.c_int, c_double_p]),
+    "hc_set_morison_members_second_order": (C.c_int, [C.c_void_p, C.c_int]),
+    "hc_get_morison_members_second_order": (C.c_int, [C.c_void_p, c_int_p]),
+    "hc_get_morison_member_increment_counts": (C.c_int, [C.c_void_p, C.c_int, c_int_p, c_int_p]),
+    "hc_get_morison_member_node_increments": (C.c_int, [C.c_void_p, C.c_int, c_double_p, c_double_p]),
+    "hc_get_morison_member_point_increments": (C.c_int, [C.c_void_p, C.c_int, c_double_p, c_double_p, c_double_p, c_double_p]),
     "hc_set_surface_panels": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(SurfacePanel), C.c_int]),
     "hc_get_surface_panel_count": (C.c_int, [C.c_void_p, C.c_int, c_int_p]),
     "hc_set_surface_triangles": (C.c_int, [C.c_void_p, C.c_int, c_double_p, C.c_int]),

@@ -127,6 +127,7 @@ struct Wk2Call {
 
 }  // namespace hc
 
+#include "hc_member_increments.hpp"
 #include "hc_modal_ring.hpp"
 #include "hc_side.hpp"  // KinTableCopy, SideLane, Order2Part: made of the types above
 
@@ -185,6 +186,14 @@ struct MorisonMemberData {
     PinnedBuffer<double> h_mout, h_out;
     bool flight = false;  // the evaluation in flight has a member part
     bool done   = false;  // h_mout holds a completed evaluation of the lists as they are (hc_get_morison_member_forces)
+    // on the second-order sea (hc_set_morison_members_second_order, DESIGN.md 3.7c''): the increments at the nodes ([nodes][4]: P,
+    // eta2) and behind them at the Gauss points ([points][8], with directions [points][10]: p, eta2, u2, a2) in one device buffer,
+    // and its two host copies, which change hands around the wait of hc_morison_end (hc_member_increments.hpp)
+    bool order2 = false;  // the switch
+    std::vector<int> node_off, point_off;  // [nloc + 1] first node / Gauss point of an owned body
+    DeviceBuffer<double> inc;
+    PinnedBuffer<double> h_inc[2];
+    MemberIncrementCopies copies;
 };
 
 // Surface panels and triangles (hc_set_surface_panels, hc_set_surface_triangles, hc_nonlinear.hip): the lists of all bodies of the

@@ -238,12 +238,6 @@ struct Mor2Args {
     double* inc;          // [n_items][kMorIncDoubles]
 };
 
-// A value every lane of the wave holds, moved to scalar registers (its bits unchanged): the point of morison2_incr_kernel<true>
-// then costs the pair sum no vector register, as the point wk2_sum_kernel loads with scalar loads costs it none
-__device__ __forceinline__ double wave_uniform(double v) {
-    return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
-}
-
 // One workgroup per element of the owned bodies: the point of morison_items_kernel (morison_frame), then the pair sum of
 // hc_wave_kinematics2 at that point and time with the epilogue of wk2_sum_kernel: the eight doubles it stores are what that call
 // returns for the stored point, bit for bit.
@@ -348,12 +342,14 @@ void morison_enqueue(hc_ctx* c, double t, const double* pos, const double* rpy, 
     const bool order2  = c->mor2.prepare(c, c->mor, dir);
     const int width    = dir ? kMorDirIncDoubles : kMorIncDoubles;
     const size_t n_inc = static_cast<size_t>(width) * a.n_items;
-    double* h_inc      = order2 ? c->mor2.stage(n_inc, width) : nullptr;
-    if (order2) a.inc = c->mor2.d_inc.p;
+    // (with members and no element on any owned body nothing of the elements' increments is staged: their getter stays as it was)
+    double* h_inc      = order2 && a.n_items != 0 ? c->mor2.stage(n_inc, width) : nullptr;
+    if (h_inc) a.inc = c->mor2.d_inc.p;
     HC_HIP(hipMemcpyAsync(d.state.p, d.h_state.p, 4 * n3 * sizeof(double), hipMemcpyHostToDevice, st));
     // strip members only (hc_morison_members.hip): no element launch, the element part of the result is zero
+    const bool members2 = order2 && c->members.order2;  // hc_set_morison_members_second_order: the lane's tables serve them too
     if (a.n_items == 0) {
-        members_enqueue(c, t, d.state.p);
+        members_enqueue(c, t, d.state.p, members2);
         return;
     }
     const dim3 item_grid((a.n_items + kMorThreads - 1) / kMorThreads);
@@ -378,7 +374,7 @@ void morison_enqueue(hc_ctx* c, double t, const double* pos, const double* rpy, 
                        c->Dloc, d.out.p);
     HC_HIP(hipGetLastError());
     HC_HIP(hipMemcpyAsync(d.h_out.p, d.out.p, static_cast<size_t>(c->Dloc) * sizeof(double), hipMemcpyDeviceToHost, st));
-    if (members_owned(c) != 0) members_enqueue(c, t, d.state.p);  // behind the element launches
+    if (members_owned(c) != 0) members_enqueue(c, t, d.state.p, members2);  // behind the element launches
 }
 
 const char* const kMorInFlight = "a Morison evaluation is in flight (hc_morison_end has not been called)";
@@ -485,14 +481,16 @@ int hc_morison_begin(hc_ctx* c, double t, const double* pos, const double* rpy, 
     require(!(c->mor2.on && hc::kin_has_components(c)) || hc::wk2_component_count(c) <= hc::kWk2MaxFreq, HC_ERR_UNSUPPORTED,
             "Morison elements on the second-order sea: more than 4096 wave components");
     const int members = hc::members_owned(c);
-    require(!(c->mor2.on && members != 0), HC_ERR_UNSUPPORTED,
-            "Morison strip members see the first-order sea only: switch the second-order sea off (hc_set_morison_second_order) or clear "
-            "the members of the owned bodies (hc_set_morison_members)");
+    require(!(c->mor2.on && members != 0 && !c->members.order2), HC_ERR_UNSUPPORTED,
+            "Morison strip members see the first-order sea only: switch the members on the second-order sea on "
+            "(hc_set_morison_members_second_order), switch the second-order sea off (hc_set_morison_second_order) or clear the members "
+            "of the owned bodies (hc_set_morison_members)");
     int items = 0;
     if (!c->morison.elems.empty())
         for (int b = c->b0; b < c->b1; ++b) items += static_cast<int>(c->morison.elems[b].size());
     c->mor2.flight    = false;
     c->members.flight = false;
+    c->members.copies.reset();
     c->mor.begin(items != 0 || members != 0, [&] { hc::morison_enqueue(c, t, pos, rpy, linvel, angvel); });
     HC_API_END(c)
 }
@@ -501,7 +499,10 @@ int hc_morison_end(hc_ctx* c, double* out) {
     HC_API_BEGIN_HOT(c)
     const bool with_members = c->members.flight;
     c->members.flight       = false;
+    // the members' increments change hands around the wait, as the elements' do inside the lane's end
+    const bool with_member_inc = c->mor.pending != 0 && c->members.copies.retire();
     const int what = c->mor.end("hc_morison_end without hc_morison_begin", &c->mor2);
+    if (with_member_inc) c->members.copies.complete();
     if (what == 2 && with_members) c->members.done = true;  // hc_get_morison_member_forces answers with this evaluation
     require(out != nullptr, HC_ERR_INVALID, "null output");
     if (what == 2 && c->morison.items != 0) std::copy(c->morison.h_out.p, c->morison.h_out.p + c->Dloc, out);

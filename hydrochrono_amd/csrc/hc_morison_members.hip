@@ -3,10 +3,16 @@
 // the Morison elements (hc_morison.hip: hc_morison_begin / hc_morison_end; hc_side.hpp), behind their launches: the lane's stream,
 // component table and options, buffers and pinned staging of its own.  DESIGN.md 3.7c' has the definition, the kernels and their
 // invariants.  The kernels carry their own component loop, built from the pieces of hc_wave_kin.hpp.
+// 3.7c'' the members on the second-order sea (hc_set_morison_members_second_order): eta2 of hc_wave_kinematics2 at every node, taken
+// off h before the cut, then u2 and a2 at the Gauss points the cut yields, added before the drag product; in a short-crested sea
+// the increments of hc_wave_kinematics2_dir.
 #include "hc_morison_members.hpp"
 
 #include "hc_internal.hpp"
 #include "hc_wave_kin.hpp"
+#include "hc_wave_kin2.hpp"
+#include "hc_wave_kin2_dir.hpp"
+#include "hc_wave_kin2_sum.hpp"
 
 using namespace hc::detail;
 
@@ -36,6 +42,8 @@ struct MemArgs {
     int finite_depth;  // 0: water depth +inf
     double* h;         // [n_nodes] P_j.z - mwl - eta_j
     double* item;      // [n_points][6] (dF, dM) of every Gauss point
+    const double* inc; // [n_points][kMemPointIncDoubles] of morison_member2_points_kernel, with directions
+                       // [n_points][kMemPointDirIncDoubles] (the order-2 instantiations only)
 };
 
 // R = Rx(rpy0) Ry(rpy1) Rz(rpy2) as the elements form it (hc_morison.hip: morison_frame)
@@ -55,6 +63,62 @@ __device__ __forceinline__ MemRot member_rotation(const double* rpy) {
     return f;
 }
 
+// P_j = pos + R (r0 + (j / n_seg)(r1 - r0)): one expression for the kernel that sums eta1 at the node and the one that sums eta2
+// there (morison_member2_nodes_kernel): the same expression in both (compiled with the default contraction, which the order-1
+// kernels keep for their bits; the stored point is the one the pair sum was given)
+struct MemNode {
+    double x, y, z;
+};
+
+__device__ __forceinline__ MemNode member_node(const double* mem, const double* pos, const double* rpy, int j, int n_seg) {
+    const MemRot f  = member_rotation(rpy);
+    const double sj = static_cast<double>(j) / static_cast<double>(n_seg);
+    const double rx = mem[0] + sj * mem[3], ry = mem[1] + sj * mem[4], rz = mem[2] + sj * mem[5];
+    MemNode p;
+    p.x = pos[0] + (f.r00 * rx + f.r01 * ry + f.r02 * rz);
+    p.y = pos[1] + (f.r10 * rx + f.r11 * ry + f.r12 * rz);
+    p.z = pos[2] + (f.r20 * rx + f.r21 * ry + f.r22 * rz);
+    return p;
+}
+
+// Gauss point g of segment `seg`: the wet interval [sa, sb] of the segment (local coordinate from node `seg`) from its two h values
+// with selects -- the cut's division runs in the cut case only --, the weight, the diameter, R, d = R r_g and p = pos + d.  One
+// expression for the kernel that evaluates the force and the one that sums the second-order increments
+// (morison_member2_points_kernel), so that the increments are those of the point the force is evaluated at: the same expression
+// from the same h in both.
+struct MemGauss {
+    bool w0, w1;  // node `seg` / node `seg + 1` is wet
+    double wg, diam;
+    MemRot f;
+    double d0, d1, d2;
+    double x, y, z;
+};
+
+__device__ __forceinline__ MemGauss member_gauss(const double* mem, const double* pos, const double* rpy, double hx, double hy, int seg, int g,
+                                                 int n_seg) {
+    MemGauss p;
+    p.w0 = hx <= 0.0, p.w1 = hy <= 0.0;
+    double sa = 0.0, sb = (p.w0 && p.w1) ? 1.0 : 0.0;
+    if (p.w0 != p.w1) {  // one cut, measured from the wet end: h_wet <= 0 < h_dry, the denominator is negative
+        const double hw = p.w0 ? hx : hy, hd = p.w0 ? hy : hx;
+        const double cut = hw / (hw - hd);
+        sa = p.w0 ? 0.0 : 1.0 - cut;
+        sb = p.w0 ? cut : 1.0;
+    }
+    const double width = sb - sa;
+    const double sg    = sa + width * (g ? kGaussHi : kGaussLo);
+    const double along = (static_cast<double>(seg) + sg) / static_cast<double>(n_seg);
+    p.wg   = 0.5 * width * mem[6] / static_cast<double>(n_seg);
+    p.diam = mem[7] + along * (mem[8] - mem[7]);
+    p.f    = member_rotation(rpy);
+    const double rx = mem[0] + along * mem[3], ry = mem[1] + along * mem[4], rz = mem[2] + along * mem[5];
+    p.d0 = p.f.r00 * rx + p.f.r01 * ry + p.f.r02 * rz;
+    p.d1 = p.f.r10 * rx + p.f.r11 * ry + p.f.r12 * rz;
+    p.d2 = p.f.r20 * rx + p.f.r21 * ry + p.f.r22 * rz;
+    p.x = pos[0] + p.d0, p.y = pos[1] + p.d1, p.z = pos[2] + p.d2;
+    return p;
+}
+
 // One work item per node of the owned bodies' members, body-major.  The frame comes from the body's state, eta from the loop over
 // the LDS-staged component tiles in index order (the cosine only); h_j = P_j.z - mwl - eta_j is stored.  A node's bits depend on
 // its body's state, its member, the table, t and mwl, not on where in the grid it sits.
@@ -70,12 +134,8 @@ __global__ void __launch_bounds__(kMemThreads) morison_member_nodes_kernel(MemAr
     const int b = ds[0], n_seg = ds[1], j = e - ds[2];
     const double* mem = a.mem + static_cast<size_t>(kMemDoubles) * m;
     const double* pos = a.state + 3 * b;
-    const MemRot f    = member_rotation(pos + 3 * a.N);
-    const double sj   = static_cast<double>(j) / static_cast<double>(n_seg);
-    const double rx = mem[0] + sj * mem[3], ry = mem[1] + sj * mem[4], rz = mem[2] + sj * mem[5];
-    const double x = pos[0] + (f.r00 * rx + f.r01 * ry + f.r02 * rz);
-    const double y = DIR ? pos[1] + (f.r10 * rx + f.r11 * ry + f.r12 * rz) : 0.0;
-    const double z = pos[2] + (f.r20 * rx + f.r21 * ry + f.r22 * rz);
+    const MemNode p   = member_node(mem, pos, pos + 3 * a.N, j, n_seg);
+    const double x = p.x, y = DIR ? p.y : 0.0, z = p.z;
     double eta = 0.0;
     for (int i0 = 0; i0 < a.nf; i0 += kKinTile) {
         const int n = min(kKinTile, a.nf - i0);
@@ -101,8 +161,12 @@ __global__ void __launch_bounds__(kMemThreads) morison_member_nodes_kernel(MemAr
 // selects; the cut's division runs in the cut case only.  Then the kinematics loop of the element kernel at the point (one pass, two
 // under stretching), the transverse force per length times the weight, and the moment about the body reference.  A point of a dry
 // segment writes exact zeros.
-template <bool DIR>
-__global__ void __launch_bounds__(kMemThreads) morison_member_items_kernel(MemArgs a) {
+// ORDER2 (morison_member2_items_kernel): the point's second-order increments (morison_member2_points_kernel, earlier on the stream,
+// summed at the same point: member_gauss) are read after the first-order loops and added to ramp u1 and ramp a1 before q and a_n;
+// the first-order part, stretching by the point's own eta1 included, is the code of order 1, and the two order-1 kernels keep
+// their arithmetic and their registers.
+template <bool DIR, bool ORDER2>
+__device__ __forceinline__ void morison_member_items_body(const MemArgs& a) {
     constexpr int kDc = kKinCols, kDs = kKinCols + 1;  // rows of the direction columns (DIR only)
     __shared__ double s[DIR ? kKinCols + kDirCols : kKinCols][kKinTile];
     const int o       = blockIdx.x * kMemThreads + threadIdx.x;
@@ -118,30 +182,13 @@ __global__ void __launch_bounds__(kMemThreads) morison_member_items_kernel(MemAr
     const double* lin = rpy + 3 * a.N;
     const double* ang = lin + 3 * a.N;
 
-    // ---- the wet interval [sa, sb] of the segment, local coordinate from node `seg` ----
-    const double hx = a.h[dsc[2] + seg], hy = a.h[dsc[2] + seg + 1];
-    const bool w0 = hx <= 0.0, w1 = hy <= 0.0;
-    double sa = 0.0, sb = (w0 && w1) ? 1.0 : 0.0;
-    if (w0 != w1) {  // one cut, measured from the wet end: h_wet <= 0 < h_dry, the denominator is negative
-        const double hw = w0 ? hx : hy, hd = w0 ? hy : hx;
-        const double cut = hw / (hw - hd);
-        sa = w0 ? 0.0 : 1.0 - cut;
-        sb = w0 ? cut : 1.0;
-    }
-    const double width = sb - sa;
-    const double sg    = sa + width * (g ? kGaussHi : kGaussLo);
-    const double along = (static_cast<double>(seg) + sg) / static_cast<double>(n_seg);
-    const double len   = mem[6];
-    const double wg    = 0.5 * width * len / static_cast<double>(n_seg);
-    const double diam  = mem[7] + along * (mem[8] - mem[7]);
-
-    // ---- R, d = R r_g, p = pos + d, the unit axis ----
-    const MemRot f  = member_rotation(rpy);
-    const double rx = mem[0] + along * mem[3], ry = mem[1] + along * mem[4], rz = mem[2] + along * mem[5];
-    const double d0 = f.r00 * rx + f.r01 * ry + f.r02 * rz;
-    const double d1 = f.r10 * rx + f.r11 * ry + f.r12 * rz;
-    const double d2 = f.r20 * rx + f.r21 * ry + f.r22 * rz;
-    const double x = pos[0] + d0, y = DIR ? pos[1] + d1 : 0.0, z = pos[2] + d2, t = a.t;
+    // ---- the wet interval of the segment, the weight and the diameter; R, d = R r_g, p = pos + d ----
+    const MemGauss gp = member_gauss(mem, pos, rpy, a.h[dsc[2] + seg], a.h[dsc[2] + seg + 1], seg, g, n_seg);
+    const bool w0 = gp.w0, w1 = gp.w1;
+    const double len = mem[6], wg = gp.wg, diam = gp.diam;
+    const MemRot f  = gp.f;
+    const double d0 = gp.d0, d1 = gp.d1, d2 = gp.d2;
+    const double x = gp.x, y = DIR ? gp.y : 0.0, z = gp.z, t = a.t;
 
     // ---- eta first under stretching ----
     double eta = 0.0;
@@ -223,10 +270,21 @@ __global__ void __launch_bounds__(kMemThreads) morison_member_items_kernel(MemAr
     const double t1 = f.r10 * ex + f.r11 * ey + f.r12 * ez;
     const double t2 = f.r20 * ex + f.r21 * ey + f.r22 * ez;
     const double w0a = ang[0], w1a = ang[1], w2a_ = ang[2];
-    const double afx = a.ramp * ax, afy = a.ramp * ay, afz = a.ramp * az;
-    const double q0 = a.ramp * ux - (lin[0] + (w1a * d2 - w2a_ * d1));
-    const double q1 = a.ramp * uy - (lin[1] + (w2a_ * d0 - w0a * d2));
-    const double q2 = a.ramp * uz - (lin[2] + (w0a * d1 - w1a * d0));
+    double u2x = 0.0, u2y = 0.0, u2z = 0.0, a2x = 0.0, a2y = 0.0, a2z = 0.0;
+    if constexpr (ORDER2 && DIR) {
+        const double* v = a.inc + static_cast<size_t>(kMemPointDirIncDoubles) * o;
+        u2x = v[4], u2y = v[5], u2z = v[6], a2x = v[7], a2y = v[8], a2z = v[9];
+    } else if constexpr (ORDER2) {
+        const double* v = a.inc + static_cast<size_t>(kMemPointIncDoubles) * o;
+        u2x = v[4], u2z = v[5], a2x = v[6], a2z = v[7];
+    }
+    const double afx = ORDER2 ? a.ramp * ax + a2x : a.ramp * ax;
+    const double afy = ORDER2 ? a.ramp * ay + a2y : a.ramp * ay;
+    const double afz = ORDER2 ? a.ramp * az + a2z : a.ramp * az;
+    const double vx = lin[0] + (w1a * d2 - w2a_ * d1), vy = lin[1] + (w2a_ * d0 - w0a * d2), vz = lin[2] + (w0a * d1 - w1a * d0);
+    const double q0 = ORDER2 ? (a.ramp * ux + u2x) - vx : a.ramp * ux - vx;
+    const double q1 = ORDER2 ? (a.ramp * uy + u2y) - vy : a.ramp * uy - vy;
+    const double q2 = ORDER2 ? (a.ramp * uz + u2z) - vz : a.ramp * uz - vz;
     const double qa = q0 * t0 + q1 * t1 + q2 * t2;
     const double n0 = q0 - qa * t0, n1 = q1 - qa * t1, n2 = q2 - qa * t2;
     const double aa = afx * t0 + afy * t1 + afz * t2;
@@ -243,6 +301,94 @@ __global__ void __launch_bounds__(kMemThreads) morison_member_items_kernel(MemAr
     out[3] = d1 * F2 - d2 * F1;
     out[4] = d2 * F0 - d0 * F2;
     out[5] = d0 * F1 - d1 * F0;
+}
+
+template <bool DIR>
+__global__ void __launch_bounds__(kMemThreads) morison_member_items_kernel(MemArgs a) {
+    morison_member_items_body<DIR, false>(a);
+}
+template <bool DIR>
+__global__ void __launch_bounds__(kMemThreads) morison_member2_items_kernel(MemArgs a) {
+    morison_member_items_body<DIR, true>(a);
+}
+
+struct Mem2Args {
+    Wk2Sea sea;               // the Morison lane's tables (hc_ctx::mor2, shared with the elements), mwl of the Morison options
+    const double* mem;        // as MemArgs
+    const int* desc;
+    const int* node_member;
+    const int* point_member;
+    const double* state;
+    int N;
+    double t;
+    int ramped;               // ramp * ramp applies (apply_ramp, a synthesised irregular model, ramp_duration > 0)
+    double ramp_duration;
+    double* h;                // [n_nodes]: h_j of the nodes kernel in, h_j - eta2_j out
+    double* nodes;            // [n_nodes][kMemNodeIncDoubles]
+    double* points;           // [n_points][kMemPointIncDoubles], with directions [n_points][kMemPointDirIncDoubles]
+};
+
+// One workgroup per node, behind morison_member_nodes_kernel: the node's point (member_node) in scalar registers, the pair sum of
+// hc_wave_kinematics2 for eta2 alone -- no depth profile is touched --, and work item 0 stores P_j, eta2_j and h_j - eta2_j: the
+// value it stores is what that call returns for the stored point, bit for bit.
+template <bool DIR>
+__global__ void __launch_bounds__(kWk2Threads) morison_member2_nodes_kernel(Mem2Args a) {
+    const int e       = blockIdx.x;  // the grid is n_nodes
+    const int m       = a.node_member[e];
+    const int* ds     = a.desc + kMemInts * m;
+    const double* pos = a.state + 3 * ds[0];
+    const MemNode p   = member_node(a.mem + static_cast<size_t>(kMemDoubles) * m, pos, pos + 3 * a.N, e - ds[2], ds[1]);
+    const double x = wave_uniform(p.x), y = wave_uniform(p.y), z = wave_uniform(p.z);
+    double sum[wk2_sums(DIR)];
+    wk2_sea_sum<DIR, true, false>(a.sea, x, y, z, a.t, sum);
+    if (threadIdx.x == 0) {
+        const double eta2 = 0.25 * sum[0] * wk2_ramp2(a.ramped != 0, a.ramp_duration, a.t);
+        double* out = a.nodes + static_cast<size_t>(kMemNodeIncDoubles) * e;
+        out[0] = x;
+        out[1] = y;
+        out[2] = z;
+        out[3] = eta2;
+        a.h[e] = a.h[e] - eta2;
+    }
+}
+
+// One workgroup per Gauss point, behind the kernel above: the point the items kernel evaluates (member_gauss, from the same h) in
+// scalar registers, then the pair sum of hc_wave_kinematics2 at that point and time with the epilogue of morison2_incr_kernel.  A
+// point of a dry segment stores its point and exact zeros and runs no pair sum: both h values are the same in every work item, so
+// the whole workgroup leaves before the sum's first barrier.
+template <bool DIR>
+__global__ void __launch_bounds__(kWk2Threads) morison_member2_points_kernel(Mem2Args a) {
+    constexpr int kWidth = DIR ? kMemPointDirIncDoubles : kMemPointIncDoubles;
+    const int e       = blockIdx.x;  // the grid is n_points
+    const int m       = a.point_member[e];
+    const int* ds     = a.desc + kMemInts * m;
+    const int local   = e - ds[3], seg = local >> 1;
+    const double* pos = a.state + 3 * ds[0];
+    const MemGauss gp = member_gauss(a.mem + static_cast<size_t>(kMemDoubles) * m, pos, pos + 3 * a.N, a.h[ds[2] + seg], a.h[ds[2] + seg + 1],
+                                     seg, local & 1, ds[1]);
+    const double x = wave_uniform(gp.x), y = wave_uniform(gp.y), z = wave_uniform(gp.z);
+    double* out = a.points + static_cast<size_t>(kWidth) * e;
+    if (!(gp.w0 || gp.w1)) {  // a dry segment
+        if (threadIdx.x == 0) {
+            out[0] = x;
+            out[1] = y;
+            out[2] = z;
+#pragma unroll
+            for (int k = 3; k < kWidth; ++k) out[k] = 0.0;
+        }
+        return;
+    }
+    double sum[wk2_sums(DIR)];
+    wk2_sea_sum<DIR, true, true>(a.sea, x, y, z, a.t, sum);
+    if (threadIdx.x == 0) {
+        const double ramp2 = wk2_ramp2(a.ramped != 0, a.ramp_duration, a.t);
+        out[0] = x;
+        out[1] = y;
+        out[2] = z;
+        out[3] = 0.25 * sum[0] * ramp2;
+#pragma unroll
+        for (int k = 1; k < wk2_sums(DIR); ++k) out[3 + k] = sum[k] * ramp2;
+    }
 }
 
 // The two sum levels, one launch each.  One work item per (group, component): the serial sum, in index order, of the rows
@@ -263,6 +409,8 @@ void upload_members(hc_ctx* c) {
     std::vector<double> tab;
     std::vector<int> desc, node_member, point_member, seg_off(1, 0);
     d.off.assign(c->nloc + 1, 0);
+    d.node_off.assign(c->nloc + 1, 0);
+    d.point_off.assign(c->nloc + 1, 0);
     int segs = 0;
     for (int b = c->b0; b < c->b1; ++b) {
         for (const hc_morison_member& m : d.lists[b]) {
@@ -285,6 +433,8 @@ void upload_members(hc_ctx* c) {
             seg_off.push_back(segs);
         }
         d.off[b - c->b0 + 1] = static_cast<int>(desc.size()) / kMemInts;
+        d.node_off[b - c->b0 + 1]  = static_cast<int>(node_member.size());
+        d.point_off[b - c->b0 + 1] = static_cast<int>(point_member.size());
     }
     // the first-segment list of level one and the first-member list of level two, one behind the other
     std::vector<int> offs(seg_off);
@@ -316,7 +466,7 @@ int members_owned(const hc_ctx* c) {
     return n;
 }
 
-void members_enqueue(hc_ctx* c, double t, const double* d_state) {
+void members_enqueue(hc_ctx* c, double t, const double* d_state, bool order2) {
     MorisonMemberData& d = c->members;
     hipStream_t st       = c->mor.stream;
     d.done               = false;
@@ -346,7 +496,38 @@ void members_enqueue(hc_ctx* c, double t, const double* d_state) {
     hipLaunchKernelGGL(dir ? morison_member_nodes_kernel<true> : morison_member_nodes_kernel<false>,
                        dim3((a.n_nodes + kMemThreads - 1) / kMemThreads), dim3(kMemThreads), 0, st, a);
     HC_HIP(hipGetLastError());
-    hipLaunchKernelGGL(dir ? morison_member_items_kernel<true> : morison_member_items_kernel<false>,
+    // the second-order sea: eta2 at the nodes, off h before the cut; then the increments at the Gauss points the cut yields
+    if (order2) {
+        const int width = dir ? kMemPointDirIncDoubles : kMemPointIncDoubles;
+        const int slot  = d.copies.stage(width, d.node_off, d.point_off);
+        const size_t n  = d.copies.layout[slot].doubles();
+        if (d.inc.n < n) d.inc.alloc(n);
+        if (d.h_inc[slot].n < n) d.h_inc[slot].alloc(n);
+        Mem2Args m{};
+        m.sea           = c->mor2.sea(c, a.mwl);
+        m.mem           = a.mem;
+        m.desc          = a.desc;
+        m.node_member   = a.node_member;
+        m.point_member  = a.point_member;
+        m.state         = a.state;
+        m.N             = a.N;
+        m.t             = t;
+        m.ramped        = c->mor2.ramped(c);
+        m.ramp_duration = c->irr.ramp_duration;
+        m.h             = d.h.p;
+        m.nodes         = d.inc.p;
+        m.points        = d.inc.p + d.copies.layout[slot].point_base();
+        a.inc           = m.points;
+        hipLaunchKernelGGL(dir ? morison_member2_nodes_kernel<true> : morison_member2_nodes_kernel<false>, dim3(a.n_nodes), dim3(kWk2Threads), 0,
+                           st, m);
+        HC_HIP(hipGetLastError());
+        hipLaunchKernelGGL(dir ? morison_member2_points_kernel<true> : morison_member2_points_kernel<false>, dim3(a.n_points), dim3(kWk2Threads),
+                           0, st, m);
+        HC_HIP(hipGetLastError());
+        HC_HIP(hipMemcpyAsync(d.h_inc[slot].p, d.inc.p, n * sizeof(double), hipMemcpyDeviceToHost, st));
+    }
+    hipLaunchKernelGGL(order2 ? (dir ? morison_member2_items_kernel<true> : morison_member2_items_kernel<false>)
+                              : (dir ? morison_member_items_kernel<true> : morison_member_items_kernel<false>),
                        dim3((a.n_points + kMemThreads - 1) / kMemThreads), dim3(kMemThreads), 0, st, a);
     HC_HIP(hipGetLastError());
     const int rows1 = 6 * d.members;
@@ -358,6 +539,16 @@ void members_enqueue(hc_ctx* c, double t, const double* d_state) {
     HC_HIP(hipGetLastError());
     HC_HIP(hipMemcpyAsync(d.h_mout.p, d.mout.p, static_cast<size_t>(rows1) * sizeof(double), hipMemcpyDeviceToHost, st));
     HC_HIP(hipMemcpyAsync(d.h_out.p, d.out.p, static_cast<size_t>(c->Dloc) * sizeof(double), hipMemcpyDeviceToHost, st));
+}
+
+// what the two increment getters answer with, or HC_ERR_INVALID (the rules of hc_get_morison_increments)
+const MemberIncrementLayout& member_increments_answer(const hc_ctx* c, int body) {
+    require(c->members.order2, HC_ERR_INVALID,
+            "Morison strip members on the second-order sea are switched off (hc_set_morison_members_second_order)");
+    require(body >= c->b0 && body < c->b1, HC_ERR_INVALID, "body not owned by this context");
+    require(c->members.copies.done, HC_ERR_INVALID,
+            "no Morison evaluation with a second-order member part has completed since a member list was last set");
+    return c->members.copies.last();
 }
 
 }  // namespace hc
@@ -384,6 +575,72 @@ int hc_set_morison_members(hc_ctx* c, int body, const hc_morison_member* members
     c->members.lists[body].assign(members, members + n);
     c->members.dirty = true;
     c->members.done  = false;  // hc_get_morison_member_forces: the lists of the last evaluation are no longer the lists
+    c->members.copies.forget();  // ... nor for the two increment getters
+    HC_API_END(c)
+}
+
+int hc_set_morison_members_second_order(hc_ctx* c, int on) {
+    HC_API_BEGIN_HOT(c)
+    c->mor.require_idle("a Morison evaluation is in flight (hc_morison_end has not been called)");
+    c->members.order2 = on != 0;
+    if (!on) {  // the increments and their two host copies go (nothing of the lane is in flight)
+        c->members.copies.forget();
+        c->members.inc.release();
+        c->members.h_inc[0].alloc(0);
+        c->members.h_inc[1].alloc(0);
+    }
+    HC_API_END(c)
+}
+
+int hc_get_morison_member_increment_counts(hc_ctx* c, int body, int* nodes, int* points) {
+    HC_API_BEGIN_HOT(c)
+    require(body >= 0 && body < c->N, HC_ERR_INVALID, "body index out of range");
+    int segs = 0, members = 0;
+    if (!c->members.lists.empty())
+        for (const hc_morison_member& m : c->members.lists[body]) segs += m.n_seg, ++members;
+    if (nodes) *nodes = segs + members;
+    if (points) *points = 2 * segs;
+    HC_API_END(c)
+}
+
+int hc_get_morison_members_second_order(hc_ctx* c, int* on) {
+    HC_API_BEGIN_HOT(c)
+    if (on) *on = c->members.order2 ? 1 : 0;
+    HC_API_END(c)
+}
+
+int hc_get_morison_member_node_increments(hc_ctx* c, int body, double* p, double* eta2) {
+    HC_API_BEGIN_HOT(c)
+    const hc::MemberIncrementLayout& l = hc::member_increments_answer(c, body);
+    const double* q = c->members.h_inc[c->members.copies.cur].p;
+    const int j0 = l.node_off[body - c->b0], j1 = l.node_off[body - c->b0 + 1];
+    for (int j = j0; j < j1; ++j) {
+        const double* v = q + static_cast<size_t>(hc::kMemNodeIncDoubles) * j;
+        const size_t i  = static_cast<size_t>(j - j0);
+        if (p) std::copy(v, v + 3, p + 3 * i);
+        if (eta2) eta2[i] = v[3];
+    }
+    HC_API_END(c)
+}
+
+int hc_get_morison_member_point_increments(hc_ctx* c, int body, double* p, double* eta2, double* vel2, double* acc2) {
+    HC_API_BEGIN_HOT(c)
+    const hc::MemberIncrementLayout& l = hc::member_increments_answer(c, body);
+    const double* q = c->members.h_inc[c->members.copies.cur].p + l.point_base();
+    const int e0 = l.point_off[body - c->b0], e1 = l.point_off[body - c->b0 + 1];
+    for (int e = e0; e < e1; ++e) {
+        const double* v = q + static_cast<size_t>(l.width) * e;
+        const size_t i  = static_cast<size_t>(e - e0);
+        if (p) std::copy(v, v + 3, p + 3 * i);
+        if (eta2) eta2[i] = v[3];
+        if (l.width == hc::kMemPointDirIncDoubles) {
+            if (vel2) std::copy(v + 4, v + 7, vel2 + 3 * i);
+            if (acc2) std::copy(v + 7, v + 10, acc2 + 3 * i);
+        } else {
+            if (vel2) vel2[3 * i] = v[4], vel2[3 * i + 1] = 0.0, vel2[3 * i + 2] = v[5];
+            if (acc2) acc2[3 * i] = v[6], acc2[3 * i + 1] = 0.0, acc2[3 * i + 2] = v[7];
+        }
+    }
     HC_API_END(c)
 }
 

@@ -179,6 +179,13 @@ __device__ inline void wk2_dir_item_sum(const Wk2Sea& a, double x, double y, dou
     for (int k = 0; k < kR; ++k) out[k] = tid == 0 ? red[k][0] : 0.0;
 }
 
+// A value every lane of the wave holds, moved to scalar registers (its bits unchanged): the point of morison2_incr_kernel<true> and
+// of the strip members' increment kernels (hc_morison_members.hip) then costs the pair sum no vector register, as the point
+// wk2_sum_kernel loads with scalar loads costs it none
+__device__ __forceinline__ double wave_uniform(double v) {
+    return __hiloint2double(__builtin_amdgcn_readfirstlane(__double2hiint(v)), __builtin_amdgcn_readfirstlane(__double2loint(v)));
+}
+
 // The pair sum of either sea behind one name, for the kernels that exist once per sea (wk2_sum_kernel, morison2_incr_kernel,
 // nl2_incr_kernel): wk2_item_sum, which has no y, or wk2_dir_item_sum.  The two stay two functions -- their arithmetic differs on
 // purpose -- and each keeps its own bits.  out: wk2_sums(DIR) values, and q2 behind them with Q2.

@@ -569,6 +569,32 @@ class HydroForces:
         self._chk(self.lib.hc_get_morison_member_forces(self.ctx, int(b), _dp(out.reshape(-1)) if out.size else _dp(np.empty(1))))
         return out
 
+    def set_morison_members_second_order(self, on=True):
+        """With set_morison_second_order() on, the strip members see the second-order sea as well: eta2 at every node moves the cut,
+        u2 and a2 at the Gauss points the cut yields enter the drag product and the inertia term (in a directional sea, with
+        set_morison_second_order_directional(), those of wave_kinematics2(directional=True)).  Off (the default), an evaluation
+        with members on the second-order sea refuses.  A switch of its own, kept when the other two change.  See
+        hc_set_morison_members_second_order in include/hydrochrono_amd.h."""
+        self._chk(self.lib.hc_set_morison_members_second_order(self.ctx, int(bool(on))))
+
+    def morison_members_second_order(self):
+        on = C.c_int()
+        self._chk(self.lib.hc_get_morison_members_second_order(self.ctx, C.byref(on)))
+        return bool(on.value)
+
+    def morison_member_increments(self, b):
+        """What the members of body b (0-based, owned) saw in the last evaluation on the second-order sea, over its members in index
+        order: dict of node_p (sum(n_seg + 1), 3), node_eta2, and of the Gauss points p (sum(2 n_seg), 3), eta2, vel2, acc2 (zeros
+        behind the point of a dry segment; the y components are zero after a long-crested evaluation)."""
+        nn, npt = C.c_int(), C.c_int()
+        self._chk(self.lib.hc_get_morison_member_increment_counts(self.ctx, int(b), C.byref(nn), C.byref(npt)))
+        nn, npt = nn.value, npt.value
+        out = dict(node_p=np.empty((nn, 3)), node_eta2=np.empty(nn), p=np.empty((npt, 3)), eta2=np.empty(npt), vel2=np.empty((npt, 3)),
+                   acc2=np.empty((npt, 3)))
+        self._chk(self.lib.hc_get_morison_member_node_increments(self.ctx, int(b), *[_dp(out[k].reshape(-1)) for k in ("node_p", "node_eta2")]))
+        self._chk(self.lib.hc_get_morison_member_point_increments(self.ctx, int(b), *[_dp(out[k].reshape(-1)) for k in ("p", "eta2", "vel2", "acc2")]))
+        return out
+
     def morison_count(self, b):
         n = C.c_int()
         self._chk(self.lib.hc_get_morison_count(self.ctx, int(b), C.byref(n)))
@@ -1277,6 +1303,16 @@ class HydroGroup:
 
     def morison_member_count(self, b):
         return self.shards[0].morison_member_count(b)
+
+    def morison_members_second_order(self):
+        return self.shards[0].morison_members_second_order()
+
+    def morison_member_increments(self, b):
+        # the shard that owns the body answers
+        for h in self.shards:
+            if h.b0 <= int(b) < h.b1:
+                return h.morison_member_increments(b)
+        raise IndexError(f"body {b} out of range")
 
     def morison_member_forces(self, b):
         # the shard that owns the body answers

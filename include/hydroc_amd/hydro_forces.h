@@ -160,6 +160,16 @@ struct MorisonIncrements {
     std::vector<double> eta2;
 };
 
+// What the strip members of a body saw of the second-order sea (TestHydro::GetMorisonMemberIncrements), over the body's members in
+// index order: per node (n_seg + 1 of each member) the world position and the elevation increment that moved the cut; per Gauss
+// point (2 n_seg of each member) the world position and the increments, exact zeros behind the point of a dry segment.
+struct MorisonMemberIncrements {
+    std::vector<std::array<double, 3>> node_p;
+    std::vector<double> node_eta2;
+    std::vector<std::array<double, 3>> p, vel2, acc2;
+    std::vector<double> eta2;
+};
+
 // What the surface points of a body saw of the second-order sea (TestHydro::GetNonlinearIncrements): per distinct point -- a panel's
 // centroid, a triangle's vertex -- the world position, the elevation increment and q2 = -d phi2 / dt [m^2/s^2].
 struct NonlinearIncrements {
@@ -338,6 +348,42 @@ class TestHydro {
         morison_member_count_[static_cast<size_t>(body_index_1_based - 1)] = raw.size();
         update_have_morison();
         have_time_ = false;
+    }
+    // The members on the second-order sea (hc_set_morison_members_second_order): with SetMorisonSecondOrder on -- and
+    // SetMorisonSecondOrderDirectional under wave directions -- eta2 at every node moves the cut and u2, a2 at the Gauss points enter
+    // the force, where CoordinateFuncForBody otherwise throws for a body with members.  A switch of its own.  Applied to every shard
+    // context.
+    void SetMorisonMembersSecondOrder(bool on) {
+        for (hc_ctx* c : ctxs_) check(c, hc_set_morison_members_second_order(c, on ? 1 : 0));
+        have_time_ = false;
+    }
+    // What the members of a body saw in the last evaluation on the second-order sea (hc_get_morison_member_node_increments,
+    // hc_get_morison_member_point_increments), answered by the shard that owns the body.
+    MorisonMemberIncrements GetMorisonMemberIncrements(int body_index_1_based) {
+        if (body_index_1_based < 1 || body_index_1_based > num_bodies_) throw std::out_of_range("GetMorisonMemberIncrements: body index out of range");
+        const int b = body_index_1_based - 1;
+        for (hc_ctx* c : ctxs_) {
+            int b0 = 0, b1 = 0;
+            check(c, hc_get_shard(c, &b0, &b1));
+            if (b < b0 || b >= b1) continue;
+            int n_nodes = 0, n_points = 0;
+            check(c, hc_get_morison_member_increment_counts(c, b, &n_nodes, &n_points));
+            const size_t nn = static_cast<size_t>(n_nodes), np = static_cast<size_t>(n_points);
+            std::vector<double> P(3 * nn + 1), p(3 * np + 1), vel(3 * np + 1), acc(3 * np + 1);
+            MorisonMemberIncrements out;
+            out.node_eta2.resize(nn);
+            out.eta2.resize(np);
+            check(c, hc_get_morison_member_node_increments(c, b, P.data(), out.node_eta2.data()));
+            check(c, hc_get_morison_member_point_increments(c, b, p.data(), out.eta2.data(), vel.data(), acc.data()));
+            for (size_t j = 0; j < nn; ++j) out.node_p.push_back({P[3 * j], P[3 * j + 1], P[3 * j + 2]});
+            for (size_t e = 0; e < np; ++e) {
+                out.p.push_back({p[3 * e], p[3 * e + 1], p[3 * e + 2]});
+                out.vel2.push_back({vel[3 * e], vel[3 * e + 1], vel[3 * e + 2]});
+                out.acc2.push_back({acc[3 * e], acc[3 * e + 1], acc[3 * e + 2]});
+            }
+            return out;
+        }
+        throw std::out_of_range("GetMorisonMemberIncrements: no context owns the body");
     }
     // The 6-vectors of a body's members in the last evaluation (hc_get_morison_member_forces), from the context that owns the body
     std::vector<std::array<double, 6>> GetMorisonMemberForces(int body_index_1_based) {

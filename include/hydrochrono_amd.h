@@ -724,10 +724,10 @@ int hc_get_morison_increments(hc_ctx* ctx, int body, double* p, double* eta2, do
  * serially in FP64 reproduces the second bit for bit.  hc_morison_end / hc_compute_morison return, per component, elements + members
  * with one IEEE addition for a body that carries members, and exactly the bits they returned before for a body that carries none.
  * A body's bits depend on that body's state, its own member list, the wave model with its directions, t and the options only.
- * Members see the first-order sea: while hc_set_morison_second_order is on and an owned body carries members, hc_morison_begin
- * answers HC_ERR_UNSUPPORTED and nothing stays pending.
+ * Members see the first-order sea unless hc_set_morison_members_second_order (below) is on: while hc_set_morison_second_order is
+ * on, that switch is off and an owned body carries members, hc_morison_begin answers HC_ERR_UNSUPPORTED and nothing stays pending.
  * Not included: axial (end-cap) drag and added mass, which stay point elements; MacCamy-Fuchs diffraction; the body-acceleration
- * term; members on the second-order sea. */
+ * term. */
 typedef struct hc_morison_member {
     double r0[3], r1[3]; /* end points in the body frame, relative to the point pos[b] locates [m]; r0 != r1 */
     double d0, d1;       /* diameter at r0 and at r1 [m], linear in between; >= 0 */
@@ -743,6 +743,43 @@ int hc_get_morison_member_count(hc_ctx* ctx, int body, int* n);
 /* The 6-vectors of the members of `body` in the last completed evaluation, [n][6].  HC_ERR_INVALID: a body this context does not
  * own, a null output, or no evaluation with members completed since a member list was last set. */
 int hc_get_morison_member_forces(hc_ctx* ctx, int body, double* out_nx6);
+
+/* Strip members on the second-order sea (DESIGN.md 3.7c''), long- and short-crested: with `on` (default 0) and
+ * hc_set_morison_second_order on, the refusal above is lifted and the members see the increments the elements see -- before the cut
+ * and before the drag product.  R, d, P, v_e, the options and the first-order quantities are exactly those of the members above.
+ * eta2, u2, a2 are what hc_wave_kinematics2 returns for the same FP64 point and time (hc_wave_kinematics2_dir while wave directions
+ * are set), with mwl and regular_phase of the Morison options and the four cut-offs and apply_ramp of hc_set_morison_second_order;
+ * everything else of that definition applies as written there (fields held at z2 = min(z - mwl, 0) and at the bed, the true depth,
+ * ramp * ramp on all increments).
+ *     nodes      h_j = ((P_j.z - mwl) - eta1_j) - eta2_j, in that order of FP64 operations: eta1_j the first-order elevation of the
+ *                members above, eta2_j the increment at P_j (1/4 sum ramp^2);  the node is wet iff h_j <= 0
+ *     segments, quadrature, weights: unchanged, from the new h
+ *     per point  u_f = ramp u1 + u2,  a_f = ramp a1 + a2, with u2 and a2 taken at the point p the cut yields (the y components are 0
+ *                in the long-crested sea); stretching stays by the point's own eta1; no second wet test; the force formula is unchanged
+ *     dry segments: no pair sum runs at their two points; their increments and their 6-vectors are exact zeros
+ * NoWave, no wave model, a record without components or cut-offs that leave no pair inside either band: no further launch, the
+ * result is that of order 1 bit for bit.  Both sum levels and the one addition elements + members are unchanged; a body's bits depend
+ * on that body's state, its own member list, the wave model with its directions, t, the options and the cut-offs only.  The pair
+ * tables are those of hc_set_morison_second_order: elements and members share the one set of the Morison lane.
+ * The switch is independent of hc_set_morison_second_order and hc_set_morison_second_order_directional: it keeps its value when
+ * they change and has no effect while the first is off.  Two refusals of hc_morison_begin stay and are checked first: wave
+ * directions without hc_set_morison_second_order_directional, and more than 4096 components (HC_ERR_UNSUPPORTED, nothing pending).
+ * HC_ERR_INVALID: a hc_morison_begin without its end.  on = 0 frees the members' increment buffers (the pair tables are freed by
+ * on = 0 of hc_set_morison_second_order).
+ * Not included: stretching of the second-order part. */
+int hc_set_morison_members_second_order(hc_ctx* ctx, int on);
+int hc_get_morison_members_second_order(hc_ctx* ctx, int* on);
+/* What the members of `body` (0-based, owned by this context) saw in the last completed evaluation that had a second-order member
+ * part, over the body's members in index order: the nodes P[n][3] and eta2[n], n = sum (n_seg + 1); the Gauss points p[n][3] with
+ * eta2[n], vel2[n][3], acc2[n][3], n = sum 2 n_seg (segment order, the lower point first; exact zeros behind the point of a dry
+ * segment).  The increments are those hc_wave_kinematics2 / hc_wave_kinematics2_dir return for the stored points, bit for bit.  Any
+ * pointer may be NULL.  HC_ERR_INVALID: the switch is off, no such evaluation has completed, a member list has changed since, or the
+ * body is not owned by this context. */
+int hc_get_morison_member_node_increments(hc_ctx* ctx, int body, double* p_nx3, double* eta2_n);
+/* The two n of the member list of `body` (any body of the system) as it stands: sum (n_seg + 1) and sum 2 n_seg; either pointer
+ * may be NULL.  The two getters refuse after a list change, so these are the sizes of whatever they answer with. */
+int hc_get_morison_member_increment_counts(hc_ctx* ctx, int body, int* nodes, int* points);
+int hc_get_morison_member_point_increments(hc_ctx* ctx, int body, double* p_nx3, double* eta2, double* vel2_nx3, double* acc2_nx3);
 
 /* ------------------------------------------------------------------------------------------------
  * Nonlinear buoyancy and Froude-Krylov forces on body surface panels (not in the reference: src/hydro_types.h:33 is a TODO): the
