@@ -201,6 +201,10 @@ SIGNATURES = {
     "hc_set_morison_members": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(MorisonMember), C.c_int]),
     "hc_get_morison_member_count": (C.c_int, [C.c_void_p, C.c_int, c_int_p]),
     "hc_get_morison_member_forces": (C.c_int, [C.c_void_p, C.c_int, c_double_p]),
+    "hc_set_morison_member_added_mass": (C.c_int, [C.c_void_p, C.c_int, c_double_p, C.c_int]),
+    "hc_get_morison_member_added_mass_coefficients": (C.c_int, [C.c_void_p, C.c_int, c_double_p]),
+    "hc_get_morison_added_mass": (C.c_int, [C.c_void_p, C.c_int, c_double_p]),
+    "hc_get_morison_member_added_mass": (C.c_int, [C.c_void_p, C.c_int, c_double_p]),
     "hc_set_morison_members_second_order": (C.c_int, [C.c_void_p, C.c_int]),
     "hc_get_morison_members_second_order": (C.c_int, [C.c_void_p, c_int_p]),
     "hc_get_morison_member_increment_counts": (C.c_int, [C.c_void_p, C.c_int, c_int_p, c_int_p]),

@@ -194,6 +194,17 @@ struct MorisonMemberData {
     DeviceBuffer<double> inc;
     PinnedBuffer<double> h_inc[2];
     MemberIncrementCopies copies;
+    // the added-mass matrix on the wet length (hc_set_morison_member_added_mass, DESIGN.md 3.7c'''): ca of all bodies of the system
+    // on the host (an empty list: zeros), those of the owned bodies' members on the device, and the 21 upper entries of every Gauss
+    // point, member and owned body with the pinned staging of the two sum levels.  Nothing of it exists while no owned member has
+    // ca > 0.
+    std::vector<std::vector<double>> ca;  // [N], each empty or as long as the body's member list
+    bool ca_dirty   = false;  // a ca list has changed since the device copy was made
+    bool mass       = false;  // some owned member has ca > 0 (as of the device copy)
+    bool mass_flight = false;  // the evaluation in flight has a mass part
+    bool mass_done  = false;  // h_mass_mout / h_mass_out hold a completed evaluation of the lists and ca as they are
+    DeviceBuffer<double> d_ca, mass_item, mass_mout, mass_out;  // [members], [points][21], [members][21], [nloc][21]
+    PinnedBuffer<double> h_mass_mout, h_mass_out;
 };
 
 // Surface panels and triangles (hc_set_surface_panels, hc_set_surface_triangles, hc_nonlinear.hip): the lists of all bodies of the

@@ -490,6 +490,7 @@ int hc_morison_begin(hc_ctx* c, double t, const double* pos, const double* rpy, 
         for (int b = c->b0; b < c->b1; ++b) items += static_cast<int>(c->morison.elems[b].size());
     c->mor2.flight    = false;
     c->members.flight = false;
+    c->members.mass_flight = false;
     c->members.copies.reset();
     c->mor.begin(items != 0 || members != 0, [&] { hc::morison_enqueue(c, t, pos, rpy, linvel, angvel); });
     HC_API_END(c)
@@ -499,11 +500,14 @@ int hc_morison_end(hc_ctx* c, double* out) {
     HC_API_BEGIN_HOT(c)
     const bool with_members = c->members.flight;
     c->members.flight       = false;
+    const bool with_mass    = c->members.mass_flight;  // the members' added-mass matrices change hands as their forces do
+    c->members.mass_flight  = false;
     // the members' increments change hands around the wait, as the elements' do inside the lane's end
     const bool with_member_inc = c->mor.pending != 0 && c->members.copies.retire();
     const int what = c->mor.end("hc_morison_end without hc_morison_begin", &c->mor2);
     if (with_member_inc) c->members.copies.complete();
     if (what == 2 && with_members) c->members.done = true;  // hc_get_morison_member_forces answers with this evaluation
+    if (what == 2 && with_mass) c->members.mass_done = true;  // hc_get_morison_added_mass and the per-member getter too
     require(out != nullptr, HC_ERR_INVALID, "null output");
     if (what == 2 && c->morison.items != 0) std::copy(c->morison.h_out.p, c->morison.h_out.p + c->Dloc, out);
     else std::fill(out, out + c->Dloc, 0.0);

@@ -6,6 +6,8 @@
 // 3.7c'' the members on the second-order sea (hc_set_morison_members_second_order): eta2 of hc_wave_kinematics2 at every node, taken
 // off h before the cut, then u2 and a2 at the Gauss points the cut yields, added before the drag product; in a short-crested sea
 // the increments of hc_wave_kinematics2_dir.
+// 3.7c''' the added-mass matrix on the same wet cut (hc_set_morison_member_added_mass): one more item kernel and the two sum levels
+// over 21 entries, behind the force's launches, and only while some owned member has ca > 0.
 #include "hc_morison_members.hpp"
 
 #include "hc_internal.hpp"
@@ -25,6 +27,7 @@ constexpr int kMemInts = 4;         // body, n_seg, first node, first Gauss poin
 constexpr double kGaussLo = 0.21132486540518711775;  // 1/2 - 1/(2 sqrt 3)
 constexpr double kGaussHi = 0.78867513459481288225;  // 1/2 + 1/(2 sqrt 3)
 constexpr double kQuarterPi = 0.78539816339744830962;
+constexpr int kMassEntries = 21;     // the upper triangle of a 6 x 6 matrix, row by row
 
 struct MemArgs {
     const double* tab;  // the lane's table: [kKinCols][nf], with directions [kKinCols + kDirCols][nf]; nf = 0: still water
@@ -393,14 +396,99 @@ __global__ void __launch_bounds__(kWk2Threads) morison_member2_points_kernel(Mem
 
 // The two sum levels, one launch each.  One work item per (group, component): the serial sum, in index order, of the rows
 // [scale off[g], scale off[g + 1]) of `in`.  Level one: a member's Gauss points (off: the members' first segments, scale 2).
-// Level two: a body's members (off: the owned bodies' first members, scale 1).  Plain vector stores, no atomics.
-__global__ void __launch_bounds__(kMemThreads) morison_member_sum_kernel(const double* in, const int* off, int scale, int rows, double* out) {
+// Level two: a body's members (off: the owned bodies' first members, scale 1).  Plain vector stores, no atomics.  W components per
+// row: 6 for the force, kMassEntries for the added-mass matrix (morison_member_mass_sum_kernel).
+template <int W>
+__device__ __forceinline__ void morison_member_sum_body(const double* in, const int* off, int scale, int rows, double* out) {
     const int row = blockIdx.x * kMemThreads + threadIdx.x;
     if (row >= rows) return;
-    const int g = row / 6, k = row - 6 * g;
+    const int g = row / W, k = row - W * g;
     double acc = 0.0;
-    for (int e = scale * off[g]; e < scale * off[g + 1]; ++e) acc += in[6 * static_cast<size_t>(e) + k];
+    for (int e = scale * off[g]; e < scale * off[g + 1]; ++e) acc += in[W * static_cast<size_t>(e) + k];
     out[row] = acc;
+}
+__global__ void __launch_bounds__(kMemThreads) morison_member_sum_kernel(const double* in, const int* off, int scale, int rows, double* out) {
+    morison_member_sum_body<6>(in, off, scale, rows, out);
+}
+__global__ void __launch_bounds__(kMemThreads) morison_member_mass_sum_kernel(const double* in, const int* off, int scale, int rows,
+                                                                              double* out) {
+    morison_member_sum_body<kMassEntries>(in, off, scale, rows, out);
+}
+
+// 3.7c''' the added-mass matrix on the instantaneous wet length (hc_set_morison_member_added_mass).  One work item per Gauss point,
+// indexed as in morison_member_items_kernel, behind it on the stream: whichever node kernels ran have left h (eta1, and eta2 on the
+// second-order sea) in place, and member_gauss makes of it the wet interval, w_g, D_g, R and d of the force item, bit for bit.  No
+// component loop, no LDS.  With a^ = R (r1 - r0) / L, P = I - a^ a^T, S = [d]x, c = d x a^ and m_g = w_g rho ca (pi / 4) D_g^2 the
+// item is
+//     m_g [ P, -P S ; S P, -S P S ],   -P S = -(S + a^ c^T),   -S P S = |d|^2 I - d d^T - c c^T
+// of which the 21 upper entries are stored row by row (the getters mirror them).  A point of a dry segment and a point of a member
+// with ca = 0 store exact zeros.
+struct MemMassArgs {
+    int n_points;
+    int N;
+    const double* mem;         // as MemArgs
+    const int* desc;
+    const int* point_member;
+    const double* ca;          // [members]
+    const double* state;
+    const double* h;           // [n_nodes], as the force items read it
+    double rho;
+    double* item;              // [n_points][kMassEntries]
+};
+
+__global__ void __launch_bounds__(kMemThreads) morison_member_mass_kernel(MemMassArgs a) {
+    const int o       = blockIdx.x * kMemThreads + threadIdx.x;
+    const bool active = o < a.n_points;
+    const int e       = active ? o : 0;  // items past the end evaluate item 0 and store nothing
+    const int m       = a.point_member[e];
+    const int* dsc    = a.desc + kMemInts * m;
+    const int n_seg = dsc[1], local = e - dsc[3];
+    const int seg = local >> 1, g = local & 1;
+    const double* mem = a.mem + static_cast<size_t>(kMemDoubles) * m;
+    const double* pos = a.state + 3 * dsc[0];
+    const MemGauss gp = member_gauss(mem, pos, pos + 3 * a.N, a.h[dsc[2] + seg], a.h[dsc[2] + seg + 1], seg, g, n_seg);
+    if (!active) return;
+    double* out     = a.item + static_cast<size_t>(kMassEntries) * o;
+    const double ca = a.ca[m];
+    if (!(gp.w0 || gp.w1) || ca == 0.0) {
+#pragma unroll
+        for (int k = 0; k < kMassEntries; ++k) out[k] = 0.0;
+        return;
+    }
+    const MemRot f   = gp.f;
+    const double len = mem[6];
+    const double ex = mem[3] / len, ey = mem[4] / len, ez = mem[5] / len;
+    const double t0 = f.r00 * ex + f.r01 * ey + f.r02 * ez;
+    const double t1 = f.r10 * ex + f.r11 * ey + f.r12 * ez;
+    const double t2 = f.r20 * ex + f.r21 * ey + f.r22 * ez;
+    const double d0 = gp.d0, d1 = gp.d1, d2 = gp.d2;
+    const double c0 = d1 * t2 - d2 * t1, c1 = d2 * t0 - d0 * t2, c2 = d0 * t1 - d1 * t0;
+    const double mg = gp.wg * (a.rho * ca * kQuarterPi * gp.diam * gp.diam);
+    // row 0: P00 P01 P02 | -(P S)00 -(P S)01 -(P S)02
+    out[0] = mg * (1.0 - t0 * t0);
+    out[1] = mg * (-(t0 * t1));
+    out[2] = mg * (-(t0 * t2));
+    out[3] = mg * (-(t0 * c0));
+    out[4] = mg * (d2 - t0 * c1);
+    out[5] = mg * (-d1 - t0 * c2);
+    // row 1: P11 P12 | -(P S)10 -(P S)11 -(P S)12
+    out[6]  = mg * (1.0 - t1 * t1);
+    out[7]  = mg * (-(t1 * t2));
+    out[8]  = mg * (-d2 - t1 * c0);
+    out[9]  = mg * (-(t1 * c1));
+    out[10] = mg * (d0 - t1 * c2);
+    // row 2: P22 | -(P S)20 -(P S)21 -(P S)22
+    out[11] = mg * (1.0 - t2 * t2);
+    out[12] = mg * (d1 - t2 * c0);
+    out[13] = mg * (-d0 - t2 * c1);
+    out[14] = mg * (-(t2 * c2));
+    // rows 3 to 5: the upper entries of -S P S
+    out[15] = mg * ((d1 * d1 + d2 * d2) - c0 * c0);
+    out[16] = mg * (-(d0 * d1) - c0 * c1);
+    out[17] = mg * (-(d0 * d2) - c0 * c2);
+    out[18] = mg * ((d0 * d0 + d2 * d2) - c1 * c1);
+    out[19] = mg * (-(d1 * d2) - c1 * c2);
+    out[20] = mg * ((d0 * d0 + d1 * d1) - c2 * c2);
 }
 
 // the device copy of the owned bodies' lists, body-major
@@ -454,7 +542,86 @@ void upload_members(hc_ctx* c) {
     if (d.h_mout.n < 6 * static_cast<size_t>(d.members)) d.h_mout.alloc(6 * static_cast<size_t>(d.members));
     if (d.out.n < static_cast<size_t>(c->Dloc)) d.out.alloc(c->Dloc);
     if (d.h_out.n < static_cast<size_t>(c->Dloc)) d.h_out.alloc(c->Dloc);
-    d.dirty = false;
+    d.dirty    = false;
+    d.ca_dirty = true;  // the members have other places
+}
+
+// The device copy of ca, in the order of the member table (upload_members has run).  With no ca > 0 on any owned member the mass
+// part has no buffer at all.
+void upload_added_mass(hc_ctx* c) {
+    MorisonMemberData& d = c->members;
+    std::vector<double> ca;
+    bool any = false;
+    for (int b = c->b0; b < c->b1; ++b) {
+        const size_t n = d.lists[b].size();
+        if (d.ca.empty() || d.ca[b].empty()) ca.insert(ca.end(), n, 0.0);
+        else ca.insert(ca.end(), d.ca[b].begin(), d.ca[b].end());
+    }
+    for (double v : ca) any = any || v > 0.0;
+    d.mass     = any;
+    d.ca_dirty = false;
+    if (!any) {
+        d.d_ca.release();
+        d.mass_item.release();
+        d.mass_mout.release();
+        d.mass_out.release();
+        d.h_mass_mout.alloc(0);
+        d.h_mass_out.alloc(0);
+        return;
+    }
+    const size_t W = kMassEntries;
+    d.d_ca.upload(ca, c->mor.stream);
+    if (d.mass_item.n < W * d.points) d.mass_item.alloc(W * d.points);
+    if (d.mass_mout.n < W * d.members) d.mass_mout.alloc(W * d.members);
+    if (d.h_mass_mout.n < W * d.members) d.h_mass_mout.alloc(W * d.members);
+    if (d.mass_out.n < W * c->nloc) d.mass_out.alloc(W * c->nloc);
+    if (d.h_mass_out.n < W * c->nloc) d.h_mass_out.alloc(W * c->nloc);
+}
+
+// The mass launches of one evaluation, behind the member force's on the lane's stream: the items from the h the force items read,
+// then the two sum levels of the force over kMassEntries components, and the copies to the pinned staging.
+void mass_enqueue(hc_ctx* c, const double* d_state) {
+    MorisonMemberData& d = c->members;
+    hipStream_t st       = c->mor.stream;
+    MemMassArgs a{};
+    a.n_points     = d.points;
+    a.N            = c->N;
+    a.mem          = d.tab.p;
+    a.desc         = d.desc.p;
+    a.point_member = d.point_member.p;
+    a.ca           = d.d_ca.p;
+    a.state        = d_state;
+    a.h            = d.h.p;
+    a.rho          = c->rho;
+    a.item         = d.mass_item.p;
+    d.mass_flight  = true;
+    hipLaunchKernelGGL(morison_member_mass_kernel, dim3((a.n_points + kMemThreads - 1) / kMemThreads), dim3(kMemThreads), 0, st, a);
+    HC_HIP(hipGetLastError());
+    const int rows1 = kMassEntries * d.members, rows2 = kMassEntries * c->nloc;
+    hipLaunchKernelGGL(morison_member_mass_sum_kernel, dim3((rows1 + kMemThreads - 1) / kMemThreads), dim3(kMemThreads), 0, st,
+                       d.mass_item.p, d.d_off.p, 2, rows1, d.mass_mout.p);
+    HC_HIP(hipGetLastError());
+    hipLaunchKernelGGL(morison_member_mass_sum_kernel, dim3((rows2 + kMemThreads - 1) / kMemThreads), dim3(kMemThreads), 0, st,
+                       d.mass_mout.p, d.d_off.p + (d.members + 1), 1, rows2, d.mass_out.p);
+    HC_HIP(hipGetLastError());
+    HC_HIP(hipMemcpyAsync(d.h_mass_mout.p, d.mass_mout.p, static_cast<size_t>(rows1) * sizeof(double), hipMemcpyDeviceToHost, st));
+    HC_HIP(hipMemcpyAsync(d.h_mass_out.p, d.mass_out.p, static_cast<size_t>(rows2) * sizeof(double), hipMemcpyDeviceToHost, st));
+}
+
+// the 36 entries of a matrix from its 21 upper ones: M == M^T bitwise
+void mass_unpack(const double* up, double* M) {
+    int k = 0;
+    for (int i = 0; i < 6; ++i)
+        for (int j = i; j < 6; ++j, ++k) M[6 * i + j] = M[6 * j + i] = up[k];
+}
+
+// what the two matrix getters answer from, or HC_ERR_INVALID
+void require_mass_answer(const hc_ctx* c, int body, const double* out) {
+    require(body >= c->b0 && body < c->b1, HC_ERR_INVALID, "body not owned by this context");
+    require(out != nullptr, HC_ERR_INVALID, "null output");
+    require(c->members.mass_done, HC_ERR_INVALID,
+            "no Morison evaluation with an added-mass part has completed since a member list or ca was last set "
+            "(hc_set_morison_member_added_mass)");
 }
 
 }  // namespace
@@ -539,6 +706,10 @@ void members_enqueue(hc_ctx* c, double t, const double* d_state, bool order2) {
     HC_HIP(hipGetLastError());
     HC_HIP(hipMemcpyAsync(d.h_mout.p, d.mout.p, static_cast<size_t>(rows1) * sizeof(double), hipMemcpyDeviceToHost, st));
     HC_HIP(hipMemcpyAsync(d.h_out.p, d.out.p, static_cast<size_t>(c->Dloc) * sizeof(double), hipMemcpyDeviceToHost, st));
+    // the added-mass matrix on the same wet cut; with no ca > 0 on an owned member nothing more is launched
+    d.mass_done = false;
+    if (d.ca_dirty) upload_added_mass(c);
+    if (d.mass) mass_enqueue(c, d_state);
 }
 
 // what the two increment getters answer with, or HC_ERR_INVALID (the rules of hc_get_morison_increments)
@@ -576,6 +747,53 @@ int hc_set_morison_members(hc_ctx* c, int body, const hc_morison_member* members
     c->members.dirty = true;
     c->members.done  = false;  // hc_get_morison_member_forces: the lists of the last evaluation are no longer the lists
     c->members.copies.forget();  // ... nor for the two increment getters
+    if (!c->members.ca.empty()) c->members.ca[body].clear();  // the new list starts with ca = 0
+    c->members.mass_done = false;
+    HC_API_END(c)
+}
+
+int hc_set_morison_member_added_mass(hc_ctx* c, int body, const double* ca, int n) {
+    HC_API_BEGIN_HOT(c)
+    require(body >= 0 && body < c->N, HC_ERR_INVALID, "body index out of range");
+    c->mor.require_idle("a Morison evaluation is in flight (hc_morison_end has not been called)");
+    const int members = c->members.lists.empty() ? 0 : static_cast<int>(c->members.lists[body].size());
+    const bool clear  = ca == nullptr || n == 0;
+    require(clear || n == members, HC_ERR_INVALID, "n is not the member count of the body (hc_get_morison_member_count)");
+    if (!clear) {
+        require(hc::all_finite(ca, static_cast<size_t>(n)), HC_ERR_INVALID, "non-finite added-mass coefficient of a Morison member");
+        for (int e = 0; e < n; ++e) require(ca[e] >= 0.0, HC_ERR_INVALID, "negative added-mass coefficient of a Morison member");
+    }
+    if (c->members.ca.empty()) c->members.ca.resize(c->N);
+    if (clear) c->members.ca[body].clear();
+    else c->members.ca[body].assign(ca, ca + n);
+    c->members.ca_dirty  = true;
+    c->members.mass_done = false;  // the matrices of the last evaluation are no longer those of the coefficients
+    HC_API_END(c)
+}
+
+int hc_get_morison_member_added_mass_coefficients(hc_ctx* c, int body, double* ca) {
+    HC_API_BEGIN_HOT(c)
+    require(body >= 0 && body < c->N, HC_ERR_INVALID, "body index out of range");
+    const size_t n = c->members.lists.empty() ? 0 : c->members.lists[body].size();
+    require(n == 0 || ca, HC_ERR_INVALID, "null output");
+    if (c->members.ca.empty() || c->members.ca[body].empty()) std::fill(ca, ca + n, 0.0);
+    else std::copy(c->members.ca[body].begin(), c->members.ca[body].end(), ca);
+    HC_API_END(c)
+}
+
+int hc_get_morison_added_mass(hc_ctx* c, int body, double* M) {
+    HC_API_BEGIN_HOT(c)
+    hc::require_mass_answer(c, body, M);
+    hc::mass_unpack(c->members.h_mass_out.p + static_cast<size_t>(hc::kMassEntries) * (body - c->b0), M);
+    HC_API_END(c)
+}
+
+int hc_get_morison_member_added_mass(hc_ctx* c, int body, double* out) {
+    HC_API_BEGIN_HOT(c)
+    hc::require_mass_answer(c, body, out);
+    const int m0 = c->members.off[body - c->b0], m1 = c->members.off[body - c->b0 + 1];
+    for (int m = m0; m < m1; ++m)
+        hc::mass_unpack(c->members.h_mass_mout.p + static_cast<size_t>(hc::kMassEntries) * m, out + 36 * static_cast<size_t>(m - m0));
     HC_API_END(c)
 }
 

@@ -569,6 +569,48 @@ class HydroForces:
         self._chk(self.lib.hc_get_morison_member_forces(self.ctx, int(b), _dp(out.reshape(-1)) if out.size else _dp(np.empty(1))))
         return out
 
+    def set_morison_member_added_mass(self, b, ca):
+        """The added-mass coefficients ca >= 0 of the members of body b (0-based): a scalar or (n,) with n the body's member count;
+        None or an empty array clears them, and set_morison_members() resets them to 0.  From the next Morison evaluation on,
+        morison_added_mass() returns the body's 6 x 6 added-mass matrix on the instantaneous wet length; the forces do not change.
+        See hc_set_morison_member_added_mass in include/hydrochrono_amd.h."""
+        n = self.morison_member_count(b)
+        ca = np.zeros(0) if ca is None else np.ascontiguousarray(np.broadcast_to(np.asarray(ca, dtype=np.float64), (n,)) if np.ndim(ca) == 0
+                                                                 else np.asarray(ca, dtype=np.float64).reshape(-1))
+        self._chk(self.lib.hc_set_morison_member_added_mass(self.ctx, int(b), _dp(ca) if ca.size else None, int(ca.size)))
+
+    def morison_member_added_mass_coefficients(self, b):
+        ca = np.zeros(self.morison_member_count(b))
+        self._chk(self.lib.hc_get_morison_member_added_mass_coefficients(self.ctx, int(b), _dp(ca) if ca.size else None))
+        return ca
+
+    def morison_added_mass(self, body=None):
+        """The added-mass matrix (6, 6) of body `body` (0-based, owned) in the last completed Morison evaluation, in world axes at
+        the body's reference point; body=None: (N_local, 6, 6) over the owned bodies.  A body no member of which has ca > 0 gives
+        zeros."""
+        if body is None:
+            return np.stack([self.morison_added_mass(b) for b in range(self.b0, self.b1)])
+        M = np.zeros((6, 6))
+        if np.any(self.morison_member_added_mass_coefficients(body) > 0.0):
+            self._chk(self.lib.hc_get_morison_added_mass(self.ctx, int(body), _dp(M.reshape(-1))))
+        return M
+
+    def morison_member_added_mass(self, b):
+        """The matrices (n, 6, 6) of the members of body b (0-based, owned) in the last completed evaluation; their serial sum in
+        member order is morison_added_mass(b), bit for bit.  Zeros as well for a body no member of which has ca > 0."""
+        out = np.zeros((self.morison_member_count(b), 6, 6))
+        if np.any(self.morison_member_added_mass_coefficients(b) > 0.0):
+            self._chk(self.lib.hc_get_morison_member_added_mass(self.ctx, int(b), _dp(out.reshape(-1))))
+        return out
+
+    def morison_added_mass_force(self, linacc, angacc):
+        """-M (a_lin, alpha) per owned body, (N_local, 6), on the host from morison_added_mass(): the body-acceleration term of
+        Morison's equation for a caller without a mass-matrix hook (the centripetal part is left out).  linacc, angacc: the
+        accelerations of all bodies of the system, (N, 3) in world axes."""
+        n3 = 3 * self.N
+        acc = np.concatenate([_arr(linacc, n3).reshape(-1, 3), _arr(angacc, n3).reshape(-1, 3)], axis=1)[self.b0:self.b1]
+        return -np.matmul(self.morison_added_mass(), acc[:, :, None])[:, :, 0]
+
     def set_morison_members_second_order(self, on=True):
         """With set_morison_second_order() on, the strip members see the second-order sea as well: eta2 at every node moves the cut,
         u2 and a2 at the Gauss points the cut yields enter the drag product and the inertia term (in a directional sea, with
@@ -1327,6 +1369,27 @@ class HydroGroup:
             if h.b0 <= int(b) < h.b1:
                 return h.morison_increments(b)
         raise IndexError(f"body {b} out of range")
+
+    def morison_member_added_mass_coefficients(self, b):
+        return self.shards[0].morison_member_added_mass_coefficients(b)
+
+    def morison_added_mass(self, body=None):
+        # the shard that owns a body answers; body=None: (N, 6, 6), the shards' blocks in body order
+        if body is None:
+            return np.concatenate([h.morison_added_mass() for h in sorted(self.shards, key=lambda h: h.b0)])
+        for h in self.shards:
+            if h.b0 <= int(body) < h.b1:
+                return h.morison_added_mass(body)
+        raise IndexError(f"body {body} out of range")
+
+    def morison_member_added_mass(self, b):
+        for h in self.shards:
+            if h.b0 <= int(b) < h.b1:
+                return h.morison_member_added_mass(b)
+        raise IndexError(f"body {b} out of range")
+
+    def morison_added_mass_force(self, linacc, angacc):
+        return np.concatenate([h.morison_added_mass_force(linacc, angacc) for h in sorted(self.shards, key=lambda h: h.b0)])
 
     def add_waves_irregular_eta(self, t, eta, simulation_dt, num_bodies=None):
         # every shard takes the whole record

@@ -77,11 +77,29 @@ class ChLoadAddedMass : public chrono::ChLoadCustomMultiple {
         m_jacobians->M = infinite_added_mass_system_;
         m_jacobians->R.setZero();
         m_jacobians->K.setZero();
+        if (include_morison_) {  // each body's last strip-member matrix on that body's diagonal block
+            const int N = static_cast<int>(infinite_added_mass_.rows()) / 6;
+            for (int b = 0; b < N; ++b) {
+                const std::array<double, 36> Mb = hydro_->GetMorisonAddedMass(b + 1);
+                for (int i = 0; i < 6; ++i)
+                    for (int j = 0; j < 6; ++j) m_jacobians->M(6 * b + i, 6 * b + j) += Mb[static_cast<size_t>(6 * i + j)];
+            }
+        }
     }
     // :55-70: R += c * M * w
     void LoadIntLoadResidual_Mv(chrono::ChVectorDynamic<>& R, const chrono::ChVectorDynamic<>& w, const double c) override {
         if (!this->m_jacobians) return;
         const int D = static_cast<int>(infinite_added_mass_.rows());
+        if (include_morison_ && R.size() >= D && w.size() >= D) {  // the block-diagonal part on the host, on top of either product below
+            for (int b = 0; b < D / 6; ++b) {
+                const std::array<double, 36> Mb = hydro_->GetMorisonAddedMass(b + 1);
+                for (int i = 0; i < 6; ++i) {
+                    double s = 0.0;
+                    for (int j = 0; j < 6; ++j) s += Mb[static_cast<size_t>(6 * i + j)] * w(6 * b + j);
+                    R(6 * b + i) += c * s;
+                }
+            }
+        }
         if (D <= host_product_limit_ && R.size() >= D && w.size() >= D) {
             // small system: the product on the host copy (src/chloadaddedmass.cpp:70 is the same Eigen expression on the system-sized
             // matrix, whose rows and columns beyond 6N are zero)
@@ -98,10 +116,19 @@ class ChLoadAddedMass : public chrono::ChLoadCustomMultiple {
 
     // Not in the reference: up to how many coordinates the product stays on the host (default kHostProductMaxDofs; 0 = always the GPU)
     void SetHostProductLimit(int dofs) { host_product_limit_ = dofs; }
+    // Not in the reference: with `on` (default off) ComputeJacobian adds to every body's diagonal 6 x 6 block of M the added-mass
+    // matrix of its Morison strip members in the last force evaluation (TestHydro::GetMorisonAddedMass, set with
+    // TestHydro::SetMorisonMemberAddedMass), and LoadIntLoadResidual_Mv includes the same blocks.  The angular part is in world
+    // axes, as the BEM block is used here.  A load built from HydroData::BodyInfo alone has no members: std::logic_error.
+    void SetIncludeMorisonAddedMass(bool on) {
+        if (on && !hydro_) throw std::logic_error("ChLoadAddedMass::SetIncludeMorisonAddedMass: this load was not created by a TestHydro");
+        include_morison_ = on;
+    }
 
   private:
     bool IsStiff() override { return true; }
     int host_product_limit_ = kHostProductMaxDofs;
+    bool include_morison_   = false;
     TestHydro* hydro_;                 // the object that read the file (the load it creates itself), or null:
     std::shared_ptr<hc_ctx> own_ctx_;  // ... a context of the load's own (the constructor over HydroData::BodyInfo; clones share it)
     chrono::ChSystem* system_;

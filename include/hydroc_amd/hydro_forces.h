@@ -346,6 +346,7 @@ class TestHydro {
         for (hc_ctx* c : ctxs_) check(c, hc_set_morison_members(c, body_index_1_based - 1, raw.data(), static_cast<int>(raw.size())));
         morison_member_count_.resize(static_cast<size_t>(num_bodies_), 0);
         morison_member_count_[static_cast<size_t>(body_index_1_based - 1)] = raw.size();
+        if (static_cast<size_t>(body_index_1_based - 1) < morison_member_ca_.size()) morison_member_ca_[static_cast<size_t>(body_index_1_based - 1)] = false;
         update_have_morison();
         have_time_ = false;
     }
@@ -402,6 +403,46 @@ class TestHydro {
             return out;
         }
         throw std::out_of_range("GetMorisonMemberForces: no context owns the body");
+    }
+    // The added-mass coefficients ca >= 0 of a body's members (hc_set_morison_member_added_mass), one per member of the list as it
+    // stands; an empty vector clears them and SetMorisonMembers resets them to 0.  The forces do not change; from the next
+    // evaluation on GetMorisonAddedMass returns the body's 6 x 6 matrix on the instantaneous wet length, which
+    // ChLoadAddedMass::SetIncludeMorisonAddedMass hands to Chrono.  Applied to every shard context.
+    void SetMorisonMemberAddedMass(int body_index_1_based, const std::vector<double>& ca) {
+        if (body_index_1_based < 1 || body_index_1_based > num_bodies_) throw std::out_of_range("SetMorisonMemberAddedMass: body index out of range");
+        for (hc_ctx* c : ctxs_) check(c, hc_set_morison_member_added_mass(c, body_index_1_based - 1, ca.data(), static_cast<int>(ca.size())));
+        bool any = false;
+        for (double v : ca) any = any || v > 0.0;
+        morison_member_ca_.resize(static_cast<size_t>(num_bodies_), false);
+        morison_member_ca_[static_cast<size_t>(body_index_1_based - 1)] = any;
+        have_time_ = false;  // the next read evaluates again: the matrices belong to an evaluation with these coefficients
+    }
+    // The body's added-mass matrix [6][6] (row-major; world axes, at the body's reference point) in the last evaluation
+    // (hc_get_morison_added_mass), from the context that owns the body; zeros for a body no member of which has ca > 0
+    std::array<double, 36> GetMorisonAddedMass(int body_index_1_based) {
+        if (body_index_1_based < 1 || body_index_1_based > num_bodies_) throw std::out_of_range("GetMorisonAddedMass: body index out of range");
+        const int b = body_index_1_based - 1;
+        std::array<double, 36> out{};
+        if (static_cast<size_t>(b) >= morison_member_ca_.size() || !morison_member_ca_[static_cast<size_t>(b)]) return out;
+        hc_ctx* c = owner_of(b, "GetMorisonAddedMass");
+        check(c, hc_get_morison_added_mass(c, b, out.data()));
+        return out;
+    }
+    // ... and those of its members (hc_get_morison_member_added_mass): their serial sum in member order is the body's, bit for bit;
+    // zeros as well for a body no member of which has ca > 0
+    std::vector<std::array<double, 36>> GetMorisonMemberAddedMass(int body_index_1_based) {
+        if (body_index_1_based < 1 || body_index_1_based > num_bodies_) throw std::out_of_range("GetMorisonMemberAddedMass: body index out of range");
+        const int b = body_index_1_based - 1;
+        hc_ctx* c   = owner_of(b, "GetMorisonMemberAddedMass");
+        int n       = 0;
+        check(c, hc_get_morison_member_count(c, b, &n));
+        std::vector<std::array<double, 36>> out(static_cast<size_t>(n));  // (zeros)
+        if (static_cast<size_t>(b) >= morison_member_ca_.size() || !morison_member_ca_[static_cast<size_t>(b)]) return out;
+        std::vector<double> flat(36 * static_cast<size_t>(n) + 1);
+        check(c, hc_get_morison_member_added_mass(c, b, flat.data()));
+        for (size_t e = 0; e < out.size(); ++e)
+            for (size_t k = 0; k < 36; ++k) out[e][k] = flat[36 * e + k];
+        return out;
     }
     // mwl, regular phase and stretching of the kinematics the elements see (those of WaveBase::GetVelocity & co.)
     void SetMorisonOptions(double mwl = 0.0, double regular_phase = 0.0, bool wave_stretching = true) {
@@ -816,6 +857,11 @@ class TestHydro {
         else check(ctx_, hc_added_mass_mv_multi(ctxs_.data(), static_cast<int>(ctxs_.size()), w, c, R, n_sys));
     }
 
+#ifdef HYDROCHRONO_AMD_WITH_CHRONO
+    // the added-mass load the ChBody constructor put into the system (for ChLoadAddedMass::SetIncludeMorisonAddedMass)
+    std::shared_ptr<ChLoadAddedMass> GetAddedMassLoad() const { return my_loadbodyinertia; }
+#endif
+
     hc_ctx* context() const { return ctx_; }
     const std::vector<hc_ctx*>& contexts() const { return ctxs_; }
     int num_shards() const { return static_cast<int>(ctxs_.size()); }
@@ -994,6 +1040,15 @@ class TestHydro {
     std::vector<double> morison_force_;  // the Morison term of the last evaluation
     std::vector<size_t> morison_count_;  // elements per body
     std::vector<size_t> morison_member_count_;  // strip members per body
+    std::vector<bool> morison_member_ca_;       // per body: some member has an added-mass coefficient ca > 0
+    hc_ctx* owner_of(int body_0_based, const char* who) {  // the shard context that owns a body
+        for (hc_ctx* c : ctxs_) {
+            int b0 = 0, b1 = 0;
+            check(c, hc_get_shard(c, &b0, &b1));
+            if (body_0_based >= b0 && body_0_based < b1) return c;
+        }
+        throw std::out_of_range(std::string(who) + ": no context owns the body");
+    }
     bool have_morison_ = false;  // some body carries elements or members
     void update_have_morison() {
         const auto any = [](const std::vector<size_t>& v) { return std::any_of(v.begin(), v.end(), [](size_t n) { return n != 0; }); };

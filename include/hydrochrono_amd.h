@@ -726,8 +726,8 @@ int hc_get_morison_increments(hc_ctx* ctx, int body, double* p, double* eta2, do
  * A body's bits depend on that body's state, its own member list, the wave model with its directions, t and the options only.
  * Members see the first-order sea unless hc_set_morison_members_second_order (below) is on: while hc_set_morison_second_order is
  * on, that switch is off and an owned body carries members, hc_morison_begin answers HC_ERR_UNSUPPORTED and nothing stays pending.
- * Not included: axial (end-cap) drag and added mass, which stay point elements; MacCamy-Fuchs diffraction; the body-acceleration
- * term. */
+ * Not included: axial (end-cap) drag and added mass, which stay point elements; MacCamy-Fuchs diffraction.  The body-acceleration
+ * term comes as a matrix: hc_set_morison_member_added_mass (below). */
 typedef struct hc_morison_member {
     double r0[3], r1[3]; /* end points in the body frame, relative to the point pos[b] locates [m]; r0 != r1 */
     double d0, d1;       /* diameter at r0 and at r1 [m], linear in between; >= 0 */
@@ -743,6 +743,36 @@ int hc_get_morison_member_count(hc_ctx* ctx, int body, int* n);
 /* The 6-vectors of the members of `body` in the last completed evaluation, [n][6].  HC_ERR_INVALID: a body this context does not
  * own, a null output, or no evaluation with members completed since a member list was last set. */
 int hc_get_morison_member_forces(hc_ctx* ctx, int body, double* out_nx6);
+
+/* Strip members: the added-mass matrix on the instantaneous wet length (DESIGN.md 3.7c''').  The body-acceleration term of
+ * Morison's equation, -rho Ca V a_body, needs an input the step does not carry, so it is handed over in the form an integrator
+ * wants: a 6 x 6 matrix per body, as the BEM added mass is (hc_added_mass_matrix).  Each member has a coefficient ca >= 0, default
+ * 0, set beside the list.  R, d = R r_g, the nodes, h_j, the wet interval, the Gauss points, w_g, D_g and a^ are exactly those of the
+ * member force in the same evaluation -- eta2 in h_j included while hc_set_morison_members_second_order applies, the directional
+ * eta while directions are set.  Per Gauss point, with m_g = w_g rho ca (pi / 4) D_g^2, P = I - a^ a^T and S = [d]x (S x = d x x):
+ *     M_g = m_g [  P     -P S  ]
+ *               [ S P   -S P S ]
+ * in world axes at the body's reference point, with the sign of a mass: the force the member puts on the body is -M (a_lin, alpha),
+ * from a_p = a_lin + alpha x d; the centripetal part omega x (omega x d) is left out.  M_g is symmetric and positive semi-definite;
+ * a dry segment and a member with ca = 0 contribute exact zeros.  A member's matrix is the serial sum of its points (segment order,
+ * the lower point first), a body's the serial sum of its members in index order; the 21 upper entries are computed and mirrored, so
+ * M == M^T bitwise, and summing the rows of hc_get_morison_member_added_mass serially in FP64 gives hc_get_morison_added_mass bit
+ * for bit.  A body's matrix depends on its pos and rpy, its member list and ca, the wave model with its directions, t, the Morison
+ * options and, on the second-order sea, the cut-offs -- not on linvel or angvel, not on other bodies, N or the shard.  The member
+ * forces keep their bits whether ca is set or not, and while no owned member has ca > 0 an evaluation launches and allocates nothing
+ * more than it did.
+ * Not included: point elements (heave-plate added mass normally comes with the BEM data); axial and end-cap added mass; the
+ * centripetal term; a frequency-dependent Ca.
+ * ca[n] with n the member count of `body` (0-based, any body of the system) as it stands; NULL or n = 0 clears it, and
+ * hc_set_morison_members resets the body's ca to 0.  HC_ERR_INVALID: body out of range, n neither 0 nor the member count, a negative
+ * or non-finite value, or a hc_morison_begin without its end. */
+int hc_set_morison_member_added_mass(hc_ctx* ctx, int body, const double* ca, int n);
+int hc_get_morison_member_added_mass_coefficients(hc_ctx* ctx, int body, double* ca_n);
+/* The matrix of `body` [6][6] and those of its members [n][6][6] in the last completed evaluation.  HC_ERR_INVALID: a body this
+ * context does not own, a null output, or no evaluation with an added-mass part (some owned member with ca > 0) completed since a
+ * member list or ca was last set. */
+int hc_get_morison_added_mass(hc_ctx* ctx, int body, double* M_6x6);
+int hc_get_morison_member_added_mass(hc_ctx* ctx, int body, double* out_nx36);
 
 /* Strip members on the second-order sea (DESIGN.md 3.7c''), long- and short-crested: with `on` (default 0) and
  * hc_set_morison_second_order on, the refusal above is lifted and the members see the increments the elements see -- before the cut
